@@ -2,6 +2,7 @@
 """Contract benchmark: images/sec of the two-stream 224^2 vit_small MF-CA train step (BASELINE.json metric).
 
   python bench.py --gpus N --steps K --warmup W            (N>1: launched by torch.distributed.run, one rank per GPU)
+  python bench.py ... --dump-outputs DIR                    (also write what the last timed step computed, rank 0, as DIR/<name>.npy)
 
 A "step" is one full pass of the hot path over one synthetic batch that is already resident in HBM:
   Fus_CrossViT forward (two ViT-S/16 encoders + cross-attention exchange + heads) -> output sum -> cross entropy ->
@@ -39,6 +40,7 @@ ARITH = {"bf16": "bf16", "fp16": "f16", "fp32": "f32", "bf16x3": "bf16x3 (split 
 PEAK_HBM_GBS = 8000.0
 NCLS = 10
 TRAFFIC_FILE = "r06_hbm_traffic_by_class.json"      # newest PMC traffic summary (tools/profile_bench.sh), used only when its source hash matches the tree
+DUMP_SAMPLE = 1 << 20     # elements in each of the parameter / gradient samples of --dump-outputs (4 MB each as float32)
 
 
 def parse():
@@ -63,7 +65,45 @@ def parse():
     ap.add_argument("--cpu-steps", type=int, default=10)
     ap.add_argument("--arch", choices=["vit_small", "vit_base"], default="vit_small",
                     help="backbone of the `single` workload (MAIN_MOCO:50 `-a`): vit_base runs the unfused encoder path (tile GEMMs + LayerNorm row passes)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (loss, logits where the step returns them, a seeded "
+                         "sample of the updated parameters and of their gradients, float32; the sample's positions, float64) as DIR/<name>.npy on "
+                         "rank 0, so that two builds can be compared output for output (the inputs depend only on the arguments)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def step_outputs(loss, logits, modules):
+    """What a timed step leaves its caller, as float32 numpy arrays: the loss, the logits (when the step returns them), and the same
+    DUMP_SAMPLE seeded positions (`sample_index`, float64) of the concatenation of every parameter of `modules` (parameters() order) taken
+    from the updated parameters and from their gradients (zeros where a parameter has none: frozen).  Call right after the timed region:
+    the gradients are views of a workspace that the next backward reuses."""
+    params, seen = [], set()
+    for m in modules:
+        for p in m.parameters():
+            if id(p) not in seen:
+                seen.add(id(p))
+                params.append(p)
+    flat_p = torch.cat([p.detach().float().flatten() for p in params])
+    flat_g = torch.cat([(p.grad.detach().float() if p.grad is not None else torch.zeros_like(p, dtype=torch.float32)).flatten() for p in params])
+    n = flat_p.numel()
+    idx = torch.arange(n) if n <= DUMP_SAMPLE else torch.randint(n, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+    idx = idx.to(flat_p.device)
+    out = dict(loss=loss.detach().float().reshape(1).cpu().numpy(), param_sample=flat_p[idx].cpu().numpy(),
+               grad_sample=flat_g[idx].cpu().numpy(), sample_index=idx.cpu().numpy().astype("float64"))
+    if logits is not None:
+        out["logits"] = logits.detach().float().cpu().numpy()
+    return out
+
+
+def write_outputs(dirpath, arrays):
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+    print(f"[bench] wrote {', '.join(sorted(arrays))} ({sum(a.nbytes for a in arrays.values()) / 2**20:.1f} MB) to {dirpath}", file=sys.stderr)
 
 
 def build_models(args, dev, precision=None, mode=None):
@@ -261,6 +301,8 @@ def other_workloads(args, world, rank, dev, lib):
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t)
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, step_outputs(loss, None, [model]))
     ser_ms, per = attribution_pass(step, lib, args.precision)     # one stream by construction in these workloads
     if rank == 0:
         print(json.dumps(dict(metric=name, value=B * world * args.steps / dt, unit="images/sec", n_gpus=world, steps=args.steps,
@@ -376,7 +418,7 @@ def timed_region(run, steps, warmup, world, dev):
     barrier()
     t0 = time.perf_counter()
     for _ in range(steps):
-        loss, _ = step()
+        loss, out = step()
     t_host = time.perf_counter() - t0                       # the host has queued every step (stderr only: how far it runs ahead of the GPU)
     barrier()
     dt = time.perf_counter() - t0
@@ -389,7 +431,7 @@ def timed_region(run, steps, warmup, world, dev):
         dist.all_gather(every, t)                           # per-rank times: the first multi-GPU run diagnoses its own stragglers
         timed_region.rank_seconds = [float(x) for x in every]
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-    return float(t), loss
+    return float(t), loss, out
 
 
 def parity_vs_oracle(run, ref_out):
@@ -435,7 +477,9 @@ def main():
         lib.mfvit_set_wgrad_stream(0)
 
     run.sync.timing = world > 1
-    dt, loss = timed_region(run, args.steps, args.warmup, world, dev)
+    dt, loss, logits = timed_region(run, args.steps, args.warmup, world, dev)
+    if args.dump_outputs and rank == 0:      # before the attribution pass below runs more steps on these weights
+        write_outputs(args.dump_outputs, step_outputs(loss, logits, [run.model] + run.backs))
     rank_s = list(timed_region.rank_seconds)
     wait_ms = run.sync.finish_wait_ms() if world > 1 else 0.0
     run.sync.timing = False
@@ -570,7 +614,7 @@ def main():
                 if (prec, mode) == (args.precision, args.mode):
                     continue
                 r2 = CaRun(args, dev, rank, prec, mode)
-                dt2, loss2 = timed_region(r2, 10, 3, 1, dev)
+                dt2, loss2, _ = timed_region(r2, 10, 3, 1, dev)
                 e = dict(value=B * 10 / dt2, unit="images/sec", ms_per_step=1e3 * dt2 / 10, steps=10, warmup=3, precision=prec, mode=mode,
                          model_tflops=(GFLOP_PER_PAIR[mode] * B * 10 / dt2 / 1e3) if args.img == 224 else None)
                 if ref_out is not None and mode == args.mode:
