@@ -482,9 +482,6 @@ __global__ __launch_bounds__(512) void attn_fwd_pp_kernel(const typename Vec4<T>
             continue;
         }
         if (!act) continue;
-#ifdef MFVIT_FWD_STAGGER
-        if (wave >= 4) __builtin_amdgcn_s_sleep(MFVIT_FWD_STAGGER);
-#endif
         frag_t qf[2], ql[2];
 #pragma unroll
         for (int s = 0; s < 2; ++s) { qf[s] = qnf[s]; ql[s] = qnl[s]; }
@@ -975,9 +972,6 @@ __global__ __launch_bounds__(512) void attn_bwd_mfma_kernel(const typename Vec4<
     stage();
     __syncthreads();                                                   // (also: Os may be refilled)
     if (vi + (int)gridDim.x < npair) fetch(vi + gridDim.x);
-#ifdef MFVIT_BWD_OLD_STAGGER
-    if (wave >= 4) __builtin_amdgcn_s_sleep(MFVIT_BWD_OLD_STAGGER);
-#endif
     const float c = scale * 1.4426950408889634f;
     const int nt = Tpad >> 5;
     // ---------------- phase A: dQ, wave = query tile
@@ -1326,9 +1320,6 @@ __global__ __launch_bounds__(512) void attn_bwd_sp_kernel(const typename Vec4<T>
     // (lane-derived values of these helpers come from a laundered copy of the lane id handed in by the caller: derived from `lane` itself they are
     // loop invariants, which the compiler keeps across the pair loop in scratch - and every reload is a drain of the vector-memory queue)
     auto do_prefetch = [&](const OE* dosrc, int lane_) __attribute__((always_inline)) {
-#ifdef MFVIT_SP_NOPF
-        return;
-#endif
         if constexpr (DM) return;
         const int q = wave * 32 + (lane_ & 31), qc = q < Tn ? q : Tn - 1;
         const OE* dp_ = dosrc + (long)qc * os + 16 * (lane_ >> 5);
@@ -1496,10 +1487,8 @@ __global__ __launch_bounds__(512) void attn_bwd_sp_kernel(const typename Vec4<T>
     // reload waits for every LDS-DMA in flight).
     if (helper) {
         // The helper is the longest wave of every step and shares its SIMD with key wave 3, which reaches the step barriers ~2,000 cycles early:
-        // issue priority to the helper (MFVIT_SP_PRIO: A/B macro).
-#ifndef MFVIT_SP_NOPRIO
+        // issue priority to the helper.
         __builtin_amdgcn_s_setprio(3);
-#endif
         for (int kp = 0; kp < npl; ++kp) {
             const int bid = pair_bid(kp);
             const int b = bid / H, h = bid % H;
@@ -1869,10 +1858,13 @@ template <typename T, int NPX> int launch_bwd_t(const void* qkv, const void* out
     const int Tpad = (Tn + 31) & ~31;
     const bool wide = 4 * Tpad * RSB + 2 * Tpad * 4 + Tpad * RB + 64 <= 160 * 1024;
     const int bytes = 4 * Tpad * (wide ? RSB : RB) + 2 * Tpad * 4 + Tpad * RB;      // Q, K, V, dO images, lse / D rows, the next pair's O rows
+    // (the unpadded images serve the plain types at Tpad = 448 / 480; the split types stop at Tpad = 224 (attn_mfma_supported), where the padded ones fit)
+    if (AttnT<T>::SP && !wide) return MFVIT_EINVAL;
     static PerDeviceOnce attr;
     if (attr.first()) {
         (void)hipFuncSetAttribute((const void*)attn_bwd_mfma_kernel<T, RSB, NPX>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
-        (void)hipFuncSetAttribute((const void*)attn_bwd_mfma_kernel<T, RB, NPX>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
+        if constexpr (!AttnT<T>::SP)
+            (void)hipFuncSetAttribute((const void*)attn_bwd_mfma_kernel<T, RB, NPX>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
     }
     auto colsum = [&]() -> int {
         if (!dbias) return MFVIT_OK;
@@ -1920,7 +1912,7 @@ template <typename T, int NPX> int launch_bwd_t(const void* qkv, const void* out
         if (wide)
             MFVIT_LAUNCH((attn_bwd_mfma_kernel<T, RSB, NPX>), dim3(grid), dim3(512), bytes, st, (const E*)qkv, (const OE*)out, (const OE*)dout, lse,
                          (OE*)dqkv, Tn, H, 1.0f / sqrtf((float)HD), B * H);
-        else
+        else if constexpr (!AttnT<T>::SP)
             MFVIT_LAUNCH((attn_bwd_mfma_kernel<T, RB, NPX>), dim3(grid), dim3(512), bytes, st, (const E*)qkv, (const OE*)out, (const OE*)dout, lse,
                          (OE*)dqkv, Tn, H, 1.0f / sqrtf((float)HD), B * H);
         MFVIT_CHECK_LAUNCH();

@@ -14,12 +14,6 @@
 // C/D map (both): col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5).
 #pragma once
 #include "common.cuh"
-#ifndef MFVIT_NT_PIPE
-#define MFVIT_NT_PIPE 1
-#endif
-#ifndef MFVIT_TN_PIPE
-#define MFVIT_TN_PIPE 1
-#endif
 
 #include <type_traits>
 
@@ -252,7 +246,6 @@ __device__ __forceinline__ int acc_row(int reg, int lane) { return (reg & 3) + 8
 // tiles ahead through a second register set.  Measured inside the step, split bf16: proj / fc2 + LN 118.8 -> 147 us, LN-backward
 // 156 -> 190 us - the extra live registers and the longer dependency chain cost more than the HBM latency they were meant to hide.)
 template <typename T, int BM, int BN, int BKB, int WM, int WN> struct NtLoop {
-    static constexpr bool PIPE = MFVIT_NT_PIPE;
     static constexpr int NT = WM * WN * 64;
     static constexpr int BK = BKB / (int)sizeof(T);
     static constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
@@ -332,7 +325,7 @@ template <typename T, int BM, int BN, int BKB, int WM, int WN> struct NtLoop {
                         bl[1][j] = TB::frag(tb, (wn * TN + j) * 32, 3, lane);
                     }
                 }
-                if (PIPE) __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int t = 0; t < 3 * TM * TN; ++t) {
                     const int term = t / (TM * TN), i = (t % (TM * TN)) / TN, j = t % TN;
@@ -340,7 +333,7 @@ template <typename T, int BM, int BN, int BKB, int WM, int WN> struct NtLoop {
                     side(s * 3 * TM * TN + t);
                     if (HOOKED) __builtin_amdgcn_sched_barrier(0);
                 }
-                if (PIPE) __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_sched_barrier(0);
             }
         }
     }
@@ -361,12 +354,12 @@ template <typename T, int BM, int BN, int BKB, int WM, int WN> struct NtLoop {
 #pragma unroll
                     for (int j = 0; j < TN; ++j) b[(s + 1) & 1][j] = TB::frag(tb, (wn * TN + j) * 32, s + 1, lane);
                 }
-                if (PIPE) __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
                     for (int j = 0; j < TN; ++j) acc[i][j] = MmaTraits<T>::mma(a[s & 1][i], b[s & 1][j], acc[i][j]);
-                if (PIPE) __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_sched_barrier(0);
             }
         }
     }

@@ -17,11 +17,6 @@
 
 #include <type_traits>
 
-// A/B builds only (tools/build_variant_lib.sh): 1 = plain (L2-resident) stores for EVERY output of the tile kernel (default: qkv only, see copy_tile), 2 = for the fc2 data gradient, 3 = for gelu(h)
-#ifndef MFVIT_TILE_PLAIN_STORE
-#define MFVIT_TILE_PLAIN_STORE 0
-#endif
-
 namespace mfvit {
 
 
@@ -31,7 +26,7 @@ namespace mfvit {
 // (Round 5 tried an N-wide 128 x 256 tile of 8 waves, one workgroup per CU - half the A re-reads across the N tiles of a row block, 3/4 of the staged
 // operand bytes per MFMA: bit-identical, L2 requests - 17 %, and 4 - 9 % SLOWER (fc1 + GELU 130.0 -> 135.7 us, fc2 data gradient 112.9 -> 122.9 us);
 // like the M-tall 256 x 128 tile of round 4 it gives up the second independent workgroup per CU.  Removed; profiles/r05_tile_gemm_experiments.txt.)
-template <typename T, int EPI, int DEEP = 0>     // DEEP: K tiles kept in flight by the main loop (0: NtLoop's one; 2: NtLoopDeep, 16-bit types; 12: interleaved, split)
+template <typename T, int EPI, int DEEP = 0>     // DEEP: K tiles kept in flight by the main loop (0: NtLoop's one; 2: NtLoopDeep, plain 16-bit types; 12: interleaved, split)
 __global__ __launch_bounds__(256, 2) void gemm_nt_tile_kernel(GemmP p) {   // 2 workgroups per CU (64 - 68 KB of LDS each): register budget 256 per wave
     constexpr int BM = 128, BN = 128, BKB = 128, WM = 2, WN = 2, NTHR = WM * WN * 64;
     typedef NtLoop<T, BM, BN, BKB, WM, WN> Loop;
@@ -79,10 +74,8 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_tile_kernel(GemmP p) {   // 2 
                 // qkv (the attention core reads it NEXT, 116 MB): a PLAIN store - the lines stay in the L2 / Infinity Cache on their way out and the
                 // forward attention launch behind it runs 54.5 -> 50.5 us in the step (same-box A/B, round 5; an `nt` store does not: 54.4).  Every
                 // other output of this kernel leaves through system-scope streaming stores (no write-allocate fetch, common.cuh).
-                if constexpr (EPI == EPI_BIAS_X3F16 || EPI == EPI_BIAS || MFVIT_TILE_PLAIN_STORE == 1 || (MFVIT_TILE_PLAIN_STORE == 2 && EPI == EPI_GELU_BWD) ||
-                              (MFVIT_TILE_PLAIN_STORE == 3 && EPI == EPI_BIAS_GELU && RB == ROWB && ROWB != AROWB)) *gp = *lp;
-                else
-                store16_stream(gp, *lp);                                         // system-scope streaming store: no write-allocate fetch (common.cuh)
+                if constexpr (EPI == EPI_BIAS_X3F16 || EPI == EPI_BIAS) *gp = *lp;
+                else store16_stream(gp, *lp);
             } else {
                 *lp = *gp;
             }
@@ -893,7 +886,7 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(GemmP p) {
 #pragma unroll
                     for (int j = 0; j < 2; ++j) b[(s + 1) & 1][j] = TB::frag(tb, (wn * 2 + j) * 32, s + 1, lane);
                 }
-                if (MFVIT_TN_PIPE) __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -903,7 +896,7 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(GemmP p) {
 #pragma unroll
                     for (int i = 0; i < 2; ++i) bacc[i] = MmaTraits<T>::mma(a[s & 1][i], ones, bacc[i]);
                 }
-                if (MFVIT_TN_PIPE) __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_sched_barrier(0);
             }
             if (st + 1 < nst) {
                 char* na = lds + (cur ^ 1) * STAGE;
@@ -1021,7 +1014,7 @@ template <typename T, int EPI> static int launch_tile(const GemmP& pin, hipStrea
     static PerDeviceOnce attr_set;
     if (attr_set.first()) {
         (void)hipFuncSetAttribute((const void*)gemm_nt_tile_kernel<T, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-        if constexpr (sizeof(T) == 2)
+        if constexpr (sizeof(T) == 2 && !is_split<T>::value)
             (void)hipFuncSetAttribute((const void*)gemm_nt_tile_kernel<T, EPI, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
     }
     ProfScope ps(PROF_GEMM_TILE, 2.0 * p.M * p.N * p.K * (p.nb > 1 ? p.nb : 1), 0, st);
@@ -1041,8 +1034,7 @@ template <typename T, int EPI> static int launch_tile(const GemmP& pin, hipStrea
                 MFVIT_CHECK_LAUNCH();
                 return MFVIT_OK;
             }
-        }
-        if (deep_ok) {
+        } else if (deep_ok) {
             MFVIT_LAUNCH((gemm_nt_tile_kernel<T, EPI, 2>), dim3(nwg, 1, p.nb > 1 ? p.nb : 1), dim3(256), lds_bytes, st, p);
             MFVIT_CHECK_LAUNCH();
             return MFVIT_OK;

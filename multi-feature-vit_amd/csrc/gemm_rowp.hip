@@ -32,17 +32,6 @@
 
 #include <type_traits>
 
-#ifndef MFVIT_ROWX_STORE
-#define MFVIT_ROWX_STORE 1
-#endif
-#ifndef MFVIT_ROWY_STORE
-#define MFVIT_ROWY_STORE 1
-#endif
-// timing ablations of the forward mode (tools/build_variant_lib.sh; WRONG results): 1 no x_out store, 2 no y store, 4 no main loop, 8 no residual prefetch
-#ifndef MFVIT_RP_ABL
-#define MFVIT_RP_ABL 0
-#endif
-
 namespace mfvit {
 
 namespace {
@@ -201,7 +190,7 @@ __device__ __forceinline__ void rowp_body(GemmP& p, const int tile, const int m0
     // W(1) and A(1 .. 3), 90 KB per CU that the first stage does not need (profiles/r06_row_fwd_ablation.txt: 9 us of the launch).
     f32x4v acc[MF][3];
     {
-        const bool with_res = REPI == REPI_RES_LN && p.res && ks == 0 && !(MFVIT_RP_ABL & 8);      // (one K split carries the residual)
+        const bool with_res = REPI == REPI_RES_LN && p.res && ks == 0;      // (one K split carries the residual)
         const char* gR = rp_uniform_ptr(p.res);
 #pragma unroll
         for (int i = 0; i < MF; ++i)
@@ -370,7 +359,7 @@ __device__ __forceinline__ void rowp_body(GemmP& p, const int tile, const int m0
         return m0e + (r < rows ? r : rows - 1);
     };
 
-    for (int g = 0; g < ((MFVIT_RP_ABL & 4) && REPI == REPI_RES_LN ? 2 : G); g += 2) {
+    for (int g = 0; g < G; g += 2) {
         constexpr int AN = SPACED ? 0 : 1;                             // MF >= 5: one set (the fragments are dead by the time the next are read)
         stage_body(g, wh[0], wl[0], wh[1], wl[1], a01h[0], a01l[0], a01h[AN], a01l[AN]);
         advance_streams();
@@ -519,12 +508,8 @@ __device__ __forceinline__ void rowp_body(GemmP& p, const int tile, const int m0
             r = r < rows ? r : rows - 1;
             // a PLAIN store for the operand-type output (y of the forward, the residual gradient of the backward): the NEXT launches read it - as the A
             // operand of a tile GEMM, once per 128-column tile - and find it in the L2 / Infinity Cache: tile class 90.4 -> 85.4 us per launch in the
-            // step, this kernel + 1 us (same-box A/B, round 5).  MFVIT_ROWY_STORE=0 (A/B builds): system-scope streaming stores (no write-allocate fetch).
-#if MFVIT_ROWY_STORE
+            // step, this kernel + 1 us, against system-scope streaming stores (same-box A/B, round 5: DESIGN_HISTORY.md).
             *(u32x4*)((char*)out + (long)(m0 + r) * ldo * 2 + 16 * ch) = v;
-#else
-            store16_stream((char*)out + (long)(m0 + r) * ldo * 2 + 16 * ch, v);
-#endif
         }
         __syncthreads();
     };
@@ -588,19 +573,15 @@ __device__ __forceinline__ void rowp_body(GemmP& p, const int tile, const int m0
             for (int j = 0; j < 3; ++j) {
                 const int n = ncol0 + 16 * j;
                 // x_out: a plain store, like the operand-type output below - the next row kernel starts its accumulators from these rows (fc2 / proj + LN
-                // 79.5 -> 74.3 us per launch in the step, round 5; MFVIT_ROWX_STORE=0 (A/B builds): the streaming store).  (Issued in front of the row
+                // 79.5 -> 74.3 us per launch in the step against the streaming store, round 5: DESIGN_HISTORY.md).  (Issued in front of the row
                 // statistics instead - the rows are complete there - the class ran 1 us SLOWER, round 6: profiles/r06_row_fwd_ablation.txt)
-#if MFVIT_ROWX_STORE
-                if (p.out0 && !(MFVIT_RP_ABL & 1)) *(f32x4v*)((float*)p.out0 + m * (unsigned)p.ldo0 + n) = acc[i][j];
-#else
-                if (p.out0) store16_stream((float*)p.out0 + m * (unsigned)p.ldo0 + n, __builtin_bit_cast(u32x4_st, acc[i][j]));
-#endif
+                if (p.out0) *(f32x4v*)((float*)p.out0 + m * (unsigned)p.ldo0 + n) = acc[i][j];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) acc[i][j][r] = (acc[i][j][r] - mu[i]) * rs * gj[j][r] + bej[j][r];
                 if (p.y_f32) *(f32x4v*)((float*)p.out1 + m * (unsigned)p.ldo1 + n) = acc[i][j];
             }
         }
-        if (!p.y_f32 && !(MFVIT_RP_ABL & 2)) {
+        if (!p.y_f32) {
             __syncthreads();                                           // (red / red2 live outside the ring; the ring itself is free)
             store_split(p.out1, p.ldo1, 0, MF < 4 ? MF : 4);
             if constexpr (MF > 4) store_split(p.out1, p.ldo1, 4, MF);

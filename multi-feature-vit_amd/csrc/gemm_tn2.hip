@@ -13,7 +13,7 @@
 //   * W8 (round 3, default): EIGHT waves per workgroup.  Waves 4 - 7 own the same four 64 x 64 quadrants as waves 0 - 3 and take the second
 //     half of every stage's reduction rows; the two halves are added through LDS (the ring is free by then) before the float atomics.  The
 //     tile, the LDS traffic and the L2 traffic are unchanged - what changes is that every SIMD holds two MFMA-issuing waves instead of one, so
-//     one wave's transposing fragment reads hide behind the other's MFMAs (MFVIT_TN2_W8=0 restores four waves).
+//     one wave's transposing fragment reads hide behind the other's MFMAs (four waves before round 3: DESIGN.md 5).
 //   * a split's last stage may be partial: its rows past the end are fetched clamped (finite data) and the A-operand rows are
 //     zeroed in LDS before use, so they add nothing.
 #include <stdlib.h>
@@ -22,10 +22,6 @@
 #include "gemm.cuh"
 #include "kernels.h"
 #include "prof.h"
-
-#ifndef MFVIT_TNPART_PLAIN
-#define MFVIT_TNPART_PLAIN 0
-#endif
 
 namespace mfvit {
 
@@ -388,11 +384,7 @@ __global__ __launch_bounds__(W8 ? 512 : 256) void gemm_tn_glds_kernel(GemmP p) {
                     for (int r = 0; r < 16; ++r) {
                         const int n = nw + i * 32 + acc_row(r, lane);
                         const int k = kw + j * 32 + (lane & 31);
-#if MFVIT_TNPART_PLAIN        // A/B builds only: plain stores for the split partials (the reduce launch reads them back within microseconds)
-                        part[(long)n * p.K + k] = acc[i][j][r];
-#else
                         __builtin_nontemporal_store(acc[i][j][r], part + (long)n * p.K + k);
-#endif
                     }
         } else {
 #pragma unroll

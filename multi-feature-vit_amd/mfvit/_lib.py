@@ -13,6 +13,7 @@ from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int64, c_size
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MFVIT_LIB") or os.path.join(_HERE, "libmfvit_hip.so")   # MFVIT_LIB: experiment builds
+ABI_VERSION = 5   # mfvit_abi_version() of the library the ctypes structs below are written for (include/mfvit.h)
 
 F32, BF16, BF16X3, F16, X3F16 = 0, 1, 2, 3, 4   # X3F16: split fp16, the qkv operand of the attention core in bf16x3 mode
 EPI_BIAS, EPI_BIAS_GELU, EPI_NONE, EPI_BIAS_X3F16 = 0, 1, 3, 5
@@ -110,7 +111,7 @@ class MfvitError(RuntimeError):
 
 
 def lib():
-    """Load (once) and return the HIP library; raise loudly when it is absent."""
+    """Load (once) and return the HIP library; raise loudly when it is absent or built for another C ABI."""
     global _lib
     if _lib is not None:
         return _lib
@@ -122,6 +123,9 @@ def lib():
         h = ctypes.CDLL(LIB_PATH)
     except OSError as e:  # missing ROCm runtime etc.
         raise MfvitError(f"cannot load {LIB_PATH}: {e}") from e
+    abi = h.mfvit_abi_version()
+    if abi != ABI_VERSION:   # (an older variant build through MFVIT_LIB: its structs differ from the ones passed here)
+        raise MfvitError(f"{LIB_PATH} has C ABI {abi}, this package expects ABI {ABI_VERSION}: rebuild the library")
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(h, name)
         fn.restype = res

@@ -32,6 +32,21 @@ def test_library_loads_and_exports_every_declared_symbol():
     assert b"gfx950" in h.mfvit_build_info()
 
 
+def test_library_of_another_abi_is_refused(monkeypatch):
+    """A stale variant library (MFVIT_LIB) of another C ABI fails at load time instead of being handed structs of the wrong layout."""
+    from mfvit import _lib
+
+    class StaleLib:
+        def mfvit_abi_version(self):
+            return 4
+
+    monkeypatch.setattr(_lib, "_lib", None)
+    monkeypatch.setattr(_lib, "LIB_PATH", __file__)
+    monkeypatch.setattr(_lib.ctypes, "CDLL", lambda path: StaleLib())
+    with pytest.raises(_lib.MfvitError, match="ABI 4.*rebuild"):
+        _lib.lib()
+
+
 def test_vit_layouts_agree_between_c_and_python():
     import ctypes
     import vits

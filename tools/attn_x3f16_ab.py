@@ -47,12 +47,12 @@ def f16_rounded(x):
 
 refs = {"bf16": ref(ops.split_unpack(q_b.cpu().view(-1, 6 * D)).view(B, T, 3 * D)), "f16": ref(f16_rounded(x))}
 # (MFVIT_ATTN_PF, the one-part forward, existed until the end of round 5: 2.2e-4 on the output for 46 instead of 48 us - profiles/r05_attention_x3f16_ab.txt)
-variants = [("split bf16 qkv (round 4)", q_b, "bf16", None, None), ("split fp16, P 2 parts / dS 2 parts", q_h, "f16", "2", "2"),
-            ("split fp16, P 2 parts / dS 1 part", q_h, "f16", "2", "1")]
+variants = [("split bf16 qkv (round 4)", q_b, "bf16", None), ("split fp16, P 2 parts / dS 2 parts", q_h, "f16", "2"),
+            ("split fp16, P 2 parts / dS 1 part", q_h, "f16", "1")]
 outs = {}
-for name, qkv, rk, pf, pb in variants:
-    if pf:
-        os.environ["MFVIT_ATTN_PF"], os.environ["MFVIT_ATTN_PB"] = pf, pb
+for name, qkv, rk, pb in variants:
+    if pb:
+        os.environ["MFVIT_ATTN_PB"] = pb
     o, lse = ops.attention_fwd(qkv, H, split=True)
     dq, _ = ops.attention_bwd(qkv, o, do, lse, H, want_dbias=False, split=True)
     torch.cuda.synchronize()
@@ -67,9 +67,9 @@ for name, qkv, rk, pf, pb in variants:
 tf = {n: [] for n, *_ in variants}
 tb = {n: [] for n, *_ in variants}
 for rnd in range(5):
-    for name, qkv, rk, pf, pb in variants:
-        if pf:
-            os.environ["MFVIT_ATTN_PF"], os.environ["MFVIT_ATTN_PB"] = pf, pb
+    for name, qkv, rk, pb in variants:
+        if pb:
+            os.environ["MFVIT_ATTN_PB"] = pb
         o, lse = outs[name]
         tf[name].append(timeit(lambda: ops.attention_fwd(qkv, H, split=True)))
         tb[name].append(timeit(lambda: ops.attention_bwd(qkv, o, do, lse, H, want_dbias=False, split=True)))
