@@ -243,13 +243,15 @@ int mfvit_eval_counts(const float* scores, int64_t ld, const int64_t* labels, in
 /* ------------------------------------------------------------------------------------------------------------
  * Two-stream fusion: bidirectional cls<->patch cross-attention exchange + heads (f32).
  * Replaces PreNorm / CrossAttention (MOD:15-21,108-137), MultiScaleTransformerEncoder.forward (FUS:35-65) and
- * Fus_CrossViT.forward (FUS:126-157) for pool='cls', cross_attn_depth = multi_scale_enc_depth = 1.
+ * Fus_CrossViT.forward (FUS:126-157).  dim 384 or 768 (vit_small / vit_base), heads 3, 6 or 12 (head_dim = dim / heads); any other
+ * value gives MFVIT_EINVAL / 0 bytes.  mfvit_fusion_* run one exchange layer with pool='cls'; the mfvit_fusion_ex_* entry points below
+ * add cross_attn_depth and pool='mean'.
  * ------------------------------------------------------------------------------------------------------------ */
 typedef struct mfvit_fusion_cfg {
     int batch;
     int tokens;       /* 1 + patches (197 at 224^2) */
-    int dim;          /* 384 */
-    int heads;        /* 3 (FUS:75) -> head_dim 128 */
+    int dim;          /* 384 or 768 */
+    int heads;        /* 3 (FUS:75), 6 or 12 -> head_dim = dim / heads */
     int num_classes;  /* 3 */
     float eps_pre;    /* 1e-5: PreNorm's nn.LayerNorm default (MOD:18) */
     float eps_post;   /* 1e-6: FUS:26,31 */
@@ -274,10 +276,31 @@ int mfvit_fusion_backward(const mfvit_fusion_cfg* cfg, const float* params, cons
                           float* dparams, float* df_cxr, float* df_enh, float* dhw_cxr, float* dhb_cxr, float* dhw_enh, float* dhb_enh,
                           mfvit_stream_t stream);
 
+/* Fus_CrossViT with cross_attn_depth = L (1 .. 16) chained exchange layers and pool_mean = 0 ('cls') or 1 ('mean').
+ * Parameter arena: the L layer blocks of ONE MultiScaleTransformerEncoder (each laid out as cross_attn_layers.0 above, 8 D^2 + 10 D
+ * floats) followed by the two heads - L (8 D^2 + 10 D) + 2 (C D + C) floats.  In Fus_CrossViT's named_parameters() order this is the
+ * contiguous tail of its arena when the LAST of its multi_scale_enc_depth encoders is passed: every encoder reads the backbone features
+ * and only the last one's output is used (FUS:137-139), so the earlier ones have no effect and are not passed.
+ * Layer l (FUS:40-63) reads X_l (X_0 = the features) and outputs, per stream, X_{l+1} = LN_1e-6([cls_l + CA(LN_1e-5([cls_l ; other
+ * stream's patches of X_l])) ; own patches of X_l]) over ALL rows; both directions of a layer read the layer's input.
+ * Pooling (FUS:141-145): 'cls' pools row 0 of X_0 + X_L, 'mean' averages all T rows of X_0 + X_L; x_cxr / x_enh stay on row 0 of X_0.
+ * L = 1 with 'cls' is exactly mfvit_fusion_forward / _backward (same bits, same workspace).  Otherwise every layer's (2, B, T, dim)
+ * output rows are kept in the workspace for the backward.  Arguments and accumulation rules as mfvit_fusion_forward / _backward;
+ * every sum is taken in a fixed order. */
+size_t mfvit_fusion_ex_param_count(const mfvit_fusion_cfg* cfg, int cross_attn_depth, int pool_mean);
+size_t mfvit_fusion_ex_workspace_bytes(const mfvit_fusion_cfg* cfg, int cross_attn_depth, int pool_mean);
+int mfvit_fusion_ex_forward(const mfvit_fusion_cfg* cfg, int cross_attn_depth, int pool_mean, const float* params, const float* f_cxr,
+                            const float* f_enh, const float* hw_cxr, const float* hb_cxr, const float* hw_enh, const float* hb_enh,
+                            void* workspace, float* fused, float* x_cxr, float* x_enh, mfvit_stream_t stream);
+int mfvit_fusion_ex_backward(const mfvit_fusion_cfg* cfg, int cross_attn_depth, int pool_mean, const float* params, const float* f_cxr,
+                             const float* f_enh, const float* hw_cxr, const float* hw_enh, void* workspace, const float* dfused,
+                             const float* dx_cxr, const float* dx_enh, float* dparams, float* df_cxr, float* df_enh, float* dhw_cxr,
+                             float* dhb_cxr, float* dhw_enh, float* dhb_enh, mfvit_stream_t stream);
+
 /* Stand-alone PreNorm(CrossAttention) (MOD:15-21,108-137): out[b] = proj(attn(LN_1e-5([x_own[b,0] ; x_oth[b,1:]]))) -> (B, dim).
  * params = one block [norm.weight, norm.bias, fn.wq.weight, fn.wk.weight, fn.wv.weight, fn.proj.weight, fn.proj.bias]
- * (4 D^2 + 3 D floats).  x_own == x_oth reproduces PreNorm(dim, CrossAttention(...))(x) exactly.  cfg: batch, tokens, dim 384,
- * heads 3, eps_pre; workspace of mfvit_fusion_workspace_bytes(cfg).  Backward: dparams accumulated; dx_own receives row 0 only,
+ * (4 D^2 + 3 D floats).  x_own == x_oth reproduces PreNorm(dim, CrossAttention(...))(x) exactly.  cfg: batch, tokens, dim,
+ * heads, eps_pre; workspace of mfvit_fusion_workspace_bytes(cfg).  Backward: dparams accumulated; dx_own receives row 0 only,
  * dx_oth rows 1.. only (the caller zero-fills both), or both NULL. */
 int mfvit_prenorm_xattn_forward(const mfvit_fusion_cfg* cfg, const float* params, const float* x_own, const float* x_oth,
                                 void* workspace, float* out, mfvit_stream_t stream);

@@ -11,7 +11,10 @@
 // i.e. the two (B*T) x 384 x 384 K/V projections (99% of the reference's 117 MFLOP per direction) fold into three
 // 384-vectors per sample.  What remains is HBM-bound: one streaming pass pair over the (B, T, 384) tokens of the other
 // stream (roofline: HBM bytes = tokens read twice, second time from L2), plus batch-sized f32 MFMA GEMMs.
-// Only row 0 of the post-exchange LayerNorm / residual is consumed (pool = 'cls', FUS:144-145), so only that row is computed.
+// With one exchange layer and pool = 'cls' only row 0 of the post-exchange LayerNorm / residual is consumed (FUS:144-145), so only that
+// row is computed.  Deeper stacks (cross_attn_depth > 1) and pool = 'mean' take the full-row path (x_rows_* / x_post0_bwd / x_head_*,
+// mfvit_fusion_ex_*): every layer's post-LN rows are materialised.  Kernels are templates on the width D (384 | 768); heads beyond 3 run
+// in chunks of 3 (gridDim.z) with the token gradient of the backward in x_stream_dz_kernel.
 //
 // Parameter arena (f32, state-dict order of Fus_CrossViT; 8 D^2 + 10 D + 2 (C D + C) floats):
 //   [0].norm.{w,b} [0].fn.{wq,wk,wv,proj.w,proj.b}  [1].{w,b}  [2].norm.{w,b} [2].fn.{...}  [3].{w,b}
@@ -27,7 +30,7 @@ using namespace mfvit;
 
 namespace {
 
-constexpr int D = 384, NPL = 6, NH = 3, DH = 128;
+constexpr int NH = 3;   // heads per streaming-pass workgroup (a head chunk; more heads run as more chunks, see x_stream_fwd_kernel)
 
 struct FusLayout {  // parameter offsets (floats)
     long ca[2], post[2], head[2];
@@ -36,7 +39,7 @@ struct FusLayout {  // parameter offsets (floats)
     long total;
     int no_norm;   // bare CrossAttention (MOD:123-137 without the PreNorm around it): z = x, the norm entries of a block are never touched
 };
-FusLayout fus_layout(int C) {
+FusLayout fus_layout(int D, int C) {
     FusLayout L;
     const long blk = 4L * D * D + 3L * D;
     L.n_w = 0; L.n_b = D; L.wq = 2L * D; L.wk = L.wq + (long)D * D; L.wv = L.wk + (long)D * D; L.wp = L.wv + (long)D * D;
@@ -61,9 +64,10 @@ struct FusWs {  // workspace offsets (floats)
     //   pc [2][B][2 C]    d head bias | d backbone-head bias              (x_finish_bwd)
     //   pd [2][2 B][2 D]  d pre-norm weight | bias: rows 0 .. B - 1 from x_stream_bwd (token rows 1 ..), rows B .. 2 B - 1 from x_row0_bwd (the cls row)
     long pa, pb, pc, pd;
+    long ds;       // [2][B][heads][T] d scores of the chunked backward (heads > 3 only, x_stream_bwd_kernel<.., true> -> x_stream_dz_kernel)
     long total;
 };
-FusWs fus_ws(int B, int T, int C) {
+FusWs fus_ws(int B, int T, int C, int D, int NH) {
     FusWs W;
     long o = 0;
     auto take = [&](long n) { long r = o; o += (n + 63) & ~63L; return r; };
@@ -74,12 +78,14 @@ FusWs fus_ws(int B, int T, int C) {
     W.dout = take(2L * B * D); W.dqp = take(2L * B * D); W.dob = take(2L * B * D); W.du = take(2L * B * NH * D);
     W.dkq = take(2L * B * NH * D); W.dz0p = take(2L * B * D); W.dqv = take(2L * B * D); W.dz0q = take(2L * B * D);
     W.pa = take(2L * B * 3 * D); W.pb = take(2L * B * 2 * C * D); W.pc = take(2L * B * 2 * C); W.pd = take(2L * 2 * B * 2 * D);
+    W.ds = NH > 3 ? take(2L * B * NH * T) : 0;
     W.total = o;
     return W;
 }
 
 // ---------------------------------------------------------------------------------------------- kernels
 // z0[dir][b] = LN_pre(own cls row); one wave per (b, dir)
+template <int D>
 __global__ __launch_bounds__(64) void x_cls_ln_kernel(const float* __restrict__ fc, const float* __restrict__ fe,
                                                        const float* __restrict__ params, FusLayout L, float eps, int B, int T,
                                                        float* __restrict__ z0, float* __restrict__ st0) {
@@ -87,6 +93,7 @@ __global__ __launch_bounds__(64) void x_cls_ln_kernel(const float* __restrict__ 
     const float* row = (dir == 0 ? fc : fe) + (long)b * T * D;
     const float* g = params + L.ca[dir] + L.n_w;
     const float* be = params + L.ca[dir] + L.n_b;
+    constexpr int NPL = D / 64;
     float v[NPL], s = 0.f;
 #pragma unroll
     for (int i = 0; i < NPL; ++i) { v[i] = row[lane + 64 * i]; s += v[i]; }
@@ -110,7 +117,9 @@ __global__ __launch_bounds__(64) void x_cls_ln_kernel(const float* __restrict__ 
 //   stats, scores against kq_h, softmax over t, u_h = sum_t a_h[t] z_t.   LDS: sc[3][T] | st[2][T] | red[XW][18*64]
 // XW waves per workgroup, a wave per row: ONE workgroup per CU (256 (sample, direction) pairs at the bench shape), so the rows in flight per
 // CU are the waves of that workgroup - with four (round 1 - 3) the pass ran at 1.7 TB/s.
-template <int XW>
+// CH: more than NH = 3 heads - workgroup z runs heads 3 z .. 3 z + 2 of the nh = 3 gridDim.z (the softmax is per head, so the chunks are
+// independent; each re-derives the row statistics, the same values in every chunk).  A row stays NPL = D / 64 floats per lane.
+template <int XW, int D, bool CH>
 __global__ __launch_bounds__(XW * 64) void x_stream_fwd_kernel(const float* __restrict__ fc, const float* __restrict__ fe,
                                                            const float* __restrict__ params, FusLayout L, float eps, float scale, int B,
                                                            int T, const float* __restrict__ kq, float* __restrict__ u,
@@ -119,7 +128,9 @@ __global__ __launch_bounds__(XW * 64) void x_stream_fwd_kernel(const float* __re
     float* sc = xs;
     float* st = sc + NH * T;
     float* red = st + 2 * T;
+    constexpr int NPL = D / 64;
     const int b = blockIdx.x, dir = blockIdx.y, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int nh = CH ? NH * gridDim.z : NH, h0 = CH ? NH * blockIdx.z : 0;
     const float* own = (dir == 0 ? fc : fe) + (long)b * T * D;
     const float* oth = (dir == 0 ? fe : fc) + (long)b * T * D;
     float g[NPL], be[NPL], kqv[NH][NPL];
@@ -128,7 +139,7 @@ __global__ __launch_bounds__(XW * 64) void x_stream_fwd_kernel(const float* __re
         g[i] = L.no_norm ? 1.f : params[L.ca[dir] + L.n_w + lane + 64 * i];
         be[i] = L.no_norm ? 0.f : params[L.ca[dir] + L.n_b + lane + 64 * i];
 #pragma unroll
-        for (int h = 0; h < NH; ++h) kqv[h][i] = kq[(((long)dir * B + b) * NH + h) * D + lane + 64 * i];
+        for (int h = 0; h < NH; ++h) kqv[h][i] = kq[(((long)dir * B + b) * nh + h0 + h) * D + lane + 64 * i];
     }
     for (int t = w; t < T; t += XW) {
         const float* row = t == 0 ? own : oth + (long)t * D;
@@ -163,9 +174,9 @@ __global__ __launch_bounds__(XW * 64) void x_stream_fwd_kernel(const float* __re
         for (int t = lane; t < T; t += 64) {
             const float p = sc[w * T + t] * s;
             sc[w * T + t] = p;
-            a_out[(((long)dir * B + b) * NH + w) * T + t] = p;
+            a_out[(((long)dir * B + b) * nh + h0 + w) * T + t] = p;
         }
-    } else if (w == NH) {
+    } else if (w == NH && h0 == 0) {
         for (int t = lane; t < T; t += 64) {
             st_out[(((long)dir * B + b) * 2) * T + t] = st[t];
             st_out[(((long)dir * B + b) * 2 + 1) * T + t] = st[T + t];
@@ -196,12 +207,13 @@ __global__ __launch_bounds__(XW * 64) void x_stream_fwd_kernel(const float* __re
         float v = 0.f;
 #pragma unroll
         for (int w2 = 0; w2 < XW; ++w2) v += red[w2 * NH * D + q];
-        u[((long)dir * B + b) * NH * D + q] = v;
+        u[(((long)dir * B + b) * nh + h0) * D + q] = v;
     }
 }
 
 // cal = cls + outp ; c = LN_post(cal) ; fus_cls = cls + c ; ds = head(fus_cls) ; fused = ds_cxr + ds_enh ;
 // x_S = backbone head_S(cls_S) (optional).  One block per sample, wave = direction.
+template <int D>
 __global__ __launch_bounds__(128) void x_finish_fwd_kernel(const float* __restrict__ fc, const float* __restrict__ fe,
                                                            const float* __restrict__ params, FusLayout L, float eps, int B, int T, int C,
                                                            const float* __restrict__ outp, float* __restrict__ fus,
@@ -209,6 +221,7 @@ __global__ __launch_bounds__(128) void x_finish_fwd_kernel(const float* __restri
                                                            const float* __restrict__ hb_c, const float* __restrict__ hw_e,
                                                            const float* __restrict__ hb_e, float* __restrict__ fused,
                                                            float* __restrict__ x_c, float* __restrict__ x_e) {
+    constexpr int NPL = D / 64;
     __shared__ float dsm[2][64];
     const int b = blockIdx.x, dir = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const float* cls = (dir == 0 ? fc : fe) + (long)b * T * D;
@@ -256,6 +269,7 @@ __global__ __launch_bounds__(128) void x_finish_fwd_kernel(const float* __restri
 }
 
 // Backward of x_finish_fwd: head, residual, post-LN; emits dout (= d outp) and the partial cls gradient dqp.
+template <int D>
 __global__ __launch_bounds__(128) void x_finish_bwd_kernel(const float* __restrict__ fc, const float* __restrict__ fe,
                                                            const float* __restrict__ params, FusLayout L, int B, int T, int C,
                                                            const float* __restrict__ outp, const float* __restrict__ fus,
@@ -266,6 +280,7 @@ __global__ __launch_bounds__(128) void x_finish_bwd_kernel(const float* __restri
                                                            float* __restrict__ dhb_c, float* __restrict__ dhw_e,
                                                            float* __restrict__ dhb_e, float* __restrict__ dout, float* __restrict__ dqp,
                                                            float* __restrict__ pa, float* __restrict__ pb, float* __restrict__ pc) {
+    constexpr int NPL = D / 64;
     const int b = blockIdx.x, dir = threadIdx.x >> 6, lane = threadIdx.x & 63;
     // this sample's terms of the small parameter gradients: plain stores into its rows of the partial buffers (FusWs::pa / pb / pc), summed over the batch in a
     // fixed order by fus_reduce_partials
@@ -324,14 +339,18 @@ __global__ __launch_bounds__(128) void x_finish_bwd_kernel(const float* __restri
     for (int i = 0; i < NPL; ++i) dqp[((long)dir * B + b) * D + lane + 64 * i] = dq[i];
 }
 
-// Backward of the streaming pass.  LDS: sa[3][T] (a) | sd[3][T] (da -> ds) | st[2][T] | red[XW][30*64]
-template <int XW>
+// Backward of the streaming pass.  LDS: sa[3][T] (a) | sd[3][T] (da -> ds) | st[2][T] | red[XW][5 D]
+// CH (more than 3 heads): workgroup z owns heads 3 z .. 3 z + 2 and stops at dkq and the score gradients ds_out[dir][b][h][t]; the token
+// gradient, which sums over ALL heads, is x_stream_dz_kernel's.
+template <int XW, int D, bool CH>
 __global__ __launch_bounds__(XW * 64) void x_stream_bwd_kernel(const float* __restrict__ fc, const float* __restrict__ fe,
                                                            const float* __restrict__ params, FusLayout L, float scale, int B, int T,
                                                            const float* __restrict__ kq, const float* __restrict__ a_in,
                                                            const float* __restrict__ st_in, const float* __restrict__ du,
                                                            float* __restrict__ dkq, float* __restrict__ dz0p, float* __restrict__ pd,
-                                                           float* __restrict__ dfc, float* __restrict__ dfe) {
+                                                           float* __restrict__ dfc, float* __restrict__ dfe, float* __restrict__ ds_out) {
+    constexpr int NPL = D / 64;
+    const int nh = CH ? NH * gridDim.z : NH, h0 = CH ? NH * blockIdx.z : 0;
     extern __shared__ __attribute__((aligned(16))) float xs[];
     float* sa = xs;
     float* sd = sa + NH * T;
@@ -348,11 +367,11 @@ __global__ __launch_bounds__(XW * 64) void x_stream_bwd_kernel(const float* __re
         be[i] = L.no_norm ? 0.f : params[L.ca[dir] + L.n_b + lane + 64 * i];
 #pragma unroll
         for (int h = 0; h < NH; ++h) {
-            kqv[h][i] = kq[(((long)dir * B + b) * NH + h) * D + lane + 64 * i];
-            duv[h][i] = du[(((long)dir * B + b) * NH + h) * D + lane + 64 * i];
+            kqv[h][i] = kq[(((long)dir * B + b) * nh + h0 + h) * D + lane + 64 * i];
+            duv[h][i] = du[(((long)dir * B + b) * nh + h0 + h) * D + lane + 64 * i];
         }
     }
-    for (int q = threadIdx.x; q < NH * T; q += XW * 64) sa[q] = a_in[((long)dir * B + b) * NH * T + q];
+    for (int q = threadIdx.x; q < NH * T; q += XW * 64) sa[q] = a_in[(((long)dir * B + b) * nh + h0) * T + q];
     for (int q = threadIdx.x; q < 2 * T; q += XW * 64) st[q] = st_in[((long)dir * B + b) * 2 * T + q];
     __syncthreads();
     for (int t = w; t < T; t += XW) {
@@ -373,8 +392,39 @@ __global__ __launch_bounds__(XW * 64) void x_stream_bwd_kernel(const float* __re
         for (int t = lane; t < T; t += 64) s = fmaf(sa[w * T + t], sd[w * T + t], s);
         s = wave_sum(s);
         for (int t = lane; t < T; t += 64) sd[w * T + t] = sa[w * T + t] * (sd[w * T + t] - s);
+        if (CH)
+            for (int t = lane; t < T; t += 64) ds_out[(((long)dir * B + b) * nh + h0 + w) * T + t] = sd[w * T + t];
     }
     __syncthreads();
+    if constexpr (CH) {   // dkq_h = scale sum_t ds_h[t] z_t of this chunk's heads
+        float akq[NH][NPL];
+#pragma unroll
+        for (int h = 0; h < NH; ++h)
+#pragma unroll
+            for (int i = 0; i < NPL; ++i) akq[h][i] = 0.f;
+        for (int t = w; t < T; t += XW) {
+            const float* row = t == 0 ? own : oth + (long)t * D;
+            const float mu = st[t], rs = st[T + t];
+            const float s0 = sd[t] * scale, s1 = sd[T + t] * scale, s2 = sd[2 * T + t] * scale;
+#pragma unroll
+            for (int i = 0; i < NPL; ++i) {
+                const float z = (row[lane + 64 * i] - mu) * rs * g[i] + be[i];
+                akq[0][i] = fmaf(s0, z, akq[0][i]); akq[1][i] = fmaf(s1, z, akq[1][i]); akq[2][i] = fmaf(s2, z, akq[2][i]);
+            }
+        }
+#pragma unroll
+        for (int h = 0; h < NH; ++h)
+#pragma unroll
+            for (int i = 0; i < NPL; ++i) red[(w * NH + h) * D + lane + 64 * i] = akq[h][i];
+        __syncthreads();
+        for (int q = threadIdx.x; q < NH * D; q += XW * 64) {
+            float v = 0.f;
+#pragma unroll
+            for (int w2 = 0; w2 < XW; ++w2) v += red[w2 * NH * D + q];
+            dkq[(((long)dir * B + b) * nh + h0) * D + q] = v;
+        }
+        return;
+    }
     float akq[NH][NPL], ag[NPL], ab[NPL];
 #pragma unroll
     for (int i = 0; i < NPL; ++i) {
@@ -430,11 +480,13 @@ __global__ __launch_bounds__(XW * 64) void x_stream_bwd_kernel(const float* __re
 }
 
 // cls row of the pre-norm: dz0 = dz0p + dz0q (through Wq); LN backward; total cls gradient of the own stream.
+template <int D>
 __global__ __launch_bounds__(128) void x_row0_bwd_kernel(const float* __restrict__ fc, const float* __restrict__ fe,
                                                          const float* __restrict__ params, FusLayout L, int B, int T,
                                                          const float* __restrict__ st0, const float* __restrict__ dz0p,
                                                          const float* __restrict__ dz0q, const float* __restrict__ dqp,
                                                          float* __restrict__ pd, float* __restrict__ dfc, float* __restrict__ dfe) {
+    constexpr int NPL = D / 64;
     const int b = blockIdx.x, dir = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const float* cls = (dir == 0 ? fc : fe) + (long)b * T * D;
     float* down = dir == 0 ? dfc : dfe;
@@ -464,29 +516,384 @@ __global__ __launch_bounds__(128) void x_row0_bwd_kernel(const float* __restrict
         down[(long)b * T * D + lane + 64 * i] = dqp[((long)dir * B + b) * D + lane + 64 * i] + rs * (dz[i] * g[lane + 64 * i] - c1 - xh[i] * c2);
 }
 
+// Token gradient of the streaming pass for more than 3 heads (after x_stream_bwd_kernel<.., true>): per row t of [own cls ; other patches]
+//   dz_t = sum_h a_h[t] du_h + scale ds_h[t] kq_h,  then the pre-norm LayerNorm backward as in the fused kernel.
+// du_h / kq_h of all heads sit in LDS (2 heads D floats) instead of registers.  LDS: du[nh][D] | kq[nh][D] | a[nh][T] | ds[nh][T] | st[2][T];
+// the cross-wave reduce buffer red[XW][2 D] reuses the front of it once the row loop is done.
+template <int XW, int D>
+__global__ __launch_bounds__(XW * 64) void x_stream_dz_kernel(const float* __restrict__ fc, const float* __restrict__ fe,
+                                                          const float* __restrict__ params, FusLayout L, float scale, int B, int T, int nh,
+                                                          const float* __restrict__ kq, const float* __restrict__ a_in,
+                                                          const float* __restrict__ st_in, const float* __restrict__ du,
+                                                          const float* __restrict__ ds_in, float* __restrict__ dz0p, float* __restrict__ pd,
+                                                          float* __restrict__ dfc, float* __restrict__ dfe) {
+    constexpr int NPL = D / 64;
+    extern __shared__ __attribute__((aligned(16))) float xs[];
+    const long big = (long)2 * nh * D + 2L * nh * T, redn = (long)XW * 2 * D;
+    float* sdu = xs;
+    float* skq = sdu + nh * D;
+    float* sa = skq + nh * D;
+    float* sds = sa + nh * T;
+    float* st = xs + (big > redn ? big : redn);
+    float* red = xs;
+    const int b = blockIdx.x, dir = blockIdx.y, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const long sb = (long)dir * B + b;
+    const float* own = (dir == 0 ? fc : fe) + (long)b * T * D;
+    const float* oth = (dir == 0 ? fe : fc) + (long)b * T * D;
+    float* doth = dir == 0 ? dfe : dfc;
+    for (int q = threadIdx.x; q < nh * D; q += XW * 64) { sdu[q] = du[sb * nh * D + q]; skq[q] = kq[sb * nh * D + q]; }
+    for (int q = threadIdx.x; q < nh * T; q += XW * 64) { sa[q] = a_in[sb * nh * T + q]; sds[q] = ds_in[sb * nh * T + q] * scale; }
+    for (int q = threadIdx.x; q < 2 * T; q += XW * 64) st[q] = st_in[sb * 2 * T + q];
+    float g[NPL], ag[NPL], ab[NPL];
+#pragma unroll
+    for (int i = 0; i < NPL; ++i) { g[i] = L.no_norm ? 1.f : params[L.ca[dir] + L.n_w + lane + 64 * i]; ag[i] = ab[i] = 0.f; }
+    __syncthreads();
+    for (int t = w; t < T; t += XW) {
+        const float* row = t == 0 ? own : oth + (long)t * D;
+        const float mu = st[t], rs = st[T + t];
+        float xh[NPL], dz[NPL], p1 = 0.f, p2 = 0.f;
+#pragma unroll
+        for (int i = 0; i < NPL; ++i) { xh[i] = (row[lane + 64 * i] - mu) * rs; dz[i] = 0.f; }
+        for (int h = 0; h < nh; ++h) {
+            const float a = sa[h * T + t], sc = sds[h * T + t];
+#pragma unroll
+            for (int i = 0; i < NPL; ++i) dz[i] = fmaf(sc, skq[h * D + lane + 64 * i], fmaf(a, sdu[h * D + lane + 64 * i], dz[i]));
+        }
+#pragma unroll
+        for (int i = 0; i < NPL; ++i) { const float tg = dz[i] * g[i]; p1 += tg; p2 += tg * xh[i]; }
+        if (t == 0) {
+#pragma unroll
+            for (int i = 0; i < NPL; ++i) dz0p[sb * D + lane + 64 * i] = dz[i];
+        } else {
+#pragma unroll
+            for (int i = 0; i < NPL; ++i) { ag[i] = fmaf(dz[i], xh[i], ag[i]); ab[i] += dz[i]; }
+            if (doth) {
+                const float c1 = L.no_norm ? 0.f : wave_sum(p1) * (1.f / D), c2 = L.no_norm ? 0.f : wave_sum(p2) * (1.f / D);
+#pragma unroll
+                for (int i = 0; i < NPL; ++i) doth[((long)b * T + t) * D + lane + 64 * i] = rs * (dz[i] * g[i] - c1 - xh[i] * c2);
+            }
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < NPL; ++i) { red[(w * 2) * D + lane + 64 * i] = ag[i]; red[(w * 2 + 1) * D + lane + 64 * i] = ab[i]; }
+    __syncthreads();
+    if (L.no_norm) return;
+    for (int q = threadIdx.x; q < 2 * D; q += XW * 64) {
+        float v = 0.f;
+        for (int w2 = 0; w2 < XW; ++w2) v += red[w2 * 2 * D + q];
+        pd[((long)dir * 2 * B + b) * 2 * D + q] = v;
+    }
+}
+
+// ------------------------------------------------------------------ full-row path (cross_attn_depth > 1 or pool = 'mean')
+// Layer l of MultiScaleTransformerEncoder outputs LN_post([cls + CA ; own patches]) for ALL T rows (FUS:54-55,62-63); layer l + 1 reads them.
+// Y[dir][b][t] = LN_post(t == 0 ? X_own[0] + outp : X_own[t]); the row statistics go to yst[dir][b][t][2] for the backward.
+// pool (last layer only): 1 = cls: fusv = X0_own[0] + Y[0];  2 = mean: fusv = (1/T) sum_t (X0_own[t] + Y[t])  (FUS:141-145), the sum over t
+// taken wave by wave and then over the waves in a fixed order.  X0 = the layer-0 input (the backbone features).
+template <int XW, int D>
+__global__ __launch_bounds__(XW * 64) void x_rows_fwd_kernel(const float* __restrict__ xc, const float* __restrict__ xe,
+                                                         const float* __restrict__ x0c, const float* __restrict__ x0e,
+                                                         const float* __restrict__ params, FusLayout L, float eps, int B, int T,
+                                                         const float* __restrict__ outp, float* __restrict__ Y, float* __restrict__ yst,
+                                                         int pool, float* __restrict__ fusv) {
+    constexpr int NPL = D / 64;
+    __shared__ float red[XW * D];
+    const int b = blockIdx.x, dir = blockIdx.y, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const long sb = (long)dir * B + b;
+    const float* own = (dir == 0 ? xc : xe) + (long)b * T * D;
+    const float* x0 = (dir == 0 ? x0c : x0e) + (long)b * T * D;
+    const float* gp = params + L.post[dir];
+    float g[NPL], be[NPL], acc[NPL];
+#pragma unroll
+    for (int i = 0; i < NPL; ++i) { g[i] = gp[lane + 64 * i]; be[i] = gp[D + lane + 64 * i]; acc[i] = 0.f; }
+    for (int t = w; t < T; t += XW) {
+        float v[NPL], s = 0.f;
+#pragma unroll
+        for (int i = 0; i < NPL; ++i) {
+            v[i] = own[(long)t * D + lane + 64 * i] + (t == 0 ? outp[sb * D + lane + 64 * i] : 0.f);
+            s += v[i];
+        }
+        const float mu = wave_sum(s) * (1.f / D);
+        float q = 0.f;
+#pragma unroll
+        for (int i = 0; i < NPL; ++i) { v[i] -= mu; q += v[i] * v[i]; }
+        const float rs = rsqrtf(wave_sum(q) * (1.f / D) + eps);
+#pragma unroll
+        for (int i = 0; i < NPL; ++i) {
+            const float y = v[i] * rs * g[i] + be[i];
+            Y[(sb * T + t) * D + lane + 64 * i] = y;
+            if (pool == 2 || (pool == 1 && t == 0)) acc[i] += x0[(long)t * D + lane + 64 * i] + y;
+        }
+        if (lane == 0) { yst[(sb * T + t) * 2] = mu; yst[(sb * T + t) * 2 + 1] = rs; }
+    }
+    if (pool == 1 && w == 0) {
+#pragma unroll
+        for (int i = 0; i < NPL; ++i) fusv[sb * D + lane + 64 * i] = acc[i];
+    } else if (pool == 2) {
+#pragma unroll
+        for (int i = 0; i < NPL; ++i) red[w * D + lane + 64 * i] = acc[i];
+        __syncthreads();
+        for (int q = threadIdx.x; q < D; q += XW * 64) {
+            float v = 0.f;
+            for (int w2 = 0; w2 < XW; ++w2) v += red[w2 * D + q];
+            fusv[sb * D + q] = v / (float)T;
+        }
+    }
+}
+
+// heads on the pooled rows: ds = head(fusv) ; fused = ds_cxr + ds_enh ; x_S = backbone head_S(X0_S[0]) (optional).  One block per sample.
+template <int D>
+__global__ __launch_bounds__(128) void x_head_fwd_kernel(const float* __restrict__ x0c, const float* __restrict__ x0e,
+                                                         const float* __restrict__ params, FusLayout L, int B, int T, int C,
+                                                         const float* __restrict__ fusv, const float* __restrict__ hw_c,
+                                                         const float* __restrict__ hb_c, const float* __restrict__ hw_e,
+                                                         const float* __restrict__ hb_e, float* __restrict__ fused,
+                                                         float* __restrict__ x_c, float* __restrict__ x_e) {
+    constexpr int NPL = D / 64;
+    __shared__ float dsm[2][64];
+    const int b = blockIdx.x, dir = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const float* cls = (dir == 0 ? x0c : x0e) + (long)b * T * D;
+    float c0[NPL], f[NPL];
+#pragma unroll
+    for (int i = 0; i < NPL; ++i) { c0[i] = cls[lane + 64 * i]; f[i] = fusv[((long)dir * B + b) * D + lane + 64 * i]; }
+    const float* hw = params + L.head[dir];
+    const float* hb = hw + (long)C * D;
+    for (int c = 0; c < C; ++c) {
+        float d = 0.f;
+#pragma unroll
+        for (int i = 0; i < NPL; ++i) d = fmaf(f[i], hw[(long)c * D + lane + 64 * i], d);
+        d = wave_sum(d);
+        if (lane == 0) dsm[dir][c] = d + hb[c];
+    }
+    const float* bw = dir == 0 ? hw_c : hw_e;
+    const float* bb = dir == 0 ? hb_c : hb_e;
+    float* xo = dir == 0 ? x_c : x_e;
+    if (bw && xo) {
+        for (int c = 0; c < C; ++c) {
+            float d = 0.f;
+#pragma unroll
+            for (int i = 0; i < NPL; ++i) d = fmaf(c0[i], bw[(long)c * D + lane + 64 * i], d);
+            d = wave_sum(d);
+            if (lane == 0) xo[(long)b * C + c] = d + (bb ? bb[c] : 0.f);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < C) fused[(long)b * C + threadIdx.x] = dsm[0][threadIdx.x] + dsm[1][threadIdx.x];
+}
+
+// Backward of x_head_fwd: per-sample head-gradient terms (pb / pc as in x_finish_bwd), ev = the gradient of each pooled row of X0 + Y
+// (e = head^T dfused for cls, e / T for mean) and bb = the backbone head's gradient of X0[0].
+template <int D>
+__global__ __launch_bounds__(128) void x_head_bwd_kernel(const float* __restrict__ x0c, const float* __restrict__ x0e,
+                                                         const float* __restrict__ params, FusLayout L, int B, int T, int C, int pool_mean,
+                                                         const float* __restrict__ fusv, const float* __restrict__ hw_c,
+                                                         const float* __restrict__ hw_e, const float* __restrict__ dfused,
+                                                         const float* __restrict__ dx_c, const float* __restrict__ dx_e,
+                                                         float* __restrict__ ev, float* __restrict__ bbv, float* __restrict__ pb,
+                                                         float* __restrict__ pc) {
+    constexpr int NPL = D / 64;
+    const int b = blockIdx.x, dir = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long sb = (long)dir * B + b;
+    float* pb_r = pb + sb * 2 * C * D;
+    float* pc_r = pc + sb * 2 * C;
+    const float* cls = (dir == 0 ? x0c : x0e) + (long)b * T * D;
+    const float* hw = params + L.head[dir];
+    float e[NPL], c0[NPL], f[NPL];
+#pragma unroll
+    for (int i = 0; i < NPL; ++i) { e[i] = 0.f; c0[i] = cls[lane + 64 * i]; f[i] = fusv[sb * D + lane + 64 * i]; }
+    for (int c = 0; c < C; ++c) {
+        const float gc = dfused ? dfused[(long)b * C + c] : 0.f;
+#pragma unroll
+        for (int i = 0; i < NPL; ++i) {
+            e[i] = fmaf(gc, hw[(long)c * D + lane + 64 * i], e[i]);
+            pb_r[(long)c * D + lane + 64 * i] = gc * f[i];
+        }
+        if (lane == 0) pc_r[c] = gc;
+    }
+#pragma unroll
+    for (int i = 0; i < NPL; ++i) ev[sb * D + lane + 64 * i] = pool_mean ? e[i] / (float)T : e[i];
+    const float* bw = dir == 0 ? hw_c : hw_e;
+    const float* dxs = dir == 0 ? dx_c : dx_e;
+    float q[NPL];
+#pragma unroll
+    for (int i = 0; i < NPL; ++i) q[i] = 0.f;
+    for (int c = 0; c < C; ++c) {
+        const float gc = bw && dxs ? dxs[(long)b * C + c] : 0.f;
+#pragma unroll
+        for (int i = 0; i < NPL; ++i) {
+            if (bw && dxs) q[i] = fmaf(gc, bw[(long)c * D + lane + 64 * i], q[i]);
+            pb_r[(long)(C + c) * D + lane + 64 * i] = gc * c0[i];
+        }
+        if (lane == 0) pc_r[C + c] = gc;
+    }
+#pragma unroll
+    for (int i = 0; i < NPL; ++i) bbv[sb * D + lane + 64 * i] = q[i];
+}
+
+// Backward of row 0 of x_rows_fwd (cal = X_own[0] + outp -> LN_post): dout = dcal feeds the exchange's backward, dqp = dcal (+ ev + bb on
+// layer 0, where X_own = X0 is also pooled / read by the backbone head).  dY = the full row gradient of the layer above, or ev on the top
+// layer.  Partials: pr row B + b = (dy xh, dy) (post-LN weight | bias), pbp row b = dcal (proj.bias).
+template <int D>
+__global__ __launch_bounds__(128) void x_post0_bwd_kernel(const float* __restrict__ xc, const float* __restrict__ xe,
+                                                          const float* __restrict__ params, FusLayout L, int B, int T,
+                                                          const float* __restrict__ outp, const float* __restrict__ yst,
+                                                          const float* __restrict__ dY, const float* __restrict__ ev,
+                                                          const float* __restrict__ bbv, int first, float* __restrict__ dout,
+                                                          float* __restrict__ dqp, float* __restrict__ pr, float* __restrict__ pbp) {
+    constexpr int NPL = D / 64;
+    const int b = blockIdx.x, dir = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long sb = (long)dir * B + b;
+    const float* cls = (dir == 0 ? xc : xe) + (long)b * T * D;
+    const float* g = params + L.post[dir];
+    const float mu = yst[sb * T * 2], rs = yst[sb * T * 2 + 1];
+    float dy[NPL], xh[NPL], s1 = 0.f, s2 = 0.f;
+    float* pr_r = pr + ((long)dir * 2 * B + B + b) * 2 * D;
+#pragma unroll
+    for (int i = 0; i < NPL; ++i) {
+        dy[i] = dY ? dY[sb * T * D + lane + 64 * i] : ev[sb * D + lane + 64 * i];
+        xh[i] = (cls[lane + 64 * i] + outp[sb * D + lane + 64 * i] - mu) * rs;
+        const float t = dy[i] * g[lane + 64 * i];
+        s1 += t; s2 += t * xh[i];
+        pr_r[lane + 64 * i] = dy[i] * xh[i];
+        pr_r[D + lane + 64 * i] = dy[i];
+    }
+    const float c1 = wave_sum(s1) * (1.f / D), c2 = wave_sum(s2) * (1.f / D);
+#pragma unroll
+    for (int i = 0; i < NPL; ++i) {
+        const float dcal = rs * (dy[i] * g[lane + 64 * i] - c1 - xh[i] * c2);
+        dout[sb * D + lane + 64 * i] = dcal;
+        pbp[sb * D + lane + 64 * i] = dcal;
+        dqp[sb * D + lane + 64 * i] = first ? dcal + ev[sb * D + lane + 64 * i] + bbv[sb * D + lane + 64 * i] : dcal;
+    }
+}
+
+// Backward of rows 1 .. T-1 of x_rows_fwd: dX_own[t] += LN_post backward of dY[t] (+ ev on layer 0 with mean pooling, where X0[t] itself is
+// pooled).  dX_own rows 1 .. already hold the exchange's gradient (x_stream_bwd / x_stream_dz of the other direction).  mode: 0 = dY is a
+// full (2, B, T, D) gradient, 1 = every row's gradient is ev (mean pooling, top layer), 2 = zero (cls pooling, top layer).
+// Partials: pr row b = sum over t >= 1 of (dy xh, dy), per wave and then over the waves in a fixed order.
+template <int XW, int D>
+__global__ __launch_bounds__(XW * 64) void x_rows_bwd_kernel(const float* __restrict__ xc, const float* __restrict__ xe,
+                                                         const float* __restrict__ params, FusLayout L, int B, int T,
+                                                         const float* __restrict__ yst, const float* __restrict__ dY,
+                                                         const float* __restrict__ ev, int mode, int add_ev, float* __restrict__ dxc,
+                                                         float* __restrict__ dxe, float* __restrict__ pr) {
+    constexpr int NPL = D / 64;
+    __shared__ float red[XW * 2 * D];
+    const int b = blockIdx.x, dir = blockIdx.y, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const long sb = (long)dir * B + b;
+    float* pr_r = pr + ((long)dir * 2 * B + b) * 2 * D;
+    float* dx = dir == 0 ? dxc : dxe;
+    if (mode == 2) {
+        for (int q = threadIdx.x; q < 2 * D; q += XW * 64) pr_r[q] = 0.f;
+        return;
+    }
+    const float* own = (dir == 0 ? xc : xe) + (long)b * T * D;
+    const float* gp = params + L.post[dir];
+    float g[NPL], e[NPL], ag[NPL], ab[NPL];
+#pragma unroll
+    for (int i = 0; i < NPL; ++i) {
+        g[i] = gp[lane + 64 * i];
+        e[i] = mode == 1 || add_ev ? ev[sb * D + lane + 64 * i] : 0.f;
+        ag[i] = ab[i] = 0.f;
+    }
+    for (int t = 1 + w; t < T; t += XW) {
+        const float mu = yst[(sb * T + t) * 2], rs = yst[(sb * T + t) * 2 + 1];
+        float dy[NPL], xh[NPL], s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int i = 0; i < NPL; ++i) {
+            dy[i] = mode == 0 ? dY[(sb * T + t) * D + lane + 64 * i] : e[i];
+            xh[i] = (own[(long)t * D + lane + 64 * i] - mu) * rs;
+            const float tg = dy[i] * g[i];
+            s1 += tg; s2 += tg * xh[i];
+            ag[i] = fmaf(dy[i], xh[i], ag[i]); ab[i] += dy[i];
+        }
+        if (dx) {
+            const float c1 = wave_sum(s1) * (1.f / D), c2 = wave_sum(s2) * (1.f / D);
+#pragma unroll
+            for (int i = 0; i < NPL; ++i) {
+                float* o = dx + ((long)b * T + t) * D + lane + 64 * i;
+                *o = *o + rs * (dy[i] * g[i] - c1 - xh[i] * c2) + (add_ev ? e[i] : 0.f);
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < NPL; ++i) { red[(w * 2) * D + lane + 64 * i] = ag[i]; red[(w * 2 + 1) * D + lane + 64 * i] = ab[i]; }
+    __syncthreads();
+    for (int q = threadIdx.x; q < 2 * D; q += XW * 64) {
+        float v = 0.f;
+        for (int w2 = 0; w2 < XW; ++w2) v += red[w2 * 2 * D + q];
+        pr_r[q] = v;
+    }
+}
+
 GemmP zg() { GemmP p; memset(&p, 0, sizeof(p)); return p; }
 
-constexpr int XW_FWD = 16, XW_BWD = 8;      // waves per workgroup of the streaming passes (the backward holds ~100 registers per lane)
+// waves per workgroup of the streaming passes: the same bytes in flight per CU at both widths (a D = 768 row is twice a D = 384 row; the
+// backward holds ~100 registers per lane at D = 384, ~180 at D = 768)
+template <int D> constexpr int xw_fwd() { return D == 384 ? 16 : 8; }
+constexpr int XW_BWD = 8, XW_DZ = 8, XW_ROWS = 8;
+constexpr int MAX_XDEPTH = 16;   // cross_attn_depth accepted by the _ex entry points
 #define FUS_TRY(expr) do { int rc__ = (expr); if (rc__ != MFVIT_OK) return rc__; } while (0)
+#define FUS_BY_DIM(dim, CALL) ((dim) == 384 ? CALL<384> : CALL<768>)
 
 bool fus_ok(const mfvit_fusion_cfg* c) {
-    return c && c->batch > 0 && c->tokens > 1 && c->dim == D && c->heads == NH && c->num_classes > 0 && c->num_classes <= 64;
+    return c && c->batch > 0 && c->tokens > 1 && (c->dim == 384 || c->dim == 768) && (c->heads == 3 || c->heads == 6 || c->heads == 12) &&
+           c->num_classes > 0 && c->num_classes <= 64;
+}
+bool fus_ex_ok(const mfvit_fusion_cfg* c, int depth, int pool_mean) {
+    return fus_ok(c) && depth >= 1 && depth <= MAX_XDEPTH && (pool_mean == 0 || pool_mean == 1);
+}
+// the full-row path: every row of every layer's post-LN is live (the default cls / one-layer form needs row 0 only)
+bool fus_full(int depth, int pool_mean) { return depth > 1 || pool_mean; }
+
+// layer l of an arena of `depth` exchange layers followed by the two heads: layer l is the block of fus_layout at l (8 D^2 + 10 D floats)
+FusLayout fus_layer_layout(int D, int C, int depth, int l) {
+    FusLayout L = fus_layout(D, C);
+    const long lay = 8L * D * D + 10L * D;
+    for (int dir = 0; dir < 2; ++dir) { L.ca[dir] += l * lay; L.post[dir] += l * lay; }
+    L.head[0] = depth * lay;
+    L.head[1] = L.head[0] + (long)C * D + C;
+    L.total = depth * lay + 2 * ((long)C * D + C);
+    return L;
+}
+
+// workspace of the full-row path (floats): one slab per layer [FusWs | Y | yst | pr | pbp], then dx[2] | ev | bb | fusv
+//   Y   [2][B][T][D]   the layer's output rows (the next layer's input)        yst [2][B][T][2]  their post-LN mean, rstd
+//   pr  [2][2 B][2 D]  post-LN weight | bias partials: rows 0 .. B-1 rows 1 .. T-1 (x_rows_bwd), rows B .. 2B-1 row 0 (x_post0_bwd)
+//   pbp [2][B][D]      proj.bias partials (x_post0_bwd)
+//   dx  two [2][B][T][D] gradients of the intermediate rows (layer l writes dx[l & 1], reads dx[(l + 1) & 1]); only when depth > 1
+//   ev, bb, fusv [2][B][D]   pooled-row gradient, backbone-head gradient of X0[0], pooled rows
+struct FusExWs {
+    long Y, yst, pr, pbp, slab;
+    long dx, ev, bb, fusv;
+    long total;
+};
+FusExWs fus_ex_ws(int B, int T, int C, int D, int NH, int depth) {
+    FusExWs E;
+    long o = 0;
+    auto take = [&](long n) { long r = o; o += (n + 63) & ~63L; return r; };
+    take(fus_ws(B, T, C, D, NH).total);
+    E.Y = take(2L * B * T * D); E.yst = take(2L * B * T * 2); E.pr = take(2L * 2 * B * 2 * D); E.pbp = take(2L * B * D);
+    E.slab = o;
+    o = depth * E.slab;
+    E.dx = take(depth > 1 ? 2 * 2L * B * T * D : 0);
+    E.ev = take(2L * B * D); E.bb = take(2L * B * D); E.fusv = take(2L * B * D);
+    E.total = o;
+    return E;
+}
+
+template <typename K> void max_lds(K* kern, PerDeviceOnce& once) {
+    if (once.first()) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }
 
 }  // namespace
 
-static int xattn_core_backward(int ndir, const FusLayout& L, const FusWs& W, const float* params, const float* f_cxr, const float* f_enh,
-                               float* ws, int B, int T, float* dparams, float* df_cxr, float* df_enh, hipStream_t st);
-static int fus_prenorm_job(int dir, const FusLayout& L, const FusWs& W, float* ws, int B, float* dparams, hipStream_t st);
-
-extern "C" {
-
-size_t mfvit_fusion_param_count(const mfvit_fusion_cfg* cfg) { return fus_ok(cfg) ? (size_t)fus_layout(cfg->num_classes).total : 0; }
-size_t mfvit_fusion_workspace_bytes(const mfvit_fusion_cfg* cfg) { return fus_ok(cfg) ? (size_t)fus_ws(cfg->batch, cfg->tokens, cfg->num_classes).total * 4 : 0; }
-
 // PreNorm -> CrossAttention of `ndir` directions up to the projection output outp[dir][b][D] (MOD:20,123-137)
-static int xattn_core_forward(int ndir, const FusLayout& L, const FusWs& W, const float* params, const float* f_cxr, const float* f_enh,
-                              float* ws, int B, int T, float eps_pre, hipStream_t st) {
+template <int D>
+static int xattn_core_forward(int ndir, int nh, const FusLayout& L, const FusWs& W, const float* params, const float* f_cxr,
+                              const float* f_enh, float* ws, int B, int T, float eps_pre, hipStream_t st) {
+    const int DH = D / nh;
     const float scale = 1.0f / sqrtf((float)DH);
     // transposed copies of wq, wk, wv, wp (used by kq here and by the backward)
     for (int dir = 0; dir < ndir; ++dir) {
@@ -494,7 +901,7 @@ static int xattn_core_forward(int ndir, const FusLayout& L, const FusWs& W, cons
         for (int k = 0; k < 4; ++k)
             FUS_TRY(cast_transpose(MFVIT_F32, params + L.ca[dir] + offs[k], nullptr, ws + W.wT + ((long)dir * 4 + k) * D * D, D, D, st));
     }
-    MFVIT_LAUNCH(x_cls_ln_kernel, dim3(B, ndir), dim3(64), 0, st, f_cxr, f_enh, params, L, eps_pre, B, T, ws + W.z0, ws + W.st0);
+    MFVIT_LAUNCH(x_cls_ln_kernel<D>, dim3(B, ndir), dim3(64), 0, st, f_cxr, f_enh, params, L, eps_pre, B, T, ws + W.z0, ws + W.st0);
     MFVIT_CHECK_LAUNCH();
     {   // qv = z0 Wq^T
         GemmP p = zg();
@@ -503,27 +910,34 @@ static int xattn_core_forward(int ndir, const FusLayout& L, const FusWs& W, cons
         p.nb = ndir; p.nbi = 1; p.sAo = (long)B * D; p.sWo = L.ca_stride; p.sOo = (long)B * D;
         FUS_TRY(gemm_nt_tile(MFVIT_F32, EPI_NONE, p, st));
     }
-    {   // kq_h = qv_h Wk_h  (W operand = WkT[:, h*128 ..])
+    {   // kq_h = qv_h Wk_h  (W operand = WkT[:, h*DH ..])
         GemmP p = zg();
         p.A = ws + W.qv; p.lda = D; p.W = ws + W.wT + 1L * D * D; p.ldw = D; p.M = B; p.N = D; p.K = DH;
-        p.out0 = ws + W.kq; p.ldo0 = NH * D;
-        p.nb = ndir * NH; p.nbi = NH; p.sAo = (long)B * D; p.sAi = DH; p.sWo = 4L * D * D; p.sWi = DH; p.sOo = (long)B * NH * D; p.sOi = D;
+        p.out0 = ws + W.kq; p.ldo0 = nh * D;
+        p.nb = ndir * nh; p.nbi = nh; p.sAo = (long)B * D; p.sAi = DH; p.sWo = 4L * D * D; p.sWi = DH; p.sOo = (long)B * nh * D; p.sOi = D;
         FUS_TRY(gemm_nt_tile(MFVIT_F32, EPI_NONE, p, st));
     }
     {
-        const size_t lds = (size_t)(5 * T + XW_FWD * NH * D) * 4;
-        static PerDeviceOnce attr;
-        if (attr.first()) { (void)hipFuncSetAttribute((const void*)x_stream_fwd_kernel<XW_FWD>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); }
-        ProfScope ps(PROF_XATTN_FWD, 0, 2.0 * B * T * D * 4 * 2, st);
-        MFVIT_LAUNCH(x_stream_fwd_kernel<XW_FWD>, dim3(B, ndir), dim3(XW_FWD * 64), lds, st, f_cxr, f_enh, params, L, eps_pre, scale, B, T,
-                           ws + W.kq, ws + W.u, ws + W.a, ws + W.st);
+        constexpr int XW = xw_fwd<D>();
+        const size_t lds = (size_t)(5 * T + XW * NH * D) * 4;
+        static PerDeviceOnce attr1, attrc;
+        ProfScope ps(PROF_XATTN_FWD, 0, 2.0 * B * T * D * 4 * 2 * (nh / NH), st);
+        if (nh == NH) {
+            max_lds((x_stream_fwd_kernel<XW, D, false>), attr1);
+            MFVIT_LAUNCH((x_stream_fwd_kernel<XW, D, false>), dim3(B, ndir), dim3(XW * 64), lds, st, f_cxr, f_enh, params, L, eps_pre, scale, B, T,
+                               ws + W.kq, ws + W.u, ws + W.a, ws + W.st);
+        } else {
+            max_lds((x_stream_fwd_kernel<XW, D, true>), attrc);
+            MFVIT_LAUNCH((x_stream_fwd_kernel<XW, D, true>), dim3(B, ndir, nh / NH), dim3(XW * 64), lds, st, f_cxr, f_enh, params, L, eps_pre, scale,
+                               B, T, ws + W.kq, ws + W.u, ws + W.a, ws + W.st);
+        }
         MFVIT_CHECK_LAUNCH();
     }
     {   // o_h = u_h Wv_h^T
         GemmP p = zg();
-        p.A = ws + W.u; p.lda = NH * D; p.W = params + L.ca[0] + L.wv; p.ldw = D; p.M = B; p.N = DH; p.K = D;
+        p.A = ws + W.u; p.lda = nh * D; p.W = params + L.ca[0] + L.wv; p.ldw = D; p.M = B; p.N = DH; p.K = D;
         p.out0 = ws + W.o; p.ldo0 = D;
-        p.nb = ndir * NH; p.nbi = NH; p.sAo = (long)B * NH * D; p.sAi = D; p.sWo = L.ca_stride; p.sWi = (long)DH * D; p.sOo = (long)B * D; p.sOi = DH;
+        p.nb = ndir * nh; p.nbi = nh; p.sAo = (long)B * nh * D; p.sAi = D; p.sWo = L.ca_stride; p.sWi = (long)DH * D; p.sOo = (long)B * D; p.sOi = DH;
         FUS_TRY(gemm_nt_tile(MFVIT_F32, EPI_NONE, p, st));
     }
     {   // outp = o Wp^T + bp
@@ -537,66 +951,18 @@ static int xattn_core_forward(int ndir, const FusLayout& L, const FusWs& W, cons
     return MFVIT_OK;
 }
 
-int mfvit_fusion_forward(const mfvit_fusion_cfg* cfg, const float* params, const float* f_cxr, const float* f_enh, const float* hw_cxr,
-                         const float* hb_cxr, const float* hw_enh, const float* hb_enh, void* workspace, float* fused, float* x_cxr,
-                         float* x_enh, mfvit_stream_t stream) {
-    if (!fus_ok(cfg) || !params || !f_cxr || !f_enh || !workspace || !fused) return MFVIT_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    const int B = cfg->batch, T = cfg->tokens, C = cfg->num_classes;
-    const FusLayout L = fus_layout(C);
-    const FusWs W = fus_ws(B, T, cfg->num_classes);
-    float* ws = (float*)workspace;
-    FUS_TRY(xattn_core_forward(2, L, W, params, f_cxr, f_enh, ws, B, T, cfg->eps_pre, st));
-    MFVIT_LAUNCH(x_finish_fwd_kernel, dim3(B), dim3(128), 0, st, f_cxr, f_enh, params, L, cfg->eps_post, B, T, C, ws + W.outp,
-                       ws + W.fus, ws + W.stc, hw_cxr, hb_cxr, hw_enh, hb_enh, fused, x_cxr, x_enh);
-    MFVIT_CHECK_LAUNCH();
-    return MFVIT_OK;
-}
-
-int mfvit_fusion_backward(const mfvit_fusion_cfg* cfg, const float* params, const float* f_cxr, const float* f_enh, const float* hw_cxr,
-                          const float* hw_enh, void* workspace, const float* dfused, const float* dx_cxr, const float* dx_enh,
-                          float* dparams, float* df_cxr, float* df_enh, float* dhw_cxr, float* dhb_cxr, float* dhw_enh, float* dhb_enh,
-                          mfvit_stream_t stream) {
-    if (!fus_ok(cfg) || !params || !f_cxr || !f_enh || !workspace || !dparams) return MFVIT_EINVAL;
-    if ((df_cxr == nullptr) != (df_enh == nullptr)) return MFVIT_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    const int B = cfg->batch, T = cfg->tokens, C = cfg->num_classes;
-    const FusLayout L = fus_layout(C);
-    const FusWs W = fus_ws(B, T, cfg->num_classes);
-    float* ws = (float*)workspace;
-    MFVIT_LAUNCH(x_finish_bwd_kernel, dim3(B), dim3(128), 0, st, f_cxr, f_enh, params, L, B, T, C, ws + W.outp, ws + W.fus,
-                       ws + W.stc, hw_cxr, hw_enh, dfused, dx_cxr, dx_enh, dparams, dhw_cxr, dhb_cxr, dhw_enh, dhb_enh, ws + W.dout,
-                       ws + W.dqp, ws + W.pa, ws + W.pb, ws + W.pc);
-    MFVIT_CHECK_LAUNCH();
-    FUS_TRY(xattn_core_backward(2, L, W, params, f_cxr, f_enh, ws, B, T, dparams, df_cxr, df_enh, st));
-    // the batch sums of the small gradients, every one in a fixed order (one launch)
-    ColpartBatch batch;
-    ColpartBatch* prev = colpart_batch_begin(&batch);
-    int rc = MFVIT_OK;
-    for (int dir = 0; dir < 2 && rc == MFVIT_OK; ++dir) {
-        float* dhw = dparams + L.head[dir];
-        float* dg = dparams + L.post[dir];
-        rc = colpart_reduce(ws + W.pa + (long)dir * B * 3 * D, B, D, 3, dg, dg + D, dparams + L.ca[dir] + L.bp, st);
-        if (rc == MFVIT_OK) rc = colpart_reduce(ws + W.pb + (long)dir * B * 2 * C * D, B, C * D, 2, dhw, dir == 0 ? dhw_cxr : dhw_enh, nullptr, st);
-        if (rc == MFVIT_OK) rc = colpart_reduce(ws + W.pc + (long)dir * B * 2 * C, B, C, 2, dhw + (long)C * D, dir == 0 ? dhb_cxr : dhb_enh, nullptr, st);
-        if (rc == MFVIT_OK) rc = fus_prenorm_job(dir, L, W, ws, B, dparams, st);
-    }
-    if (rc == MFVIT_OK) rc = colpart_batch_flush(st);
-    colpart_batch_begin(prev);
-    return rc;
-}
-
-}  // extern "C"
-
-// d pre-norm weight | bias of direction `dir` += the sum over its 2 B partial rows (x_stream_bwd: token rows 1 .., x_row0_bwd: the cls row), fixed order
-static int fus_prenorm_job(int dir, const FusLayout& L, const FusWs& W, float* ws, int B, float* dparams, hipStream_t st) {
+// d pre-norm weight | bias of direction `dir` += the sum over its 2 B partial rows (x_stream_bwd / x_stream_dz: token rows 1 ..,
+// x_row0_bwd: the cls row), fixed order
+static int fus_prenorm_job(int D, int dir, const FusLayout& L, const FusWs& W, float* ws, int B, float* dparams, hipStream_t st) {
     if (L.no_norm) return MFVIT_OK;
     return colpart_reduce(ws + W.pd + (long)dir * 2 * B * 2 * D, 2 * B, D, 2, dparams + L.ca[dir] + L.n_w, dparams + L.ca[dir] + L.n_b, nullptr, st);
 }
 
 // backward of xattn_core_forward: consumes ws.dout (= d outp) and ws.dqp (cls gradient that bypasses the attention)
-static int xattn_core_backward(int ndir, const FusLayout& L, const FusWs& W, const float* params, const float* f_cxr, const float* f_enh,
-                               float* ws, int B, int T, float* dparams, float* df_cxr, float* df_enh, hipStream_t st) {
+template <int D>
+static int xattn_core_backward(int ndir, int nh, const FusLayout& L, const FusWs& W, const float* params, const float* f_cxr,
+                               const float* f_enh, float* ws, int B, int T, float* dparams, float* df_cxr, float* df_enh, hipStream_t st) {
+    const int DH = D / nh;
     const float scale = 1.0f / sqrtf((float)DH);
     const float* wT = ws + W.wT;
     {   // dWp += dout^T o
@@ -615,39 +981,52 @@ static int xattn_core_backward(int ndir, const FusLayout& L, const FusWs& W, con
     }
     {   // dWv_h += do_h^T u_h
         GemmP p = zg();
-        p.A = ws + W.dob; p.lda = D; p.W = ws + W.u; p.ldw = NH * D; p.M = B; p.N = DH; p.K = D;
+        p.A = ws + W.dob; p.lda = D; p.W = ws + W.u; p.ldw = nh * D; p.M = B; p.N = DH; p.K = D;
         p.out0 = dparams + L.ca[0] + L.wv; p.ldo0 = D;
-        p.nb = ndir * NH; p.nbi = NH; p.sAo = (long)B * D; p.sAi = DH; p.sWo = (long)B * NH * D; p.sWi = D; p.sOo = L.ca_stride; p.sOi = (long)DH * D;
+        p.nb = ndir * nh; p.nbi = nh; p.sAo = (long)B * D; p.sAi = DH; p.sWo = (long)B * nh * D; p.sWi = D; p.sOo = L.ca_stride; p.sOi = (long)DH * D;
         FUS_TRY(gemm_tn(MFVIT_F32, p, st));
     }
-    {   // du_h = do_h Wv_h   (W operand = WvT[:, h*128 ..])
+    {   // du_h = do_h Wv_h   (W operand = WvT[:, h*DH ..])
         GemmP p = zg();
         p.A = ws + W.dob; p.lda = D; p.W = wT + 2L * D * D; p.ldw = D; p.M = B; p.N = D; p.K = DH;
-        p.out0 = ws + W.du; p.ldo0 = NH * D;
-        p.nb = ndir * NH; p.nbi = NH; p.sAo = (long)B * D; p.sAi = DH; p.sWo = 4L * D * D; p.sWi = DH; p.sOo = (long)B * NH * D; p.sOi = D;
+        p.out0 = ws + W.du; p.ldo0 = nh * D;
+        p.nb = ndir * nh; p.nbi = nh; p.sAo = (long)B * D; p.sAi = DH; p.sWo = 4L * D * D; p.sWi = DH; p.sOo = (long)B * nh * D; p.sOi = D;
         FUS_TRY(gemm_nt_tile(MFVIT_F32, EPI_NONE, p, st));
     }
     {
         const size_t lds = (size_t)(8 * T + XW_BWD * 5 * D) * 4;
-        static PerDeviceOnce attr;
-        if (attr.first()) { (void)hipFuncSetAttribute((const void*)x_stream_bwd_kernel<XW_BWD>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); }
-        ProfScope ps(PROF_XATTN_BWD, 0, 2.0 * B * T * D * 4 * 3, st);
-        MFVIT_LAUNCH(x_stream_bwd_kernel<XW_BWD>, dim3(B, ndir), dim3(XW_BWD * 64), lds, st, f_cxr, f_enh, params, L, scale, B, T, ws + W.kq, ws + W.a,
-                           ws + W.st, ws + W.du, ws + W.dkq, ws + W.dz0p, ws + W.pd, df_cxr, df_enh);
-        MFVIT_CHECK_LAUNCH();
+        static PerDeviceOnce attr1, attrc, attrz;
+        ProfScope ps(PROF_XATTN_BWD, 0, 2.0 * B * T * D * 4 * 3 * (nh == NH ? 1 : nh / NH + 1), st);
+        if (nh == NH) {
+            max_lds((x_stream_bwd_kernel<XW_BWD, D, false>), attr1);
+            MFVIT_LAUNCH((x_stream_bwd_kernel<XW_BWD, D, false>), dim3(B, ndir), dim3(XW_BWD * 64), lds, st, f_cxr, f_enh, params, L, scale, B, T,
+                               ws + W.kq, ws + W.a, ws + W.st, ws + W.du, ws + W.dkq, ws + W.dz0p, ws + W.pd, df_cxr, df_enh, nullptr);
+            MFVIT_CHECK_LAUNCH();
+        } else {   // heads in chunks of 3 (dkq, ds), then the token gradient over all heads
+            max_lds((x_stream_bwd_kernel<XW_BWD, D, true>), attrc);
+            MFVIT_LAUNCH((x_stream_bwd_kernel<XW_BWD, D, true>), dim3(B, ndir, nh / NH), dim3(XW_BWD * 64), lds, st, f_cxr, f_enh, params, L, scale,
+                               B, T, ws + W.kq, ws + W.a, ws + W.st, ws + W.du, ws + W.dkq, ws + W.dz0p, ws + W.pd, df_cxr, df_enh, ws + W.ds);
+            MFVIT_CHECK_LAUNCH();
+            const long big = 2L * nh * D + 2L * nh * T, redn = (long)XW_DZ * 2 * D;
+            const size_t ldz = (size_t)((big > redn ? big : redn) + 2L * T) * 4;
+            max_lds((x_stream_dz_kernel<XW_DZ, D>), attrz);
+            MFVIT_LAUNCH((x_stream_dz_kernel<XW_DZ, D>), dim3(B, ndir), dim3(XW_DZ * 64), ldz, st, f_cxr, f_enh, params, L, scale, B, T, nh,
+                               ws + W.kq, ws + W.a, ws + W.st, ws + W.du, ws + W.ds, ws + W.dz0p, ws + W.pd, df_cxr, df_enh);
+            MFVIT_CHECK_LAUNCH();
+        }
     }
     {   // dWk_h += qv_h^T dkq_h
         GemmP p = zg();
-        p.A = ws + W.qv; p.lda = D; p.W = ws + W.dkq; p.ldw = NH * D; p.M = B; p.N = DH; p.K = D;
+        p.A = ws + W.qv; p.lda = D; p.W = ws + W.dkq; p.ldw = nh * D; p.M = B; p.N = DH; p.K = D;
         p.out0 = dparams + L.ca[0] + L.wk; p.ldo0 = D;
-        p.nb = ndir * NH; p.nbi = NH; p.sAo = (long)B * D; p.sAi = DH; p.sWo = (long)B * NH * D; p.sWi = D; p.sOo = L.ca_stride; p.sOi = (long)DH * D;
+        p.nb = ndir * nh; p.nbi = nh; p.sAo = (long)B * D; p.sAi = DH; p.sWo = (long)B * nh * D; p.sWi = D; p.sOo = L.ca_stride; p.sOi = (long)DH * D;
         FUS_TRY(gemm_tn(MFVIT_F32, p, st));
     }
     {   // dqv_h = dkq_h Wk_h^T
         GemmP p = zg();
-        p.A = ws + W.dkq; p.lda = NH * D; p.W = params + L.ca[0] + L.wk; p.ldw = D; p.M = B; p.N = DH; p.K = D;
+        p.A = ws + W.dkq; p.lda = nh * D; p.W = params + L.ca[0] + L.wk; p.ldw = D; p.M = B; p.N = DH; p.K = D;
         p.out0 = ws + W.dqv; p.ldo0 = D;
-        p.nb = ndir * NH; p.nbi = NH; p.sAo = (long)B * NH * D; p.sAi = D; p.sWo = L.ca_stride; p.sWi = (long)DH * D; p.sOo = (long)B * D; p.sOi = DH;
+        p.nb = ndir * nh; p.nbi = nh; p.sAo = (long)B * nh * D; p.sAi = D; p.sWo = L.ca_stride; p.sWi = (long)DH * D; p.sOo = (long)B * D; p.sOi = DH;
         FUS_TRY(gemm_nt_tile(MFVIT_F32, EPI_NONE, p, st));
     }
     {   // dWq += dqv^T z0
@@ -664,11 +1043,192 @@ static int xattn_core_backward(int ndir, const FusLayout& L, const FusWs& W, con
         p.nb = ndir; p.nbi = 1; p.sAo = (long)B * D; p.sWo = 4L * D * D; p.sOo = (long)B * D;
         FUS_TRY(gemm_nt_tile(MFVIT_F32, EPI_NONE, p, st));
     }
-    MFVIT_LAUNCH(x_row0_bwd_kernel, dim3(B), dim3(64 * ndir), 0, st, f_cxr, f_enh, params, L, B, T, ws + W.st0, ws + W.dz0p, ws + W.dz0q,
+    MFVIT_LAUNCH(x_row0_bwd_kernel<D>, dim3(B), dim3(64 * ndir), 0, st, f_cxr, f_enh, params, L, B, T, ws + W.st0, ws + W.dz0p, ws + W.dz0q,
                        ws + W.dqp, ws + W.pd, df_cxr, df_enh);
     MFVIT_CHECK_LAUNCH();
     return MFVIT_OK;
 }
+
+// ------------------------------------------------------------------------------------------------ Fus_CrossViT, one exchange layer, cls pooling
+template <int D>
+static int fusion_forward(const mfvit_fusion_cfg* cfg, const float* params, const float* f_cxr, const float* f_enh, const float* hw_cxr,
+                          const float* hb_cxr, const float* hw_enh, const float* hb_enh, float* ws, float* fused, float* x_cxr, float* x_enh,
+                          hipStream_t st) {
+    const int B = cfg->batch, T = cfg->tokens, C = cfg->num_classes;
+    const FusLayout L = fus_layout(D, C);
+    const FusWs W = fus_ws(B, T, C, D, cfg->heads);
+    FUS_TRY(xattn_core_forward<D>(2, cfg->heads, L, W, params, f_cxr, f_enh, ws, B, T, cfg->eps_pre, st));
+    MFVIT_LAUNCH(x_finish_fwd_kernel<D>, dim3(B), dim3(128), 0, st, f_cxr, f_enh, params, L, cfg->eps_post, B, T, C, ws + W.outp,
+                       ws + W.fus, ws + W.stc, hw_cxr, hb_cxr, hw_enh, hb_enh, fused, x_cxr, x_enh);
+    MFVIT_CHECK_LAUNCH();
+    return MFVIT_OK;
+}
+
+template <int D>
+static int fusion_backward(const mfvit_fusion_cfg* cfg, const float* params, const float* f_cxr, const float* f_enh, const float* hw_cxr,
+                           const float* hw_enh, float* ws, const float* dfused, const float* dx_cxr, const float* dx_enh, float* dparams,
+                           float* df_cxr, float* df_enh, float* dhw_cxr, float* dhb_cxr, float* dhw_enh, float* dhb_enh, hipStream_t st) {
+    const int B = cfg->batch, T = cfg->tokens, C = cfg->num_classes;
+    const FusLayout L = fus_layout(D, C);
+    const FusWs W = fus_ws(B, T, C, D, cfg->heads);
+    MFVIT_LAUNCH(x_finish_bwd_kernel<D>, dim3(B), dim3(128), 0, st, f_cxr, f_enh, params, L, B, T, C, ws + W.outp, ws + W.fus,
+                       ws + W.stc, hw_cxr, hw_enh, dfused, dx_cxr, dx_enh, dparams, dhw_cxr, dhb_cxr, dhw_enh, dhb_enh, ws + W.dout,
+                       ws + W.dqp, ws + W.pa, ws + W.pb, ws + W.pc);
+    MFVIT_CHECK_LAUNCH();
+    FUS_TRY(xattn_core_backward<D>(2, cfg->heads, L, W, params, f_cxr, f_enh, ws, B, T, dparams, df_cxr, df_enh, st));
+    // the batch sums of the small gradients, every one in a fixed order (one launch)
+    ColpartBatch batch;
+    ColpartBatch* prev = colpart_batch_begin(&batch);
+    int rc = MFVIT_OK;
+    for (int dir = 0; dir < 2 && rc == MFVIT_OK; ++dir) {
+        float* dhw = dparams + L.head[dir];
+        float* dg = dparams + L.post[dir];
+        rc = colpart_reduce(ws + W.pa + (long)dir * B * 3 * D, B, D, 3, dg, dg + D, dparams + L.ca[dir] + L.bp, st);
+        if (rc == MFVIT_OK) rc = colpart_reduce(ws + W.pb + (long)dir * B * 2 * C * D, B, C * D, 2, dhw, dir == 0 ? dhw_cxr : dhw_enh, nullptr, st);
+        if (rc == MFVIT_OK) rc = colpart_reduce(ws + W.pc + (long)dir * B * 2 * C, B, C, 2, dhw + (long)C * D, dir == 0 ? dhb_cxr : dhb_enh, nullptr, st);
+        if (rc == MFVIT_OK) rc = fus_prenorm_job(D, dir, L, W, ws, B, dparams, st);
+    }
+    if (rc == MFVIT_OK) rc = colpart_batch_flush(st);
+    colpart_batch_begin(prev);
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------------------ Fus_CrossViT, full-row path
+template <int D>
+static int fusion_full_forward(const mfvit_fusion_cfg* cfg, int depth, int pool_mean, const float* params, const float* f_cxr,
+                               const float* f_enh, const float* hw_cxr, const float* hb_cxr, const float* hw_enh, const float* hb_enh, float* ws,
+                               float* fused, float* x_cxr, float* x_enh, hipStream_t st) {
+    const int B = cfg->batch, T = cfg->tokens, C = cfg->num_classes, nh = cfg->heads;
+    const FusWs W = fus_ws(B, T, C, D, nh);
+    const FusExWs E = fus_ex_ws(B, T, C, D, nh, depth);
+    const long btd = (long)B * T * D;
+    for (int l = 0; l < depth; ++l) {
+        const FusLayout L = fus_layer_layout(D, C, depth, l);
+        float* wl = ws + l * E.slab;
+        const float* xc = l == 0 ? f_cxr : ws + (l - 1) * E.slab + E.Y;
+        const float* xe = l == 0 ? f_enh : xc + btd;
+        FUS_TRY(xattn_core_forward<D>(2, nh, L, W, params, xc, xe, wl, B, T, cfg->eps_pre, st));
+        const int pool = l < depth - 1 ? 0 : (pool_mean ? 2 : 1);
+        MFVIT_LAUNCH((x_rows_fwd_kernel<XW_ROWS, D>), dim3(B, 2), dim3(XW_ROWS * 64), 0, st, xc, xe, f_cxr, f_enh, params, L, cfg->eps_post, B, T,
+                           wl + W.outp, wl + E.Y, wl + E.yst, pool, ws + E.fusv);
+        MFVIT_CHECK_LAUNCH();
+    }
+    MFVIT_LAUNCH(x_head_fwd_kernel<D>, dim3(B), dim3(128), 0, st, f_cxr, f_enh, params, fus_layer_layout(D, C, depth, depth - 1), B, T, C,
+                       ws + E.fusv, hw_cxr, hb_cxr, hw_enh, hb_enh, fused, x_cxr, x_enh);
+    MFVIT_CHECK_LAUNCH();
+    return MFVIT_OK;
+}
+
+template <int D>
+static int fusion_full_backward(const mfvit_fusion_cfg* cfg, int depth, int pool_mean, const float* params, const float* f_cxr,
+                                const float* f_enh, const float* hw_cxr, const float* hw_enh, float* ws, const float* dfused,
+                                const float* dx_cxr, const float* dx_enh, float* dparams, float* df_cxr, float* df_enh, float* dhw_cxr,
+                                float* dhb_cxr, float* dhw_enh, float* dhb_enh, hipStream_t st) {
+    const int B = cfg->batch, T = cfg->tokens, C = cfg->num_classes, nh = cfg->heads;
+    const FusWs W = fus_ws(B, T, C, D, nh);
+    const FusExWs E = fus_ex_ws(B, T, C, D, nh, depth);
+    const long btd = (long)B * T * D;
+    const FusLayout Lt = fus_layer_layout(D, C, depth, depth - 1);
+    float* wt = ws + (depth - 1) * E.slab;
+    MFVIT_LAUNCH(x_head_bwd_kernel<D>, dim3(B), dim3(128), 0, st, f_cxr, f_enh, params, Lt, B, T, C, pool_mean, ws + E.fusv, hw_cxr, hw_enh,
+                       dfused, dx_cxr, dx_enh, ws + E.ev, ws + E.bb, wt + W.pb, wt + W.pc);
+    MFVIT_CHECK_LAUNCH();
+    ColpartBatch batch;
+    ColpartBatch* prev = colpart_batch_begin(&batch);
+    int rc = MFVIT_OK;
+    for (int l = depth - 1; l >= 0 && rc == MFVIT_OK; --l) {
+        const FusLayout L = fus_layer_layout(D, C, depth, l);
+        float* wl = ws + l * E.slab;
+        const float* xc = l == 0 ? f_cxr : ws + (l - 1) * E.slab + E.Y;
+        const float* xe = l == 0 ? f_enh : xc + btd;
+        const bool top = l == depth - 1;
+        const float* dY = top ? nullptr : ws + E.dx + ((l + 1) & 1) * 2 * btd;        // the gradient of this layer's output rows
+        float* dxc = l > 0 ? ws + E.dx + (l & 1) * 2 * btd : df_cxr;                  // ... and of its input rows
+        float* dxe = l > 0 ? dxc + btd : df_enh;
+        MFVIT_LAUNCH(x_post0_bwd_kernel<D>, dim3(B), dim3(128), 0, st, xc, xe, params, L, B, T, wl + W.outp, wl + E.yst, dY, ws + E.ev, ws + E.bb,
+                           l == 0 ? 1 : 0, wl + W.dout, wl + W.dqp, wl + E.pr, wl + E.pbp);
+        MFVIT_CHECK_LAUNCH();
+        rc = xattn_core_backward<D>(2, nh, L, W, params, xc, xe, wl, B, T, dparams, dxc, dxe, st);
+        if (rc != MFVIT_OK) break;
+        const int mode = top ? (pool_mean ? 1 : 2) : 0;
+        MFVIT_LAUNCH((x_rows_bwd_kernel<XW_ROWS, D>), dim3(B, 2), dim3(XW_ROWS * 64), 0, st, xc, xe, params, L, B, T, wl + E.yst, dY, ws + E.ev, mode,
+                           l == 0 && pool_mean ? 1 : 0, dxc, dxe, wl + E.pr);
+        MFVIT_CHECK_LAUNCH();
+        for (int dir = 0; dir < 2 && rc == MFVIT_OK; ++dir) {
+            rc = colpart_reduce(wl + E.pr + (long)dir * 2 * B * 2 * D, 2 * B, D, 2, dparams + L.post[dir], dparams + L.post[dir] + D, nullptr, st);
+            if (rc == MFVIT_OK) rc = colpart_reduce(wl + E.pbp + (long)dir * B * D, B, D, 1, dparams + L.ca[dir] + L.bp, nullptr, nullptr, st);
+            if (rc == MFVIT_OK) rc = fus_prenorm_job(D, dir, L, W, wl, B, dparams, st);
+        }
+    }
+    for (int dir = 0; dir < 2 && rc == MFVIT_OK; ++dir) {
+        float* dhw = dparams + Lt.head[dir];
+        rc = colpart_reduce(wt + W.pb + (long)dir * B * 2 * C * D, B, C * D, 2, dhw, dir == 0 ? dhw_cxr : dhw_enh, nullptr, st);
+        if (rc == MFVIT_OK) rc = colpart_reduce(wt + W.pc + (long)dir * B * 2 * C, B, C, 2, dhw + (long)C * D, dir == 0 ? dhb_cxr : dhb_enh, nullptr, st);
+    }
+    if (rc == MFVIT_OK) rc = colpart_batch_flush(st);
+    colpart_batch_begin(prev);
+    return rc;
+}
+
+extern "C" {
+
+size_t mfvit_fusion_param_count(const mfvit_fusion_cfg* cfg) { return fus_ok(cfg) ? (size_t)fus_layout(cfg->dim, cfg->num_classes).total : 0; }
+size_t mfvit_fusion_workspace_bytes(const mfvit_fusion_cfg* cfg) {
+    return fus_ok(cfg) ? (size_t)fus_ws(cfg->batch, cfg->tokens, cfg->num_classes, cfg->dim, cfg->heads).total * 4 : 0;
+}
+
+int mfvit_fusion_forward(const mfvit_fusion_cfg* cfg, const float* params, const float* f_cxr, const float* f_enh, const float* hw_cxr,
+                         const float* hb_cxr, const float* hw_enh, const float* hb_enh, void* workspace, float* fused, float* x_cxr,
+                         float* x_enh, mfvit_stream_t stream) {
+    if (!fus_ok(cfg) || !params || !f_cxr || !f_enh || !workspace || !fused) return MFVIT_EINVAL;
+    return FUS_BY_DIM(cfg->dim, fusion_forward)(cfg, params, f_cxr, f_enh, hw_cxr, hb_cxr, hw_enh, hb_enh, (float*)workspace, fused, x_cxr,
+                                                x_enh, (hipStream_t)stream);
+}
+
+int mfvit_fusion_backward(const mfvit_fusion_cfg* cfg, const float* params, const float* f_cxr, const float* f_enh, const float* hw_cxr,
+                          const float* hw_enh, void* workspace, const float* dfused, const float* dx_cxr, const float* dx_enh,
+                          float* dparams, float* df_cxr, float* df_enh, float* dhw_cxr, float* dhb_cxr, float* dhw_enh, float* dhb_enh,
+                          mfvit_stream_t stream) {
+    if (!fus_ok(cfg) || !params || !f_cxr || !f_enh || !workspace || !dparams) return MFVIT_EINVAL;
+    if ((df_cxr == nullptr) != (df_enh == nullptr)) return MFVIT_EINVAL;
+    return FUS_BY_DIM(cfg->dim, fusion_backward)(cfg, params, f_cxr, f_enh, hw_cxr, hw_enh, (float*)workspace, dfused, dx_cxr, dx_enh, dparams,
+                                                 df_cxr, df_enh, dhw_cxr, dhb_cxr, dhw_enh, dhb_enh, (hipStream_t)stream);
+}
+
+size_t mfvit_fusion_ex_param_count(const mfvit_fusion_cfg* cfg, int cross_attn_depth, int pool_mean) {
+    return fus_ex_ok(cfg, cross_attn_depth, pool_mean) ? (size_t)fus_layer_layout(cfg->dim, cfg->num_classes, cross_attn_depth, 0).total : 0;
+}
+size_t mfvit_fusion_ex_workspace_bytes(const mfvit_fusion_cfg* cfg, int cross_attn_depth, int pool_mean) {
+    if (!fus_ex_ok(cfg, cross_attn_depth, pool_mean)) return 0;
+    if (!fus_full(cross_attn_depth, pool_mean)) return mfvit_fusion_workspace_bytes(cfg);
+    return (size_t)fus_ex_ws(cfg->batch, cfg->tokens, cfg->num_classes, cfg->dim, cfg->heads, cross_attn_depth).total * 4;
+}
+
+int mfvit_fusion_ex_forward(const mfvit_fusion_cfg* cfg, int cross_attn_depth, int pool_mean, const float* params, const float* f_cxr,
+                            const float* f_enh, const float* hw_cxr, const float* hb_cxr, const float* hw_enh, const float* hb_enh,
+                            void* workspace, float* fused, float* x_cxr, float* x_enh, mfvit_stream_t stream) {
+    if (!fus_ex_ok(cfg, cross_attn_depth, pool_mean) || !params || !f_cxr || !f_enh || !workspace || !fused) return MFVIT_EINVAL;
+    if (!fus_full(cross_attn_depth, pool_mean))
+        return mfvit_fusion_forward(cfg, params, f_cxr, f_enh, hw_cxr, hb_cxr, hw_enh, hb_enh, workspace, fused, x_cxr, x_enh, stream);
+    return FUS_BY_DIM(cfg->dim, fusion_full_forward)(cfg, cross_attn_depth, pool_mean, params, f_cxr, f_enh, hw_cxr, hb_cxr, hw_enh, hb_enh,
+                                                     (float*)workspace, fused, x_cxr, x_enh, (hipStream_t)stream);
+}
+
+int mfvit_fusion_ex_backward(const mfvit_fusion_cfg* cfg, int cross_attn_depth, int pool_mean, const float* params, const float* f_cxr,
+                             const float* f_enh, const float* hw_cxr, const float* hw_enh, void* workspace, const float* dfused,
+                             const float* dx_cxr, const float* dx_enh, float* dparams, float* df_cxr, float* df_enh, float* dhw_cxr,
+                             float* dhb_cxr, float* dhw_enh, float* dhb_enh, mfvit_stream_t stream) {
+    if (!fus_ex_ok(cfg, cross_attn_depth, pool_mean) || !params || !f_cxr || !f_enh || !workspace || !dparams) return MFVIT_EINVAL;
+    if ((df_cxr == nullptr) != (df_enh == nullptr)) return MFVIT_EINVAL;
+    if (!fus_full(cross_attn_depth, pool_mean))
+        return mfvit_fusion_backward(cfg, params, f_cxr, f_enh, hw_cxr, hw_enh, workspace, dfused, dx_cxr, dx_enh, dparams, df_cxr, df_enh,
+                                     dhw_cxr, dhb_cxr, dhw_enh, dhb_enh, stream);
+    return FUS_BY_DIM(cfg->dim, fusion_full_backward)(cfg, cross_attn_depth, pool_mean, params, f_cxr, f_enh, hw_cxr, hw_enh, (float*)workspace,
+                                                      dfused, dx_cxr, dx_enh, dparams, df_cxr, df_enh, dhw_cxr, dhb_cxr, dhw_enh, dhb_enh,
+                                                      (hipStream_t)stream);
+}
+
+}  // extern "C"
 
 // ------------------------------------------------------------------------------------------------ stand-alone PreNorm(CrossAttention)
 __global__ void x_copy_out_kernel(const float* __restrict__ src, float* __restrict__ dst, long n) {
@@ -676,47 +1236,54 @@ __global__ void x_copy_out_kernel(const float* __restrict__ src, float* __restri
     if (i < n) dst[i] = src[i];
 }
 
-extern "C" {
-
 // layout of ONE cross-attention block as the parameter arena: norm.{w,b}, wq, wk, wv, proj.{w,b}; bare: the block starts at wq
 // (L.ca[0] = -2 D puts wq at offset 0; the norm offsets are never dereferenced under no_norm)
 static FusLayout one_block_layout(const mfvit_fusion_cfg* cfg, bool bare) {
-    FusLayout L = fus_layout(cfg->num_classes);
-    L.ca[0] = bare ? -2L * D : 0;
+    FusLayout L = fus_layout(cfg->dim, cfg->num_classes);
+    L.ca[0] = bare ? -2L * cfg->dim : 0;
     L.no_norm = bare ? 1 : 0;
     return L;
 }
-static int xattn_one_forward(const mfvit_fusion_cfg* cfg, bool bare, const float* params, const float* x_own, const float* x_oth,
-                             void* workspace, float* out, mfvit_stream_t stream) {
-    if (!fus_ok(cfg) || !params || !x_own || !x_oth || !workspace || !out) return MFVIT_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
+template <int D>
+static int xattn_one_forward_t(const mfvit_fusion_cfg* cfg, bool bare, const float* params, const float* x_own, const float* x_oth,
+                               float* ws, float* out, hipStream_t st) {
     const int B = cfg->batch, T = cfg->tokens;
     const FusLayout L = one_block_layout(cfg, bare);
-    const FusWs W = fus_ws(B, T, cfg->num_classes);
-    float* ws = (float*)workspace;
-    FUS_TRY(xattn_core_forward(1, L, W, params, x_own, x_oth, ws, B, T, cfg->eps_pre, st));
+    const FusWs W = fus_ws(B, T, cfg->num_classes, D, cfg->heads);
+    FUS_TRY(xattn_core_forward<D>(1, cfg->heads, L, W, params, x_own, x_oth, ws, B, T, cfg->eps_pre, st));
     MFVIT_LAUNCH(x_copy_out_kernel, dim3((unsigned)(((long)B * D + 255) / 256)), dim3(256), 0, st, ws + W.outp, out, (long)B * D);
     MFVIT_CHECK_LAUNCH();
     return MFVIT_OK;
 }
+static int xattn_one_forward(const mfvit_fusion_cfg* cfg, bool bare, const float* params, const float* x_own, const float* x_oth,
+                             void* workspace, float* out, mfvit_stream_t stream) {
+    if (!fus_ok(cfg) || !params || !x_own || !x_oth || !workspace || !out) return MFVIT_EINVAL;
+    return FUS_BY_DIM(cfg->dim, xattn_one_forward_t)(cfg, bare, params, x_own, x_oth, (float*)workspace, out, (hipStream_t)stream);
+}
 
-static int xattn_one_backward(const mfvit_fusion_cfg* cfg, bool bare, const float* params, const float* x_own, const float* x_oth,
-                              void* workspace, const float* dout, float* dparams, float* dx_own, float* dx_oth, mfvit_stream_t stream) {
-    if (!fus_ok(cfg) || !params || !x_own || !x_oth || !workspace || !dout || !dparams) return MFVIT_EINVAL;
-    if ((dx_own == nullptr) != (dx_oth == nullptr)) return MFVIT_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
+template <int D>
+static int xattn_one_backward_t(const mfvit_fusion_cfg* cfg, bool bare, const float* params, const float* x_own, const float* x_oth,
+                                float* ws, const float* dout, float* dparams, float* dx_own, float* dx_oth, hipStream_t st) {
     const int B = cfg->batch, T = cfg->tokens;
     const FusLayout L = one_block_layout(cfg, bare);
-    const FusWs W = fus_ws(B, T, cfg->num_classes);
-    float* ws = (float*)workspace;
+    const FusWs W = fus_ws(B, T, cfg->num_classes, D, cfg->heads);
     MFVIT_LAUNCH(x_copy_out_kernel, dim3((unsigned)(((long)B * D + 255) / 256)), dim3(256), 0, st, dout, ws + W.dout, (long)B * D);
     MFVIT_CHECK_LAUNCH();
     if (hipMemsetAsync(ws + W.dqp, 0, sizeof(float) * B * D, st) != hipSuccess) return MFVIT_ELAUNCH;
     // d proj.bias = column sums of dout (x_finish_bwd does this in the fused model)
     FUS_TRY(colsum_rows(dout, D, dparams + L.ca[0] + L.bp, B, 1, 0, D, st));
-    FUS_TRY(xattn_core_backward(1, L, W, params, x_own, x_oth, ws, B, T, dparams, dx_own, dx_oth, st));
-    return fus_prenorm_job(0, L, W, ws, B, dparams, st);
+    FUS_TRY(xattn_core_backward<D>(1, cfg->heads, L, W, params, x_own, x_oth, ws, B, T, dparams, dx_own, dx_oth, st));
+    return fus_prenorm_job(D, 0, L, W, ws, B, dparams, st);
 }
+static int xattn_one_backward(const mfvit_fusion_cfg* cfg, bool bare, const float* params, const float* x_own, const float* x_oth,
+                              void* workspace, const float* dout, float* dparams, float* dx_own, float* dx_oth, mfvit_stream_t stream) {
+    if (!fus_ok(cfg) || !params || !x_own || !x_oth || !workspace || !dout || !dparams) return MFVIT_EINVAL;
+    if ((dx_own == nullptr) != (dx_oth == nullptr)) return MFVIT_EINVAL;
+    return FUS_BY_DIM(cfg->dim, xattn_one_backward_t)(cfg, bare, params, x_own, x_oth, (float*)workspace, dout, dparams, dx_own, dx_oth,
+                                                      (hipStream_t)stream);
+}
+
+extern "C" {
 
 int mfvit_prenorm_xattn_forward(const mfvit_fusion_cfg* cfg, const float* params, const float* x_own, const float* x_oth,
                                 void* workspace, float* out, mfvit_stream_t stream) {

@@ -74,6 +74,10 @@ SIGNATURES = {
     "mfvit_fusion_param_count": (c_size_t, [POINTER(FusionCfg)]),
     "mfvit_fusion_workspace_bytes": (c_size_t, [POINTER(FusionCfg)]),
     "mfvit_fusion_forward": (I, [POINTER(FusionCfg), P, P, P, P, P, P, P, P, P, P, P, P]),
+    "mfvit_fusion_ex_param_count": (c_size_t, [POINTER(FusionCfg), I, I]),
+    "mfvit_fusion_ex_workspace_bytes": (c_size_t, [POINTER(FusionCfg), I, I]),
+    "mfvit_fusion_ex_forward": (I, [POINTER(FusionCfg), I, I, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "mfvit_fusion_ex_backward": (I, [POINTER(FusionCfg), I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "mfvit_bn_stats": (I, [I, P, I, I, P, P, P]),
     "mfvit_bn_combine": (I, [P, P, P, I, I, F, F, P, P, P, P, P]),
     "mfvit_bn_apply": (I, [I, P, P, P, P, P, I, P, I, I, P]),

@@ -1,39 +1,82 @@
-"""Two-stream fusion engine: one autograd node over mfvit_fusion_forward / mfvit_fusion_backward (f32)."""
+"""Two-stream fusion engine: one autograd node over mfvit_fusion_ex_forward / mfvit_fusion_ex_backward (f32).
+
+The node's parameters are the LIVE tail of the Fus_CrossViT arena: the last multi-scale encoder's cross_attn_depth layers and the two
+heads (FUS:137-139: only the last encoder's output is used).  The earlier encoders never enter the graph, so their .grad stays None."""
 import torch
 
 from . import _lib
 from ._lib import FusionCfg, check, lib, ptr, stream
 
+DIMS = (384, 768)
+HEADS = (3, 6, 12)
+MAX_CROSS_ATTN_DEPTH = 16   # csrc/fusion.hip MAX_XDEPTH
 
-def fusion_cfg(B, T, C):
+
+def fusion_cfg(B, T, C, dim=384, heads=3):
     c = FusionCfg()
-    c.batch, c.tokens, c.dim, c.heads, c.num_classes = B, T, 384, 3, C
+    c.batch, c.tokens, c.dim, c.heads, c.num_classes = B, T, dim, heads, C
     c.eps_pre, c.eps_post = 1e-5, 1e-6
     return c
 
 
+def check_fusion_shape(dim, heads):
+    """The widths / head counts the exchange kernels are instantiated for."""
+    if dim not in DIMS:
+        raise NotImplementedError(f"the fused exchange is built for dim in {DIMS} (vit_small / vit_base), got {dim}")
+    if heads not in HEADS:
+        raise NotImplementedError(f"the fused exchange is built for heads in {HEADS}, got {heads}")
+
+
+class FusionSpec:
+    """What one FusionFn call needs besides tensors: the arena, where its live tail starts, and the exchange shape."""
+
+    def __init__(self, arena, first_live, dim, heads, depth, pool_mean):
+        self.arena, self.first_live = arena, first_live
+        self.dim, self.heads, self.depth, self.pool_mean = dim, heads, depth, int(pool_mean)
+
+    def live(self):
+        return self.arena.params[self.first_live:]
+
+    def tail(self, flat):
+        off = self.arena.offsets[self.arena.named[self.first_live][0]][0]
+        return flat[off:], off
+
+    def grad_views(self, gtail, off):
+        out = []
+        for name, p in self.arena.named[self.first_live:]:
+            if p.requires_grad:
+                o, n = self.arena.offsets[name]
+                out.append(gtail[o - off:o - off + n].view(p.shape))
+            else:
+                out.append(None)
+        return out
+
+
 class FusionFn(torch.autograd.Function):
-    """(f_cxr, f_enh, backbone heads, 22 fusion params) -> (fused, x_cxr, x_enh)   [FUS:126-157]"""
+    """(f_cxr, f_enh, backbone heads, live fusion params) -> (fused, x_cxr, x_enh)   [FUS:126-157]"""
 
     @staticmethod
-    def forward(ctx, arena, f_cxr, f_enh, hw_c, hb_c, hw_e, hb_e, *params):
+    def forward(ctx, spec, f_cxr, f_enh, hw_c, hb_c, hw_e, hb_e, *params):
         _lib.require_cuda(f_cxr, f_enh)
         B, T, D = f_cxr.shape
-        flat = arena.ensure()
-        C = (flat.numel() - 8 * D * D - 10 * D) // (2 * (D + 1))
-        cfg = fusion_cfg(B, T, C)
-        if lib().mfvit_fusion_param_count(cfg) != flat.numel():
+        if D != spec.dim:
+            raise _lib.MfvitError(f"fusion built for dim {spec.dim}, features have {D}")
+        flat, off = spec.tail(spec.arena.ensure())
+        L = spec.depth
+        C = (flat.numel() - L * (8 * D * D + 10 * D)) // (2 * (D + 1))
+        cfg = fusion_cfg(B, T, C, D, spec.heads)
+        if lib().mfvit_fusion_ex_param_count(cfg, L, spec.pool_mean) != flat.numel():
             raise _lib.MfvitError("fusion parameter arena does not match the C ABI layout")
         f_cxr = f_cxr.contiguous().float()
         f_enh = f_enh.contiguous().float()
-        ws = torch.empty(lib().mfvit_fusion_workspace_bytes(cfg), device=f_cxr.device, dtype=torch.uint8)
+        ws = torch.empty(lib().mfvit_fusion_ex_workspace_bytes(cfg, L, spec.pool_mean), device=f_cxr.device, dtype=torch.uint8)
         fused = torch.empty(B, C, device=f_cxr.device, dtype=torch.float32)
         have_heads = hw_c is not None and hw_e is not None
         x_c = torch.empty_like(fused) if have_heads else None
         x_e = torch.empty_like(fused) if have_heads else None
-        check(lib().mfvit_fusion_forward(cfg, ptr(flat), ptr(f_cxr), ptr(f_enh), ptr(hw_c), ptr(hb_c), ptr(hw_e), ptr(hb_e), ptr(ws),
-                                         ptr(fused), ptr(x_c), ptr(x_e), stream()), "mfvit_fusion_forward")
-        ctx.arena, ctx.cfg, ctx.ws = arena, cfg, ws
+        check(lib().mfvit_fusion_ex_forward(cfg, L, spec.pool_mean, ptr(flat), ptr(f_cxr), ptr(f_enh), ptr(hw_c), ptr(hb_c), ptr(hw_e),
+                                            ptr(hb_e), ptr(ws), ptr(fused), ptr(x_c), ptr(x_e), stream()), "mfvit_fusion_ex_forward")
+        ctx.spec, ctx.cfg, ctx.ws = spec, cfg, ws
         ctx.have_heads = have_heads
         ctx.save_for_backward(f_cxr, f_enh, hw_c, hw_e)
         if not have_heads:
@@ -44,11 +87,11 @@ class FusionFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dfused, dx_c, dx_e):
         f_cxr, f_enh, hw_c, hw_e = ctx.saved_tensors
-        arena, cfg = ctx.arena, ctx.cfg
-        flat = arena.ensure()
+        spec, cfg = ctx.spec, ctx.cfg
+        flat, off = spec.tail(spec.arena.ensure())
         need_df = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
-        # ONE zeroed buffer for every accumulated gradient of this node (the fusion arena + the four head tensors): one fill launch per step
-        # instead of five; every view starts 16-byte aligned
+        # ONE zeroed buffer for every accumulated gradient of this node (the live fusion parameters + the four head tensors): one fill launch
+        # per step instead of five; every view starts 16-byte aligned
         sizes = [flat.numel()]
         want = [False] * 4
         if ctx.have_heads:
@@ -75,9 +118,9 @@ class FusionFn(torch.autograd.Function):
         dfused = dfused.contiguous().float()
         dx_c = dx_c.contiguous().float() if ctx.have_heads else None
         dx_e = dx_e.contiguous().float() if ctx.have_heads else None
-        check(lib().mfvit_fusion_backward(cfg, ptr(flat), ptr(f_cxr), ptr(f_enh), ptr(hw_c) if ctx.have_heads else None,
-                                          ptr(hw_e) if ctx.have_heads else None, ptr(ctx.ws), ptr(dfused), ptr(dx_c), ptr(dx_e),
-                                          ptr(gflat), ptr(df_c), ptr(df_e), ptr(dhw_c), ptr(dhb_c), ptr(dhw_e), ptr(dhb_e), stream()),
-              "mfvit_fusion_backward")
+        check(lib().mfvit_fusion_ex_backward(cfg, spec.depth, spec.pool_mean, ptr(flat), ptr(f_cxr), ptr(f_enh),
+                                             ptr(hw_c) if ctx.have_heads else None, ptr(hw_e) if ctx.have_heads else None, ptr(ctx.ws),
+                                             ptr(dfused), ptr(dx_c), ptr(dx_e), ptr(gflat), ptr(df_c), ptr(df_e), ptr(dhw_c), ptr(dhb_c),
+                                             ptr(dhw_e), ptr(dhb_e), stream()), "mfvit_fusion_ex_backward")
         ctx.ws = None
-        return (None, df_c, df_e, dhw_c, dhb_c, dhw_e, dhb_e) + tuple(arena.grad_views(gflat))
+        return (None, df_c, df_e, dhw_c, dhb_c, dhw_e, dhb_e) + tuple(spec.grad_views(gflat, off))

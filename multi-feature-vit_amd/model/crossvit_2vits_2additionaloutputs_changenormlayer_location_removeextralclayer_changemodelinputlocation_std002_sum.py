@@ -1,13 +1,18 @@
 """Drop-in for the reference's two-stream fusion model file
 (moco_pretraining/moco/model/crossvit_2vits_2additionaloutputs_changenormlayer_location_removeextralclayer_
 changemodelinputlocation_std002_sum.py): ``MultiScaleTransformerEncoder`` and ``Fus_CrossViT`` with the same constructor
-signatures, the same 22 state-dict keys and the same ``forward(vit_cxr, vit_enh, img_cxr, img_enh) -> (fused, x_cxr,
+signatures, the same state-dict keys (22 at the defaults) and the same ``forward(vit_cxr, vit_enh, img_cxr, img_enh) -> (fused, x_cxr,
 x_enh)`` contract, running on the gfx950 kernels of libmfvit_hip.so (csrc/fusion.hip + the ViT encoder).
 
 Reference behaviours kept: the backbones are NOT submodules (Q1: only ``features3D`` bound
 methods are stored, the modules arrive as forward arguments), so ``parameters()`` / ``state_dict()`` hold exactly the
-22 fusion tensors; each backbone's two per-step evaluations on the same image are computed once (Q2); only the cls
-row of the post-exchange LayerNorm / residual is consumed (Q3).
+fusion tensors; each backbone's two per-step evaluations on the same image are computed once (Q2); with one exchange layer and
+pool='cls' only the cls row of the post-exchange LayerNorm / residual is consumed (Q3).
+
+Constructor arguments as FUS:73-76: small_dim == large_dim in {384, 768} (vit_small / vit_base), heads in {3, 6, 12},
+cross_attn_depth >= 1 (chained layers, FUS:40-63), multi_scale_enc_depth >= 1 (every encoder reads the backbone features and only the
+last one's output is used, FUS:137-139: the earlier encoders are kept in the state dict but never run, so their .grad stays None),
+pool in {'cls', 'mean'} (FUS:144-145).
 """
 import os
 
@@ -16,7 +21,7 @@ import torch.nn as nn
 
 from mfvit import _lib
 from mfvit.arena import ParamArena
-from mfvit.fusion import FusionFn
+from mfvit.fusion import MAX_CROSS_ATTN_DEPTH, FusionFn, FusionSpec, check_fusion_shape
 from model.module import Attention, CrossAttention, FeedForward, PreNorm  # noqa: F401  (same import list as FUS:6)
 
 
@@ -26,10 +31,13 @@ class MultiScaleTransformerEncoder(nn.Module):
 
     def __init__(self, small_dim=384, large_dim=384, cross_attn_depth=1, cross_attn_heads=3, dropout=0.):
         super().__init__()
-        if small_dim != 384 or large_dim != 384 or cross_attn_heads != 3:
-            raise NotImplementedError("the fused exchange is built for dim 384 / 3 heads (FUS:73-75 defaults)")
-        if cross_attn_depth != 1:
-            raise NotImplementedError("cross_attn_depth != 1 is not used by the reference (FUS:74 default)")
+        if small_dim != large_dim:
+            # FUS:51,59 concatenate rows of both streams: the reference fails at forward; here at construction
+            raise ValueError(f"small_dim ({small_dim}) must equal large_dim ({large_dim}): the exchange concatenates rows of both streams")
+        check_fusion_shape(small_dim, cross_attn_heads)
+        if not 1 <= cross_attn_depth <= MAX_CROSS_ATTN_DEPTH:
+            raise NotImplementedError(f"cross_attn_depth must be in 1 .. {MAX_CROSS_ATTN_DEPTH}, got {cross_attn_depth}")
+        self.dim, self.heads, self.depth = small_dim, cross_attn_heads, cross_attn_depth
         self.cross_attn_layers = nn.ModuleList([])
         for _ in range(cross_attn_depth):
             self.cross_attn_layers.append(nn.ModuleList([
@@ -48,10 +56,10 @@ class Fus_CrossViT(nn.Module):
     def __init__(self, model_vit_cxr, model_vit_enh, num_classes=3, small_dim=384, large_dim=384, cross_attn_depth=1,
                  multi_scale_enc_depth=1, heads=3, dropout=0., pool='cls'):
         super().__init__()
-        if pool != 'cls':
-            raise NotImplementedError("pool='mean' is not used by the reference (FUS:76 default 'cls')")
-        if multi_scale_enc_depth != 1:
-            raise NotImplementedError("multi_scale_enc_depth != 1 is not used by the reference (FUS:74 default)")
+        if pool not in ('cls', 'mean'):
+            raise ValueError(f"pool must be 'cls' or 'mean', got {pool!r}")
+        if multi_scale_enc_depth < 1:
+            raise ValueError(f"multi_scale_enc_depth must be >= 1, got {multi_scale_enc_depth}")
         # bound methods, as in FUS:80,83: the backbones do not become submodules
         self.vit_features_cxr = model_vit_cxr.features3D
         self.vit_features_enh = model_vit_enh.features3D
@@ -65,6 +73,10 @@ class Fus_CrossViT(nn.Module):
         self.mlp_head_enh = nn.Sequential(nn.Linear(large_dim, num_classes))
         self.apply(self._init_weights)
         self._arena = ParamArena(list(self.named_parameters()))
+        # the live tail of the arena: the last encoder's layers + the two heads (named_parameters order)
+        first_live = next(i for i, (n, _) in enumerate(self._arena.named)
+                          if n.startswith(f"multi_scale_transformers.{multi_scale_enc_depth - 1}."))
+        self._spec = FusionSpec(self._arena, first_live, small_dim, heads, cross_attn_depth, pool == 'mean')
         self._two_streams = os.environ.get("MFVIT_TWO_STREAMS", "1") == "1"
         self._side = None
 
@@ -111,11 +123,11 @@ class Fus_CrossViT(nn.Module):
             self._side.wait_stream(main)
             with torch.cuda.stream(self._side):
                 enh_ftrs = self.vit_features_enh(img_enh)  #             FUS:133
-            cxr_ftrs = self.vit_features_cxr(img_cxr)      # (B, 197, 384) FUS:128
+            cxr_ftrs = self.vit_features_cxr(img_cxr)      # (B, 197, dim) FUS:128
             main.wait_stream(self._side)
             enh_ftrs.record_stream(main)
         else:
-            cxr_ftrs = self.vit_features_cxr(img_cxr)      # (B, 197, 384)   FUS:128
+            cxr_ftrs = self.vit_features_cxr(img_cxr)      # (B, 197, dim)   FUS:128
             enh_ftrs = self.vit_features_enh(img_enh)      #                 FUS:133
         hc, he = self._plain_head(vit_cxr), self._plain_head(vit_enh)
         fused_heads = hc is not None and he is not None and hc.out_features == self.num_classes == he.out_features \
@@ -123,6 +135,6 @@ class Fus_CrossViT(nn.Module):
             and getattr(vit_enh, "features3D", None) == self.vit_features_enh
         if fused_heads:
             # x_S = vit_S(img_S) = head_S(features3D(img_S)[:, 0])  (FUS:131,135; dropouts are 0): evaluated inside the fused node
-            return FusionFn.apply(self._arena, cxr_ftrs, enh_ftrs, hc.weight, hc.bias, he.weight, he.bias, *self._arena.params)
-        fused, _, _ = FusionFn.apply(self._arena, cxr_ftrs, enh_ftrs, None, None, None, None, *self._arena.params)
+            return FusionFn.apply(self._spec, cxr_ftrs, enh_ftrs, hc.weight, hc.bias, he.weight, he.bias, *self._spec.live())
+        fused, _, _ = FusionFn.apply(self._spec, cxr_ftrs, enh_ftrs, None, None, None, None, *self._spec.live())
         return fused, vit_cxr(img_cxr), vit_enh(img_enh)
