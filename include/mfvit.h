@@ -218,18 +218,26 @@ int mfvit_cross_entropy(const float* logits, const int64_t* target, float* loss_
                         mfvit_stream_t stream);
 
 /* GPU-side input pipeline (replaces the torchvision / Pillow chain of aihc_utils/image_transform.py:50-84 run by
- * the DataLoader workers, moco/loader.py:121-137): Resize((S,S), bilinear) -> horizontal flip -> rotation (nearest, fill 0) -> crop
- * -> ToTensor -> Normalize, fused, bit-exact against Pillow's fixed-point arithmetic.
+ * the DataLoader workers, moco/loader.py:121-137): Resize((S,S)) or Resize(S) (bilinear; shorter side S, aspect ratio kept) ->
+ * horizontal flip -> rotation (nearest, fill 0) -> crop -> ToTensor -> Normalize, fused, bit-exact against Pillow's fixed-point arithmetic.
  *   src    : decoded uint8 HWC (3 channels, channel order as decoded) images of n samples, packed back to back, on the device
  *   desc   : device int64 [n][20]: 0 byte offset in src of the top-left pixel of the source window, 1 in_h, 2 in_w, 3 / 4 offsets (in int32 units) of the x / y
  *            resample tables, 5 / 6 their ksize, 7 flip (0/1), 8 rotation mode (0 none, 1 affine, 2/3/4 = transpose 90/180/270),
  *            9..14 the 16.16 fixed-point affine terms a0 a1 a2 a3 a4 a5 of libImaging's affine_fixed, 15 (crop_i << 32) | crop_j,
- *            16 source row pitch in bytes (3 * image width; a RandomResizedCrop box is a window of the image), 17..19 zero
- *   tables : device int32: per axis S rows of [first source index, tap count, taps[ksize]] (22-bit fixed point)
+ *            16 source row pitch in bytes (3 * image width; a RandomResizedCrop box is a window of the image),
+ *            17 the sample's resized frame (Sh << 32) | Sw, or 0 for the square S x S frame, 18..19 zero.
+ *            Flip mirrors across Sw, the affine map tests Sw and Sh separately, the transposes 2 / 4 need Sh == Sw, and the crop window
+ *            must lie inside the frame.
+ *   tables : device int32: per axis one row per pixel of the frame along it (Sw rows for x, Sh rows for y) of
+ *            [first source index, tap count, taps[ksize]] (22-bit fixed point)
  *   out    : float32 [n][3][crop][crop]
  * mfvit.input_pipeline builds desc / tables from image sizes and the random draws exactly as Pillow's Python / C code does. */
 int mfvit_input_transform(const uint8_t* src, const int64_t* desc, const int32_t* tables, int n, int S, int crop, const float* mean3,
                           const float* std3, float* out, mfvit_stream_t stream);
+/* The same transform with an out_h x out_w output window: float32 [n][3][out_h][out_w] (Resize(S) without a crop keeps a
+ * non-square frame). */
+int mfvit_input_transform_rect(const uint8_t* src, const int64_t* desc, const int32_t* tables, int n, int S, int out_h, int out_w,
+                               const float* mean3, const float* std3, float* out, mfvit_stream_t stream);
 
 /* Epoch metrics on the device (replaces the per-batch .cpu() copies MAIN_CA:886-899 and the scikit-learn calls
  * MAIN_CA:901-911).  scores f32 [n][C] (row stride ld), labels int64 [n].  ACCUMULATES into caller-zeroed uint64 arrays:

@@ -1,12 +1,14 @@
 """GPU-side input pipeline: the finetune transform chain of aihc_utils/image_transform.py:50-84 as one HIP kernel.
 
-    tf = GpuTransform(img_type="CheXpert-v1.0-small", img_size=256, crop=224, rotate=10, training=True)
+    tf = GpuTransform(img_type="CheXpert-v1.0-small", img_size=256, crop=224, rotate=10, training=True, maintain_ratio=True)
     batch = tf(list_of_uint8_HWC_arrays)            # float32 [B, 3, 224, 224] on the GPU, what the DataLoader used to deliver
+    q, k = tf.two_views(list_of_uint8_HWC_arrays)   # MoCo: two random views of each image (moco/loader.py:121-137)
 
 The DataLoader workers then only decode (cv2.imread, moco/loader.py:121) and hand over uint8 HWC arrays of any size; Resize((S,S))
--> RandomHorizontalFlip -> RandomRotation(rotate) -> RandomCrop((crop,crop)) | CenterCrop -> ToTensor -> Normalize run fused on
-the device, bit-exact against Pillow's integer arithmetic (the backend torchvision's PIL transforms call).  This module is the
-host half: the per-axis fixed-point coefficient tables and the 16.16 affine terms, computed in double exactly as Pillow does.
+or Resize(S) (maintain_ratio: shorter side S) -> RandomHorizontalFlip -> RandomRotation(rotate) -> RandomCrop((crop,crop)) |
+CenterCrop -> ToTensor -> Normalize run fused on the device, bit-exact against Pillow's integer arithmetic (the backend
+torchvision's PIL transforms call).  This module is the host half: the per-axis fixed-point coefficient tables and the 16.16
+affine terms, computed in double exactly as Pillow does.
 """
 import ctypes
 import math
@@ -59,33 +61,44 @@ def axis_table(in_size, out_size):
     return ksize, tab
 
 
-def rotation_terms(angle, size):
-    """(mode, a0..a5): Image.rotate(angle, NEAREST, expand=False) on a size x size image.  mode 0 none, 1 affine (16.16 fixed-point
-    terms of libImaging's affine_fixed), 2/3/4 the transpose fast paths for 90/180/270 degrees."""
+def resized_size(h, w, size):
+    """(h, w) of transforms.Resize(size) with an int size (torchvision's _compute_resized_output_size): the shorter side becomes
+    `size`, the longer int(size * long / short)."""
+    short, long = (w, h) if w <= h else (h, w)
+    new_long = int(size * long / short)
+    return (new_long, size) if w <= h else (size, new_long)
+
+
+def rotation_terms(angle, w, h=None):
+    """(mode, a0..a5): Image.rotate(angle, NEAREST, expand=False) on a w x h image (h defaults to w).  mode 0 none, 1 affine
+    (16.16 fixed-point terms of libImaging's affine_fixed), 2/3/4 the transpose fast paths for 90/180/270 degrees - which Pillow
+    takes for 90 and 270 only on a square image."""
+    h = w if h is None else h
     angle = angle % 360.0
     if angle == 0:
         return 0, (0,) * 6
-    if angle in (90, 180, 270):
+    if angle == 180 or (angle in (90, 270) and w == h):
         return {90: 2, 180: 3, 270: 4}[int(angle)], (0,) * 6
-    c = size / 2
+    cx, cy = w / 2, h / 2
     a = -math.radians(angle)
     m = [round(math.cos(a), 15), round(math.sin(a), 15), 0.0, round(-math.sin(a), 15), round(math.cos(a), 15), 0.0]
-    m[2] = m[0] * (-c) + m[1] * (-c) + m[2] + c
-    m[5] = m[3] * (-c) + m[4] * (-c) + m[5] + c
+    m[2] = m[0] * (-cx) + m[1] * (-cy) + m[2] + cx
+    m[5] = m[3] * (-cx) + m[4] * (-cy) + m[5] + cy
     fix = lambda v: int(math.floor(v * 65536.0 + 0.5))
     return 1, (fix(m[0]), fix(m[1]), fix(m[2] + m[0] * 0.5 + m[1] * 0.5), fix(m[3]), fix(m[4]), fix(m[5] + m[3] * 0.5 + m[4] * 0.5))
 
 
 class GpuTransform:
-    """Mirror of `get_transform_type(args, training, img_type)` (image_transform.py:50-84) with args.maintain_ratio False:
-    args.img_size -> img_size, args.crop -> crop (0 = no crop), args.rotate -> rotate (degrees; RandomRotation draws from
-    [-rotate, rotate])."""
+    """Mirror of `get_transform_type(args, training, img_type)` (image_transform.py:50-84): args.img_size -> img_size, args.crop ->
+    crop (0 = no crop), args.rotate -> rotate (degrees; RandomRotation draws from [-rotate, rotate]), args.maintain_ratio ->
+    maintain_ratio (False: Resize((S, S)) squashes every image to a square; True: Resize(S), the shorter side becomes S and the
+    aspect ratio is kept)."""
 
     def __init__(self, img_type="CheXpert-v1.0-small", img_size=256, crop=224, rotate=10, training=True, device="cuda:0",
-                 mocov3=False, crop_min=0.08):
+                 mocov3=False, crop_min=0.08, maintain_ratio=False):
         """mocov3=True mirrors `get_transform_type_mocov3` (image_transform.py:86-124, MoCo pretraining): training =
-        RandomResizedCrop(img_size, scale=(crop_min, 1)) -> flip -> rotation (no further crop); evaluation = Resize((256, 256)) ->
-        CenterCrop(crop)."""
+        RandomResizedCrop(img_size, scale=(crop_min, 1)) -> flip -> rotation (no further crop; maintain_ratio has no effect);
+        evaluation = Resize((256, 256)) | Resize(256) (maintain_ratio) -> CenterCrop(crop)."""
         self.mocov3, self.crop_min = bool(mocov3), float(crop_min)
         if mocov3:
             if training:
@@ -96,9 +109,16 @@ class GpuTransform:
             raise _lib.MfvitError(f"unknown img_type {img_type!r} (image_transform.py:72-81 knows {sorted(NORMALIZE)})")
         self.mean, self.std = NORMALIZE[img_type]
         self.size, self.crop, self.rotate, self.training = int(img_size), int(crop) if crop else int(img_size), float(rotate), training
+        self.no_crop = not crop
+        # the resized frame follows the image's aspect ratio (RandomResizedCrop's output is square whatever the flag says)
+        self.maintain_ratio = bool(maintain_ratio) and not (self.mocov3 and training)
         if self.crop > self.size:
             raise _lib.MfvitError("crop larger than the resized image")
         self.device = torch.device(device)
+
+    def frame(self, h, w):
+        """(Sh, Sw): the resized frame of an h x w source (window)."""
+        return resized_size(h, w, self.size) if self.maintain_ratio else (self.size, self.size)
 
     @staticmethod
     def resized_crop_box(height, width, scale, generator=None, ratio=(3.0 / 4.0, 4.0 / 3.0)):
@@ -128,8 +148,12 @@ class GpuTransform:
     def sample_params(self, n, generator=None, sizes=None):
         """The random draws of one batch, in torchvision's order per image: [mocov3: the RandomResizedCrop box, needs `sizes` =
         [(h, w)] of the images], flip (torch.rand(1) < 0.5), angle (uniform in [-rotate, rotate]), crop offsets (randint);
-        evaluation: no flip, no rotation, CenterCrop offsets.  Tuples (flip, angle, crop_i, crop_j[, box])."""
+        evaluation: no flip, no rotation, CenterCrop offsets.  Tuples (flip, angle, crop_i, crop_j[, box]).  maintain_ratio
+        needs `sizes` too: the offsets range over each image's own frame, and RandomCrop draws nothing when the frame equals the
+        crop."""
         S, C = self.size, self.crop
+        if (self.maintain_ratio or (self.training and self.mocov3)) and (sizes is None or len(sizes) < n):
+            raise _lib.MfvitError("sample_params needs the (h, w) of every image (sizes)")
         out = []
         for s in range(n):
             if self.training and self.mocov3:
@@ -137,6 +161,9 @@ class GpuTransform:
                 flip = bool(torch.rand(1, generator=generator) < 0.5)
                 angle = float(torch.empty(1).uniform_(-self.rotate, self.rotate, generator=generator))
                 out.append((flip, angle, 0, 0, box))
+                continue
+            if self.maintain_ratio:
+                out.append(self._ratio_params(*self.frame(*sizes[s][:2]), generator))
                 continue
             if self.training:
                 flip = bool(torch.rand(1, generator=generator) < 0.5)
@@ -149,47 +176,108 @@ class GpuTransform:
             out.append((flip, angle, i, j))
         return out
 
-    def __call__(self, images, params=None, generator=None):
-        """images: list of uint8 HWC (3-channel) numpy arrays / CPU tensors of any size.  Returns float32 [n, 3, crop, crop] on
-        the device.  params: list of (flip, angle, crop_i, crop_j) per image (default: sample_params)."""
-        if not torch.cuda.is_available():
-            raise _lib.MfvitError("GpuTransform needs the GPU (no CPU fallback)")
-        n = len(images)
-        S, C = self.size, self.crop
+    def _ratio_params(self, fh, fw, generator):
+        """(flip, angle, i, j) of one fh x fw frame: RandomCrop.get_params / CenterCrop offsets (no crop: (0, 0), nothing drawn)."""
+        C = self.crop
+        if not self.no_crop and (fh < C or fw < C):
+            raise _lib.MfvitError(f"crop {C} larger than the resized frame {fh} x {fw}")
+        if not self.training:
+            if self.no_crop:
+                return False, 0.0, 0, 0
+            return False, 0.0, int(round((fh - C) / 2.0)), int(round((fw - C) / 2.0))
+        flip = bool(torch.rand(1, generator=generator) < 0.5)
+        angle = float(torch.empty(1).uniform_(-self.rotate, self.rotate, generator=generator))
+        if self.no_crop or (fh == C and fw == C):
+            return flip, angle, 0, 0
+        i = int(torch.randint(0, fh - C + 1, (1,), generator=generator))
+        j = int(torch.randint(0, fw - C + 1, (1,), generator=generator))
+        return flip, angle, i, j
+
+    def sample_view_pairs(self, n, generator=None, sizes=None):
+        """[(q_params, k_params)] of two_views: all of image 0's q draws, then its k draws, then image 1's, ... - the order of
+        Dataset_covid.__getitem__ inside one DataLoader worker."""
+        sizes = [None] * n if sizes is None else sizes
+        return [tuple(self.sample_params(1, generator, None if sz is None else [sz])[0] for _ in range(2)) for sz in sizes[:n]]
+
+    @staticmethod
+    def _arrays(images):
         arrs = []
         for im in images:
             a = im.numpy() if isinstance(im, torch.Tensor) else np.asarray(im)
             if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
                 raise _lib.MfvitError("images must be uint8 HWC with 3 channels (Image.fromarray(cv2.imread(..)), loader.py:121-125)")
             arrs.append(np.ascontiguousarray(a))
+        return arrs
+
+    def __call__(self, images, params=None, generator=None):
+        """images: list of uint8 HWC (3-channel) numpy arrays / CPU tensors of any size.  Returns float32 [n, 3, crop, crop] on
+        the device ([n, 3, Sh, Sw] for maintain_ratio without a crop, when every frame is Sh x Sw).  params: list of
+        (flip, angle, crop_i, crop_j) per image (default: sample_params)."""
+        arrs = self._arrays(images)
         if params is None:
-            params = self.sample_params(n, generator, [a.shape[:2] for a in arrs])
+            params = self.sample_params(len(arrs), generator, [a.shape[:2] for a in arrs])
+        if len(params) != len(arrs):
+            raise _lib.MfvitError(f"{len(params)} params for {len(arrs)} images")
+        return self._run(arrs, list(enumerate(params)))
+
+    def two_views(self, images, params=None, generator=None):
+        """MoCo's two views (Dataset_covid.__getitem__, moco/loader.py:121-137: the random transform applied twice to one decoded
+        image): (q, k), each float32 [n, 3, crop, crop].  Every source is uploaded once and all 2n samples run in one launch.
+        params: list of (q_params, k_params) pairs (default: sample_view_pairs)."""
+        arrs = self._arrays(images)
+        n = len(arrs)
+        if params is None:
+            params = self.sample_view_pairs(n, generator, [a.shape[:2] for a in arrs])
+        if len(params) != n or not all(isinstance(p, (tuple, list)) and len(p) == 2 and
+                                        all(isinstance(v, (tuple, list)) and len(v) in (4, 5) for v in p) for p in params):
+            raise _lib.MfvitError("two_views params: one (q_params, k_params) pair per image, each (flip, angle, crop_i, crop_j[, box])")
+        out = self._run(arrs, [(s, p[0]) for s, p in enumerate(params)] + [(s, p[1]) for s, p in enumerate(params)])
+        return out[:n], out[n:]
+
+    def _run(self, arrs, samples):
+        """One launch over `samples` = [(source index, params)]; each source is uploaded once."""
+        n = len(samples)
+        S, C = self.size, self.crop
+        offs, off = [], 0
+        for a in arrs:
+            offs.append(off)
+            off += a.size
         desc = np.zeros((n, 20), dtype=np.int64)
-        tabs, tab_off, tab_pos, off = [], {}, 0, 0
-        for s, (a, prm) in enumerate(zip(arrs, params)):
+        tabs, tab_off, tab_pos = [], {}, 0
+        out_hw = None
+        for s, (src_i, prm) in enumerate(samples):
+            a = arrs[src_i]
             flip, angle, ci, cj = prm[:4]
             H, W = a.shape[:2]
             bi, bj, h, w = prm[4] if len(prm) > 4 else (0, 0, H, W)      # source window (RandomResizedCrop box) or the whole image
             if not (0 <= bi and 0 <= bj and h > 0 and w > 0 and bi + h <= H and bj + w <= W):
                 raise _lib.MfvitError("source window outside the image")
-            for axis, size in ((0, w), (1, h)):
-                if size not in tab_off:
-                    ks, t = axis_table(size, S)
-                    tab_off[size] = (tab_pos, ks)
+            fh, fw = self.frame(h, w)
+            oh, ow = (fh, fw) if self.maintain_ratio and self.no_crop else (C, C)
+            if out_hw is None:
+                out_hw = (oh, ow)
+            elif out_hw != (oh, ow):
+                raise _lib.MfvitError(f"maintain_ratio without a crop: resized frames {out_hw} and {(oh, ow)} cannot form one batch")
+            for key in ((w, fw), (h, fh)):
+                if key not in tab_off:
+                    ks, t = axis_table(*key)
+                    tab_off[key] = (tab_pos, ks)
                     tabs.append(t.reshape(-1))
                     tab_pos += t.size
-            mode, terms = rotation_terms(angle, S)
-            if not (0 <= ci <= S - C and 0 <= cj <= S - C):
+            mode, terms = rotation_terms(angle, fw, fh)
+            if not (0 <= ci <= fh - oh and 0 <= cj <= fw - ow):
                 raise _lib.MfvitError("crop offset out of range")
-            desc[s] = [off + (bi * W + bj) * 3, h, w, tab_off[w][0], tab_off[h][0], tab_off[w][1], tab_off[h][1], int(flip), mode, *terms,
-                       (ci << 32) | cj, W * 3, 0, 0, 0]
-            off += a.size
+            tx, ty = tab_off[(w, fw)], tab_off[(h, fh)]
+            desc[s] = [offs[src_i] + (bi * W + bj) * 3, h, w, tx[0], ty[0], tx[1], ty[1], int(flip), mode, *terms, (ci << 32) | cj, W * 3,
+                       (fh << 32) | fw if self.maintain_ratio else 0, 0, 0]
+        if not torch.cuda.is_available():
+            raise _lib.MfvitError("GpuTransform needs the GPU (no CPU fallback)")
         src = torch.from_numpy(np.concatenate([a.reshape(-1) for a in arrs])).to(self.device, non_blocking=True)
         dsc = torch.from_numpy(desc).to(self.device, non_blocking=True)
         tab = torch.from_numpy(np.concatenate(tabs)).to(self.device, non_blocking=True)
-        out = torch.empty(n, 3, C, C, device=self.device, dtype=torch.float32)
+        out = torch.empty(n, 3, *out_hw, device=self.device, dtype=torch.float32)
         mean = (ctypes.c_float * 3)(*self.mean)
         std = (ctypes.c_float * 3)(*self.std)
-        check(lib().mfvit_input_transform(ptr(src), ptr(dsc), ptr(tab), n, S, C, ctypes.cast(mean, ctypes.c_void_p),
-                                          ctypes.cast(std, ctypes.c_void_p), ptr(out), stream()), "mfvit_input_transform")
+        check(lib().mfvit_input_transform_rect(ptr(src), ptr(dsc), ptr(tab), n, S, out_hw[0], out_hw[1], ctypes.cast(mean, ctypes.c_void_p),
+                                               ctypes.cast(std, ctypes.c_void_p), ptr(out), stream()), "mfvit_input_transform_rect")
         return out
