@@ -332,8 +332,8 @@ int mfvit_xattn_backward(const mfvit_fusion_cfg* cfg, const float* params, const
  * mfvit_prof_collect waits for the recorded events and fills out[cls*4 + {0 launches, 1 ms, 2 algorithmic flops,
  * 3 algorithmic bytes}] (ncls <= 10), then clears the records. */
 int mfvit_prof_enable(int class_mask); /* bit c set = time class c; 0 = off */
-/* Weight-gradient GEMMs of mfvit_vit_backward run on a library-owned side stream beside the dgrad chain (default on; also
- * MFVIT_WGRAD_STREAM=0).  0 serialises them on the caller's stream - used by bench.py's attribution pass so that a kernel's
+/* Weight-gradient GEMMs of mfvit_vit_backward run on a library-owned side stream beside the dgrad chain (default on: at 1,024 ... 4,096
+ * token rows).  0 serialises them on the caller's stream - used by bench.py's attribution pass so that a kernel's
  * event-timed duration is its own, not a share of a co-scheduled GPU.  Results are identical either way. */
 int mfvit_set_wgrad_stream(int enabled);
 /* How many independent kernel streams the caller runs side by side on this GPU (default 1: a kernel may size its grid for the whole chip).  The

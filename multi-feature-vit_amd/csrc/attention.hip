@@ -10,8 +10,6 @@
 #include "common.cuh"
 #include "prof.h"
 
-#include <stdlib.h>
-
 namespace mfvit {
 
 template <typename T, int HD> __device__ __forceinline__ void load_row(const T* p, float (&r)[HD]) {
@@ -281,36 +279,25 @@ int attn_fwd_tiled(int dtype, const void* qkv, void* out, float* lse, int B, int
 int attn_bwd_tiled(int dtype, const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int B, int Tn, int H, int HDim,
                    hipStream_t st);
 int attn_colsum(int dtype, const void* dqkv, int M, int N, float* dbias, hipStream_t st);
-static bool force_exact() {
-    static const bool v = [] { const char* e = getenv("MFVIT_ATTN_EXACT"); return e && e[0] == '1'; }();
-    return v;
-}
-static bool force_tiled() {   // MFVIT_ATTN_TILED=1: the streaming kernels also where the whole-head-in-LDS kernels would fit (tests, profiling)
-    static const bool v = [] { const char* e = getenv("MFVIT_ATTN_TILED"); return e && e[0] == '1'; }();
-    return v;
-}
 // whole-(image, head)-in-LDS MFMA kernels where they fit (ViT-S at 224^2: fastest) -> streaming MFMA kernels (long sequences, wide
 // heads, split bf16 beyond the LDS limits) -> exact VALU kernels (f32)
 int attn_qkv_dtype(int dtype, int Tn, int HDim) {
-    if (dtype == MFVIT_BF16X3 && !force_tiled() && attn_mfma_supported(MFVIT_X3F16, Tn, HDim, false) && attn_mfma_supported(MFVIT_X3F16, Tn, HDim, true))
+    if (dtype == MFVIT_BF16X3 && attn_mfma_supported(MFVIT_X3F16, Tn, HDim, false) && attn_mfma_supported(MFVIT_X3F16, Tn, HDim, true))
         return MFVIT_X3F16;
     return dtype;
 }
 int attn_fwd(int dtype, const void* qkv, void* out, float* lse, int B, int Tn, int H, int HDim, hipStream_t st) {
     if (dtype == MFVIT_X3F16) return attn_mfma_supported(dtype, Tn, HDim, false) ? attn_fwd_mfma(dtype, qkv, out, lse, B, Tn, H, st) : MFVIT_ENOSYS;
-    const bool exact = force_exact() && dtype != MFVIT_BF16X3;
-    if (!exact && !force_tiled() && attn_mfma_supported(dtype, Tn, HDim, false)) return attn_fwd_mfma(dtype, qkv, out, lse, B, Tn, H, st);
-    if (!exact && attn_tiled_supported(dtype, Tn, HDim)) return attn_fwd_tiled(dtype, qkv, out, lse, B, Tn, H, HDim, st);
+    if (attn_mfma_supported(dtype, Tn, HDim, false)) return attn_fwd_mfma(dtype, qkv, out, lse, B, Tn, H, st);
+    if (attn_tiled_supported(dtype, Tn, HDim)) return attn_fwd_tiled(dtype, qkv, out, lse, B, Tn, H, HDim, st);
     return attn_fwd_exact(dtype, qkv, out, lse, B, Tn, H, HDim, st);
 }
 int attn_bwd(int dtype, const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* dbias, int B, int Tn, int H,
              int HDim, hipStream_t st, const unsigned* domax) {
     if (dtype == MFVIT_X3F16)
         return attn_mfma_supported(dtype, Tn, HDim, true) ? attn_bwd_mfma(dtype, qkv, out, dout, lse, dqkv, dbias, B, Tn, H, st, domax) : MFVIT_ENOSYS;
-    const bool exact = force_exact() && dtype != MFVIT_BF16X3;
-    if (!exact && !force_tiled() && attn_mfma_supported(dtype, Tn, HDim, true))
-        return attn_bwd_mfma(dtype, qkv, out, dout, lse, dqkv, dbias, B, Tn, H, st);
-    if (!exact && attn_tiled_supported(dtype, Tn, HDim)) {
+    if (attn_mfma_supported(dtype, Tn, HDim, true)) return attn_bwd_mfma(dtype, qkv, out, dout, lse, dqkv, dbias, B, Tn, H, st);
+    if (attn_tiled_supported(dtype, Tn, HDim)) {
         const int rc = attn_bwd_tiled(dtype, qkv, out, dout, lse, dqkv, B, Tn, H, HDim, st);
         if (rc != MFVIT_OK || !dbias) return rc;
         return attn_colsum(dtype, dqkv, B * Tn, 3 * H * HDim, dbias, st);

@@ -63,8 +63,11 @@ template <typename T> struct AttnT {
     static constexpr float LAZY = X ? 14.f : 24.f;             // lazy-maximum threshold (log2): P <= 2^LAZY must fit the operand type
     static __device__ __forceinline__ f32x16 mma(frag_t a, frag_t b, f32x16 c) { return MmaTraits_mma(a, b, c); }
 };
-// parts of P / dS that feed the second products: plain types 1, split bf16 2 (hi + lo), split fp16 NPX (1: hi only = 11 bits; 2: hi + lo)
-template <typename T, int NPX> struct PParts { static constexpr int value = AttnT<T>::X ? NPX : (AttnT<T>::SP ? 2 : 1); };
+// parts of P / dS that feed the second products: plain types 1, split bf16 2 (hi + lo).  Split fp16: forward 2 (hi + lo: f32-grade outputs - one part
+// measured 2.2e-4 on the output and 8e-5 ... 9e-5 on the logits of a 12-block encoder for 46 instead of 48 us, and was removed), backward 1 (hi only
+// = 11 bits, like the saved activation derivative of the MLP: gradients at 2^-11 relative; worst parameter gradient of the encoder unchanged at 3.3e-4;
+// two parts gave dqkv at 5e-6 against float64 for +14 % time and were retired)
+template <typename T, bool BWD> struct PParts { static constexpr int value = AttnT<T>::X ? (BWD ? 1 : 2) : (AttnT<T>::SP ? 2 : 1); };
 __device__ __forceinline__ f32x16 MmaTraits_mma(bf16x8 a, bf16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ f32x16 MmaTraits_mma(f16x8 a, f16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
 
@@ -167,14 +170,14 @@ template <typename T> __device__ __forceinline__ void store_tile_T(typename Vec4
 
 constexpr int NKC = 4;  // key tiles per register-resident chunk (4 x 16 = 64 score registers -> 2 waves per SIMD)
 
-template <typename T, int NPX>
+template <typename T>
 __global__ __launch_bounds__(256) void attn_fwd_mfma_kernel(const typename Vec4<T>::elem* __restrict__ qkv, typename AttnT<T>::OE* __restrict__ out,
                                                             float* __restrict__ lse, int Tn, int H, float scale) {
     typedef AttnT<T> A;
     typedef typename A::E E;
     typedef typename A::OT OT;
     typedef typename A::frag_t frag_t;
-    constexpr int EP = A::EP, KP = A::RSB, VP = A::RB, CPR = A::RB / 16, NP = PParts<T, NPX>::value;
+    constexpr int EP = A::EP, KP = A::RSB, VP = A::RB, CPR = A::RB / 16, NP = PParts<T, false>::value;
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int Tpad = (Tn + 31) & ~31;
     char* Ks = lds;
@@ -350,7 +353,7 @@ __device__ __forceinline__ float xhalf(float x) {
     return __builtin_bit_cast(float, (threadIdx.x & 32) ? r[0] : r[1]);
 }
 
-template <typename T, int NPX>
+template <typename T>
 __global__ __launch_bounds__(512) void attn_fwd_pp_kernel(const typename Vec4<T>::elem* __restrict__ qkv, typename AttnT<T>::OE* __restrict__ out,
                                                           float* __restrict__ lse, int Tn, int H, float scale, int npair) {
     typedef AttnT<T> A;
@@ -358,7 +361,7 @@ __global__ __launch_bounds__(512) void attn_fwd_pp_kernel(const typename Vec4<T>
     typedef typename A::E E;
     typedef typename A::OE OE;
     typedef typename A::frag_t frag_t;
-    constexpr int EP = A::EP, RB = G::RB, CPR = G::CPR, RPP = G::RPP, LO = A::SP ? 1 : 0, SPB = G::SPB, NCW = G::NCW, NP = PParts<T, NPX>::value;
+    constexpr int EP = A::EP, RB = G::RB, CPR = G::CPR, RPP = G::RPP, LO = A::SP ? 1 : 0, SPB = G::SPB, NCW = G::NCW, NP = PParts<T, false>::value;
     constexpr int NQK = A::SP ? 6 : 2;                                 // MFMAs of one score tile
     constexpr int NPV = A::SP ? 2 * (NP + 1) : 2;                      // ... of one PV tile (P in NP parts)
     constexpr bool PSUM = A::X && NP == 1;                             // row sum taken from the rounded probabilities (pack8x)
@@ -799,7 +802,7 @@ __device__ __forceinline__ void pow2_scale(float mx, float& s, float& sinv) {
     sinv = __builtin_bit_cast(float, (unsigned)(127 - e) << 23);
 }
 
-template <typename T, int PITCH, int NPX>
+template <typename T, int PITCH>
 __global__ __launch_bounds__(512) void attn_bwd_mfma_kernel(const typename Vec4<T>::elem* __restrict__ qkv, const typename AttnT<T>::OE* __restrict__ out,
                                                             const typename AttnT<T>::OE* __restrict__ dout, const float* __restrict__ lse,
                                                             typename AttnT<T>::OE* __restrict__ dqkv, int Tn, int H, float scale, int nbh) {
@@ -809,7 +812,7 @@ __global__ __launch_bounds__(512) void attn_bwd_mfma_kernel(const typename Vec4<
     typedef typename A::OT OT;
     typedef typename A::frag_t frag_t;
     typedef typename A::ofrag_t ofrag_t;
-    constexpr int EP = A::EP, CPR = A::RB / 16, LO = A::SP ? 1 : 0, NP = PParts<T, NPX>::value;
+    constexpr int EP = A::EP, CPR = A::RB / 16, LO = A::SP ? 1 : 0, NP = PParts<T, true>::value;
     extern __shared__ __attribute__((aligned(16))) char lds[];
     __shared__ float red[8];                                           // (split fp16: block maximum of |dO|)
     (void)red;
@@ -950,7 +953,15 @@ __global__ __launch_bounds__(512) void attn_bwd_mfma_kernel(const typename Vec4<
                 for (int j = 0; j < 8; ++j) mx = fmaxf(mx, fabsf((float)cd.f[j]));
             }
         }
-        mx = block_max<512>(mx, red);
+        // (block maximum written out here, with the kernel's own wave index: through a shared helper whose only caller passes `red`, the compiler
+        // folds the LDS address differently and this kernel spills 12 bytes)
+        mx = wave_max(mx);
+        __syncthreads();
+        if (lane == 0) red[wave] = mx;
+        __syncthreads();
+        mx = red[0];
+#pragma unroll
+        for (int w = 1; w < 8; ++w) mx = fmaxf(mx, red[w]);
         pow2_scale(mx, sE, sEinv);
 #pragma unroll
         for (int i = 0; i < NCH; ++i) {
@@ -1154,7 +1165,7 @@ template <typename T> struct SpGeo {
 };
 
 // NT: row tiles of a pair (= computing waves): 7 (T = 193 .. 224); other lengths stay with the two-phase kernels
-template <typename T, int NT, int NPX, bool DM = false>     // DM: the pairs' |dO| maxima come from the producer of dO (domax)
+template <typename T, int NT, bool DM = false>     // DM: the pairs' |dO| maxima come from the producer of dO (domax)
 __global__ __launch_bounds__(512) void attn_bwd_sp_kernel(const typename Vec4<T>::elem* __restrict__ qkv, const typename AttnT<T>::OE* __restrict__ out,
                                                           const typename AttnT<T>::OE* __restrict__ dout, const float* __restrict__ lse,
                                                           typename AttnT<T>::OE* __restrict__ dqkv, int Tn, int H, float scale, int npair,
@@ -1166,7 +1177,7 @@ __global__ __launch_bounds__(512) void attn_bwd_sp_kernel(const typename Vec4<T>
     typedef typename A::OT OT;
     typedef typename A::frag_t frag_t;
     typedef typename A::ofrag_t ofrag_t;
-    constexpr int EP = A::EP, RB = G::RB, CPR = G::CPR, RPP = G::RPP, LO = A::SP ? 1 : 0, NCW = G::NCW, SCR = G::SCR, NP = PParts<T, NPX>::value;
+    constexpr int EP = A::EP, RB = G::RB, CPR = G::CPR, RPP = G::RPP, LO = A::SP ? 1 : 0, NCW = G::NCW, SCR = G::SCR, NP = PParts<T, true>::value;
     constexpr int NM = A::SP ? 6 : 2;                                  // MFMAs of one 32 x 32 x 32 product of two tensors
     constexpr int NPT = A::SP ? NP + 1 : 1;                            // MFMAs per k-step of a product with P / dS (NP parts)
     constexpr int PLO = NP - 1;                                        // index of the last P / dS part
@@ -1815,13 +1826,7 @@ int attn_cus() {   // CUs of the CURRENT device, a multiple of 8 (a persistent w
     return n >= 8 ? n : 8;
 }
 
-// parts of P / dS in the split-fp16 kernels (see the top of the file): forward 2 (hi + lo: f32-grade outputs - one part measured 2.2e-4 on the output
-// and 8e-5 ... 9e-5 on the logits of a 12-block encoder for 46 instead of 48 us, and was removed), backward 1 (11 bits, like the saved activation
-// derivative of the MLP: gradients at 2^-11 relative; worst parameter gradient of the encoder unchanged at 3.3e-4); MFVIT_ATTN_PB=2: two parts
-// in the backward too (dqkv at 5e-6 against float64, +14 % time)
-static int parts_bwd() { static int sw = INT_MIN; return env_switch("MFVIT_ATTN_PB", 1, sw) == 2 ? 2 : 1; }
-
-template <typename T, int NPX> int launch_fwd_t(const void* qkv, void* out, float* lse, int B, int Tn, int H, hipStream_t st) {
+template <typename T> int launch_fwd_t(const void* qkv, void* out, float* lse, int B, int Tn, int H, hipStream_t st) {
     typedef typename Vec4<T>::elem E;
     typedef typename AttnT<T>::OE OE;
     if constexpr (is_split<T>::value) {
@@ -1833,9 +1838,9 @@ template <typename T, int NPX> int launch_fwd_t(const void* qkv, void* out, floa
         const int bytes = RingGeo<T>::lds_bytes(Tn);
         if (B * H >= 2 * cus && nt >= 5 && nt <= RingGeo<T>::NCW && bytes <= 160 * 1024) {
             static PerDeviceOnce attr_pp;
-            if (attr_pp.first()) (void)hipFuncSetAttribute((const void*)attn_fwd_pp_kernel<T, NPX>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            if (attr_pp.first()) (void)hipFuncSetAttribute((const void*)attn_fwd_pp_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             ProfScope ps(PROF_ATTN_FWD, 4.0 * B * H * (double)Tn * Tn * HD, 0, st);
-            MFVIT_LAUNCH((attn_fwd_pp_kernel<T, NPX>), dim3(cus), dim3(512), bytes, st, (const E*)qkv, (OE*)out, lse, Tn, H, 1.0f / sqrtf((float)HD), B * H);
+            MFVIT_LAUNCH((attn_fwd_pp_kernel<T>), dim3(cus), dim3(512), bytes, st, (const E*)qkv, (OE*)out, lse, Tn, H, 1.0f / sqrtf((float)HD), B * H);
             MFVIT_CHECK_LAUNCH();
             return MFVIT_OK;
         }
@@ -1843,14 +1848,14 @@ template <typename T, int NPX> int launch_fwd_t(const void* qkv, void* out, floa
     const int Tpad = (Tn + 31) & ~31;
     const int bytes = Tpad * (AttnT<T>::RSB + AttnT<T>::RB);
     static PerDeviceOnce attr;
-    if (attr.first()) { (void)hipFuncSetAttribute((const void*)attn_fwd_mfma_kernel<T, NPX>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); }
+    if (attr.first()) { (void)hipFuncSetAttribute((const void*)attn_fwd_mfma_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); }
     ProfScope ps(PROF_ATTN_FWD, 4.0 * B * H * (double)Tn * Tn * HD, 0, st);
-    MFVIT_LAUNCH((attn_fwd_mfma_kernel<T, NPX>), dim3(B * H), dim3(256), bytes, st, (const E*)qkv, (OE*)out, lse, Tn, H, 1.0f / sqrtf((float)HD));
+    MFVIT_LAUNCH((attn_fwd_mfma_kernel<T>), dim3(B * H), dim3(256), bytes, st, (const E*)qkv, (OE*)out, lse, Tn, H, 1.0f / sqrtf((float)HD));
     MFVIT_CHECK_LAUNCH();
     return MFVIT_OK;
 }
-template <typename T, int NPX> int launch_bwd_t(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* dbias, int B, int Tn,
-                                                int H, hipStream_t st, const unsigned* domax = nullptr) {
+template <typename T> int launch_bwd_t(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* dbias, int B, int Tn,
+                                       int H, hipStream_t st, const unsigned* domax = nullptr) {
     typedef typename Vec4<T>::elem E;
     typedef typename AttnT<T>::OE OE;
     typedef typename AttnT<T>::OT OT;
@@ -1862,9 +1867,9 @@ template <typename T, int NPX> int launch_bwd_t(const void* qkv, const void* out
     if (AttnT<T>::SP && !wide) return MFVIT_EINVAL;
     static PerDeviceOnce attr;
     if (attr.first()) {
-        (void)hipFuncSetAttribute((const void*)attn_bwd_mfma_kernel<T, RSB, NPX>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
+        (void)hipFuncSetAttribute((const void*)attn_bwd_mfma_kernel<T, RSB>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
         if constexpr (!AttnT<T>::SP)
-            (void)hipFuncSetAttribute((const void*)attn_bwd_mfma_kernel<T, RB, NPX>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
+            (void)hipFuncSetAttribute((const void*)attn_bwd_mfma_kernel<T, RB>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
     }
     auto colsum = [&]() -> int {
         if (!dbias) return MFVIT_OK;
@@ -1882,22 +1887,22 @@ template <typename T, int NPX> int launch_bwd_t(const void* qkv, const void* out
         if (env_switch("MFVIT_ATTN_BWD_SP", 1, sws) != 0 && B * H >= 2 * cus3 && nt == 7 && b3 <= 160 * 1024) {
             static PerDeviceOnce attr_sp;
             if (attr_sp.first()) {
-                (void)hipFuncSetAttribute((const void*)attn_bwd_sp_kernel<T, 7, NPX>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                (void)hipFuncSetAttribute((const void*)attn_bwd_sp_kernel<T, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
                 if constexpr (AttnT<T>::X)
-                    (void)hipFuncSetAttribute((const void*)attn_bwd_sp_kernel<T, 7, NPX, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+                    (void)hipFuncSetAttribute((const void*)attn_bwd_sp_kernel<T, 7, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             }
             {
                 ProfScope ps(PROF_ATTN_BWD, 8.0 * B * H * (double)Tn * Tn * HD, 0, st);
                 bool done = false;
                 if constexpr (AttnT<T>::X) {
                     if (domax) {
-                        MFVIT_LAUNCH((attn_bwd_sp_kernel<T, 7, NPX, true>), dim3(cus3), dim3(512), b3, st, (const E*)qkv, (const OE*)out, (const OE*)dout, lse,
+                        MFVIT_LAUNCH((attn_bwd_sp_kernel<T, 7, true>), dim3(cus3), dim3(512), b3, st, (const E*)qkv, (const OE*)out, (const OE*)dout, lse,
                                      (OE*)dqkv, Tn, H, 1.0f / sqrtf((float)HD), B * H, domax);
                         done = true;
                     }
                 }
                 if (!done)
-                    MFVIT_LAUNCH((attn_bwd_sp_kernel<T, 7, NPX>), dim3(cus3), dim3(512), b3, st, (const E*)qkv, (const OE*)out, (const OE*)dout, lse, (OE*)dqkv,
+                    MFVIT_LAUNCH((attn_bwd_sp_kernel<T, 7>), dim3(cus3), dim3(512), b3, st, (const E*)qkv, (const OE*)out, (const OE*)dout, lse, (OE*)dqkv,
                                  Tn, H, 1.0f / sqrtf((float)HD), B * H, (const unsigned*)nullptr);
                 MFVIT_CHECK_LAUNCH();
             }
@@ -1910,10 +1915,10 @@ template <typename T, int NPX> int launch_bwd_t(const void* qkv, const void* out
         const int cus = attn_cus();
         const int grid = B * H < cus ? B * H : cus;
         if (wide)
-            MFVIT_LAUNCH((attn_bwd_mfma_kernel<T, RSB, NPX>), dim3(grid), dim3(512), bytes, st, (const E*)qkv, (const OE*)out, (const OE*)dout, lse,
+            MFVIT_LAUNCH((attn_bwd_mfma_kernel<T, RSB>), dim3(grid), dim3(512), bytes, st, (const E*)qkv, (const OE*)out, (const OE*)dout, lse,
                          (OE*)dqkv, Tn, H, 1.0f / sqrtf((float)HD), B * H);
         else if constexpr (!AttnT<T>::SP)
-            MFVIT_LAUNCH((attn_bwd_mfma_kernel<T, RB, NPX>), dim3(grid), dim3(512), bytes, st, (const E*)qkv, (const OE*)out, (const OE*)dout, lse,
+            MFVIT_LAUNCH((attn_bwd_mfma_kernel<T, RB>), dim3(grid), dim3(512), bytes, st, (const E*)qkv, (const OE*)out, (const OE*)dout, lse,
                          (OE*)dqkv, Tn, H, 1.0f / sqrtf((float)HD), B * H);
         MFVIT_CHECK_LAUNCH();
     }
@@ -1943,20 +1948,18 @@ int attn_colsum(int dtype, const void* dqkv, int M, int N, float* dbias, hipStre
 }
 
 int attn_fwd_mfma(int dtype, const void* qkv, void* out, float* lse, int B, int Tn, int H, hipStream_t st) {
-    if (dtype == MFVIT_BF16) return launch_fwd_t<bf16, 2>(qkv, out, lse, B, Tn, H, st);
-    if (dtype == MFVIT_BF16X3) return launch_fwd_t<sbf16, 2>(qkv, out, lse, B, Tn, H, st);
-    if (dtype == MFVIT_F16) return launch_fwd_t<f16, 2>(qkv, out, lse, B, Tn, H, st);
-    if (dtype == MFVIT_X3F16) return launch_fwd_t<sf16, 2>(qkv, out, lse, B, Tn, H, st);
+    if (dtype == MFVIT_BF16) return launch_fwd_t<bf16>(qkv, out, lse, B, Tn, H, st);
+    if (dtype == MFVIT_BF16X3) return launch_fwd_t<sbf16>(qkv, out, lse, B, Tn, H, st);
+    if (dtype == MFVIT_F16) return launch_fwd_t<f16>(qkv, out, lse, B, Tn, H, st);
+    if (dtype == MFVIT_X3F16) return launch_fwd_t<sf16>(qkv, out, lse, B, Tn, H, st);
     return MFVIT_EINVAL;
 }
 int attn_bwd_mfma(int dtype, const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* dbias, int B, int Tn, int H,
                   hipStream_t st, const unsigned* domax) {
-    if (dtype == MFVIT_BF16) return launch_bwd_t<bf16, 2>(qkv, out, dout, lse, dqkv, dbias, B, Tn, H, st);
-    if (dtype == MFVIT_BF16X3) return launch_bwd_t<sbf16, 2>(qkv, out, dout, lse, dqkv, dbias, B, Tn, H, st);
-    if (dtype == MFVIT_F16) return launch_bwd_t<f16, 2>(qkv, out, dout, lse, dqkv, dbias, B, Tn, H, st);
-    if (dtype == MFVIT_X3F16)
-        return parts_bwd() == 1 ? launch_bwd_t<sf16, 1>(qkv, out, dout, lse, dqkv, dbias, B, Tn, H, st, domax)
-                                : launch_bwd_t<sf16, 2>(qkv, out, dout, lse, dqkv, dbias, B, Tn, H, st, domax);
+    if (dtype == MFVIT_BF16) return launch_bwd_t<bf16>(qkv, out, dout, lse, dqkv, dbias, B, Tn, H, st);
+    if (dtype == MFVIT_BF16X3) return launch_bwd_t<sbf16>(qkv, out, dout, lse, dqkv, dbias, B, Tn, H, st);
+    if (dtype == MFVIT_F16) return launch_bwd_t<f16>(qkv, out, dout, lse, dqkv, dbias, B, Tn, H, st);
+    if (dtype == MFVIT_X3F16) return launch_bwd_t<sf16>(qkv, out, dout, lse, dqkv, dbias, B, Tn, H, st, domax);
     return MFVIT_EINVAL;
 }
 

@@ -234,17 +234,6 @@ template <int NT> __device__ __forceinline__ float block_sum(float v, float* scr
     for (int i = 0; i < NT / 64; ++i) t += scratch[i];
     return t;
 }
-template <int NT> __device__ __forceinline__ float block_max(float v, float* scratch) {
-    v = wave_max(v);
-    const int w = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) scratch[w] = v;
-    __syncthreads();
-    float t = scratch[0];
-#pragma unroll
-    for (int i = 1; i < NT / 64; ++i) t = fmaxf(t, scratch[i]);
-    return t;
-}
 
 // Streaming 16-byte OUTPUT store (`sc0 sc1 nt`: system scope, non-temporal).  Round 5, measured with FETCH_SIZE: with plain or nt-only stores the L2
 // FETCHES every output line it allocates (write-allocate: fc1 + GELU read 135 MB from HBM for 41 MB of operands, the fc2 data gradient 221 for 119 -

@@ -494,15 +494,15 @@ template <typename T> int pp_by_epi(int epi, const GemmP& p, hipStream_t st) {
 
 }  // namespace
 
-// MFVIT_PP: 1 (default) the ping-pong kernel wherever it pays, 0 never (the round-5 tile kernel everywhere), 2 wherever it CAN run (tests); MFVIT_PP_MINROWS: smallest M it takes
+// MFVIT_PP: 1 (default) the ping-pong kernel wherever it pays (M >= 2,048 and enough tiles), 0 never (the round-5 tile kernel everywhere), 2 wherever it CAN run (tests)
 bool gemm_nt_pp_supported(int dtype, int epi, const GemmP& p) {
-    static int c_on = INT_MIN, c_min = INT_MIN;
+    static int c_on = INT_MIN;
     const int on = env_switch("MFVIT_PP", 1, c_on);            // 2: wherever the kernel CAN run (tests: small shapes, few tiles)
     if (!on) return false;
     if (dtype != MFVIT_BF16X3 && dtype != MFVIT_BF16 && dtype != MFVIT_F16) return false;
     if (epi == EPI_BIAS_X3F16 && dtype != MFVIT_BF16X3) return false;
     const int kps = dtype == MFVIT_BF16X3 ? 32 : 64;
-    if (p.nb > 1 || (on != 2 && p.M < env_switch("MFVIT_PP_MINROWS", 2048, c_min)) || p.M < 1 || p.N % PP_BN || p.K % kps || p.K < 2 * kps) return false;
+    if (p.nb > 1 || (on != 2 && p.M < 2048) || p.M < 1 || p.N % PP_BN || p.K % kps || p.K < 2 * kps) return false;
     if (p.omax) return false;                                   // per-(image, head) output maxima: the round-5 kernel's epilogue (proj data gradient)
     if (on != 2) {   // enough tiles to fill the persistent grid's rounds: 256 x 128 tiles on one workgroup per CU quantise coarsely (proj data gradient at the bench shape:
         // 297 tiles = 2 rounds at 58 % - 35.3 us against 31.7 us of the 128 x 128 kernel on two workgroups per CU; qkv 891 tiles = 4 rounds at 87 %)

@@ -78,9 +78,7 @@ template <typename T> __device__ __forceinline__ typename Vec8<T>::type t2_frag(
 // T = bf16 | f16 | sbf16 (split bf16, see T2Geo)
 // RM: the rows of A are REMAPPED (GemmP::orow_*: the patch-embedding weight gradient reads the token rows 1 .. np of every image of a [B][np + 1][D]
 // gradient tensor); instantiated for the default split-bf16 form only
-// TWO (opt-in, MFVIT_WGRAD_TERMS=2; pipelined split form only): the dY_lo x_hi term is dropped - two MFMAs per product, dY enters at bf16 precision
-// (2^-9 per element, averaged down by the sum over the token rows), x keeps both parts
-template <typename T, bool CS, bool W8, bool IL, bool RM = false, bool TWO = false>
+template <typename T, bool CS, bool W8, bool IL, bool RM = false>
 __global__ __launch_bounds__(W8 ? 512 : 256) void gemm_tn_glds_kernel(GemmP p) {
     typedef T2Geo<T> G;
     constexpr int NWV = W8 ? 8 : 4;                          // waves
@@ -200,7 +198,6 @@ __global__ __launch_bounds__(W8 ? 512 : 256) void gemm_tn_glds_kernel(GemmP p) {
         auto mfma_t = [&](auto set_tag, int t) __attribute__((always_inline)) {
             constexpr int SET = decltype(set_tag)::value;
             const int term = t / (NL * NL), i = (t % (NL * NL)) / NL, j = t % NL;
-            if (TWO && term == 0) return;                        // (a_lo b_hi: its fragment reads become dead code as well)
             acc[i][j] = MmaTraits<T>::mma(fa[SET][2 * i + (term == 0 ? 1 : 0)], fb[SET][2 * j + (term == 1 ? 1 : 0)], acc[i][j]);
         };
         auto stage = [&](int st, auto set_tag, auto nset_tag, int slot) __attribute__((always_inline)) {
@@ -440,10 +437,9 @@ template <typename T> static int launch_t2(GemmP p, hipStream_t st) {
     typedef T2Geo<T> G;
     const int tiles = ((p.N + p.res_mod) / 128) * (p.K / 128);          // res_mod = N of the paired second GEMM (0: none)
     if (p.splits <= 0) {
-        static const int target_env = [] { const char* e = getenv("MFVIT_TN2_TARGET"); return e ? atoi(e) : 0; }();
         // one workgroup per CU (96 KB of LDS): tiles x splits <= 256; with a second kernel stream beside this one (stream_share(), common.cuh) and a
         // reduction short enough that the splits are latency (M < 8,192 rows) half of that, so that the other encoder's launch fits beside it
-        const int target = target_env > 0 ? target_env : (stream_share() >= 2 && p.M < 8192 ? 128 : 256);
+        const int target = stream_share() >= 2 && p.M < 8192 ? 128 : 256;
         int s = target / tiles;
         const int maxs = (p.M + 4 * G::KR - 1) / (4 * G::KR);
         p.splits = s < 1 ? 1 : (s > maxs ? maxs : s);
@@ -462,19 +458,8 @@ template <typename T> static int launch_t2(GemmP p, hipStream_t st) {
     // (eight waves per workgroup and the LDS-DMA issue interleaved with the MFMAs - the W8 / IL template flags of the kernel - are the only forms
     // launched since round 5; their four-wave / burst-issue alternatives and measurements: DESIGN.md 5, round 3)
     ProfScope ps(PROF_GEMM_TN, 2.0 * p.M * (p.N + p.res_mod) * p.K, 0, st);
-    static int sw2 = INT_MIN;
-    const bool two = is_split<T>::value && !p.orow_in && env_switch("MFVIT_WGRAD_TERMS", 3, sw2) == 2;
     auto go = [&](auto cs, auto w, auto i) {
         constexpr bool CS = decltype(cs)::value, W8 = decltype(w)::value, IL = decltype(i)::value;
-        if constexpr (is_split<T>::value && W8 && IL) {
-            if (two) {
-                static PerDeviceOnce attr2;
-                if (attr2.first())
-                    (void)hipFuncSetAttribute((const void*)gemm_tn_glds_kernel<T, CS, true, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-                MFVIT_LAUNCH((gemm_tn_glds_kernel<T, CS, true, true, false, true>), dim3(tiles * p.splits), dim3(512), bytes, st, p);
-                return;
-            }
-        }
         static PerDeviceOnce attr;
         if (attr.first()) {
             (void)hipFuncSetAttribute((const void*)gemm_tn_glds_kernel<T, CS, W8, IL>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);

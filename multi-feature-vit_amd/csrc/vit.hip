@@ -237,10 +237,11 @@ GemmP zero_gemm() {
 }
 
 // Weight-gradient GEMMs are leaves of the backward graph: they CAN run on a second (library-owned, lazily created) HIP stream beside the
-// dgrad chain, ordered by events (MFVIT_WGRAD_STREAM=1).  Default since round 3: the caller's stream.  The side stream was worth 3 - 4 % while the
-// weight-gradient and row kernels left half of every CU's LDS and issue slots free (round 2); now they are one-workgroup-per-CU kernels that own
-// the chip while they run, nothing co-resides with them, and the second queue only adds event waits and a worse launch order: measured on one box,
-// three alternating repeats, 31.25 / 31.33 / 31.36 ms per step with the side stream, 30.81 / 30.80 / 30.86 without (profiles/r03_streams_ab.txt).
+// dgrad chain, ordered by events.  Round 3 made the caller's stream the default; round 5 brought the side stream back at small M only (the rule
+// in encoder_backward).  The side stream was worth 3 - 4 % while the weight-gradient and row kernels left half of every CU's LDS and issue slots
+// free (round 2); now they are one-workgroup-per-CU kernels that own the chip while they run, nothing co-resides with them, and the second queue
+// only adds event waits and a worse launch order: measured on one box, three alternating repeats, 31.25 / 31.33 / 31.36 ms per step with the side
+// stream, 30.81 / 30.80 / 30.86 without (profiles/r03_streams_ab.txt).
 struct SideStream {
     hipStream_t owner = nullptr;    // caller stream this side stream is paired with
     hipStream_t s = nullptr;
@@ -262,9 +263,8 @@ SideStream& side_stream(hipStream_t caller) {
         px->owner = caller;
     }
     SideStream& x = *px;
-    if (!x.s) {
-        static const bool enabled = [] { const char* e = getenv("MFVIT_WGRAD_STREAM"); return !(e && e[0] == '0'); }();   // (0: never; created on first use)
-        if (enabled && hipStreamCreateWithFlags(&x.s, hipStreamNonBlocking) == hipSuccess &&
+    if (!x.s) {   // (created on first use)
+        if (hipStreamCreateWithFlags(&x.s, hipStreamNonBlocking) == hipSuccess &&
             hipEventCreateWithFlags(&x.in, hipEventDisableTiming) == hipSuccess &&
             hipEventCreateWithFlags(&x.end, hipEventDisableTiming) == hipSuccess) {
             x.ok = true;
@@ -294,7 +294,7 @@ int mfvit_set_wgrad_stream(int enabled) {
     g_wgrad_stream.store(enabled ? 1 : 0, std::memory_order_relaxed);
     return MFVIT_OK;
 }
-const char* mfvit_build_info(void) { return "libmfvit_hip gfx950 (MFMA bf16 | split-bf16 x3 | f16 32x32x16, f32 32x32x2), wave64, abi 4"; }
+const char* mfvit_build_info(void) { return "libmfvit_hip gfx950 (MFMA bf16 | split-bf16 x3 | f16 32x32x16, f32 32x32x2), wave64, abi 5"; }
 
 size_t mfvit_vit_param_count(const mfvit_vit_cfg* cfg) {
     Dims d;
@@ -557,30 +557,27 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const float* params, const
     // the end of every BLOCK that adds the splits in a fixed order: dW is the same bits on every run (the float atomics it replaces add in whatever
     // order the workgroups finish).  Round 3 measured the same idea with a reduce launch behind EVERY gradient as a loss (77.2 -> 80.8 us per
     // launch); batched it costs 0.4 - 0.6 % of the step (round 5, profiles/r05_wgrad_partials_ab.txt: weight-gradient class 95.6 -> 90.8 us per launch,
-    // the reduce launches take most of it back; per block - partials still in the Infinity Cache - beats per call by 0.07 ms).  MFVIT_TN_PART=0: float
-    // atomics.  (With the weight-gradient side stream the partial path stays ON: every weight gradient and every reduce of a call then runs in the side stream's order.)
-    static const bool tn_part_env = [] { const char* e = getenv("MFVIT_TN_PART"); return !(e && e[0] == '0'); }();
+    // the reduce launches take most of it back; per block - partials still in the Infinity Cache - beats per call by 0.07 ms).  (With the weight-gradient
+    // side stream the partial path stays ON: every weight gradient and every reduce of a call then runs in the side stream's order.)
     int tn_used = 0;
-    bool tn_part = tn_part_env;                // (decided below, once use_side is known)
     auto next_tnpart = [&]() -> float* {       // (more launches than slots between two flushes: float atomics for the rest - never a slot still in use)
-        return tn_part && tn_used < TN_SLOTS ? (float*)(ws + W.tnpart + (size_t)(tn_used++) * W.tnpart_stride) : nullptr;
+        return tn_used < TN_SLOTS ? (float*)(ws + W.tnpart + (size_t)(tn_used++) * W.tnpart_stride) : nullptr;
     };
     TnPartBatch tbatch;
     struct TnScope {
-        TnPartBatch* prev; bool on;
-        TnScope(TnPartBatch* b, bool on_) : on(on_) { if (on) prev = tnpart_batch_begin(b); }
-        ~TnScope() { if (on) tnpart_batch_begin(prev); }
-    } tn_scope(&tbatch, tn_part_env);
+        TnPartBatch* prev;
+        TnScope(TnPartBatch* b) : prev(tnpart_batch_begin(b)) {}
+        ~TnScope() { tnpart_batch_begin(prev); }
+    } tn_scope(&tbatch);
     // dY buffers by layer parity (the embed stage counts as layer -1 -> parity 1)
     auto pp = [&](size_t off, int l) { return (void*)(ws + off + (size_t)(l & 1) * W.pp_stride); };
     // (side_wanted, below, decides whether the side stream of this caller stream is looked up - and created - at all)
-    static const int side_env = [] { const char* e = getenv("MFVIT_WGRAD_STREAM"); return e ? (e[0] == '1' ? 1 : (e[0] == '0' ? 0 : -1)) : -1; }();
     // (never inside a caller's stream capture: the library-owned side stream is not part of the caller's capture, and its last weight gradients are joined by the
     // NEXT call's fork, not before this one returns - a capture ending in between would hold unjoined work.  The package itself no longer captures steps:
     // the whole-step HIP graph of round 5 gained nothing, 8.22 vs 8.12 ms, and was removed in round 6)
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     const bool capturing = hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
-    const bool side_wanted = (side_env == 1 || (side_env < 0 && d.M >= 1024 && d.M <= 4096)) && g_wgrad_stream.load(std::memory_order_relaxed) != 0 && !(d.p_resid > 0.f) &&
+    const bool side_wanted = d.M >= 1024 && d.M <= 4096 && g_wgrad_stream.load(std::memory_order_relaxed) != 0 && !(d.p_resid > 0.f) &&
                              !capturing;
     static SideStream no_side;
     SideStream& ss = side_wanted ? side_stream(st) : no_side;
@@ -588,12 +585,11 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const float* params, const
     // Default since round 5: the side stream at SMALL M only (1,024 ... 4,096 token rows: 6 - 20 images) - there no kernel fills the chip, the launches of a
     // block are a dependent chain of ~10 us kernels with ~5 us of dispatch gap each, and the weight gradients (leaves) beside the data-gradient chain
     // shorten it: 20 pairs per step 7.31 -> 6.66 ms, 16 pairs 6.31 -> 6.10 (then host-bound), 8 pairs 5.18 -> 4.96; 4 pairs LOSE (host-bound either way, 5.1 ->
-    // 6.9 ms) and 32 pairs gain 1 % (profiles/r05_small_batch.txt).  MFVIT_WGRAD_STREAM=1: at every M (round 2 behaviour), 0: never.
+    // 6.9 ms) and 32 pairs gain 1 % (profiles/r05_small_batch.txt).
     const bool use_side = side_wanted && ss.ok && W.pp_stride != 0;
     hipStream_t wst = use_side ? ss.s : st;                       // stream of the weight-gradient GEMMs
     // (with the side stream every weight gradient AND every reduce of their partials runs on it - the patch embedding's too, below - so the scratch slots
     // are still written and read in one stream's order)
-    tn_part = tn_part_env;
     // the side stream may only start after everything already queued on the caller's stream (activations, zeroed gradients)
     auto fork = [&]() -> int {                                    // main -> side dependency at this point of the main stream
         if (!use_side) return MFVIT_OK;
@@ -763,10 +759,8 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const float* params, const
                     MFVIT_TRY(gemm_tn(d.dtype, p, wst));
                 }
             }
-            if (tn_part) {                                        // dW += this block's split partials, splits in a fixed order; the slots are free again
-                MFVIT_TRY(tnpart_batch_flush(wst));
-                tn_used = 0;
-            }
+            MFVIT_TRY(tnpart_batch_flush(wst));                   // dW += this block's split partials, splits in a fixed order; the slots are free again
+            tn_used = 0;
             if (use_side && hipEventRecord(ss.done[l & 63], ss.s) != hipSuccess) return MFVIT_ELAUNCH;
             MFVIT_TRY(wait_layer(l + 1));                         // fc2-wgrad of layer l+1 reads the gxT copy written next
             {   // gx = LN1bwd(dqkv Wqkv) + gmid ; d ln1_w, d ln1_b, d fc2_b of block l-1 (or scratch for the embed stage)

@@ -209,8 +209,8 @@ class Bf16Mode(Mode):
 
 class X3F16Mode(Mode):
     """What the encoder runs in bf16x3 mode (round 5): qkv in SPLIT FP16 (dtype tag MFVIT_X3F16), out / dout / dqkv split bf16.  The forward
-    splits P into two fp16 parts (f32-grade); the backward feeds P and dS as ONE fp16 part by default (11 bits: gradients at the level of the
-    MLP's saved fp16 activation derivative), MFVIT_ATTN_PB=2 splits them too."""
+    splits P into two fp16 parts (f32-grade); the backward feeds P and dS as ONE fp16 part (11 bits: gradients at the level of the
+    MLP's saved fp16 activation derivative)."""
 
     def __init__(self):
         super().__init__("bf16x3")
@@ -323,14 +323,11 @@ def test_attention_persistent_forward_row_tile_counts(monkeypatch, mode, T):
     assert e_o < mode.tol and e_l < 1e-5 and e_d < bwd_tol(mode) and torch.isfinite(out.float()).all()
 
 
-@pytest.mark.parametrize("pb", [2, 1])
-def test_attention_split_fp16_part_counts(monkeypatch, pb):
-    """The split-fp16 backward with dS / P in TWO fp16 parts (MFVIT_ATTN_PB=2: f32-grade gradients, the bound of the split-bf16 kernels) and in
-    ONE (the default: 11 bits), with a gradient-scale dO (1e-4: below fp16's normal range - the kernels scale it per (image, head)), at the bench
-    kernels' shape class (B * H = 540: persistent forward, single-pass backward) and on the per-pair kernels (B = 2)."""
+def test_attention_split_fp16_part_counts():
+    """The split-fp16 attention with P in two fp16 parts in the forward and dS / P in ONE in the backward (11 bits), with a gradient-scale dO
+    (1e-4: below fp16's normal range - the kernels scale it per (image, head)), at the bench kernels' shape class (B * H = 540: persistent forward,
+    single-pass backward) and on the per-pair kernels (B = 2)."""
     from mfvit import ops
-    pf = 2
-    monkeypatch.setenv("MFVIT_ATTN_PB", str(pb))
     mode = X3F16Mode()
     H, D, T = 12, 384, 197
     for B in (45, 2):
@@ -341,8 +338,8 @@ def test_attention_split_fp16_part_counts(monkeypatch, pb):
         o_ref.backward(mode.rounded(dout))
         dqkv, dbias = ops.attention_bwd(mode.pack_qkv(qkv), out, mode.pack(dout), lse, H, split=True)
         e_o, e_d = rel_err(mode.unpack(out), o_ref), rel_err(mode.unpack(dqkv), qd.grad)
-        log(f"attention split fp16, parts fwd {pf} bwd {pb} [B={B}] out {e_o:.2e} dqkv {e_d:.2e} dbias {rel_err(dbias, qd.grad.sum((0, 1))):.2e}")
-        assert e_o < SPLIT_TOL and e_d < (2e-4 if pb == 2 else 1e-3)
+        log(f"attention split fp16, parts fwd 2 bwd 1 [B={B}] out {e_o:.2e} dqkv {e_d:.2e} dbias {rel_err(dbias, qd.grad.sum((0, 1))):.2e}")
+        assert e_o < SPLIT_TOL and e_d < 1e-3
 
 
 def test_layernorm_rows_split_and_f16():

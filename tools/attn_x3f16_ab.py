@@ -1,8 +1,7 @@
 """Attention core at the bench shape (B = 128, T = 197, 12 heads x 32), split bf16 qkv (round 4) against split FP16 qkv (MFVIT_X3F16, round 5)
-with P / dS in one or two fp16 parts: error of out / dqkv against float64 on the first images, and time per launch (interleaved rounds in
-ONE process; MFVIT_AB_LIVE=1 makes the library re-read the switches at every launch)."""
+(P in two fp16 parts in the forward, dS / P in one in the backward): error of out / dqkv against float64 on the first images, and time per launch
+(interleaved rounds in ONE process)."""
 import os, sys
-os.environ["MFVIT_AB_LIVE"] = "1"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "multi-feature-vit_amd"))
 import torch
@@ -46,13 +45,11 @@ def f16_rounded(x):
 
 
 refs = {"bf16": ref(ops.split_unpack(q_b.cpu().view(-1, 6 * D)).view(B, T, 3 * D)), "f16": ref(f16_rounded(x))}
-# (MFVIT_ATTN_PF, the one-part forward, existed until the end of round 5: 2.2e-4 on the output for 46 instead of 48 us - profiles/r05_attention_x3f16_ab.txt)
-variants = [("split bf16 qkv (round 4)", q_b, "bf16", None), ("split fp16, P 2 parts / dS 2 parts", q_h, "f16", "2"),
-            ("split fp16, P 2 parts / dS 1 part", q_h, "f16", "1")]
+# (MFVIT_ATTN_PF, the one-part forward, existed until the end of round 5: 2.2e-4 on the output for 46 instead of 48 us - profiles/r05_attention_x3f16_ab.txt;
+# the two-part backward, dS / P in two fp16 parts, was retired later: dqkv at 5e-6 for + 14 % time)
+variants = [("split bf16 qkv (round 4)", q_b, "bf16"), ("split fp16, P 2 parts / dS 1 part", q_h, "f16")]
 outs = {}
-for name, qkv, rk, pb in variants:
-    if pb:
-        os.environ["MFVIT_ATTN_PB"] = pb
+for name, qkv, rk in variants:
     o, lse = ops.attention_fwd(qkv, H, split=True)
     dq, _ = ops.attention_bwd(qkv, o, do, lse, H, want_dbias=False, split=True)
     torch.cuda.synchronize()
@@ -67,9 +64,7 @@ for name, qkv, rk, pb in variants:
 tf = {n: [] for n, *_ in variants}
 tb = {n: [] for n, *_ in variants}
 for rnd in range(5):
-    for name, qkv, rk, pb in variants:
-        if pb:
-            os.environ["MFVIT_ATTN_PB"] = pb
+    for name, qkv, rk in variants:
         o, lse = outs[name]
         tf[name].append(timeit(lambda: ops.attention_fwd(qkv, H, split=True)))
         tb[name].append(timeit(lambda: ops.attention_bwd(qkv, o, do, lse, H, want_dbias=False, split=True)))

@@ -29,8 +29,8 @@ def run():
     return g
 
 
-for env in ({}, {"MFVIT_PP": "0"}, {"MFVIT_ATTN_BWD_SP": "0"}, {"MFVIT_PP": "0", "MFVIT_ATTN_BWD_SP": "0"}, {"MFVIT_TN_PART": "0"}):
-    for k in ("MFVIT_PP", "MFVIT_ATTN_BWD_SP", "MFVIT_TN_PART"):
+for env in ({}, {"MFVIT_PP": "0"}, {"MFVIT_ATTN_BWD_SP": "0"}, {"MFVIT_PP": "0", "MFVIT_ATTN_BWD_SP": "0"}):
+    for k in ("MFVIT_PP", "MFVIT_ATTN_BWD_SP"):
         os.environ.pop(k, None)
     os.environ.update(env)
     run()

@@ -16,7 +16,6 @@ def timeit(fn, flops, name, n=20):
     us = s.elapsed_time(e) * 1e3 / n
     print(f"{name:34s} {us:8.1f} us  {flops/us/1e6:7.1f} TFLOP/s", flush=True)
 x384, x1536, dy1152, dy1536 = r(M, D), r(M, F), r(M, 3*D), r(M, F)
-t = os.environ.get("MFVIT_TN2_TARGET", "def")      # workgroups per launch of gemm_tn_glds, which takes these shapes
 for name, a, b, n, k in (("qkv", dy1152, x384, 3*D, D), ("fc1", dy1536, x384, F, D), ("fc2", x384, x1536, D, F), ("proj", x384, x384, D, D)):
     out = torch.zeros(n, k, device=dev)
-    timeit(lambda: ops.linear_wgrad(a, b, out=out), 2.0*M*n*k, f"wgrad {name} target={t}")
+    timeit(lambda: ops.linear_wgrad(a, b, out=out), 2.0*M*n*k, f"wgrad {name}")
