@@ -76,7 +76,7 @@ typedef struct mfvit_vit_cfg {
     int use_pos;         /* token_input: add the learnable pos_emb (args.pos_embed, fuseattention.py:186-189) */
     int act;             /* MLP activation: 0 erf-GELU (timm Block), 1 ReLU (fuseattention.py:67-72) */
     /* ---- token_input, training: the three dropout sites of the GPT (fuseattention.py:33-34,71,112; config.py:40-42 sets 0.1 each).
-     * 0 = off (evaluation, and the whole ViT path).  Masks are counter-based hashes of (seed, site, element index), regenerated by the
+     * 0 = off (evaluation; ignored in image mode, whose sites are mfvit_vit_drop's).  Masks are counter-based hashes of (seed, site, element index), regenerated by the
      * backward from the same cfg (mfvit_attention_drop_fwd explains the scheme; sites: 1 = embedding, 16 l + 2 = attention of block l,
      * 16 l + 3 = after proj, 16 l + 4 = after the MLP).  The caller draws a fresh seed per forward. */
     float p_embd, p_attn, p_resid;
@@ -116,6 +116,32 @@ int mfvit_vit_forward(const mfvit_vit_cfg* cfg, const float* params, const void*
  * dfeatures: (B,T,dim) f32, read only when stage_hi == depth. */
 int mfvit_vit_backward(const mfvit_vit_cfg* cfg, const float* params, const void* shadow, void* workspace, const float* dfeatures,
                        float* dparams, int stage_hi, int stage_lo, mfvit_stream_t stream);
+
+/* Training-mode regularisation of the image encoder (cfg->token_input = 0): the dropout sites of timm 0.4.9's VisionTransformer that moco-v3's
+ * vits.py passes on (drop_rate, attn_drop_rate, drop_path_rate).  Additive in ABI 5: mfvit_vit_cfg and the entry points above are unchanged
+ * and run no dropout.  Sites (the mask scheme of mfvit_attention_drop_fwd; keep values scaled by 1 / (1 - p); l = block):
+ *    1          pos_drop: x_0 = drop(cat(cls, patch_embed(x)) + pos_embed), cls rows included          rate `drop`      element (row * dim + n)
+ *    16 l + 2   attn.attn_drop on the softmax probabilities                                          rate `attn_drop` ((b * H + h) * T + i) * T + j
+ *    16 l + 3   attn.proj_drop on the output of proj                                                 rate `drop`      row * dim + n
+ *    16 l + 4   the second mlp.drop, on the output of fc2                                            rate `drop`      row * dim + n
+ *    16 l + 5   the first mlp.drop, after the GELU (before fc2; folded into the fc1 epilogue)        rate `drop`      row * mlp_dim + n
+ *    16 l + 6   drop_path of the attention branch: x + s_b * (branch)                                 drop_path[l]     sample b = row / T
+ *    16 l + 7   drop_path of the MLP branch                                                           drop_path[l]     sample b = row / T
+ * (sites 1 - 4 are the GPT's numbers for the same places.)  mfvit_dropout_mask(p, seed, site, n) exports the keeps of any site - with
+ * n = batch for the drop-path sites.  The backward takes the same struct and rebuilds the same masks; its workspace is
+ * mfvit_vit_workspace_bytes_drop (a masked branch needs a scratch row block).  All rates in [0, 1); a rate > 0 needs a 16-bit dtype
+ * (MFVIT_F32 gives MFVIT_EINVAL / 0 bytes).  All rates 0 runs the same kernels, with the same results, as mfvit_vit_forward / _backward. */
+typedef struct mfvit_vit_drop {
+    float drop;               /* pos_drop, attn.proj_drop, both mlp.drop sites */
+    float attn_drop;          /* attn.attn_drop */
+    const float* drop_path;   /* HOST array of cfg->depth per-block drop-path rates (timm: linspace(0, drop_path_rate, depth)), or NULL */
+    uint64_t seed;            /* drawn afresh for every forward by the caller */
+} mfvit_vit_drop;
+size_t mfvit_vit_workspace_bytes_drop(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop);
+int mfvit_vit_forward_drop(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, const float* params, const void* shadow, const float* img,
+                           void* workspace, float* features, mfvit_stream_t stream);
+int mfvit_vit_backward_drop(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, const float* params, const void* shadow, void* workspace,
+                            const float* dfeatures, float* dparams, int stage_hi, int stage_lo, mfvit_stream_t stream);
 
 /* Token-input encoder (cfg->token_input = 1): the GPT of the TransFuser fusion (fuseattention.py:84-212), heads x head_dim with
  * head_dim in {32, 64, 96} (config.py: n_embd 384, n_head 4 -> 96), mlp_dim = block_exp * dim.

@@ -220,6 +220,9 @@ struct GemmP {
     // two-level batch over blockIdx.z = zo * nbi + zi (element offsets; bias/out0 only)
     int nb, nbi;
     long sAo, sAi, sWo, sWi, sOo, sOi, sBo, sBi;
+    DropP drop;        // EPI_BIAS_GELU_DROP: dropout on the activation, keep of element (m, n) = drop_mul(drop, m * N + n);
+                       // REPI_RES_LN_DP: the drop-path factor of row m = drop_mul(drop, m / drop_tpr)
+    int drop_tpr;      // REPI_RES_LN_DP: token rows per sample
 };
 
 // apply the batch offsets of blockIdx.z to a by-value copy of the parameter block

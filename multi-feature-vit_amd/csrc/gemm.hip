@@ -87,13 +87,21 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_tile_kernel(GemmP p) {   // 2 
         __syncthreads();
         copy_tile(rb_t, std::true_type(), (char*)out, ldo * (long)sizeof(T), (long)n0 * EP * (long)sizeof(T));
     };
+    constexpr bool GELU = EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_GELU_DROP;
     float bj[Loop::TN], csums[Loop::TN];
 #pragma unroll
     for (int j = 0; j < Loop::TN; ++j) {
         csums[j] = 0.f;
         const int n = n0 + (wn * Loop::TN + j) * 32 + (lane & 31);
-        bj[j] = ((EPI == EPI_BIAS || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_RELU || EPI == EPI_BIAS_X3F16) && p.bias) ? p.bias[n] : 0.f;
+        bj[j] = ((EPI == EPI_BIAS || GELU || EPI == EPI_BIAS_RELU || EPI == EPI_BIAS_X3F16) && p.bias) ? p.bias[n] : 0.f;
     }
+    // EPI_BIAS_GELU_DROP: keep factor (0 or 1 / (1 - p)) of accumulator (i, j, r).  Rows >= M take row M - 1's mask: their duplicates of that
+    // row are stored too (see above), and must carry the same bytes.
+    auto keep = [&](int i, int j, int r) -> float {
+        int m = m0 + (wm * Loop::TM + i) * 32 + acc_row(r, lane);
+        m = m < p.M ? m : p.M - 1;
+        return drop_mul(p.drop, (unsigned)m * (unsigned)p.N + (unsigned)(n0 + ecol(j)));
+    };
     if constexpr (EPI == EPI_GELU_BWD) {
         // aux = act'(pre-activation) saved by the forward: its tile comes in with 16-byte reads, every lane multiplies its accumulators in
         // place, and only then (barrier) the product goes into the same LDS as a tile of T
@@ -158,7 +166,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_tile_kernel(GemmP p) {   // 2 
         }
     }
     const bool want_grad = p.out0 != nullptr;           // GELU / ReLU epilogues: no-grad forwards pass out0 = NULL and skip the derivative
-    if ((EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_RELU) ? want_grad : true) {
+    if ((GELU || EPI == EPI_BIAS_RELU) ? want_grad : true) {
 #pragma unroll
         for (int j = 0; j < Loop::TN; ++j)
 #pragma unroll
@@ -166,10 +174,14 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_tile_kernel(GemmP p) {   // 2 
 #pragma unroll
                 for (int r = 0; r < 16; r += 2) {     // two rows at a time: one packed conversion per pair of values
                     const float v0 = acc[i][j][r] + bj[j], v1 = acc[i][j][r + 1] + bj[j];
-                    if (EPI == EPI_BIAS_GELU) {
+                    if (GELU) {
                         float g0, g1, d0, d1;
                         gelu_both_t<T>(v0, g0, d0);                         // one erf / exp evaluation for both outputs
                         gelu_both_t<T>(v1, g1, d1);
+                        if constexpr (EPI == EPI_BIAS_GELU_DROP) {          // dropout after the activation: d hpre = d hact * mask * gelu'
+                            const float k0 = keep(i, j, r), k1 = keep(i, j, r + 1);
+                            g0 *= k0; d0 *= k0; g1 *= k1; d1 *= k1;
+                        }
                         acc[i][j][r] = g0;                                  // gelu(pre): the second output, stored below
                         acc[i][j][r + 1] = g1;
                         store_elem_pair<AX>((AX*)trow(i, r, AROWB + 16), (AX*)trow(i, r + 1, AROWB + 16), ecol(j), d0, d1);   // out0 = gelu'(pre)
@@ -184,7 +196,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_tile_kernel(GemmP p) {   // 2 
                         store_elem_pair<T>((T*)trow(i, r, ROWB + 16), (T*)trow(i, r + 1, ROWB + 16), ecol(j), v0, v1);
                     }
                 }
-        if (EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_RELU) {
+        if (GELU || EPI == EPI_BIAS_RELU) {
             __syncthreads();
             copy_tile(rb_a, std::true_type(), (char*)p.out0, p.ldo0 * (long)sizeof(AX), (long)n0 * (long)sizeof(AX));
         } else {
@@ -200,6 +212,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_tile_kernel(GemmP p) {   // 2 
                 for (int r = 0; r < 16; ++r) {
                     const float v = acc[i][j][r] + bj[j];
                     acc[i][j][r] = EPI == EPI_BIAS_RELU ? fmaxf(v, 0.f) : gelu_t<T>(v);
+                    if constexpr (EPI == EPI_BIAS_GELU_DROP) acc[i][j][r] *= keep(i, j, r);
                 }
     }
     if (EPI == EPI_GELU_BWD && p.cs0 && p.cpart) {   // per-workgroup partial column sums: [m-tile][N], plain stores
@@ -212,7 +225,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_tile_kernel(GemmP p) {   // 2 
         __syncthreads();
         if (tid < BN) p.cpart[(long)(m0 / BM) * p.N + n0 + tid] = sc[tid] + sc[BN + tid];
     }
-    if (EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_RELU) {
+    if (GELU || EPI == EPI_BIAS_RELU) {
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < Loop::TN; ++j)
@@ -1262,6 +1275,13 @@ int gemm_nt_tile(int dtype, int epi, const GemmP& p, hipStream_t st) {
         case EPI_NONE: return tile_by_dtype<EPI_NONE>(dtype, p, st);
         case EPI_BIAS_RELU: return tile_by_dtype<EPI_BIAS_RELU>(dtype, p, st);
         case EPI_BIAS_X3F16: return dtype == MFVIT_BF16X3 ? launch_tile<sbf16, EPI_BIAS_X3F16>(p, st) : MFVIT_EINVAL;
+        case EPI_BIAS_GELU_DROP:                                                     // (the dropout sites exist for the 16-bit operand types)
+            switch (dtype) {
+                case MFVIT_BF16: return launch_tile<bf16, EPI_BIAS_GELU_DROP>(p, st);
+                case MFVIT_BF16X3: return launch_tile<sbf16, EPI_BIAS_GELU_DROP>(p, st);
+                case MFVIT_F16: return launch_tile<f16, EPI_BIAS_GELU_DROP>(p, st);
+            }
+            return MFVIT_EINVAL;
     }
     return MFVIT_EINVAL;
 }

@@ -99,7 +99,8 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_pp_kernel(GemmP p, int ntiles,
     typedef typename Vec4<T>::elem E16;
     typedef typename act_grad_type<T>::type AX;                // saved activation derivative: fp16 for split tensors, T otherwise (2 bytes either way)
     typedef pp_u32x4 u32x4;
-    constexpr bool ACT = EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_RELU;
+    constexpr bool GELU = EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_GELU_DROP;
+    constexpr bool ACT = GELU || EPI == EPI_BIAS_RELU;
     constexpr bool HAS_BIAS = EPI == EPI_BIAS || ACT || EPI == EPI_BIAS_X3F16;
     // Accumulator layout.  SWAP (every epilogue but x act'): MFMA operands swapped (W fragment first), so a lane owns ONE row (lane & 15) of a 16 x 16 tile and FOUR
     // CONSECUTIVE columns 4 (lane >> 4) .. + 3 - the bias enters as the accumulators' initial value (4 registers per column tile, fetched once per tile), the 16-bit
@@ -334,9 +335,16 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_pp_kernel(GemmP p, int ntiles,
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
                             const float v = acc[i][j][r];
-                            if constexpr (EPI == EPI_BIAS_GELU) {
+                            if constexpr (GELU) {
                                 float gg, dd;
                                 gelu_both_t<T>(v, gg, dd);      // one erf / exp evaluation for both outputs
+                                if constexpr (EPI == EPI_BIAS_GELU_DROP) {
+                                    // dropout after the activation (element m * N + n; rows past M take row M - 1's mask: flush stores their duplicates there)
+                                    int m = row0 + l15;
+                                    m = m < p.M ? m : p.M - 1;
+                                    const float k = drop_mul(p.drop, (unsigned)m * (unsigned)p.N + (unsigned)(nw + 16 * j + 4 * q4 + r));
+                                    gg *= k; dd *= k;
+                                }
                                 g[r] = gg; d[r] = dd;
                             } else {                            // fuseattention.py:69: nn.ReLU
                                 g[r] = fmaxf(v, 0.f); d[r] = v > 0.f ? 1.f : 0.f;
@@ -482,6 +490,7 @@ template <typename T> int pp_by_epi(int epi, const GemmP& p, hipStream_t st) {
     switch (epi) {
         case EPI_BIAS: return launch_pp<T, EPI_BIAS>(p, st);
         case EPI_BIAS_GELU: return launch_pp<T, EPI_BIAS_GELU>(p, st);
+        case EPI_BIAS_GELU_DROP: return launch_pp<T, EPI_BIAS_GELU_DROP>(p, st);
         case EPI_GELU_BWD: return launch_pp<T, EPI_GELU_BWD>(p, st);
         case EPI_NONE: return launch_pp<T, EPI_NONE>(p, st);
         case EPI_BIAS_RELU: return launch_pp<T, EPI_BIAS_RELU>(p, st);

@@ -85,7 +85,7 @@ __device__ __forceinline__ void rp_gload16(f32x4v& dst, unsigned voff, const cha
 __device__ __forceinline__ f32x4v rp_mfma(bf16x8 a, bf16x8 b, f32x4v c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ f32x4v rp_mfma(f16x8 a, f16x8 b, f32x4v c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
 
-// MODE: the two row-complete epilogues (REPI_RES_LN = 0, REPI_LNBWD_RES = 1; N = 384: one pass, npass = 1).  (Round 3 also ran the plain
+// MODE: the row-complete epilogues (REPI_RES_LN = 0, REPI_LNBWD_RES = 1, REPI_RES_LN_DP = 2 - the forward one with a per-sample drop-path factor; N = 384: one pass, npass = 1).  (Round 3 also ran the plain
 // linears on this kernel as `npass` passes of 384 columns, MFVIT_ROWT=1: qkv 107 - 119 us against 80 of the 128 x 128 tile kernel, fc1 + GELU
 // 144 - 152 against 135 - the 8-byte-per-lane partial-line stores of this accumulator layout cost 20 - 45 us per launch; removed in round 4,
 // the measurements stay in DESIGN.md 5.)
@@ -514,11 +514,13 @@ __device__ __forceinline__ void rowp_body(GemmP& p, const int tile, const int m0
         __syncthreads();
     };
 
-    if constexpr (REPI == REPI_RES_LN) {
+    if constexpr (REPI == REPI_RES_LN || REPI == REPI_RES_LN_DP) {
         const float invN = 1.0f / (float)RP_N;
         float part[MF];
         fresh_lane();
-        // v = (residual + products) + bias: the residual rows were the accumulators' initial values
+        // v = (residual + products) + bias: the residual rows were the accumulators' initial values.  REPI_RES_LN_DP (drop path, timm's per-sample
+        // stochastic depth): the accumulators started at zero, and v = aux + s_b (products + bias) with aux the residual rows (f32, ldaux) and
+        // s_b = drop_mul(drop, row / drop_tpr) the factor of the row's sample - 0 or 1 / (1 - p)
         f32x4v bj[3], gj[3], bej[3];                    // (gamma / beta too: requested in front of the x_out stores, or the wait for them waits for the stores)
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
@@ -530,13 +532,27 @@ __device__ __forceinline__ void rowp_body(GemmP& p, const int tile, const int m0
 #pragma unroll
         for (int i = 0; i < MF; ++i) {
             float s = 0.f;
+            if constexpr (REPI == REPI_RES_LN_DP) {
+                const unsigned m = (unsigned)row_of(i);
+                const float sk = drop_mul(p.drop, m / (unsigned)p.drop_tpr);
 #pragma unroll
-            for (int j = 0; j < 3; ++j)
+                for (int j = 0; j < 3; ++j) {
+                    const f32x4v rv = *(const f32x4v*)((const float*)p.aux + m * (unsigned)p.ldaux + ncol0 + 16 * j);
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    acc[i][j][r] += bj[j][r];
-                    s += acc[i][j][r];
+                    for (int r = 0; r < 4; ++r) {
+                        acc[i][j][r] = rv[r] + sk * (acc[i][j][r] + bj[j][r]);
+                        s += acc[i][j][r];
+                    }
                 }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 3; ++j)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        acc[i][j][r] += bj[j][r];
+                        s += acc[i][j][r];
+                    }
+            }
             part[i] = s;
         }
         row_total(part, red);
@@ -879,7 +895,7 @@ template <int MODE, typename T> int launch_rowp(const GemmP& p, hipStream_t st) 
     if (geo.S > 1 && tiles > 512) return MFVIT_EINVAL;                  // (cannot happen: tiles <= #CUs)
     q.splits = geo.S;
     const int grid = tiles * geo.S;                                      // workgroups: tile * S + k split
-    ProfScope ps(MODE == REPI_RES_LN ? PROF_GEMM_ROW_FWD : PROF_GEMM_ROW_BWD, 2.0 * p.M * p.N * p.K, 0, st);
+    ProfScope ps(MODE != REPI_LNBWD_RES ? PROF_GEMM_ROW_FWD : PROF_GEMM_ROW_BWD, 2.0 * p.M * p.N * p.K, 0, st);
     const int mf = (rpt + 15) / 16;
     if (mf >= 2 && tiles > 1 && rpt % 16) {
         // mixed heights: n_lo tiles of 16 (mf - 1) rows, the rest as many rows as it takes, at most 16 mf and the mode's cap
@@ -932,8 +948,8 @@ bool gemm_nt_rowp_supported(int dtype, int repi, const GemmP& p) {
     static int sw_on = INT_MIN;
     if ((dtype != MFVIT_BF16X3 && dtype != MFVIT_BF16 && dtype != MFVIT_F16) || env_switch("MFVIT_ROWP", 1, sw_on) == 0) return false;
     const bool split = dtype == MFVIT_BF16X3;
-    if (repi != REPI_RES_LN && repi != REPI_LNBWD_RES) return false;
-    const int minm = repi == REPI_RES_LN ? RP_MINM_FWD : RP_MINM_BWD;
+    if (repi != REPI_RES_LN && repi != REPI_LNBWD_RES && repi != REPI_RES_LN_DP) return false;
+    const int minm = repi == REPI_LNBWD_RES ? RP_MINM_BWD : RP_MINM_FWD;
     // an even number of stages (128-byte k groups: 32 logical columns split, 64 plain), at least 4
     if (p.N != RP_N || p.K % (split ? 64 : 128) || p.K < (split ? 128 : 256) || p.M < minm || p.nb > 1) return false;
     if (!split && p.res_t) return false;                                 // (the operand-type residual-gradient copy is a split-bf16 path)
@@ -948,6 +964,9 @@ bool gemm_nt_rowp_supported(int dtype, int repi, const GemmP& p) {
         return true;
     }
     if (!p.out1 || !p.gamma || !p.beta) return false;
+    if (repi == REPI_RES_LN_DP) {   // the residual rows come in through aux (f32), read in the epilogue with 32-bit float offsets; res must be unset
+        if (p.res || !p.aux || p.drop_tpr <= 0 || p.ldaux % 4 || (size_t)p.aux % 16 || (unsigned long long)p.M * p.ldaux >= (1ull << 32)) return false;
+    }
     if (p.res && (unsigned long long)p.M * p.ldres * 4 >= (1ull << 32)) return false;                                 // 32-bit offsets of the asm residual loads
     if ((unsigned long long)p.M * p.lda * 2 >= (1ull << 32) || (unsigned long long)p.N * p.ldw * 2 >= (1ull << 32)) return false;
     if (p.lda % 8 || p.ldw % 8 || (p.out0 && p.ldo0 % 4) || p.ldo1 % (p.y_f32 ? 4 : 8) || (p.res && p.ldres % 4)) return false;
@@ -966,6 +985,7 @@ template <int MODE> static int launch_rowp_t(int dtype, const GemmP& p, hipStrea
 
 int gemm_nt_rowp(int dtype, int repi, const GemmP& p, hipStream_t st) {
     if (repi == REPI_RES_LN) return launch_rowp_t<REPI_RES_LN>(dtype, p, st);
+    if (repi == REPI_RES_LN_DP) return launch_rowp_t<REPI_RES_LN_DP>(dtype, p, st);
     if (repi == REPI_LNBWD_RES) {
         const int rc = launch_rowp_t<REPI_LNBWD_RES>(dtype, p, st);
         if (rc != MFVIT_OK || !p.cpart) return rc;

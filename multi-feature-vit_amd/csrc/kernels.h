@@ -5,8 +5,10 @@
 namespace mfvit {
 
 enum { EPI_BIAS = 0, EPI_BIAS_GELU = 1, EPI_GELU_BWD = 2, EPI_NONE = 3, EPI_BIAS_RELU = 4,    // 4: out0 = relu'(pre), out1 = relu(pre)
-       EPI_BIAS_X3F16 = 5 };                                                                  // 5: bias, output written as split FP16 (sbf16 inputs only: qkv)
-enum { REPI_RES_LN = 0, REPI_LNBWD_RES = 1 };
+       EPI_BIAS_X3F16 = 5,                                                                    // 5: bias, output written as split FP16 (sbf16 inputs only: qkv)
+       EPI_BIAS_GELU_DROP = 6 };   // 6: EPI_BIAS_GELU with dropout on the activation (GemmP::drop, element m * N + n): out1 = gelu * mask, out0 = gelu' * mask
+enum { REPI_RES_LN = 0, REPI_LNBWD_RES = 1,
+       REPI_RES_LN_DP = 2 };   // 2: gemm_rowp only - REPI_RES_LN with x = aux + drop_mul(drop, row / drop_tpr) * (products + bias) (drop path)
 
 int gemm_nt_tile(int dtype, int epi, const GemmP& p, hipStream_t st);
 bool gemm_nt_pp_supported(int dtype, int epi, const GemmP& p);     // gemm_pp.hip (round 6): persistent 256 x 128 ping-pong tile kernel, 16-bit types, large M
@@ -85,9 +87,10 @@ int attn_bwd_tiled_drop(int dtype, const void* qkv, const void* out, const void*
 bool attn_tiled_supported(int dtype, int Tn, int HDim);
 // elementwise.hip: the keep mask (1 / 0 bytes) of n elements of one dropout site - what the kernels regenerate from (seed, site, index)
 int dropout_mask(DropP drop, long n, unsigned char* out, hipStream_t st);
-// x = res + drop(t) -> LayerNorm (t: a GEMM output in the operand type, or a0 (+ a1[row % mod1]) in f32); see elementwise.hip
+// x = res + dpath(row / tpr) * drop(t) -> LayerNorm (t: a GEMM output in the operand type, or a0 (+ a1[row % mod1]) in f32); see elementwise.hip
 int drop_add_ln_rows(int dtype, int N, const void* tin, long ldt, const float* a0, long lda0, const float* a1, long lda1, int mod1,
-                     const float* res, long ldres, DropP drop, float* xout, long ldx, void* y, long ldy, int y_f32, const float* gamma,
-                     const float* beta, float eps, float* mean, float* rstd, int rows, hipStream_t st);
-int mask_scale_rows(int dtype, bool f32, const void* src, long lds_, void* dst, long ldd, DropP drop, int rows, int N, hipStream_t st);
+                     const float* res, long ldres, DropP drop, DropP dpath, int tpr, float* xout, long ldx, void* y, long ldy, int y_f32,
+                     const float* gamma, const float* beta, float eps, float* mean, float* rstd, int rows, hipStream_t st);
+int mask_scale_rows(int dtype, bool f32, const void* src, long lds_, void* dst, long ldd, DropP drop, DropP dpath, int tpr, int rows, int N,
+                    hipStream_t st);
 }  // namespace mfvit

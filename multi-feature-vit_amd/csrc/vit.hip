@@ -39,9 +39,12 @@ struct Dims {
     int dtype, B, T, np, D, depth, H, HD, F, M, Mp, es, ep;   // es: bytes per LOGICAL element of a dtype tensor; ep: storage elements per logical one
     bool save, tok, use_pos;
     int act;
-    float p_embd, p_attn, p_resid;      // token-input mode: dropout sites (0 = off)
+    float p_embd, p_attn, p_resid;      // dropout sites (0 = off): token-input mode from the cfg, image mode from mfvit_vit_drop
+    float p_gelu;                       // image mode: dropout after the MLP activation (timm Mlp.drop, folded into the fc1 epilogue)
+    const float* dpr;                   // image mode: drop-path rate of every block (host array of depth entries) or NULL
     unsigned long long seed;
     bool drop;                          // any site active
+    bool rdrop;                         // a residual branch is masked (p_resid > 0 or a drop path): branch -> scratch, then a dropout + residual + LN row pass
     bool unfused;                       // residual + LayerNorm (and its backward) as row passes behind plain tile GEMMs instead of the row-complete GEMM kernels
 };
 
@@ -76,7 +79,10 @@ bool get_dims(const mfvit_vit_cfg* c, Dims& d) {
     d.p_resid = d.tok ? c->p_resid : 0.f;
     for (float pp : {d.p_embd, d.p_attn, d.p_resid})
         if (!(pp >= 0.f && pp < 1.f)) return false;
+    d.p_gelu = 0.f;
+    d.dpr = nullptr;
     d.drop = d.p_embd > 0.f || d.p_attn > 0.f || d.p_resid > 0.f;
+    d.rdrop = d.p_resid > 0.f;
     if (d.drop && c->dtype == MFVIT_F32) return false;               // the dropout stages exist for the 16-bit operand types
     d.seed = ((unsigned long long)c->seed_hi << 32) | c->seed_lo;
     if (d.HD != 32 && d.HD != 64 && d.HD != 96) return false;
@@ -86,6 +92,30 @@ bool get_dims(const mfvit_vit_cfg* c, Dims& d) {
     // (read on every call, not cached: the workspace layout depends on it, and a test flips it between two encoders of one process)
     const char* ue = getenv("MFVIT_UNFUSED_ROWS");
     d.unfused = d.D != 384 || (ue && ue[0] == '1');
+    return true;
+}
+
+// Image mode in training (mfvit_vit_drop; NULL = none): timm's dropout sites.  pos_drop, proj_drop, the MLP's two drops: x->drop; the attention
+// probabilities: x->attn_drop; the drop path of block l's two branches: x->drop_path[l].  Sites: see include/mfvit.h.
+bool get_dims(const mfvit_vit_cfg* c, const mfvit_vit_drop* x, Dims& d) {
+    if (!get_dims(c, d)) return false;
+    if (!x) return true;
+    if (d.tok) return false;                                           // (the GPT keeps its own three sites in the cfg)
+    for (float pp : {x->drop, x->attn_drop})
+        if (!(pp >= 0.f && pp < 1.f)) return false;
+    bool dpath = false;
+    if (x->drop_path)
+        for (int l = 0; l < d.depth; ++l) {
+            if (!(x->drop_path[l] >= 0.f && x->drop_path[l] < 1.f)) return false;
+            dpath = dpath || x->drop_path[l] > 0.f;
+        }
+    d.p_embd = d.p_resid = d.p_gelu = x->drop;
+    d.p_attn = x->attn_drop;
+    d.dpr = dpath ? x->drop_path : nullptr;
+    d.seed = x->seed;
+    d.drop = x->drop > 0.f || x->attn_drop > 0.f || dpath;
+    d.rdrop = x->drop > 0.f || dpath;
+    if (d.drop && c->dtype == MFVIT_F32) return false;                 // the dropout stages exist for the 16-bit operand types
     return true;
 }
 
@@ -164,7 +194,7 @@ struct WsLayout {
     size_t y1, qkv, attn, lse, xmid, st2, y2, hpre, hact;
     // backward scratch
     size_t gx, gmid, gxT, gmidT, dhpre, dattn, dqkv, colscratch, colpart, colpart_stride = 0, tnpart, tnpart_stride = 0;
-    size_t dtmp;                // token-input mode with residual dropout: [M][D] of the operand type (branch output before the dropout; masked dY)
+    size_t dtmp;                // with a masked residual branch (Dims::rdrop): [M][D] of the operand type (branch output before the dropout; masked dY)
     size_t kpart;               // gemm_rowp with K splits (small M): partial accumulator tiles, 264 workgroups x 7 x 12 x 512 floats (gemm_rowp.hip)
     size_t utmp;                // unfused path: [M][D] of the operand type (output of the plain tile GEMM in front of a LayerNorm / LayerNorm-backward row pass)
     size_t domax;               // backward: the largest |d attn| of every (image, head) of every block, f32 bits [depth][B][H] (proj data gradient -> attention backward)
@@ -222,7 +252,7 @@ WsLayout ws_layout(const Dims& d) {
         W.gx = W.gmid = W.gxT = W.gmidT = W.dhpre = W.dattn = W.dqkv = W.colscratch = W.colpart = W.tnpart = o;
         W.pp_stride = 0;
     }
-    W.dtmp = o; o += (d.tok && d.p_resid > 0.f) ? align256(M * D * es) : 0;
+    W.dtmp = o; o += d.rdrop ? align256(M * D * es) : 0;
     W.kpart = o; o += d.D == 384 ? align256((size_t)264 * 7 * 12 * 512 * 4) : 0;
     W.utmp = o; o += align256(M * D * es);     // always there (1 / 200 of the workspace): the layout does not depend on which path a call takes
     W.domax = o; o += d.save ? align256((size_t)d.depth * d.B * d.H * 4) : 0;
@@ -319,6 +349,11 @@ size_t mfvit_vit_workspace_bytes(const mfvit_vit_cfg* cfg) {
     if (!get_dims(cfg, d)) return 0;
     return ws_layout(d).total;
 }
+size_t mfvit_vit_workspace_bytes_drop(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop) {
+    Dims d;
+    if (!get_dims(cfg, drop, d)) return 0;
+    return ws_layout(d).total;
+}
 
 int mfvit_vit_prepare_shadow(const mfvit_vit_cfg* cfg, const float* params, void* shadow, mfvit_stream_t stream) {
     Dims d;
@@ -344,10 +379,10 @@ int mfvit_vit_prepare_shadow(const mfvit_vit_cfg* cfg, const float* params, void
 
 // Shared forward of the two front ends: ViT-S/16 (img = (B,3,H,W) image, patch embedding + cls token) and the token-input GPT
 // (img = (B,T,dim) tokens, + pos_emb).  Everything behind x_0 / LN1_0 is the same pre-LN block stack.
-static int encoder_forward(const mfvit_vit_cfg* cfg, const float* params, const void* shadow, const float* img, void* workspace,
-                           float* features, mfvit_stream_t stream, bool want_tokens) {
+static int encoder_forward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* dropcfg, const float* params, const void* shadow, const float* img,
+                           void* workspace, float* features, mfvit_stream_t stream, bool want_tokens) {
     Dims d;
-    if (!get_dims(cfg, d) || !params || !shadow || !img || !workspace || !features) return MFVIT_EINVAL;
+    if (!get_dims(cfg, dropcfg, d) || !params || !shadow || !img || !workspace || !features) return MFVIT_EINVAL;
     if (d.tok != want_tokens) return MFVIT_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const ParamLayout L = param_layout(d);
@@ -365,12 +400,26 @@ static int encoder_forward(const mfvit_vit_cfg* cfg, const float* params, const 
     auto pblk = [&](int l) { return params + L.blk0 + (long)l * L.blk_stride; };
     auto sblk = [&](int l) { return sh + S.blk0 + (size_t)l * S.blk_stride; };
 
-    // dropout sites of the token-input (GPT) mode, see mfvit_vit_cfg
+    // dropout sites (include/mfvit.h): the GPT's from the cfg, the ViT's from mfvit_vit_drop
     auto site = [](int l, int which) { return 16u * (unsigned)l + (unsigned)which; };
+    const DropP off = make_drop(0.f, 0, 0);
+    auto dpath = [&](int l, int which) { return make_drop(d.dpr ? d.dpr[l] : 0.f, d.seed, site(l, which)); };   // per sample: keep of row r = sample r / T
+    // Drop path as the only masked branch (the fine-tune recipe: drop_rate = 0, drop_path_rate > 0) stays on the row-complete kernel: its drop-path
+    // epilogue (REPI_RES_LN_DP, gemm_rowp.hip) adds the residual rows (aux) to the sample-scaled branch.  p: the REPI_RES_LN parameters of the site.
+    // Returns false (nothing launched) where the kernel does not apply; the row pass below takes the site then.
+    auto rowp_dpath = [&](GemmP p, DropP dp, int& rc) -> bool {
+        if (!d.rdrop || d.p_resid > 0.f || d.unfused) return false;
+        p.aux = p.res; p.ldaux = p.ldres; p.res = nullptr; p.ldres = 0;
+        p.drop = dp; p.drop_tpr = d.T;
+        p.kpart = (float*)(ws + W.kpart);
+        if (!gemm_nt_rowp_supported(d.dtype, REPI_RES_LN_DP, p)) return false;
+        rc = gemm_nt_rowp(d.dtype, REPI_RES_LN_DP, p, st);
+        return true;
+    };
     if (d.tok && d.p_embd > 0.f) {
         // x_0 = drop(tokens + pos_emb) (fuseattention.py:187 `self.drop(self.pos_emb + token_embeddings)`); LN1_0 -> y1_0
         MFVIT_TRY(drop_add_ln_rows(d.dtype, d.D, nullptr, 0, img, D, d.use_pos ? params + L.pos : nullptr, D, d.T, nullptr, 0,
-                                   make_drop(d.p_embd, d.seed, 1), xbuf(0), D, blk(0) + W.y1, D * e, 0, pblk(0) + L.ln1_w, pblk(0) + L.ln1_b,
+                                   make_drop(d.p_embd, d.seed, 1), off, 1, xbuf(0), D, blk(0) + W.y1, D * e, 0, pblk(0) + L.ln1_w, pblk(0) + L.ln1_b,
                                    eps, stat(0), stat(0) + d.M, d.M, st));
     } else if (d.tok) {
         // token input (fuseattention.py:186-189): x_0 = tokens (+ pos_emb, shared by the batch); LN1_0 -> y1_0.  One row kernel pass.
@@ -407,6 +456,10 @@ static int encoder_forward(const mfvit_vit_cfg* cfg, const float* params, const 
     // cls rows: x_0[b,0] = cls_token + pos_embed[0]; LN1_0
     MFVIT_TRY(ln_rows(d.dtype, d.D, params + L.cls, 0, params + L.pos, D, 1, xbuf(0), D, blk(0) + W.y1, D * e, 0, pblk(0) + L.ln1_w,
                       pblk(0) + L.ln1_b, eps, stat(0), stat(0) + d.M, d.B, d.T, 0, 1, st));
+    if (d.p_embd > 0.f)
+        // timm pos_drop: x_0 = drop(cat(cls, patch_embed(x)) + pos_embed), cls rows included; in place, then LN1_0 again
+        MFVIT_TRY(drop_add_ln_rows(d.dtype, d.D, nullptr, 0, xbuf(0), D, nullptr, 0, 0, nullptr, 0, make_drop(d.p_embd, d.seed, 1), off, 1, xbuf(0), D,
+                                   blk(0) + W.y1, D * e, 0, pblk(0) + L.ln1_w, pblk(0) + L.ln1_b, eps, stat(0), stat(0) + d.M, d.M, st));
     }
 
     for (int l = 0; l < d.depth; ++l) {
@@ -443,14 +496,24 @@ static int encoder_forward(const mfvit_vit_cfg* cfg, const float* params, const 
             p.out1 = b + W.y2; p.ldo1 = D * e;
             p.gamma = pb + L.ln2_w; p.beta = pb + L.ln2_b; p.eps = eps;
             p.mean = (float*)(b + W.st2); p.rstd = (float*)(b + W.st2) + d.M;
-            if (d.p_resid > 0.f) {
-                // xmid = x + resid_drop(proj(attn)) (fuseattention.py:57): plain GEMM + bias, then dropout + residual + LN2 in one row pass
+            int rc = MFVIT_OK;
+            bool done;
+            {
+                ProfTag tag(PROF_TAG_MHSA_PROJ);
+                done = rowp_dpath(p, dpath(l, 6), rc);
+            }
+            if (done) {
+                MFVIT_TRY(rc);
+            } else if (d.rdrop) {
+                // xmid = x + resid_drop(proj(attn)) (fuseattention.py:57; timm: x + drop_path(proj_drop(proj(attn)))): plain GEMM + bias, then
+                // dropout (element mask x per-sample drop-path factor) + residual + LN2 in one row pass
                 GemmP q = zero_gemm();
                 q.A = p.A; q.lda = p.lda; q.W = p.W; q.ldw = p.ldw; q.M = p.M; q.N = p.N; q.K = p.K; q.bias = p.bias;
                 q.out0 = ws + W.dtmp; q.ldo0 = D * e;
                 MFVIT_TRY(gemm_nt_tile(d.dtype, EPI_BIAS, q, st));
                 MFVIT_TRY(drop_add_ln_rows(d.dtype, d.D, ws + W.dtmp, D * e, nullptr, 0, nullptr, 0, 0, xbuf(l), D,
-                                           make_drop(d.p_resid, d.seed, site(l, 3)), (float*)(b + W.xmid), D, b + W.y2, D * e, 0, p.gamma, p.beta,
+                                           make_drop(d.p_resid, d.seed, site(l, 3)), dpath(l, 6), d.T, (float*)(b + W.xmid), D, b + W.y2, D * e, 0,
+                                           p.gamma, p.beta,
                                            eps, p.mean, p.rstd, d.M, st));
             } else if (d.unfused) {
                 // plain GEMM + bias -> scratch, then residual + LN2 as one row pass
@@ -466,7 +529,7 @@ static int encoder_forward(const mfvit_vit_cfg* cfg, const float* params, const 
                 MFVIT_TRY(gemm_nt_row(d.dtype, REPI_RES_LN, p, st));
             }
         }
-        {   // hpre = y2 W1^T + b1 ; hact = gelu(hpre)
+        {   // hpre = y2 W1^T + b1 ; hact = gelu(hpre)   (training: hact = drop(gelu(hpre)), out0 = gelu'(hpre) * mask - timm Mlp.drop)
             GemmP p = zero_gemm();
             p.A = b + W.y2; p.lda = D * e;
             p.W = hw ? (const void*)(sb + S.fc1_w) : (const void*)(pb + L.fc1_w); p.ldw = D * e;
@@ -474,7 +537,8 @@ static int encoder_forward(const mfvit_vit_cfg* cfg, const float* params, const 
             p.bias = pb + L.fc1_b;
             p.out0 = d.save ? b + W.hpre : nullptr; p.ldo0 = F;      // act'(pre) in act_grad_type<T> (gemm.hip): F elements per row
             p.out1 = b + W.hact; p.ldo1 = F * e;
-            MFVIT_TRY(gemm_nt_tile(d.dtype, d.act == 1 ? EPI_BIAS_RELU : EPI_BIAS_GELU, p, st));
+            p.drop = make_drop(d.p_gelu, d.seed, site(l, 5));
+            MFVIT_TRY(gemm_nt_tile(d.dtype, d.act == 1 ? EPI_BIAS_RELU : (d.p_gelu > 0.f ? EPI_BIAS_GELU_DROP : EPI_BIAS_GELU), p, st));
         }
         {   // x_{l+1} = xmid + hact W2^T + b2 ; y = LN(next norm1 | final norm)
             const bool last = l + 1 == d.depth;
@@ -494,14 +558,18 @@ static int encoder_forward(const mfvit_vit_cfg* cfg, const float* params, const 
             }
             p.eps = eps;
             p.mean = stat(l + 1); p.rstd = stat(l + 1) + d.M;
-            if (d.p_resid > 0.f) {
-                // x_{l+1} = xmid + Dropout(fc2(relu(fc1(y2)))) (fuseattention.py:67-72,80)
+            int rc = MFVIT_OK;
+            if (rowp_dpath(p, dpath(l, 7), rc)) {
+                MFVIT_TRY(rc);
+            } else if (d.rdrop) {
+                // x_{l+1} = xmid + Dropout(fc2(relu(fc1(y2)))) (fuseattention.py:67-72,80; timm: xmid + drop_path(drop(fc2(..))))
                 GemmP q = zero_gemm();
                 q.A = p.A; q.lda = p.lda; q.W = p.W; q.ldw = p.ldw; q.M = p.M; q.N = p.N; q.K = p.K; q.bias = p.bias;
                 q.out0 = ws + W.dtmp; q.ldo0 = D * e;
                 MFVIT_TRY(gemm_nt_tile(d.dtype, EPI_BIAS, q, st));
                 MFVIT_TRY(drop_add_ln_rows(d.dtype, d.D, ws + W.dtmp, D * e, nullptr, 0, nullptr, 0, 0, (const float*)(b + W.xmid), D,
-                                           make_drop(d.p_resid, d.seed, site(l, 4)), xbuf(l + 1), D, p.out1, p.ldo1, p.y_f32, p.gamma, p.beta, eps,
+                                           make_drop(d.p_resid, d.seed, site(l, 4)), dpath(l, 7), d.T, xbuf(l + 1), D, p.out1, p.ldo1, p.y_f32,
+                                           p.gamma, p.beta, eps,
                                            p.mean, p.rstd, d.M, st));
             } else if (d.unfused) {
                 GemmP q = zero_gemm();
@@ -520,10 +588,10 @@ static int encoder_forward(const mfvit_vit_cfg* cfg, const float* params, const 
 }
 
 // Shared backward; dinput (token-input mode only): d loss / d tokens, written by the embedding stage.
-static int encoder_backward(const mfvit_vit_cfg* cfg, const float* params, const void* shadow, void* workspace, const float* dfeatures,
-                            float* dparams, float* dinput, int stage_hi, int stage_lo, mfvit_stream_t stream, bool want_tokens) {
+static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* dropcfg, const float* params, const void* shadow, void* workspace,
+                            const float* dfeatures, float* dparams, float* dinput, int stage_hi, int stage_lo, mfvit_stream_t stream, bool want_tokens) {
     Dims d;
-    if (!get_dims(cfg, d) || !params || !shadow || !workspace || !dparams) return MFVIT_EINVAL;
+    if (!get_dims(cfg, dropcfg, d) || !params || !shadow || !workspace || !dparams) return MFVIT_EINVAL;
     if (!d.save || d.tok != want_tokens) return MFVIT_EINVAL;
     if (stage_hi > d.depth || stage_lo < -1 || stage_lo > stage_hi) return MFVIT_EINVAL;
     hipStream_t st = (hipStream_t)stream;
@@ -552,7 +620,7 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const float* params, const
         ColpartBatch* prev; bool on;
         BatchScope(ColpartBatch* b, bool on_) : on(on_) { if (on) prev = colpart_batch_begin(b); }
         ~BatchScope() { if (on) colpart_batch_begin(prev); }
-    } batch_scope(&cbatch, !(d.p_resid > 0.f));
+    } batch_scope(&cbatch, !d.rdrop);
     // split partials of the weight-gradient GEMMs through scratch - plain stores, every launch into its OWN slot - and ONE batched reduce launch at
     // the end of every BLOCK that adds the splits in a fixed order: dW is the same bits on every run (the float atomics it replaces add in whatever
     // order the workgroups finish).  Round 3 measured the same idea with a reduce launch behind EVERY gradient as a loss (77.2 -> 80.8 us per
@@ -577,11 +645,11 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const float* params, const
     // the whole-step HIP graph of round 5 gained nothing, 8.22 vs 8.12 ms, and was removed in round 6)
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     const bool capturing = hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
-    const bool side_wanted = d.M >= 1024 && d.M <= 4096 && g_wgrad_stream.load(std::memory_order_relaxed) != 0 && !(d.p_resid > 0.f) &&
+    const bool side_wanted = d.M >= 1024 && d.M <= 4096 && g_wgrad_stream.load(std::memory_order_relaxed) != 0 && !d.rdrop &&
                              !capturing;
     static SideStream no_side;
     SideStream& ss = side_wanted ? side_stream(st) : no_side;
-    // (residual dropout: the masked dY copies live in ONE scratch buffer - everything stays on the caller's stream)
+    // (residual dropout / drop path: the masked dY copies live in ONE scratch buffer - everything stays on the caller's stream)
     // Default since round 5: the side stream at SMALL M only (1,024 ... 4,096 token rows: 6 - 20 images) - there no kernel fills the chip, the launches of a
     // block are a dependent chain of ~10 us kernels with ~5 us of dispatch gap each, and the weight gradients (leaves) beside the data-gradient chain
     // shorten it: 20 pairs per step 7.31 -> 6.66 ms, 16 pairs 6.31 -> 6.10 (then host-bound), 8 pairs 5.18 -> 4.96; 4 pairs LOSE (host-bound either way, 5.1 ->
@@ -605,7 +673,9 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const float* params, const
     // gradient to 8 / 11 mantissa bits at each of the 2 x depth LayerNorm-backward stages departs from the reference's autocast (fp32 residual grads)
     const bool lean_grad = d.dtype == MFVIT_BF16X3 && !d.unfused;   // (the unfused row passes read the f32 residual gradient)
     auto site = [](int l, int which) { return 16u * (unsigned)l + (unsigned)which; };
-    const bool rdrop = d.p_resid > 0.f;             // the bias gradients of proj / fc2 then come from the MASKED dY (wgrad column sums)
+    const bool rdrop = d.rdrop;                     // the bias gradients of proj / fc2 then come from the MASKED dY (wgrad column sums)
+    const DropP off = make_drop(0.f, 0, 0);
+    auto dpath = [&](int l, int which) { return make_drop(d.dpr ? d.dpr[l] : 0.f, d.seed, site(l, which)); };
     // The attention backward's split-fp16 core scales dO (= the proj data gradient) per (image, head) by a power of two from the pair's largest |dO|.  The
     // GEMM that produces dO leaves those maxima behind (GemmP::omax: atomicMax of f32 bits, one slice per block, zeroed here for the blocks of this call), and
     // the attention kernel reads ONE number per pair instead of prefetching the hi parts of all of dO's rows a pair ahead.  MFVIT_DO_MAX=0: the prefetch.
@@ -646,7 +716,9 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const float* params, const
             };
             const void* gy2 = gxT;                                // dY of fc2: the residual gradient, masked where the branch was dropped
             if (rdrop) {
-                MFVIT_TRY(mask_scale_rows(d.dtype, false, gxT, D * e, ws + W.dtmp, D * e, make_drop(d.p_resid, d.seed, site(l, 4)), d.M, d.D, st));
+                // (the residual gradient itself passes unscaled: gxT stays the residual operand of the LN2 backward below)
+                MFVIT_TRY(mask_scale_rows(d.dtype, false, gxT, D * e, ws + W.dtmp, D * e, make_drop(d.p_resid, d.seed, site(l, 4)), dpath(l, 7), d.T,
+                                          d.M, d.D, st));
                 gy2 = ws + W.dtmp;
             }
             {   // dW2 += gx^T hact
@@ -704,7 +776,8 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const float* params, const
             }
             const void* gyp = gmidT;                              // dY of proj
             if (rdrop) {
-                MFVIT_TRY(mask_scale_rows(d.dtype, false, gmidT, D * e, ws + W.dtmp, D * e, make_drop(d.p_resid, d.seed, site(l, 3)), d.M, d.D, st));
+                MFVIT_TRY(mask_scale_rows(d.dtype, false, gmidT, D * e, ws + W.dtmp, D * e, make_drop(d.p_resid, d.seed, site(l, 3)), dpath(l, 6), d.T,
+                                          d.M, d.D, st));
                 gyp = ws + W.dtmp;
             }
             GemmP pend_proj = zero_gemm();                        // dWproj: launched here, or held back to ride along with dWqkv (one launch for both)
@@ -791,12 +864,21 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const float* params, const
             MFVIT_TRY(colpart_batch_flush(st));
             // token-input embedding stage: gx = d x_0 = d tokens; d pos_emb = sum over the batch (fuseattention.py:187)
             if (d.p_embd > 0.f)      // d (tokens + pos_emb) = d x_0 * mask / (1 - p)
-                MFVIT_TRY(mask_scale_rows(d.dtype, true, gx, D, gx, D, make_drop(d.p_embd, d.seed, 1), d.M, d.D, st));
+                MFVIT_TRY(mask_scale_rows(d.dtype, true, gx, D, gx, D, make_drop(d.p_embd, d.seed, 1), off, 1, d.M, d.D, st));
             if (dinput && hipMemcpyAsync(dinput, gx, (size_t)d.M * D * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
                 return MFVIT_ELAUNCH;
             if (d.use_pos) MFVIT_TRY(batch_sum(gx, dparams + L.pos, d.B, (long)d.T * D, st));
         } else {
             MFVIT_TRY(colpart_batch_flush(st));                   // (colscr, read below, is one of the deferred sums)
+            if (d.p_embd > 0.f) {
+                // pos_drop: d (cat(cls, patch_embed) + pos_embed) = d x_0 * mask / (1 - p) - the f32 rows (cls, pe_b) and their operand-type copy
+                // (pe_w) - and colscr[0:D] becomes the column sum of the masked rows
+                // (the operand-type copy is cast afresh from the masked f32 rows: no second rounding of the split copy)
+                MFVIT_TRY(mask_scale_rows(d.dtype, true, gx, D, gx, D, make_drop(d.p_embd, d.seed, 1), off, 1, d.M, d.D, st));
+                MFVIT_TRY(cast_transpose(d.dtype, gx, pp(W.gxT, -1), nullptr, d.M, d.D, st));
+                if (hipMemsetAsync(colscr, 0, D * sizeof(float), st) != hipSuccess) return MFVIT_ELAUNCH;
+                MFVIT_TRY(colsum_rows(gx, D, colscr, d.M, 1, 0, d.D, st));
+            }
             // embed stage: gx = d x_0.  d cls_token = sum_b gx[b,0]; d pe_b = sum over patch rows; d pe_w = gx_patch^T patches.
             // pos_embed is a fixed table (requires_grad = False upstream): no gradient.
             MFVIT_TRY(colsum_rows(gx, D, dparams + L.cls, d.B, d.T, 0, d.D, st));
@@ -829,23 +911,35 @@ extern "C" {
 int mfvit_vit_forward(const mfvit_vit_cfg* cfg, const float* params, const void* shadow, const float* img, void* workspace,
                       float* features, mfvit_stream_t stream) {
     ShareScope share(cfg);
-    return encoder_forward(cfg, params, shadow, img, workspace, features, stream, false);
+    return encoder_forward(cfg, nullptr, params, shadow, img, workspace, features, stream, false);
+}
+int mfvit_vit_forward_drop(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, const float* params, const void* shadow, const float* img,
+                           void* workspace, float* features, mfvit_stream_t stream) {
+    if (!drop) return MFVIT_EINVAL;
+    ShareScope share(cfg);
+    return encoder_forward(cfg, drop, params, shadow, img, workspace, features, stream, false);
 }
 int mfvit_vit_backward(const mfvit_vit_cfg* cfg, const float* params, const void* shadow, void* workspace, const float* dfeatures,
                        float* dparams, int stage_hi, int stage_lo, mfvit_stream_t stream) {
     ShareScope share(cfg);
-    return encoder_backward(cfg, params, shadow, workspace, dfeatures, dparams, nullptr, stage_hi, stage_lo, stream, false);
+    return encoder_backward(cfg, nullptr, params, shadow, workspace, dfeatures, dparams, nullptr, stage_hi, stage_lo, stream, false);
+}
+int mfvit_vit_backward_drop(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, const float* params, const void* shadow, void* workspace,
+                            const float* dfeatures, float* dparams, int stage_hi, int stage_lo, mfvit_stream_t stream) {
+    if (!drop) return MFVIT_EINVAL;
+    ShareScope share(cfg);
+    return encoder_backward(cfg, drop, params, shadow, workspace, dfeatures, dparams, nullptr, stage_hi, stage_lo, stream, false);
 }
 int mfvit_gpt_forward(const mfvit_vit_cfg* cfg, const float* params, const void* shadow, const float* tokens, void* workspace, float* out,
                       mfvit_stream_t stream) {
     ShareScope share(cfg);
-    return encoder_forward(cfg, params, shadow, tokens, workspace, out, stream, true);
+    return encoder_forward(cfg, nullptr, params, shadow, tokens, workspace, out, stream, true);
 }
 int mfvit_gpt_backward(const mfvit_vit_cfg* cfg, const float* params, const void* shadow, void* workspace, const float* dout, float* dparams,
                        float* dtokens, mfvit_stream_t stream) {
     if (!cfg || !dtokens || !dout) return MFVIT_EINVAL;
     ShareScope share(cfg);
-    return encoder_backward(cfg, params, shadow, workspace, dout, dparams, dtokens, cfg->depth, -1, stream, true);
+    return encoder_backward(cfg, nullptr, params, shadow, workspace, dout, dparams, dtokens, cfg->depth, -1, stream, true);
 }
 
 // ------------------------------------------------------------------------------------------------ single ops

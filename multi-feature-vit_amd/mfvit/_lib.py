@@ -27,6 +27,11 @@ class VitCfg(Structure):
                 ("stream_share", c_int)]
 
 
+class VitDrop(Structure):
+    """mfvit_vit_drop: training-mode dropout / drop-path rates of the image encoder (include/mfvit.h)."""
+    _fields_ = [("drop", c_float), ("attn_drop", c_float), ("drop_path", POINTER(c_float)), ("seed", c_uint64)]
+
+
 class FusionCfg(Structure):
     _fields_ = [("batch", c_int), ("tokens", c_int), ("dim", c_int), ("heads", c_int), ("num_classes", c_int),
                 ("eps_pre", c_float), ("eps_post", c_float)]
@@ -48,6 +53,9 @@ SIGNATURES = {
     "mfvit_vit_workspace_bytes": (c_size_t, [POINTER(VitCfg)]),
     "mfvit_vit_forward": (I, [POINTER(VitCfg), P, P, P, P, P, P]),
     "mfvit_vit_backward": (I, [POINTER(VitCfg), P, P, P, P, P, I, I, P]),
+    "mfvit_vit_workspace_bytes_drop": (c_size_t, [POINTER(VitCfg), POINTER(VitDrop)]),
+    "mfvit_vit_forward_drop": (I, [POINTER(VitCfg), POINTER(VitDrop), P, P, P, P, P, P]),
+    "mfvit_vit_backward_drop": (I, [POINTER(VitCfg), POINTER(VitDrop), P, P, P, P, P, I, I, P]),
     "mfvit_gpt_forward": (I, [POINTER(VitCfg), P, P, P, P, P, P]),
     "mfvit_gpt_backward": (I, [POINTER(VitCfg), P, P, P, P, P, P, P]),
     "mfvit_linear_fwd": (I, [I, I, P, L, P, L, P, P, L, P, L, I, I, I, P]),

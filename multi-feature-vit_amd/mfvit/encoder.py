@@ -5,11 +5,16 @@ Stands in for the module the reference imports as ``vits`` / ``vits_returnftrs``
 state-dict keys, ``.head`` a re-assignable ``nn.Linear``, ``forward(img) -> (B, num_classes)`` and
 ``features3D(img) -> (B, 1 + HW/256, 384)``.
 
+timm's regularisation kwargs (``drop_rate``, ``attn_drop_rate``, ``drop_path_rate``; moco-v3 ``vits.py`` passes them on) are honoured in
+training mode: parameter-free ``pos_drop`` / ``attn.attn_drop`` / ``attn.proj_drop`` / ``mlp.drop`` / ``blocks[i].drop_path`` modules carry
+the rates, and every training-mode forward draws fresh masks (include/mfvit.h, mfvit_vit_drop) from a seed taken from torch's CPU generator.
+
 MI355X-first layout: every backbone parameter is a view into ONE flat f32 arena (timm registration order, the
 layout of include/mfvit.h), so the encoder kernels, the fused optimizers, the EMA update and the gradient
 all-reduce all work on contiguous slices.  Gradients come back from the C ABI as one flat arena as well.
 There is no CPU / eager fallback: forward on a non-GPU tensor raises.
 """
+import ctypes
 import math
 import os
 
@@ -49,26 +54,41 @@ class _WB(nn.Module):
 
 
 class _Attn(nn.Module):
-    def __init__(self, dim):
+    def __init__(self, dim, attn_drop=0.0, proj_drop=0.0):
         super().__init__()
         self.qkv = _WB((3 * dim, dim), (3 * dim,))
+        self.attn_drop = nn.Dropout(attn_drop)       # (rate carriers: parameter-free, the kernels apply them)
         self.proj = _WB((dim, dim), (dim,))
+        self.proj_drop = nn.Dropout(proj_drop)
 
 
 class _Mlp(nn.Module):
-    def __init__(self, dim, hidden):
+    def __init__(self, dim, hidden, drop=0.0):
         super().__init__()
         self.fc1 = _WB((hidden, dim), (hidden,))
         self.fc2 = _WB((dim, hidden), (dim,))
+        self.drop = nn.Dropout(drop)                 # timm Mlp: after the GELU and after fc2
 
 
 class _Block(nn.Module):
-    def __init__(self, dim, hidden):
+    def __init__(self, dim, hidden, drop=0.0, attn_drop=0.0, drop_path=0.0):
         super().__init__()
         self.norm1 = _WB((dim,), (dim,))
-        self.attn = _Attn(dim)
+        self.attn = _Attn(dim, attn_drop, drop)
+        self.drop_path = DropPath(drop_path) if drop_path > 0.0 else nn.Identity()     # (timm 0.4.9)
         self.norm2 = _WB((dim,), (dim,))
-        self.mlp = _Mlp(dim, hidden)
+        self.mlp = _Mlp(dim, hidden, drop)
+
+
+class DropPath(nn.Module):
+    """Rate carrier of timm's per-sample stochastic depth (``drop_prob``): the encoder kernels apply it, this module is never called."""
+
+    def __init__(self, drop_prob=0.0):
+        super().__init__()
+        self.drop_prob = drop_prob
+
+    def extra_repr(self):
+        return f"drop_prob={self.drop_prob}"
 
 
 class _PatchEmbed(nn.Module):
@@ -81,11 +101,13 @@ class _EncoderFn(torch.autograd.Function):
     """features3D as one autograd node: forward = mfvit_vit_forward, backward = mfvit_vit_backward (stage by stage)."""
 
     @staticmethod
-    def forward(ctx, model, img, need_grad, *params):
-        feats, ws = model._run_forward(img, need_grad)
+    def forward(ctx, model, img, need_grad, drop, *params):
+        # drop: the mfvit_vit_drop of THIS forward (None: no dropout site active)
+        feats, ws = model._run_forward(img, need_grad, drop)
         ctx.model = model
         ctx.ws = ws
         ctx.cfg = model._cfg(img, need_grad)
+        ctx.drop = drop                     # the backward rebuilds the same masks from it
         return feats
 
     @staticmethod
@@ -94,13 +116,13 @@ class _EncoderFn(torch.autograd.Function):
         if ctx.ws is None:
             raise _lib.MfvitError("the encoder's saved activations were already released: a second backward through the same forward "
                                   "(retain_graph=True) is not supported - run the forward again")
-        grads = model._run_backward(ctx.cfg, ctx.ws, dfeats)
+        grads = model._run_backward(ctx.cfg, ctx.ws, dfeats, drop=ctx.drop)
         model._release_ws(ctx.ws)
         ctx.ws = None
         # the single-use feature cache holds the forward's output, i.e. this graph and the parameters' AccumulateGrad nodes (which carry
         # the stream they were created under): once the backward has run it must not keep them alive into the next iteration
         model._feat_cache = None
-        return (None, None, None) + tuple(grads)
+        return (None, None, None, None) + tuple(grads)
 
 
 class _HeadFn(torch.autograd.Function):
@@ -133,8 +155,12 @@ class _HeadFn(torch.autograd.Function):
 
 class VisionTransformerMoCo(nn.Module):
     def __init__(self, img_size=224, patch_size=16, embed_dim=384, depth=12, num_heads=12, mlp_ratio=4.0, qkv_bias=True,
-                 num_classes=1000, stop_grad_conv1=False, precision=None, **unused_timm_kwargs):
+                 num_classes=1000, stop_grad_conv1=False, precision=None, drop_rate=0.0, attn_drop_rate=0.0, drop_path_rate=0.0,
+                 **unused_timm_kwargs):
         super().__init__()
+        for name, r in (("drop_rate", drop_rate), ("attn_drop_rate", attn_drop_rate), ("drop_path_rate", drop_path_rate)):
+            if not 0.0 <= float(r) < 1.0:
+                raise ValueError(f"{name} must lie in [0, 1), got {r!r}")
         if patch_size != 16:
             raise NotImplementedError("only patch_size=16 (ViT-S/16) is built")
         if embed_dim not in (384, 768):
@@ -158,7 +184,9 @@ class VisionTransformerMoCo(nn.Module):
         self.cls_token = nn.Parameter(torch.zeros(1, 1, embed_dim))
         self.pos_embed = nn.Parameter(build_2d_sincos_position_embedding(gh, gw, embed_dim), requires_grad=False)
         self.patch_embed = _PatchEmbed(embed_dim, 16)
-        self.blocks = nn.ModuleList([_Block(embed_dim, self.mlp_dim) for _ in range(depth)])
+        self.pos_drop = nn.Dropout(float(drop_rate))
+        dpr = [x.item() for x in torch.linspace(0, float(drop_path_rate), depth)]       # stochastic depth decay rule (timm)
+        self.blocks = nn.ModuleList([_Block(embed_dim, self.mlp_dim, float(drop_rate), float(attn_drop_rate), dpr[i]) for i in range(depth)])
         self.norm = _WB((embed_dim,), (embed_dim,))
         self.head = nn.Linear(embed_dim, num_classes) if num_classes > 0 else nn.Identity()
         self._init_weights()
@@ -270,6 +298,51 @@ class VisionTransformerMoCo(nn.Module):
         o, n = self._offsets[f"blocks.{i}.mlp.fc2.bias"]
         return a, o + n - a
 
+    # ------------------------------------------------------------------ training-mode dropout
+    def drop_rates(self):
+        """(drop_rate, attn_drop_rate, [drop-path rate of every block]) as the rate-carrier modules hold them now."""
+        # (read on every training-mode forward: plain `_modules` lookups, not nn.Module.__getattr__ - host time of a small-batch step)
+        blocks = list(self._modules["blocks"]._modules.values())
+        drop = float(self._modules["pos_drop"].p)
+        attn = float(blocks[0]._modules["attn"]._modules["attn_drop"].p)
+        dpr = []
+        for b in blocks:
+            a, mlp = b._modules["attn"]._modules, b._modules["mlp"]._modules
+            if float(a["proj_drop"].p) != drop or float(mlp["drop"].p) != drop or float(a["attn_drop"].p) != attn:
+                raise _lib.MfvitError("the encoder kernels take one drop_rate (pos_drop, proj_drop, mlp.drop) and one attn_drop_rate for all "
+                                      "blocks: set the rate-carrier modules consistently")
+            dpr.append(float(getattr(b._modules["drop_path"], "drop_prob", 0.0)))
+        for r in [drop, attn] + dpr:
+            if not 0.0 <= r < 1.0:
+                raise _lib.MfvitError(f"dropout rates must lie in [0, 1), got {r}")
+        return drop, attn, dpr
+
+    def is_stochastic(self):
+        """True in training mode with any dropout / drop-path rate > 0: every forward then draws masks of its own."""
+        if not self.training:
+            return False
+        drop, attn, dpr = self.drop_rates()
+        return drop > 0.0 or attn > 0.0 or any(r > 0.0 for r in dpr)
+
+    def _draw_drop(self):
+        """mfvit_vit_drop of one training-mode forward (None when no site is active: eval(), or all rates 0).  The seed comes from torch's CPU
+        generator, so `torch.manual_seed` makes the masks reproducible (as model/fuseattention.py does for the GPT).  One walk over the rate
+        carriers per forward, none in eval()."""
+        if not self.training:
+            return None
+        drop, attn, dpr = self.drop_rates()
+        if not (drop > 0.0 or attn > 0.0 or any(r > 0.0 for r in dpr)):
+            return None
+        if _lib.dtype_code(self.precision) == _lib.F32:
+            raise _lib.MfvitError("dropout / drop path inside the encoder is built for precision 'bf16x3' (f32-grade), 'bf16' and 'fp16', not 'fp32': "
+                                  "use one of those, or train with the rates at 0")
+        seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+        rates = (ctypes.c_float * len(dpr))(*dpr)
+        d = _lib.VitDrop(drop, attn, ctypes.cast(rates, ctypes.POINTER(ctypes.c_float)), seed)
+        d._rates = rates                    # (keeps the host array alive as long as the struct)
+        self._last_drop = d                 # (tests: the seed of the last training-mode forward, to export its masks)
+        return d
+
     # ------------------------------------------------------------------ engine plumbing
     def _cfg(self, img, save):
         c = VitCfg()
@@ -299,8 +372,8 @@ class VisionTransformerMoCo(nn.Module):
         self._shadow_key = key
         self._feat_cache = None
 
-    def _get_ws(self, cfg):
-        nbytes = lib().mfvit_vit_workspace_bytes(cfg)
+    def _get_ws(self, cfg, drop=None):
+        nbytes = lib().mfvit_vit_workspace_bytes(cfg) if drop is None else lib().mfvit_vit_workspace_bytes_drop(cfg, drop)
         if nbytes == 0:
             raise _lib.MfvitError("invalid encoder configuration (image size must be a multiple of 16, dim 384 or 768, head_dim 32 / 64 / 96)")
         pool = self._ws_pool.setdefault(nbytes, [])
@@ -312,7 +385,7 @@ class VisionTransformerMoCo(nn.Module):
             if len(pool) < 2:
                 pool.append(ws)
 
-    def _run_forward(self, img, save):
+    def _run_forward(self, img, save, drop=None):
         _lib.require_cuda(img)
         if img.dtype != torch.float32:
             img = img.float()
@@ -324,17 +397,21 @@ class VisionTransformerMoCo(nn.Module):
             raise _lib.MfvitError(f"model on {self._arena.device} but input on {img.device}")
         cfg = self._cfg(img, save)
         self._ensure_shadow(cfg)
-        ws = self._get_ws(cfg)
+        ws = self._get_ws(cfg, drop)
         feats = torch.empty(img.shape[0], self.num_tokens, self.embed_dim, device=img.device, dtype=torch.float32)
-        check(lib().mfvit_vit_forward(cfg, ptr(self._arena), ptr(self._shadow), ptr(img), ptr(ws), ptr(feats), stream()),
-              "mfvit_vit_forward")
+        if drop is None:
+            check(lib().mfvit_vit_forward(cfg, ptr(self._arena), ptr(self._shadow), ptr(img), ptr(ws), ptr(feats), stream()),
+                  "mfvit_vit_forward")
+        else:
+            check(lib().mfvit_vit_forward_drop(cfg, drop, ptr(self._arena), ptr(self._shadow), ptr(img), ptr(ws), ptr(feats), stream()),
+                  "mfvit_vit_forward_drop")
         if not save:
             self._release_ws(ws)
             ws = None
         return feats, ws
 
-    def _run_backward(self, cfg, ws, dfeats, on_stage_done=None):
-        """Returns per-parameter gradient views (arena order) of a fresh flat gradient arena."""
+    def _run_backward(self, cfg, ws, dfeats, on_stage_done=None, drop=None):
+        """Returns per-parameter gradient views (arena order) of a fresh flat gradient arena.  drop: the forward's mfvit_vit_drop (or None)."""
         dfeats = dfeats.contiguous()
         if dfeats.dtype != torch.float32:
             dfeats = dfeats.float()
@@ -358,9 +435,16 @@ class VisionTransformerMoCo(nn.Module):
                 self._grad_arena = gflat
         self._grad_arena_lent = True
         hook = on_stage_done or getattr(self, "_grad_stage_hook", None)
+
+        def bwd(hi, lo):
+            if drop is None:
+                check(lib().mfvit_vit_backward(cfg, ptr(self._arena), ptr(self._shadow), ptr(ws), ptr(dfeats), ptr(gflat), hi, lo, stream()),
+                      "mfvit_vit_backward")
+            else:
+                check(lib().mfvit_vit_backward_drop(cfg, drop, ptr(self._arena), ptr(self._shadow), ptr(ws), ptr(dfeats), ptr(gflat), hi, lo,
+                                                    stream()), "mfvit_vit_backward_drop")
         if hook is None:
-            check(lib().mfvit_vit_backward(cfg, ptr(self._arena), ptr(self._shadow), ptr(ws), ptr(dfeats), ptr(gflat), self.depth, -1,
-                                           stream()), "mfvit_vit_backward")
+            bwd(self.depth, -1)
         else:
             # stages depth (final norm), depth-1 .. 0 (blocks), -1 (embedding) run in groups of `_grad_bucket_layers` blocks: after
             # each group its (contiguous) gradient slice can be exchanged while the next group computes.  Every library call joins
@@ -371,8 +455,7 @@ class VisionTransformerMoCo(nn.Module):
                 lo = max(hi - gb, -1) if hi == self.depth else max(hi - gb + 1, -1)
                 if lo == 0:
                     lo = -1                                   # the embedding stage rides with the last block group
-                check(lib().mfvit_vit_backward(cfg, ptr(self._arena), ptr(self._shadow), ptr(ws), ptr(dfeats), ptr(gflat), hi, lo,
-                                               stream()), "mfvit_vit_backward")
+                bwd(hi, lo)
                 hook(self, hi, lo, gflat)
                 hi = lo - 1
         self._last_grad_arena = gflat
@@ -389,15 +472,17 @@ class VisionTransformerMoCo(nn.Module):
         key = (x._version, need, self._param_version(), torch.is_grad_enabled())
         c = self._feat_cache
         self._feat_cache = None
-        if c is not None and c[0] is x and c[1] == key and c[2] != caller:
+        drop = self._draw_drop()            # (a fresh seed per training-mode forward with dropout; None otherwise)
+        stochastic = drop is not None
+        if c is not None and c[0] is x and c[1] == key and c[2] != caller and not stochastic:
             # the reference runs every backbone twice per step on the same tensor (features3D then __call__, FUS:128+131);
-            # all dropouts are 0, so the second result is head(first[:, 0]): computed once.  Single use: a repeated call of
-            # the SAME method always recomputes.
+            # without dropout the second result is head(first[:, 0]): computed once.  Single use: a repeated call of
+            # the SAME method always recomputes.  (Training mode with dropout / drop path: two forwards with their own masks, as the reference.)
             return c[3]
         c = None
         self._grad_arena_lent = False
-        feats = _EncoderFn.apply(self, x, need, *self._arena_params)
-        self._feat_cache = (x, key, caller, feats)
+        feats = _EncoderFn.apply(self, x, need, drop, *self._arena_params)
+        self._feat_cache = None if stochastic else (x, key, caller, feats)
         return feats
 
     def features3D(self, x):
@@ -413,5 +498,5 @@ class VisionTransformerMoCo(nn.Module):
         return h(feats[:, 0])      # a module the caller installed (MoCo's projector MLP: HIP Linear / BatchNorm nodes of its own)
 
     def forward(self, x):
-        """head(features3D(x)[:, 0])  (timm forward_features + head; all dropouts are 0)."""
+        """head(features3D(x)[:, 0])  (timm forward_features + head; training mode applies the dropout / drop-path rates)."""
         return self.forward_head(self._features(x, "forward"))

@@ -52,6 +52,12 @@ class MultiScaleTransformerEncoder(nn.Module):
         return exchange(self, xs, xl)
 
 
+def _stochastic(vit):
+    """True while a backbone draws dropout / drop-path masks (training mode with a rate > 0): every call is then a forward of its own."""
+    f = getattr(vit, "is_stochastic", None)
+    return bool(f()) if callable(f) else False
+
+
 class Fus_CrossViT(nn.Module):
     def __init__(self, model_vit_cxr, model_vit_enh, num_classes=3, small_dim=384, large_dim=384, cross_attn_depth=1,
                  multi_scale_enc_depth=1, heads=3, dropout=0., pool='cls'):
@@ -132,7 +138,10 @@ class Fus_CrossViT(nn.Module):
         hc, he = self._plain_head(vit_cxr), self._plain_head(vit_enh)
         fused_heads = hc is not None and he is not None and hc.out_features == self.num_classes == he.out_features \
             and getattr(vit_cxr, "features3D", None) == self.vit_features_cxr \
-            and getattr(vit_enh, "features3D", None) == self.vit_features_enh
+            and getattr(vit_enh, "features3D", None) == self.vit_features_enh \
+            and not _stochastic(vit_cxr) and not _stochastic(vit_enh)
+        # (a backbone in training mode with dropout / drop path: vit_S(img_S) is a forward of its own, with its own masks - FUS:131,135 call it
+        # after features3D, as the reference does; the CA step then runs each backbone twice)
         if fused_heads:
             # x_S = vit_S(img_S) = head_S(features3D(img_S)[:, 0])  (FUS:131,135; dropouts are 0): evaluated inside the fused node
             return FusionFn.apply(self._spec, cxr_ftrs, enh_ftrs, hc.weight, hc.bias, he.weight, he.bias, *self._spec.live())

@@ -15,7 +15,9 @@ __all__ = ["vit_small", "vit_base", "vit_conv_small", "vit_conv_base", "vit_smal
 
 def vit_small(**kwargs):
     """ViT-S/16: embed 384, depth 12, 12 heads, mlp 4x, qkv bias, LN eps 1e-6 (moco-v3 ``vit_small``).
-    kwargs: num_classes (BLD:29-30), stop_grad_conv1 (MAIN_MOCO:274), img_size, precision ('bf16x3' default | 'bf16' | 'fp16' | 'fp32')."""
+    kwargs: num_classes (BLD:29-30), stop_grad_conv1 (MAIN_MOCO:274), img_size, precision ('bf16x3' default | 'bf16' | 'fp16' | 'fp32'),
+    and timm's drop_rate / attn_drop_rate / drop_path_rate (training mode only; e.g. drop_path_rate=0.1, the DeiT / MoCo-v3 fine-tune
+    recipe; 'fp32' refuses a rate > 0 in training mode)."""
     cfg = dict(patch_size=16, embed_dim=384, depth=12, num_heads=12, mlp_ratio=4, qkv_bias=True)
     cfg.update(kwargs)
     return VisionTransformerMoCo(**cfg)
@@ -33,7 +35,8 @@ def _out_of_scope(name):
 
 
 def vit_base(**kwargs):
-    """ViT-B/16: embed 768, depth 12, 12 heads (head_dim 64), mlp 4x (moco-v3 ``vit_base``); same kwargs as vit_small."""
+    """ViT-B/16: embed 768, depth 12, 12 heads (head_dim 64), mlp 4x (moco-v3 ``vit_base``); same kwargs as vit_small, the dropout /
+    drop-path rates included."""
     cfg = dict(patch_size=16, embed_dim=768, depth=12, num_heads=12, mlp_ratio=4, qkv_bias=True)
     cfg.update(kwargs)
     return VisionTransformerMoCo(**cfg)
