@@ -143,6 +143,24 @@ int mfvit_vit_forward_drop(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop,
 int mfvit_vit_backward_drop(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, const float* params, const void* shadow, void* workspace,
                             const float* dfeatures, float* dparams, int stage_hi, int stage_lo, mfvit_stream_t stream);
 
+/* Image gradient and data-gradient-only backward of the image encoder (additive in ABI 5).
+ * dimg: (B,3,H,W) f32 NCHW, OVERWRITTEN with d loss / d img, or NULL.  It needs image mode (cfg->token_input = 0; the token-input encoder
+ *   returns its input gradient through mfvit_gpt_backward) and stage_lo == -1 (the call that runs the embedding stage).  The patch-embedding
+ *   data gradient gx[patch rows] W_pe is one tile GEMM whose epilogue stores the image directly (the inverse of im2col: non-overlapping
+ *   patches, every element written once, no sum).  W_pe takes part even under stop_grad_conv1.  The workspace must then have
+ *   mfvit_vit_workspace_bytes_ex(cfg, drop, 1) bytes (the forward may run on it: its first mfvit_vit_workspace_bytes(_drop) bytes are the
+ *   usual layout); the shadow is unchanged.
+ * dparams: accumulated into as by mfvit_vit_backward, or NULL: then no parameter gradient of any stage is formed - the data-gradient chain
+ *   alone (final LayerNorm, every block's data-gradient GEMMs, attention backward, LayerNorm backwards, dropout / drop-path masks), with no
+ *   weight-gradient GEMM, no split-partial reduce, no bias / LayerNorm column sum and no side stream.  Needs dimg.
+ * drop: the forward's mfvit_vit_drop, or NULL (no dropout site).  dimg == NULL && dparams != NULL is exactly mfvit_vit_backward(_drop).
+ * MFVIT_EINVAL (before any HIP call): dimg in token-input mode, dimg with stage_lo != -1, dimg == dparams == NULL, and the checks of
+ * mfvit_vit_backward(_drop).  mfvit_vit_workspace_bytes_ex returns 0 for an invalid cfg / drop, and for want_dimg in token-input mode or
+ * without cfg->save_for_backward. */
+size_t mfvit_vit_workspace_bytes_ex(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, int want_dimg);
+int mfvit_vit_backward_ex(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, const float* params, const void* shadow, void* workspace,
+                          const float* dfeatures, float* dparams, float* dimg, int stage_hi, int stage_lo, mfvit_stream_t stream);
+
 /* Token-input encoder (cfg->token_input = 1): the GPT of the TransFuser fusion (fuseattention.py:84-212), heads x head_dim with
  * head_dim in {32, 64, 96} (config.py: n_embd 384, n_head 4 -> 96), mlp_dim = block_exp * dim.
  * Parameter arena (f32): pos_emb [tokens][dim], then per block

@@ -87,6 +87,35 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_tile_kernel(GemmP p) {   // 2 
         __syncthreads();
         copy_tile(rb_t, std::true_type(), (char*)out, ldo * (long)sizeof(T), (long)n0 * EP * (long)sizeof(T));
     };
+    if constexpr (EPI == EPI_COL2IM16) {
+        // d patches -> d image (the inverse of im2col16, elementwise.hip).  A starts at the first patch row of image 0 (token row 1) and runs over
+        // M = B T - 1 token rows: row m is patch m % T of image m / T, or (m % T == orow_in = np) the cls row of image m / T + 1, which is skipped.
+        // Column k = c 256 + ky 16 + kx of patch (py, px) goes to out0[b][c][16 py + ky][16 px + kx]; ldo0 = image width, orow_out = T.  The
+        // patches do not overlap: every image element is written once, by a plain store (no sum).  Each 16 consecutive columns are 64
+        // contiguous bytes of one image row: four threads' 16-byte chunks.
+        constexpr int RB = BN * 4, CP = RB / 16, NC = BM * CP / NTHR;
+#pragma unroll
+        for (int j = 0; j < Loop::TN; ++j)
+#pragma unroll
+            for (int i = 0; i < Loop::TM; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) ((float*)trow(i, r, RB + 16))[ecol(j)] = acc[i][j][r];
+        __syncthreads();
+        const int np = p.orow_in, tpi = p.orow_out, Wimg = (int)p.ldo0, gw = Wimg / 16;
+        const long plane = (long)np * 256;                     // H W
+        const int c = tid % CP, k = n0 + 4 * c, ch = k >> 8, ky = (k >> 4) & 15, kx = k & 15;
+        float* out = (float*)p.out0 + (long)ch * plane + (long)ky * Wimg + kx;
+#pragma unroll
+        for (int q = 0; q < NC; ++q) {
+            const int row = tid / CP + q * (NTHR / CP), m = m0 + row;
+            const int b = m / tpi, i = m - b * tpi;
+            if (m >= p.M || i >= np) continue;
+            const int py = i / gw, px = i - py * gw;
+            typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+            store16_stream(out + b * 3 * plane + (long)py * 16 * Wimg + px * 16, *(const u32x4*)(tile + row * (RB + 16) + 16 * c));
+        }
+        return;
+    }
     constexpr bool GELU = EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_GELU_DROP;
     float bj[Loop::TN], csums[Loop::TN];
 #pragma unroll
@@ -1022,7 +1051,7 @@ template <typename T, int EPI> static int launch_tile(const GemmP& pin, hipStrea
     if (p.omax && (EPI != EPI_NONE || p.omax_rows < 64 || p.M % p.omax_rows || (p.omax_hd != 32 && p.omax_hd != 64) || p.nb > 1)) return MFVIT_EINVAL;   // (a wave's 64 rows: at most two images)
     // (output tiles leave through common.cuh::store16_stream: system-scope streaming stores)
     const int nwg = (p.N / 128) * ((p.M + 127) / 128);
-    constexpr int epi_bytes = 128 * (128 * (int)sizeof(T) * EP + 16);
+    constexpr int epi_bytes = 128 * ((EPI == EPI_COL2IM16 ? 128 * 4 : 128 * (int)sizeof(T) * EP) + 16);   // (EPI_COL2IM16 stages an f32 tile)
     constexpr int lds_bytes = Loop::LDS_BYTES > epi_bytes ? Loop::LDS_BYTES : epi_bytes;
     static PerDeviceOnce attr_set;
     if (attr_set.first()) {
@@ -1275,6 +1304,10 @@ int gemm_nt_tile(int dtype, int epi, const GemmP& p, hipStream_t st) {
         case EPI_NONE: return tile_by_dtype<EPI_NONE>(dtype, p, st);
         case EPI_BIAS_RELU: return tile_by_dtype<EPI_BIAS_RELU>(dtype, p, st);
         case EPI_BIAS_X3F16: return dtype == MFVIT_BF16X3 ? launch_tile<sbf16, EPI_BIAS_X3F16>(p, st) : MFVIT_EINVAL;
+        case EPI_COL2IM16:   // out0: f32 (B, 3, H, W) image, ldo0 = W, orow_in = patches per image, orow_out = token rows per image
+            if (!p.out0 || p.nb > 1 || p.N != 768 || p.ldo0 <= 0 || p.ldo0 % 16 || p.orow_in <= 0 || p.orow_out <= p.orow_in || p.orow_in % (p.ldo0 / 16))
+                return MFVIT_EINVAL;
+            return tile_by_dtype<EPI_COL2IM16>(dtype, p, st);
         case EPI_BIAS_GELU_DROP:                                                     // (the dropout sites exist for the 16-bit operand types)
             switch (dtype) {
                 case MFVIT_BF16: return launch_tile<bf16, EPI_BIAS_GELU_DROP>(p, st);

@@ -510,6 +510,7 @@ bool gemm_nt_pp_supported(int dtype, int epi, const GemmP& p) {
     if (!on) return false;
     if (dtype != MFVIT_BF16X3 && dtype != MFVIT_BF16 && dtype != MFVIT_F16) return false;
     if (epi == EPI_BIAS_X3F16 && dtype != MFVIT_BF16X3) return false;
+    if (epi == EPI_COL2IM16) return false;                      // (the image-gradient store is the tile kernel's epilogue, gemm.hip)
     const int kps = dtype == MFVIT_BF16X3 ? 32 : 64;
     if (p.nb > 1 || (on != 2 && p.M < 2048) || p.M < 1 || p.N % PP_BN || p.K % kps || p.K < 2 * kps) return false;
     if (p.omax) return false;                                   // per-(image, head) output maxima: the round-5 kernel's epilogue (proj data gradient)

@@ -6,7 +6,8 @@ namespace mfvit {
 
 enum { EPI_BIAS = 0, EPI_BIAS_GELU = 1, EPI_GELU_BWD = 2, EPI_NONE = 3, EPI_BIAS_RELU = 4,    // 4: out0 = relu'(pre), out1 = relu(pre)
        EPI_BIAS_X3F16 = 5,                                                                    // 5: bias, output written as split FP16 (sbf16 inputs only: qkv)
-       EPI_BIAS_GELU_DROP = 6 };   // 6: EPI_BIAS_GELU with dropout on the activation (GemmP::drop, element m * N + n): out1 = gelu * mask, out0 = gelu' * mask
+       EPI_BIAS_GELU_DROP = 6,     // 6: EPI_BIAS_GELU with dropout on the activation (GemmP::drop, element m * N + n): out1 = gelu * mask, out0 = gelu' * mask
+       EPI_COL2IM16 = 7 };         // 7: gemm.hip tile kernel only - the patch-embedding data gradient stored straight into an f32 NCHW image (see there)
 enum { REPI_RES_LN = 0, REPI_LNBWD_RES = 1,
        REPI_RES_LN_DP = 2 };   // 2: gemm_rowp only - REPI_RES_LN with x = aux + drop_mul(drop, row / drop_tpr) * (products + bias) (drop path)
 

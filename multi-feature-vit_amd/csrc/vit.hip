@@ -200,6 +200,7 @@ struct WsLayout {
     size_t domax;               // backward: the largest |d attn| of every (image, head) of every block, f32 bits [depth][B][H] (proj data gradient -> attention backward)
     size_t pp_stride;           // distance between the two ping-pong copies of gxT / gmidT / dhpre / dqkv (0 = none)
     size_t total;
+    size_t wpeT, total_dimg;    // image gradient (mfvit_vit_backward_ex): W_pe^T [768][D] of the operand type behind `total` - a workspace of total_dimg bytes
 };
 WsLayout ws_layout(const Dims& d) {
     WsLayout W;
@@ -257,6 +258,8 @@ WsLayout ws_layout(const Dims& d) {
     W.utmp = o; o += align256(M * D * es);     // always there (1 / 200 of the workspace): the layout does not depend on which path a call takes
     W.domax = o; o += d.save ? align256((size_t)d.depth * d.B * d.H * 4) : 0;
     W.total = o;
+    W.wpeT = o; o += (d.save && !d.tok) ? align256((size_t)768 * D * es) : 0;
+    W.total_dimg = o;
     return W;
 }
 
@@ -353,6 +356,13 @@ size_t mfvit_vit_workspace_bytes_drop(const mfvit_vit_cfg* cfg, const mfvit_vit_
     Dims d;
     if (!get_dims(cfg, drop, d)) return 0;
     return ws_layout(d).total;
+}
+size_t mfvit_vit_workspace_bytes_ex(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, int want_dimg) {
+    Dims d;
+    if (!get_dims(cfg, drop, d)) return 0;
+    if (!want_dimg) return ws_layout(d).total;
+    if (d.tok || !d.save) return 0;                  // the image gradient exists in image mode, behind a forward that saved its activations
+    return ws_layout(d).total_dimg;
 }
 
 int mfvit_vit_prepare_shadow(const mfvit_vit_cfg* cfg, const float* params, void* shadow, mfvit_stream_t stream) {
@@ -587,13 +597,18 @@ static int encoder_forward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* dropc
     return MFVIT_OK;
 }
 
-// Shared backward; dinput (token-input mode only): d loss / d tokens, written by the embedding stage.
+// Shared backward; dinput (token-input mode only): d loss / d tokens, written by the embedding stage.  dimg (image mode only, stage_lo == -1; the
+// workspace then has mfvit_vit_workspace_bytes_ex(.., 1) bytes): d loss / d image, overwritten.  dparams == NULL (with dimg): the data-gradient
+// chain alone - no weight-gradient GEMM, no split-partial reduce, no bias / LayerNorm column sum, no side stream.
 static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* dropcfg, const float* params, const void* shadow, void* workspace,
-                            const float* dfeatures, float* dparams, float* dinput, int stage_hi, int stage_lo, mfvit_stream_t stream, bool want_tokens) {
+                            const float* dfeatures, float* dparams, float* dinput, float* dimg, int stage_hi, int stage_lo, mfvit_stream_t stream,
+                            bool want_tokens) {
     Dims d;
-    if (!get_dims(cfg, dropcfg, d) || !params || !shadow || !workspace || !dparams) return MFVIT_EINVAL;
+    if (!get_dims(cfg, dropcfg, d) || !params || !shadow || !workspace || (!dparams && !dimg)) return MFVIT_EINVAL;
     if (!d.save || d.tok != want_tokens) return MFVIT_EINVAL;
     if (stage_hi > d.depth || stage_lo < -1 || stage_lo > stage_hi) return MFVIT_EINVAL;
+    if (dimg && (d.tok || stage_lo != -1)) return MFVIT_EINVAL;
+    const bool wg = dparams != nullptr;             // parameter gradients wanted (false: data-gradient-only backward)
     hipStream_t st = (hipStream_t)stream;
     const ParamLayout L = param_layout(d);
     const ShadowLayout S = shadow_layout(d);
@@ -606,7 +621,7 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop
     auto stat = [&](int l) { return (float*)(ws + W.st0 + (size_t)l * W.st_stride); };
     auto blk = [&](int l) { return ws + W.blk0 + (size_t)l * W.blk_stride; };
     auto pblk = [&](int l) { return params + L.blk0 + (long)l * L.blk_stride; };
-    auto gblk = [&](int l) { return dparams + L.blk0 + (long)l * L.blk_stride; };
+    auto gblk = [&](int l) { return wg ? dparams + L.blk0 + (long)l * L.blk_stride : nullptr; };
     auto sblk = [&](int l) { return sh + S.blk0 + (size_t)l * S.blk_stride; };
     float* gx = (float*)(ws + W.gx);
     float* gmid = (float*)(ws + W.gmid);
@@ -645,7 +660,7 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop
     // the whole-step HIP graph of round 5 gained nothing, 8.22 vs 8.12 ms, and was removed in round 6)
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     const bool capturing = hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
-    const bool side_wanted = d.M >= 1024 && d.M <= 4096 && g_wgrad_stream.load(std::memory_order_relaxed) != 0 && !d.rdrop &&
+    const bool side_wanted = wg && d.M >= 1024 && d.M <= 4096 && g_wgrad_stream.load(std::memory_order_relaxed) != 0 && !d.rdrop &&
                              !capturing;
     static SideStream no_side;
     SideStream& ss = side_wanted ? side_stream(st) : no_side;
@@ -691,9 +706,13 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop
         if (s == d.depth) {
             // final LayerNorm backward: dfeatures -> gx (grad of x_depth); dcol = d fc2_b of the last block
             if (!dfeatures) return MFVIT_EINVAL;
-            MFVIT_TRY(ln_bwd_rows(d.dtype, d.D, dfeatures, D, xbuf(d.depth), D, stat(d.depth), stat(d.depth) + d.M, params + L.norm_w,
-                                  nullptr, 0, gx, D, pp(W.gxT, d.depth - 1), D * e, dparams + L.norm_w, dparams + L.norm_b,
-                                  rdrop ? colscr + D : gblk(d.depth - 1) + L.fc2_b, next_colpart(), d.M, 1, 0, st));
+            if (wg)
+                MFVIT_TRY(ln_bwd_rows(d.dtype, d.D, dfeatures, D, xbuf(d.depth), D, stat(d.depth), stat(d.depth) + d.M, params + L.norm_w,
+                                      nullptr, 0, gx, D, pp(W.gxT, d.depth - 1), D * e, dparams + L.norm_w, dparams + L.norm_b,
+                                      rdrop ? colscr + D : gblk(d.depth - 1) + L.fc2_b, next_colpart(), d.M, 1, 0, st));
+            else
+                MFVIT_TRY(ln_bwd_rows(d.dtype, d.D, dfeatures, D, xbuf(d.depth), D, stat(d.depth), stat(d.depth) + d.M, params + L.norm_w,
+                                      nullptr, 0, gx, D, pp(W.gxT, d.depth - 1), D * e, nullptr, nullptr, nullptr, nullptr, d.M, 1, 0, st));
         } else if (s >= 0) {
             const int l = s;
             char* b = blk(l);
@@ -721,7 +740,7 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop
                                           d.M, d.D, st));
                 gy2 = ws + W.dtmp;
             }
-            {   // dW2 += gx^T hact
+            if (wg) {   // dW2 += gx^T hact
                 GemmP p = zero_gemm();
                 p.A = gy2; p.lda = D * e; p.W = b + W.hact; p.ldw = F * e;
                 p.M = d.M; p.N = d.D; p.K = d.F;
@@ -736,10 +755,10 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop
                 p.M = d.M; p.N = d.F; p.K = d.D;
                 p.aux = b + W.hpre; p.ldaux = F;
                 p.out0 = dhpre; p.ldo0 = F * e;
-                if (fc1b_in_tile()) { p.cs0 = gb + L.fc1_b; p.cpart = next_colpart(); }   // d fc1_b += column sums of dhpre from the accumulators of this epilogue (partials, fixed-order reduce)
+                if (fc1b_in_tile() && wg) { p.cs0 = gb + L.fc1_b; p.cpart = next_colpart(); }   // d fc1_b += column sums of dhpre from the accumulators of this epilogue (partials, fixed-order reduce)
                 MFVIT_TRY(gemm_nt_tile(d.dtype, EPI_GELU_BWD, p, st));
             }
-            {   // dW1 += dhpre^T y2
+            if (wg) {   // dW1 += dhpre^T y2
                 GemmP p = zero_gemm();
                 p.A = dhpre; p.lda = F * e; p.W = b + W.y2; p.ldw = D * e;
                 p.M = d.M; p.N = d.F; p.K = d.D;
@@ -760,7 +779,7 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop
                 if (lean_grad) { p.res_t = gxT; p.ldres_t = D * e; p.out0 = nullptr; }
                 else { p.res = gx; p.ldres = D; p.out0 = gmid; }
                 p.ldo0 = D; p.out1 = gmidT; p.ldo1 = D * e;
-                p.cs0 = gb + L.ln2_w; p.cs1 = gb + L.ln2_b; p.cs2 = rdrop ? colscr + D : gb + L.proj_b; p.cpart = next_colpart();
+                if (wg) { p.cs0 = gb + L.ln2_w; p.cs1 = gb + L.ln2_b; p.cs2 = rdrop ? colscr + D : gb + L.proj_b; p.cpart = next_colpart(); }
                 if (d.unfused) {
                     // plain data-gradient GEMM -> scratch, then the LayerNorm backward + residual-gradient add + column sums as one row pass
                     GemmP q = zero_gemm();
@@ -782,7 +801,7 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop
             }
             GemmP pend_proj = zero_gemm();                        // dWproj: launched here, or held back to ride along with dWqkv (one launch for both)
             bool have_pend = false;
-            {   // dWproj += gmid^T attn
+            if (wg) {   // dWproj += gmid^T attn
                 GemmP p = zero_gemm();
                 p.A = gyp; p.lda = D * e; p.W = b + W.attn; p.ldw = D * e;
                 p.M = d.M; p.N = d.D; p.K = d.D;
@@ -814,7 +833,7 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop
                                d.B, d.T, d.H, d.HD, st, do_max ? domax(l) : nullptr));
             MFVIT_TRY(fork());                                    // dqkv - and with it every input of this block's weight gradients - is ready
             for (int i = 0; i < ndef; ++i) MFVIT_TRY(gemm_tn(d.dtype, def_tn[i], wst));
-            {   // dWqkv += dqkv^T y1 ; d qkv_b += column sums of dqkv (ones-fragment MFMA inside the wgrad kernel)
+            if (wg) {   // dWqkv += dqkv^T y1 ; d qkv_b += column sums of dqkv (ones-fragment MFMA inside the wgrad kernel)
                 GemmP p = zero_gemm();
                 p.A = dqkv; p.lda = 3 * D * e; p.W = b + W.y1; p.ldw = D * e;
                 p.M = d.M; p.N = 3 * d.D; p.K = d.D;
@@ -837,7 +856,7 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop
             if (use_side && hipEventRecord(ss.done[l & 63], ss.s) != hipSuccess) return MFVIT_ELAUNCH;
             MFVIT_TRY(wait_layer(l + 1));                         // fc2-wgrad of layer l+1 reads the gxT copy written next
             {   // gx = LN1bwd(dqkv Wqkv) + gmid ; d ln1_w, d ln1_b, d fc2_b of block l-1 (or scratch for the embed stage)
-                if (l == 0 && hipMemsetAsync(colscr, 0, 2 * D * sizeof(float), st) != hipSuccess) return MFVIT_ELAUNCH;
+                if (wg && l == 0 && hipMemsetAsync(colscr, 0, 2 * D * sizeof(float), st) != hipSuccess) return MFVIT_ELAUNCH;
                 GemmP p = zero_gemm();
                 p.A = dqkv; p.lda = 3 * D * e; p.W = sb + S.qkv_t; p.ldw = 3 * D * e;
                 p.M = d.M; p.N = d.D; p.K = 3 * d.D;
@@ -847,7 +866,7 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop
                 if (lean_grad) { p.res_t = gmidT; p.ldres_t = D * e; p.out0 = l == 0 ? gx : nullptr; }     // (the embedding stage reads gx)
                 else { p.res = gmid; p.ldres = D; p.out0 = gx; }
                 p.ldo0 = D; p.out1 = pp(W.gxT, l - 1); p.ldo1 = D * e;
-                p.cs0 = gb + L.ln1_w; p.cs1 = gb + L.ln1_b; p.cs2 = (l > 0 && !rdrop) ? gblk(l - 1) + L.fc2_b : colscr; p.cpart = next_colpart();
+                if (wg) { p.cs0 = gb + L.ln1_w; p.cs1 = gb + L.ln1_b; p.cs2 = (l > 0 && !rdrop) ? gblk(l - 1) + L.fc2_b : colscr; p.cpart = next_colpart(); }
                 if (d.unfused) {
                     GemmP q = zero_gemm();
                     q.A = p.A; q.lda = p.lda; q.W = p.W; q.ldw = p.ldw; q.M = p.M; q.N = p.N; q.K = p.K;
@@ -876,9 +895,26 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop
                 // (the operand-type copy is cast afresh from the masked f32 rows: no second rounding of the split copy)
                 MFVIT_TRY(mask_scale_rows(d.dtype, true, gx, D, gx, D, make_drop(d.p_embd, d.seed, 1), off, 1, d.M, d.D, st));
                 MFVIT_TRY(cast_transpose(d.dtype, gx, pp(W.gxT, -1), nullptr, d.M, d.D, st));
-                if (hipMemsetAsync(colscr, 0, D * sizeof(float), st) != hipSuccess) return MFVIT_ELAUNCH;
-                MFVIT_TRY(colsum_rows(gx, D, colscr, d.M, 1, 0, d.D, st));
+                if (wg) {
+                    if (hipMemsetAsync(colscr, 0, D * sizeof(float), st) != hipSuccess) return MFVIT_ELAUNCH;
+                    MFVIT_TRY(colsum_rows(gx, D, colscr, d.M, 1, 0, d.D, st));
+                }
             }
+            if (dimg) {
+                // d img = col2im(gx[patch rows] W_pe): W_pe^T of the operand type into the workspace (the shadow keeps W_pe [D][768] only; W_pe takes
+                // part in the data gradient under stop_grad_conv1 too), then one tile GEMM whose epilogue stores the f32 image (EPI_COL2IM16, gemm.hip).
+                // A = the operand-type copy of gx from token row 1 on: B T - 1 rows, the cls rows of images 1 .. B-1 among them (skipped by the epilogue).
+                char* wpeT = ws + W.wpeT;
+                MFVIT_TRY(cast_transpose(d.dtype, params + L.pe_w, nullptr, wpeT, d.D, 768, st));
+                GemmP p = zero_gemm();
+                p.A = (const char*)pp(W.gxT, -1) + (size_t)D * d.es; p.lda = D * e;
+                p.W = wpeT; p.ldw = D * e;
+                p.M = d.M - 1; p.N = 768; p.K = d.D;
+                p.orow_in = d.np; p.orow_out = d.T;
+                p.out0 = dimg; p.ldo0 = cfg->img_w;
+                MFVIT_TRY(gemm_nt_tile(d.dtype, EPI_COL2IM16, p, st));
+            }
+            if (!wg) continue;
             // embed stage: gx = d x_0.  d cls_token = sum_b gx[b,0]; d pe_b = sum over patch rows; d pe_w = gx_patch^T patches.
             // pos_embed is a fixed table (requires_grad = False upstream): no gradient.
             MFVIT_TRY(colsum_rows(gx, D, dparams + L.cls, d.B, d.T, 0, d.D, st));
@@ -921,14 +957,20 @@ int mfvit_vit_forward_drop(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop,
 }
 int mfvit_vit_backward(const mfvit_vit_cfg* cfg, const float* params, const void* shadow, void* workspace, const float* dfeatures,
                        float* dparams, int stage_hi, int stage_lo, mfvit_stream_t stream) {
+    if (!dparams) return MFVIT_EINVAL;
     ShareScope share(cfg);
-    return encoder_backward(cfg, nullptr, params, shadow, workspace, dfeatures, dparams, nullptr, stage_hi, stage_lo, stream, false);
+    return encoder_backward(cfg, nullptr, params, shadow, workspace, dfeatures, dparams, nullptr, nullptr, stage_hi, stage_lo, stream, false);
+}
+int mfvit_vit_backward_ex(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, const float* params, const void* shadow, void* workspace,
+                          const float* dfeatures, float* dparams, float* dimg, int stage_hi, int stage_lo, mfvit_stream_t stream) {
+    ShareScope share(cfg);
+    return encoder_backward(cfg, drop, params, shadow, workspace, dfeatures, dparams, nullptr, dimg, stage_hi, stage_lo, stream, false);
 }
 int mfvit_vit_backward_drop(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, const float* params, const void* shadow, void* workspace,
                             const float* dfeatures, float* dparams, int stage_hi, int stage_lo, mfvit_stream_t stream) {
-    if (!drop) return MFVIT_EINVAL;
+    if (!drop || !dparams) return MFVIT_EINVAL;
     ShareScope share(cfg);
-    return encoder_backward(cfg, drop, params, shadow, workspace, dfeatures, dparams, nullptr, stage_hi, stage_lo, stream, false);
+    return encoder_backward(cfg, drop, params, shadow, workspace, dfeatures, dparams, nullptr, nullptr, stage_hi, stage_lo, stream, false);
 }
 int mfvit_gpt_forward(const mfvit_vit_cfg* cfg, const float* params, const void* shadow, const float* tokens, void* workspace, float* out,
                       mfvit_stream_t stream) {
@@ -939,7 +981,8 @@ int mfvit_gpt_backward(const mfvit_vit_cfg* cfg, const float* params, const void
                        float* dtokens, mfvit_stream_t stream) {
     if (!cfg || !dtokens || !dout) return MFVIT_EINVAL;
     ShareScope share(cfg);
-    return encoder_backward(cfg, nullptr, params, shadow, workspace, dout, dparams, dtokens, cfg->depth, -1, stream, true);
+    if (!dparams) return MFVIT_EINVAL;
+    return encoder_backward(cfg, nullptr, params, shadow, workspace, dout, dparams, dtokens, nullptr, cfg->depth, -1, stream, true);
 }
 
 // ------------------------------------------------------------------------------------------------ single ops

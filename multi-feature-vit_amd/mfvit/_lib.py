@@ -56,6 +56,8 @@ SIGNATURES = {
     "mfvit_vit_workspace_bytes_drop": (c_size_t, [POINTER(VitCfg), POINTER(VitDrop)]),
     "mfvit_vit_forward_drop": (I, [POINTER(VitCfg), POINTER(VitDrop), P, P, P, P, P, P]),
     "mfvit_vit_backward_drop": (I, [POINTER(VitCfg), POINTER(VitDrop), P, P, P, P, P, I, I, P]),
+    "mfvit_vit_workspace_bytes_ex": (c_size_t, [POINTER(VitCfg), POINTER(VitDrop), I]),
+    "mfvit_vit_backward_ex": (I, [POINTER(VitCfg), POINTER(VitDrop), P, P, P, P, P, P, I, I, P]),
     "mfvit_gpt_forward": (I, [POINTER(VitCfg), P, P, P, P, P, P]),
     "mfvit_gpt_backward": (I, [POINTER(VitCfg), P, P, P, P, P, P, P]),
     "mfvit_linear_fwd": (I, [I, I, P, L, P, L, P, P, L, P, L, I, I, I, P]),

@@ -98,31 +98,49 @@ class _PatchEmbed(nn.Module):
 
 
 class _EncoderFn(torch.autograd.Function):
-    """features3D as one autograd node: forward = mfvit_vit_forward, backward = mfvit_vit_backward (stage by stage)."""
+    """features3D as one autograd node: forward = mfvit_vit_forward, backward = mfvit_vit_backward (stage by stage), or mfvit_vit_backward_ex
+    when the image requires a gradient (d loss / d img from the patch-embedding data gradient; no parameter gradient at all when no arena
+    parameter requires one)."""
 
     @staticmethod
     def forward(ctx, model, img, need_grad, drop, *params):
         # drop: the mfvit_vit_drop of THIS forward (None: no dropout site active)
-        feats, ws = model._run_forward(img, need_grad, drop)
+        want_dimg = bool(need_grad and ctx.needs_input_grad[1])
+        feats, ws = model._run_forward(img, need_grad, drop, want_dimg=want_dimg)
         ctx.model = model
         ctx.ws = ws
         ctx.cfg = model._cfg(img, need_grad)
         ctx.drop = drop                     # the backward rebuilds the same masks from it
+        ctx.want_dimg = want_dimg
+        ctx.img_meta = (img.shape, img.dtype)
         return feats
 
     @staticmethod
     def backward(ctx, dfeats):
         model = ctx.model
+        if torch.is_grad_enabled():
+            raise _lib.MfvitError("double backward through the encoder (create_graph=True) is not supported: its backward is one HIP call "
+                                  "whose results are not differentiable")
         if ctx.ws is None:
             raise _lib.MfvitError("the encoder's saved activations were already released: a second backward through the same forward "
                                   "(retain_graph=True) is not supported - run the forward again")
-        grads = model._run_backward(ctx.cfg, ctx.ws, dfeats, drop=ctx.drop)
+        dimg = None
+        if ctx.want_dimg and ctx.needs_input_grad[1]:
+            shape, dtype = ctx.img_meta
+            # (allocated on the current stream - the side stream of a two-stream model's ENH encoder - and recorded there: autograd hands it
+            # to consumers on other streams)
+            dimg = torch.empty(shape, device=dfeats.device, dtype=torch.float32)
+            dimg.record_stream(torch.cuda.current_stream(dfeats.device))
+        want_params = any(ctx.needs_input_grad[4:])
+        grads = model._run_backward(ctx.cfg, ctx.ws, dfeats, drop=ctx.drop, dimg=dimg, want_params=want_params)
         model._release_ws(ctx.ws)
         ctx.ws = None
         # the single-use feature cache holds the forward's output, i.e. this graph and the parameters' AccumulateGrad nodes (which carry
         # the stream they were created under): once the backward has run it must not keep them alive into the next iteration
         model._feat_cache = None
-        return (None, None, None, None) + tuple(grads)
+        if dimg is not None and dimg.dtype != ctx.img_meta[1]:
+            dimg = dimg.to(ctx.img_meta[1])
+        return (None, dimg, None, None) + tuple(grads)
 
 
 class _HeadFn(torch.autograd.Function):
@@ -372,8 +390,11 @@ class VisionTransformerMoCo(nn.Module):
         self._shadow_key = key
         self._feat_cache = None
 
-    def _get_ws(self, cfg, drop=None):
-        nbytes = lib().mfvit_vit_workspace_bytes(cfg) if drop is None else lib().mfvit_vit_workspace_bytes_drop(cfg, drop)
+    def _get_ws(self, cfg, drop=None, want_dimg=False):
+        if want_dimg:       # (the image gradient's W_pe^T behind the usual layout: include/mfvit.h, mfvit_vit_workspace_bytes_ex)
+            nbytes = lib().mfvit_vit_workspace_bytes_ex(cfg, drop, 1)
+        else:
+            nbytes = lib().mfvit_vit_workspace_bytes(cfg) if drop is None else lib().mfvit_vit_workspace_bytes_drop(cfg, drop)
         if nbytes == 0:
             raise _lib.MfvitError("invalid encoder configuration (image size must be a multiple of 16, dim 384 or 768, head_dim 32 / 64 / 96)")
         pool = self._ws_pool.setdefault(nbytes, [])
@@ -385,7 +406,7 @@ class VisionTransformerMoCo(nn.Module):
             if len(pool) < 2:
                 pool.append(ws)
 
-    def _run_forward(self, img, save, drop=None):
+    def _run_forward(self, img, save, drop=None, want_dimg=False):
         _lib.require_cuda(img)
         if img.dtype != torch.float32:
             img = img.float()
@@ -397,7 +418,7 @@ class VisionTransformerMoCo(nn.Module):
             raise _lib.MfvitError(f"model on {self._arena.device} but input on {img.device}")
         cfg = self._cfg(img, save)
         self._ensure_shadow(cfg)
-        ws = self._get_ws(cfg, drop)
+        ws = self._get_ws(cfg, drop, want_dimg)
         feats = torch.empty(img.shape[0], self.num_tokens, self.embed_dim, device=img.device, dtype=torch.float32)
         if drop is None:
             check(lib().mfvit_vit_forward(cfg, ptr(self._arena), ptr(self._shadow), ptr(img), ptr(ws), ptr(feats), stream()),
@@ -410,11 +431,19 @@ class VisionTransformerMoCo(nn.Module):
             ws = None
         return feats, ws
 
-    def _run_backward(self, cfg, ws, dfeats, on_stage_done=None, drop=None):
-        """Returns per-parameter gradient views (arena order) of a fresh flat gradient arena.  drop: the forward's mfvit_vit_drop (or None)."""
+    def _run_backward(self, cfg, ws, dfeats, on_stage_done=None, drop=None, dimg=None, want_params=True):
+        """Returns per-parameter gradient views (arena order) of a fresh flat gradient arena.  drop: the forward's mfvit_vit_drop (or None).
+        dimg: (B,3,H,W) f32, overwritten with d loss / d img (the forward's workspace must come from _get_ws(.., want_dimg=True)).
+        want_params=False (needs dimg): the data-gradient-only backward - no gradient arena, every returned gradient None."""
         dfeats = dfeats.contiguous()
         if dfeats.dtype != torch.float32:
             dfeats = dfeats.float()
+        if not want_params:
+            if dimg is None:
+                raise _lib.MfvitError("a backward without parameter gradients needs the image gradient")
+            check(lib().mfvit_vit_backward_ex(cfg, drop, ptr(self._arena), ptr(self._shadow), ptr(ws), ptr(dfeats), None, ptr(dimg),
+                                              self.depth, -1, stream()), "mfvit_vit_backward_ex")
+            return [None] * len(self._arena_params)
         # The flat gradient arena is reused from step to step (stable addresses: the optimizers' device tables stay valid) unless a
         # parameter still holds a gradient - accumulation over several backward passes, or a second pass through this encoder
         # inside one autograd run (MoCo-v3 feeds both views through the base encoder) - in which case a fresh one is allocated.
@@ -437,7 +466,10 @@ class VisionTransformerMoCo(nn.Module):
         hook = on_stage_done or getattr(self, "_grad_stage_hook", None)
 
         def bwd(hi, lo):
-            if drop is None:
+            if dimg is not None and lo == -1:     # (the call that runs the embedding stage also writes the image gradient)
+                check(lib().mfvit_vit_backward_ex(cfg, drop, ptr(self._arena), ptr(self._shadow), ptr(ws), ptr(dfeats), ptr(gflat), ptr(dimg),
+                                                  hi, lo, stream()), "mfvit_vit_backward_ex")
+            elif drop is None:
                 check(lib().mfvit_vit_backward(cfg, ptr(self._arena), ptr(self._shadow), ptr(ws), ptr(dfeats), ptr(gflat), hi, lo, stream()),
                       "mfvit_vit_backward")
             else:
@@ -468,8 +500,10 @@ class VisionTransformerMoCo(nn.Module):
 
     # ------------------------------------------------------------------ public API (reference call sites)
     def _features(self, x, caller):
-        need = torch.is_grad_enabled() and any(p.requires_grad for p in self._arena_params)
-        key = (x._version, need, self._param_version(), torch.is_grad_enabled())
+        # activations are saved when a parameter or the image needs a gradient (saliency / FGSM with a frozen backbone: the image only)
+        need_x = torch.is_grad_enabled() and x.requires_grad
+        need = need_x or (torch.is_grad_enabled() and any(p.requires_grad for p in self._arena_params))
+        key = (x._version, need, need_x, self._param_version(), torch.is_grad_enabled())
         c = self._feat_cache
         self._feat_cache = None
         drop = self._draw_drop()            # (a fresh seed per training-mode forward with dropout; None otherwise)
