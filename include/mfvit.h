@@ -161,6 +161,40 @@ size_t mfvit_vit_workspace_bytes_ex(const mfvit_vit_cfg* cfg, const mfvit_vit_dr
 int mfvit_vit_backward_ex(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, const float* params, const void* shadow, void* workspace,
                           const float* dfeatures, float* dparams, float* dimg, int stage_hi, int stage_lo, mfvit_stream_t stream);
 
+/* Attention maps of the image encoder (additive in ABI 5): an evaluation forward (no dropout site active) that writes the same `features` as
+ * mfvit_vit_forward, on a workspace of mfvit_vit_workspace_bytes(cfg) bytes, plus the softmax probabilities of the requested blocks:
+ *   P[b][h][i][j] = exp(scale q_i.k_j - lse_i),  scale = head_dim^-1/2,
+ * recomputed after each block's attention forward from its qkv tensor and log-sum-exp, i.e. exactly as that forward's softmax normalised
+ * them (f32; every row of a per-head map sums to 1).  Heads in timm's order (qkv.reshape(B, T, 3, heads, head_dim)); tokens: cls, then
+ * the patches row by row.
+ *   blocks    bit l: write block l's map into `maps` (bits at or above cfg->depth are invalid)
+ *   fuse      0: per head [B][H][rows][T];  1 / 2 / 3: mean / max / min over the heads [B][rows][T]
+ *   cls_only  1: the cls query's row only (rows = 1; the query axis is kept in the layout), 0: all T rows
+ *   maps      the selected blocks in ascending order, each block's map contiguous; NULL iff blocks == 0
+ *   rollout   NULL, or [B][T-1]: the cls row of the attention rollout (Abnar & Zuidema 2020) over ALL blocks, of the fused maps F_l (fuse
+ *             1 - 3; its own full-row maps, whatever cls_only and blocks say):
+ *               a_l = diag(c_l) (F_l / 2 + I / 2),  c_l = 1 / (s_l / 2 + 1 / 2),  s_l = the row sums of F_l,  R = a_{depth-1} ... a_0,
+ *               rollout = R[0, 1:]  (patch order; not normalised).
+ *             The row normalisation c_l matters for max / min fusion only: a mean-fused row sums to 1, a max-fused row to more, a min-fused
+ *             row to less.  Needs T <= 8192.
+ *   scratch   mfvit_vit_attn_scratch_bytes(cfg, req) bytes: with a rollout the depth fused maps [B][T][T] and their row sums [B][T]
+ *             (4 depth B T (T + 1) bytes); 256 bytes otherwise.
+ * MFVIT_EINVAL (before any HIP call), and 0 bytes from mfvit_vit_attn_scratch_bytes, for: token-input mode, a `blocks` bit at or above
+ * cfg->depth, fuse outside 0 - 3, cls_only other than 0 / 1, a rollout with fuse 0, maps NULL with blocks != 0 (or set with blocks == 0), a
+ * request that asks for nothing (blocks == 0, rollout NULL), and the checks of mfvit_vit_forward; mfvit_vit_forward_attn also for scratch
+ * NULL.  With no such call the other entry points run exactly the launches they ran before. */
+typedef struct mfvit_vit_attn_req {
+    uint64_t blocks;   /* bit l: write the probabilities of block l into maps */
+    int fuse;          /* 0 per head | 1 mean | 2 max | 3 min over heads */
+    int cls_only;      /* 1: query row 0 only */
+    float* maps;       /* selected blocks in ascending order, each [B][H or 1][T or 1][T] f32; NULL iff blocks == 0 */
+    float* rollout;    /* NULL, or [B][T-1]: cls row of the rollout over all blocks (needs fuse 1..3) */
+    void* scratch;     /* mfvit_vit_attn_scratch_bytes(cfg, req) bytes (rollout: the depth fused maps + row sums) */
+} mfvit_vit_attn_req;
+size_t mfvit_vit_attn_scratch_bytes(const mfvit_vit_cfg* cfg, const mfvit_vit_attn_req* req);
+int mfvit_vit_forward_attn(const mfvit_vit_cfg* cfg, const mfvit_vit_attn_req* req, const float* params, const void* shadow,
+                           const float* img, void* workspace, float* features, mfvit_stream_t stream);
+
 /* Token-input encoder (cfg->token_input = 1): the GPT of the TransFuser fusion (fuseattention.py:84-212), heads x head_dim with
  * head_dim in {32, 64, 96} (config.py: n_embd 384, n_head 4 -> 96), mlp_dim = block_exp * dim.
  * Parameter arena (f32): pos_emb [tokens][dim], then per block

@@ -1,0 +1,257 @@
+// Attention maps of the ViT encoder (DINO's get_last_selfattention, per-block maps, attention rollout), formed after a block's attention
+// forward from what that forward leaves in the workspace: the qkv tensor and the natural-log log-sum-exp lse [B][H][T].
+//
+//   P[b][h][i][j] = exp(scale q_i.k_j - lse[b][h][i]),  scale = head_dim^-1/2 (the forward kernels apply it to the scores; q is not
+//   stored pre-scaled) - the probabilities exactly as normalised by the forward's softmax.
+//
+// Probability kernel.  qkv in any of the encoder's storage formats, layout [B][T][3][H][HD]: f32, bf16, fp16, split bf16 (MFVIT_BF16X3)
+// and split fp16 (MFVIT_X3F16), I32 layout for the split ones (common.cuh).  Every operand is widened to f32 on load (split: hi + lo) and
+// S = q k^T runs on v_mfma_f32_32x32x2_f32 (exact f32 products: for a 16-bit operand the recomputed S differs from the forward's only in
+// summation order).  A lane holds 16 consecutive logical columns of every 32-wide group of its row (lanes 0 - 31 the first 16, lanes
+// 32 - 63 the last 16): which k a lane half feeds is free as long as both operands agree, and so every lane reads 32 / 64 contiguous bytes.
+// Work split: one workgroup (4 waves) per (image, 32-query tile[, head]); wave w takes the key tiles w, w + 4, ...  Fused forms (mean /
+// max / min over heads) loop over the heads inside the key tile and fuse in registers: per-head maps never reach memory.  Their row sums
+// (optional) are reduced lane butterfly -> LDS -> a fixed wave order.  Query and key positions past T are clamped on load and never stored.
+//
+// Rollout kernel (Abnar & Zuidema 2020), cls row only: v = row 0 of a_{L-1}, then v <- v a_l for l = L-2 .. 0 with
+// a_l = diag(c_l) (F_l / 2 + I / 2), c_l = 1 / (s_l / 2 + 1 / 2): each step w = v o c_l, v <- (w F_l + w) / 2.  One workgroup per image,
+// v in LDS, column sums in a fixed order.
+//
+// No atomics anywhere: repeated calls return the same bits.
+#include "common.cuh"
+#include "kernels.h"
+#include "prof.h"
+
+namespace mfvit {
+
+namespace {
+
+constexpr int AM_WAVES = 4;
+
+__device__ __forceinline__ int am_acc_row(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
+
+// storage element of the qkv tensor of tag T
+template <typename T> struct AmStor { typedef T E; static constexpr int EP = 1; };
+template <> struct AmStor<sbf16> { typedef bf16 E; static constexpr int EP = 2; };
+template <> struct AmStor<sf16> { typedef f16 E; static constexpr int EP = 2; };
+
+// f[16 g + i] = logical column 32 g + 16 half + i of a head row piece (g < NB), widened to f32; split tensors: hi + lo
+template <typename T, int NB> __device__ __forceinline__ void am_load_frag(const typename AmStor<T>::E* row, int half, float (&f)[16 * NB]) {
+#pragma unroll
+    for (int g = 0; g < NB; ++g) {
+        if constexpr (std::is_same<T, float>::value) {
+            const float4* p = (const float4*)(row + 32 * g + 16 * half);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const float4 v = p[i];
+                f[16 * g + 4 * i] = v.x; f[16 * g + 4 * i + 1] = v.y; f[16 * g + 4 * i + 2] = v.z; f[16 * g + 4 * i + 3] = v.w;
+            }
+        } else if constexpr (is_split<T>::value) {
+            typedef typename Vec8<T>::type V;
+            const V* hp = (const V*)(row + 64 * g + 16 * half);
+            const V* lp = (const V*)(row + 64 * g + 32 + 16 * half);
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const V h = hp[i], l = lp[i];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) f[16 * g + 8 * i + j] = (float)h[j] + (float)l[j];
+            }
+        } else {
+            typedef typename Vec8<T>::type V;
+            const V* p = (const V*)(row + 32 * g + 16 * half);
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const V v = p[i];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) f[16 * g + 8 * i + j] = (float)v[j];
+            }
+        }
+    }
+}
+
+// S tile [32 queries][32 keys] of one head: lane (r, half) gives q row r and k row r; result row i = am_acc_row(reg, lane), column = lane & 31
+template <int NB> __device__ __forceinline__ f32x16 am_scores(const float (&qf)[16 * NB], const float (&kf)[16 * NB]) {
+    f32x16 s;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) s[r] = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16 * NB; ++i) s = __builtin_amdgcn_mfma_f32_32x32x2f32(qf[i], kf[i], s, 0, 0, 0);
+    return s;
+}
+
+// FUSED = false: out [B][H][rows][T] (grid B * H * nqt);  FUSED = true: out [B][rows][T] fused over heads by `op` (1 mean, 2 max, 3 min),
+// sums [B][rows] (or NULL) = the fused rows' sums over the T keys (grid B * nqt).  rows = T, or 1 (the cls query); nqt = ceil(rows / 32).
+template <typename T, int NB, bool FUSED>
+__global__ __launch_bounds__(256) void attn_probs_kernel(const typename AmStor<T>::E* __restrict__ qkv, const float* __restrict__ lse,
+                                                         float* __restrict__ out, float* __restrict__ sums, int Tn, int H, int rows, int nqt,
+                                                         int op, float c) {
+    typedef typename AmStor<T>::E E;
+    constexpr int HD = 32 * NB, EP = AmStor<T>::EP;
+    __shared__ float part[AM_WAVES][32];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5;
+    int bid = blockIdx.x;
+    const int qt = bid % nqt;
+    bid /= nqt;
+    const int h0 = FUSED ? 0 : bid % H, b = FUSED ? bid : bid / H;
+    const int q0 = qt * 32;
+    const long hs = (long)H * HD * EP, rs = 3 * hs;                 // storage elements of one of q / k / v of a token, and of all three
+    const E* base = qkv + (long)b * Tn * rs;
+    const int qrow = min(q0 + (lane & 31), Tn - 1);                  // (rows past the end: a valid row is read, nothing is stored)
+    const int nkt = (Tn + 31) / 32;
+    // -lse of the lane's 16 result rows in log2 units, and the q fragment: loaded once per head
+    float qf[16 * NB], nl[16];
+    auto load_head = [&](int h) __attribute__((always_inline)) {
+        am_load_frag<T, NB>(base + (long)qrow * rs + (long)h * HD * EP, half, qf);
+        const float* lrow = lse + ((long)b * H + h) * Tn;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) nl[r] = -lrow[min(q0 + am_acc_row(r, lane), Tn - 1)] * 1.4426950408889634f;
+    };
+    if constexpr (!FUSED) load_head(h0);
+    float rsum[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) rsum[r] = 0.f;
+    for (int kt = wave; kt < nkt; kt += AM_WAVES) {
+        const int key = kt * 32 + (lane & 31);
+        const E* krow = base + (long)min(key, Tn - 1) * rs + hs;
+        f32x16 f;
+        if constexpr (!FUSED) {
+            float kf[16 * NB];
+            am_load_frag<T, NB>(krow + (long)h0 * HD * EP, half, kf);
+            const f32x16 s = am_scores<NB>(qf, kf);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) f[r] = exp2f(fmaf(s[r], c, nl[r]));
+        } else {
+            for (int h = 0; h < H; ++h) {
+                load_head(h);
+                float kf[16 * NB];
+                am_load_frag<T, NB>(krow + (long)h * HD * EP, half, kf);
+                const f32x16 s = am_scores<NB>(qf, kf);
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float p = exp2f(fmaf(s[r], c, nl[r]));
+                    f[r] = h == 0 ? p : op == 1 ? f[r] + p : op == 2 ? fmaxf(f[r], p) : fminf(f[r], p);
+                }
+            }
+            if (op == 1) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) f[r] = f[r] / (float)H;
+            }
+        }
+        if (key < Tn) {
+            float* o = out + (((long)b * (FUSED ? 1 : H) + h0) * rows) * Tn + key;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int q = q0 + am_acc_row(r, lane);
+                if (q < rows) o[(long)q * Tn] = f[r];
+                rsum[r] += f[r];
+            }
+        }
+    }
+    if (!sums) return;                                                 // (uniform over the grid)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        float v = rsum[r];
+#pragma unroll
+        for (int m = 1; m < 32; m <<= 1) v += __shfl_xor(v, m, 64);   // within the lane half: every lane ends with the same bits
+        rsum[r] = v;
+    }
+    if ((lane & 31) == 0) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) part[wave][am_acc_row(r, lane)] = rsum[r];
+    }
+    __syncthreads();
+    if (threadIdx.x < 32 && q0 + (int)threadIdx.x < rows) {
+        float v = part[0][threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < AM_WAVES; ++w) v += part[w][threadIdx.x];
+        sums[(long)b * rows + q0 + threadIdx.x] = v;
+    }
+}
+
+// maps: depth x [B][T][T] fused maps, sums: depth x [B][T] their row sums; out [B][T-1] = R[0, 1:] of the rollout.  LDS: v, w [T] each.
+__global__ __launch_bounds__(256) void attn_rollout_kernel(const float* __restrict__ maps, const float* __restrict__ sums, int depth, int B,
+                                                           int Tn, float* __restrict__ out) {
+    extern __shared__ float am_lds[];
+    float* v = am_lds;
+    float* w = am_lds + Tn;
+    const int b = blockIdx.x;
+    const long mstride = (long)B * Tn * Tn, sstride = (long)B * Tn;
+    {   // v = row 0 of a_{L-1}
+        const float* F = maps + (long)(depth - 1) * mstride + (long)b * Tn * Tn;
+        const float c0 = 1.0f / (0.5f * sums[(long)(depth - 1) * sstride + (long)b * Tn] + 0.5f);
+        for (int j = threadIdx.x; j < Tn; j += blockDim.x) v[j] = c0 * (0.5f * F[j] + (j == 0 ? 0.5f : 0.f));
+    }
+    __syncthreads();
+    for (int l = depth - 2; l >= 0; --l) {
+        const float* F = maps + (long)l * mstride + (long)b * Tn * Tn;
+        const float* s = sums + (long)l * sstride + (long)b * Tn;
+        for (int i = threadIdx.x; i < Tn; i += blockDim.x) w[i] = v[i] * (1.0f / (0.5f * s[i] + 0.5f));
+        __syncthreads();
+        for (int j = threadIdx.x; j < Tn; j += blockDim.x) {
+            // four partial sums over i = 4 m + t, added in a fixed order
+            float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+            int i = 0;
+            for (; i + 4 <= Tn; i += 4) {
+                a0 = fmaf(w[i], F[(long)i * Tn + j], a0);
+                a1 = fmaf(w[i + 1], F[(long)(i + 1) * Tn + j], a1);
+                a2 = fmaf(w[i + 2], F[(long)(i + 2) * Tn + j], a2);
+                a3 = fmaf(w[i + 3], F[(long)(i + 3) * Tn + j], a3);
+            }
+            for (; i < Tn; ++i) a0 = fmaf(w[i], F[(long)i * Tn + j], a0);
+            v[j] = 0.5f * ((a0 + a1) + (a2 + a3)) + 0.5f * w[j];
+        }
+        __syncthreads();
+    }
+    for (int j = 1 + threadIdx.x; j < Tn; j += blockDim.x) out[(long)b * (Tn - 1) + j - 1] = v[j];
+}
+
+template <typename T, int NB>
+int launch_probs(const void* qkv, const float* lse, int B, int Tn, int H, int fuse, int rows, float* out, float* sums, hipStream_t st) {
+    typedef typename AmStor<T>::E E;
+    const int nqt = (rows + 31) / 32;
+    const float c = 1.0f / sqrtf((float)(32 * NB)) * 1.4426950408889634f;   // the forward kernels' scale * log2(e)
+    ProfScope ps(PROF_OTHER, 2.0 * B * H * (double)rows * Tn * 32 * NB, (double)B * (fuse ? 1 : H) * rows * Tn * 4, st);
+    if (fuse)
+        MFVIT_LAUNCH((attn_probs_kernel<T, NB, true>), dim3(B * nqt), dim3(64 * AM_WAVES), 0, st, (const E*)qkv, lse, out, sums, Tn, H, rows,
+                     nqt, fuse, c);
+    else
+        MFVIT_LAUNCH((attn_probs_kernel<T, NB, false>), dim3(B * H * nqt), dim3(64 * AM_WAVES), 0, st, (const E*)qkv, lse, out, sums, Tn, H,
+                     rows, nqt, 0, c);
+    MFVIT_CHECK_LAUNCH();
+    return MFVIT_OK;
+}
+template <typename T>
+int probs_by_hd(const void* qkv, const float* lse, int B, int Tn, int H, int HD, int fuse, int rows, float* out, float* sums, hipStream_t st) {
+    if (HD == 32) return launch_probs<T, 1>(qkv, lse, B, Tn, H, fuse, rows, out, sums, st);
+    if (HD == 64) return launch_probs<T, 2>(qkv, lse, B, Tn, H, fuse, rows, out, sums, st);
+    if (HD == 96) return launch_probs<T, 3>(qkv, lse, B, Tn, H, fuse, rows, out, sums, st);
+    return MFVIT_ENOSYS;
+}
+
+}  // namespace
+
+int attn_probs(int qdt, const void* qkv, const float* lse, int B, int Tn, int H, int HD, int fuse, int cls_only, float* out, float* sums,
+               hipStream_t st) {
+    if (!qkv || !lse || !out || B <= 0 || Tn <= 0 || H <= 0 || fuse < 0 || fuse > 3 || (sums && !fuse)) return MFVIT_EINVAL;
+    const int rows = cls_only ? 1 : Tn;
+    switch (qdt) {
+        case MFVIT_F32: return probs_by_hd<float>(qkv, lse, B, Tn, H, HD, fuse, rows, out, sums, st);
+        case MFVIT_BF16: return probs_by_hd<bf16>(qkv, lse, B, Tn, H, HD, fuse, rows, out, sums, st);
+        case MFVIT_F16: return probs_by_hd<f16>(qkv, lse, B, Tn, H, HD, fuse, rows, out, sums, st);
+        case MFVIT_BF16X3: return probs_by_hd<sbf16>(qkv, lse, B, Tn, H, HD, fuse, rows, out, sums, st);
+        case MFVIT_X3F16: return probs_by_hd<sf16>(qkv, lse, B, Tn, H, HD, fuse, rows, out, sums, st);
+        default: return MFVIT_EINVAL;
+    }
+}
+
+int attn_rollout(const float* maps, const float* sums, int depth, int B, int Tn, float* out, hipStream_t st) {
+    if (!maps || !sums || !out || depth <= 0 || B <= 0 || Tn < 2) return MFVIT_EINVAL;
+    const size_t bytes = 2 * (size_t)Tn * 4;
+    if (bytes > 64 * 1024) return MFVIT_ENOSYS;
+    ProfScope ps(PROF_OTHER, 2.0 * depth * B * (double)Tn * Tn, 4.0 * depth * B * (double)Tn * Tn, st);
+    MFVIT_LAUNCH(attn_rollout_kernel, dim3(B), dim3(256), bytes, st, maps, sums, depth, B, Tn, out);
+    MFVIT_CHECK_LAUNCH();
+    return MFVIT_OK;
+}
+
+}  // namespace mfvit

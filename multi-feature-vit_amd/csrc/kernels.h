@@ -94,4 +94,11 @@ int drop_add_ln_rows(int dtype, int N, const void* tin, long ldt, const float* a
                      const float* gamma, const float* beta, float eps, float* mean, float* rstd, int rows, hipStream_t st);
 int mask_scale_rows(int dtype, bool f32, const void* src, long lds_, void* dst, long ldd, DropP drop, DropP dpath, int tpr, int rows, int N,
                     hipStream_t st);
+// attention_maps.hip: the softmax probabilities of one block's attention forward, recomputed from its qkv (storage tag qdt, as
+// attn_qkv_dtype reports it) and lse: out [B][H][rows][T] (fuse 0) or fused over the heads (1 mean, 2 max, 3 min) [B][rows][T] with the fused
+// rows' sums [B][rows] in `sums` (fused forms only; may be NULL); rows = T, or 1 with cls_only.  And the cls row of the attention rollout over
+// `depth` such fused maps (depth x [B][T][T], row sums depth x [B][T]) -> out [B][T-1].
+int attn_probs(int qdt, const void* qkv, const float* lse, int B, int Tn, int H, int HD, int fuse, int cls_only, float* out, float* sums,
+               hipStream_t st);
+int attn_rollout(const float* maps, const float* sums, int depth, int B, int Tn, float* out, hipStream_t st);
 }  // namespace mfvit

@@ -389,8 +389,33 @@ int mfvit_vit_prepare_shadow(const mfvit_vit_cfg* cfg, const float* params, void
 
 // Shared forward of the two front ends: ViT-S/16 (img = (B,3,H,W) image, patch embedding + cls token) and the token-input GPT
 // (img = (B,T,dim) tokens, + pos_emb).  Everything behind x_0 / LN1_0 is the same pre-LN block stack.
+// Attention maps (mfvit_vit_forward_attn): validity of a request, and the optional per-block step behind block l's attention forward - its
+// probabilities into req->maps (the block's slot among the selected ones) and, for a rollout, its fused map and row sums into the scratch.
+static bool attn_req_ok(const mfvit_vit_cfg* cfg, const mfvit_vit_attn_req* r, Dims& d) {
+    if (!r || !get_dims(cfg, d) || d.tok) return false;
+    if (d.depth < 64 && (r->blocks >> d.depth) != 0) return false;
+    if (r->fuse < 0 || r->fuse > 3 || (r->cls_only != 0 && r->cls_only != 1)) return false;
+    if (r->rollout && (r->fuse == 0 || 2 * (size_t)d.T * 4 > 64 * 1024)) return false;   // (the rollout kernel keeps two [T] vectors in LDS)
+    if ((r->blocks != 0) != (r->maps != nullptr)) return false;
+    return r->blocks != 0 || r->rollout != nullptr;
+}
+// scratch of a rollout: the depth fused maps [B][T][T], then their row sums [B][T]
+static float* attn_scratch_sums(const Dims& d, const mfvit_vit_attn_req* r) { return (float*)r->scratch + (size_t)d.depth * d.B * d.T * d.T; }
+static int attn_block_step(const Dims& d, const mfvit_vit_attn_req* r, int l, int qdt, const void* qkv, const float* lse, hipStream_t st) {
+    if ((r->blocks >> l) & 1) {
+        const size_t slot = __builtin_popcountll(r->blocks & ((1ull << l) - 1));
+        const size_t per = (size_t)d.B * (r->fuse ? 1 : d.H) * (r->cls_only ? 1 : d.T) * d.T;
+        MFVIT_TRY(attn_probs(qdt, qkv, lse, d.B, d.T, d.H, d.HD, r->fuse, r->cls_only, r->maps + slot * per, nullptr, st));
+    }
+    if (r->rollout)
+        MFVIT_TRY(attn_probs(qdt, qkv, lse, d.B, d.T, d.H, d.HD, r->fuse, 0, (float*)r->scratch + (size_t)l * d.B * d.T * d.T,
+                             attn_scratch_sums(d, r) + (size_t)l * d.B * d.T, st));
+    return MFVIT_OK;
+}
+
 static int encoder_forward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* dropcfg, const float* params, const void* shadow, const float* img,
-                           void* workspace, float* features, mfvit_stream_t stream, bool want_tokens) {
+                           void* workspace, float* features, mfvit_stream_t stream, bool want_tokens,
+                           const mfvit_vit_attn_req* attn = nullptr) {
     Dims d;
     if (!get_dims(cfg, dropcfg, d) || !params || !shadow || !img || !workspace || !features) return MFVIT_EINVAL;
     if (d.tok != want_tokens) return MFVIT_EINVAL;
@@ -495,6 +520,7 @@ static int encoder_forward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* dropc
         } else {
             MFVIT_TRY(attn_fwd(qdt, b + W.qkv, b + W.attn, (float*)(b + W.lse), d.B, d.T, d.H, d.HD, st));
         }
+        if (attn) MFVIT_TRY(attn_block_step(d, attn, l, qdt, b + W.qkv, (const float*)(b + W.lse), st));
         {   // xmid = x + attn Wproj^T + b ; y2 = LN2(xmid)
             GemmP p = zero_gemm();
             p.A = b + W.attn; p.lda = D * e;
@@ -954,6 +980,20 @@ int mfvit_vit_forward_drop(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop,
     if (!drop) return MFVIT_EINVAL;
     ShareScope share(cfg);
     return encoder_forward(cfg, drop, params, shadow, img, workspace, features, stream, false);
+}
+size_t mfvit_vit_attn_scratch_bytes(const mfvit_vit_cfg* cfg, const mfvit_vit_attn_req* req) {
+    Dims d;
+    if (!attn_req_ok(cfg, req, d)) return 0;
+    return req->rollout ? align256((size_t)d.depth * d.B * d.T * (d.T + 1) * 4) : 256;
+}
+int mfvit_vit_forward_attn(const mfvit_vit_cfg* cfg, const mfvit_vit_attn_req* req, const float* params, const void* shadow, const float* img,
+                           void* workspace, float* features, mfvit_stream_t stream) {
+    Dims d;
+    if (!attn_req_ok(cfg, req, d) || !req->scratch) return MFVIT_EINVAL;
+    ShareScope share(cfg);
+    MFVIT_TRY(encoder_forward(cfg, nullptr, params, shadow, img, workspace, features, stream, false, req));
+    if (req->rollout) MFVIT_TRY(attn_rollout((const float*)req->scratch, attn_scratch_sums(d, req), d.depth, d.B, d.T, req->rollout, (hipStream_t)stream));
+    return MFVIT_OK;
 }
 int mfvit_vit_backward(const mfvit_vit_cfg* cfg, const float* params, const void* shadow, void* workspace, const float* dfeatures,
                        float* dparams, int stage_hi, int stage_lo, mfvit_stream_t stream) {

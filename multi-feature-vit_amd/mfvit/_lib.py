@@ -32,6 +32,14 @@ class VitDrop(Structure):
     _fields_ = [("drop", c_float), ("attn_drop", c_float), ("drop_path", POINTER(c_float)), ("seed", c_uint64)]
 
 
+class VitAttnReq(Structure):
+    """mfvit_vit_attn_req: which attention maps / rollout an evaluation forward writes (include/mfvit.h)."""
+    _fields_ = [("blocks", c_uint64), ("fuse", c_int), ("cls_only", c_int), ("maps", c_void_p), ("rollout", c_void_p), ("scratch", c_void_p)]
+
+
+HEAD_FUSION = {None: 0, "mean": 1, "max": 2, "min": 3}     # mfvit_vit_attn_req::fuse
+
+
 class FusionCfg(Structure):
     _fields_ = [("batch", c_int), ("tokens", c_int), ("dim", c_int), ("heads", c_int), ("num_classes", c_int),
                 ("eps_pre", c_float), ("eps_post", c_float)]
@@ -58,6 +66,8 @@ SIGNATURES = {
     "mfvit_vit_backward_drop": (I, [POINTER(VitCfg), POINTER(VitDrop), P, P, P, P, P, I, I, P]),
     "mfvit_vit_workspace_bytes_ex": (c_size_t, [POINTER(VitCfg), POINTER(VitDrop), I]),
     "mfvit_vit_backward_ex": (I, [POINTER(VitCfg), POINTER(VitDrop), P, P, P, P, P, P, I, I, P]),
+    "mfvit_vit_attn_scratch_bytes": (c_size_t, [POINTER(VitCfg), POINTER(VitAttnReq)]),
+    "mfvit_vit_forward_attn": (I, [POINTER(VitCfg), POINTER(VitAttnReq), P, P, P, P, P, P]),
     "mfvit_gpt_forward": (I, [POINTER(VitCfg), P, P, P, P, P, P]),
     "mfvit_gpt_backward": (I, [POINTER(VitCfg), P, P, P, P, P, P, P]),
     "mfvit_linear_fwd": (I, [I, I, P, L, P, L, P, P, L, P, L, I, I, I, P]),

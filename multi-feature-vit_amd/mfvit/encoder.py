@@ -16,6 +16,7 @@ There is no CPU / eager fallback: forward on a non-GPU tensor raises.
 """
 import ctypes
 import math
+import operator
 import os
 
 import torch
@@ -406,7 +407,8 @@ class VisionTransformerMoCo(nn.Module):
             if len(pool) < 2:
                 pool.append(ws)
 
-    def _run_forward(self, img, save, drop=None, want_dimg=False):
+    def _prep_img(self, img):
+        """The image as the encoder entry points take it (contiguous f32 NCHW on the model's device), or MfvitError."""
         _lib.require_cuda(img)
         if img.dtype != torch.float32:
             img = img.float()
@@ -416,6 +418,10 @@ class VisionTransformerMoCo(nn.Module):
                                   "(pos_embed is size-bound)")
         if self._arena.device != img.device:
             raise _lib.MfvitError(f"model on {self._arena.device} but input on {img.device}")
+        return img
+
+    def _run_forward(self, img, save, drop=None, want_dimg=False):
+        img = self._prep_img(img)
         cfg = self._cfg(img, save)
         self._ensure_shadow(cfg)
         ws = self._get_ws(cfg, drop, want_dimg)
@@ -534,3 +540,75 @@ class VisionTransformerMoCo(nn.Module):
     def forward(self, x):
         """head(features3D(x)[:, 0])  (timm forward_features + head; training mode applies the dropout / drop-path rates)."""
         return self.forward_head(self._features(x, "forward"))
+
+    # ------------------------------------------------------------------ attention maps (include/mfvit.h, mfvit_vit_forward_attn)
+    # All three run one evaluation forward (no dropout site, whatever self.training says) under no_grad, draw no seed, and leave the feature
+    # cache and the module's state as they were.  Heads in timm's order; tokens: cls, then the patches row by row.
+    def _attn_blocks(self, blocks):
+        if blocks is None:
+            return list(range(self.depth))
+        out = set()
+        for i in blocks:
+            try:
+                if isinstance(i, bool):
+                    raise TypeError
+                i = operator.index(i)
+            except TypeError:
+                raise ValueError(f"block indices must be integers, got {i!r}") from None
+            if not -self.depth <= i < self.depth:
+                raise ValueError(f"block index {i} out of range for depth {self.depth}")
+            out.add(i % self.depth)
+        if not out:
+            raise ValueError("no block requested")
+        return sorted(out)
+
+    def _attn_forward(self, x, blocks, fuse, cls_only, rollout):
+        img = self._prep_img(x.detach())
+        with torch.no_grad():
+            cfg = self._cfg(img, False)
+            cache = self._feat_cache
+            self._ensure_shadow(cfg)
+            self._feat_cache = cache            # (a rebuilt shadow means new parameters: the cache key no longer matches anyway)
+            B, T, H = img.shape[0], self.num_tokens, self.num_heads
+            rows = 1 if cls_only else T
+            per = B * (1 if fuse else H) * rows * T
+            dev = img.device
+            maps = torch.empty(len(blocks) * per, device=dev, dtype=torch.float32) if blocks else None
+            roll = torch.empty(B, T - 1, device=dev, dtype=torch.float32) if rollout else None
+            req = _lib.VitAttnReq(sum(1 << l for l in blocks), fuse, int(cls_only), ptr(maps), ptr(roll), None)
+            nbytes = lib().mfvit_vit_attn_scratch_bytes(cfg, req)
+            if nbytes == 0:
+                raise _lib.MfvitError("invalid attention-map request for this encoder configuration")
+            scratch = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+            req.scratch = scratch.data_ptr()
+            ws = self._get_ws(cfg)
+            feats = torch.empty(B, T, self.embed_dim, device=dev, dtype=torch.float32)
+            try:
+                check(lib().mfvit_vit_forward_attn(cfg, req, ptr(self._arena), ptr(self._shadow), ptr(img), ptr(ws), ptr(feats), stream()),
+                      "mfvit_vit_forward_attn")
+            finally:
+                self._release_ws(ws)
+        shape = ((B,) if fuse else (B, H)) + ((T,) if cls_only else (T, T))
+        return [maps[i * per:(i + 1) * per].view(shape) for i in range(len(blocks))], roll
+
+    def get_attention_maps(self, x, blocks=None, head_fusion=None, cls_only=False):
+        """Softmax probabilities of the blocks in `blocks` (indices, negative ones counted from the end; default: all), one f32 tensor per
+        block in block order: (B, H, T, T), or (B, T, T) fused over the heads with head_fusion 'mean' | 'max' | 'min'; cls_only keeps the
+        cls query's row only: (B, H, T) / (B, T).  The probabilities are recomputed on the GPU from each block's own attention forward."""
+        if head_fusion not in _lib.HEAD_FUSION:
+            raise ValueError(f"head_fusion must be None, 'mean', 'max' or 'min', got {head_fusion!r}")
+        blocks = self._attn_blocks(blocks)
+        return self._attn_forward(x, blocks, _lib.HEAD_FUSION[head_fusion], bool(cls_only), False)[0]
+
+    def get_last_selfattention(self, x):
+        """(B, H, T, T) attention probabilities of the last block (DINO's get_last_selfattention; [:, :, 0, 1:] are its cls maps)."""
+        return self.get_attention_maps(x, blocks=[self.depth - 1])[0]
+
+    def attention_rollout(self, x, head_fusion="mean"):
+        """(B, gh, gw) cls row of the attention rollout over all blocks (Abnar & Zuidema 2020; include/mfvit.h): per block the heads fused
+        by 'mean' | 'max' | 'min', half identity added, rows normalised, the blocks multiplied from the last down.  Not normalised: scale
+        it for display (e.g. divide by its max)."""
+        if head_fusion not in ("mean", "max", "min"):
+            raise ValueError(f"head_fusion must be 'mean', 'max' or 'min', got {head_fusion!r}")
+        _, roll = self._attn_forward(x, [], _lib.HEAD_FUSION[head_fusion], False, True)
+        return roll.view(roll.shape[0], self.img_size[0] // 16, self.img_size[1] // 16)
