@@ -195,6 +195,37 @@ size_t mfvit_vit_attn_scratch_bytes(const mfvit_vit_cfg* cfg, const mfvit_vit_at
 int mfvit_vit_forward_attn(const mfvit_vit_cfg* cfg, const mfvit_vit_attn_req* req, const float* params, const void* shadow,
                            const float* img, void* workspace, float* features, mfvit_stream_t stream);
 
+/* Class-specific attention relevance of the image encoder (additive in ABI 5; Chefer, Gur & Wolf 2021, the self-attention rule).  Reads the
+ * workspace of a mfvit_vit_forward with save_for_backward = 1 (no dropout) and runs the data-gradient chain of mfvit_vit_backward_ex(..,
+ * dparams = NULL, dimg = NULL) from stage depth down to block 0 - no weight-gradient GEMM, split-partial reduce, column sum, side stream or
+ * embedding stage - with one relevance step behind each block's attention backward, while the block's qkv, lse and proj data gradient are live
+ * (block 0: the step takes the place of the attention backward, and the chain ends there).  The workspace's backward scratch is overwritten.
+ * dfeatures = d y_t / d features (f32 [B][T][dim]; y_t the score of the target class, e.g. head(features[:, 0])[t]).  Per block l:
+ *   P_h = softmax(scale q_h k_h^T),  dP_h = d y_t / d P_h = dO_h V_h^T  (dO = d y_t / d (attention output before proj)),
+ *   A_l = (1/H) sum_h max(0, P_h o dP_h)  [B][T][T],  heads in timm's order; tokens: cls, then the patches row by row,
+ * and R = (I + A_{depth-1}) ... (I + A_0) (Chefer's R = I; R += A_l R for l = 0 .. depth-1), of which the cls row is kept: v = e_0, then
+ * v <- v + v A_l for l = depth-1 .. 0, i.e. in the backward's order, in O(B T) scratch.
+ *   blocks     bit l: write A_l of block l into `maps` (bits at or above cfg->depth are invalid)
+ *   maps       the selected blocks in ascending order, each [B][T][T] f32; NULL iff blocks == 0
+ *   relevance  NULL, or [B][T-1] = R[0, 1:] (patch order; not normalised)
+ *   scratch    mfvit_vit_rel_scratch_bytes(cfg, req) bytes: with a relevance v [B][T] and the per-32-query-tile row products [B][ceil(T/32)][T]
+ *              (4 B T (ceil(T/32) + 1) bytes, whatever the depth); 256 bytes otherwise, never accessed.  No (T, T) map is formed anywhere
+ *              for a relevance alone.
+ * Evaluation only: every workspace tensor is read as the forward left it; no dropout site, no seed.  No atomics: repeated calls return the same bits.
+ * MFVIT_EINVAL (before any HIP call), and 0 bytes from mfvit_vit_rel_scratch_bytes, for: token-input mode, save_for_backward == 0, a `blocks`
+ * bit at or above cfg->depth, maps NULL with blocks != 0 (or set with blocks == 0), a request that asks for nothing (blocks == 0, relevance
+ * NULL), T > 8192, and the checks of mfvit_vit_forward; mfvit_vit_backward_rel also for scratch or dfeatures NULL.  With no such call the
+ * other entry points run exactly the launches they ran before. */
+typedef struct mfvit_vit_rel_req {
+    uint64_t blocks;    /* bit l: write A_l of block l into maps */
+    float* maps;        /* selected blocks ascending, each [B][T][T] f32; NULL iff blocks == 0 */
+    float* relevance;   /* NULL, or [B][T-1] = R[0, 1:] */
+    void* scratch;      /* mfvit_vit_rel_scratch_bytes(cfg, req) bytes */
+} mfvit_vit_rel_req;
+size_t mfvit_vit_rel_scratch_bytes(const mfvit_vit_cfg* cfg, const mfvit_vit_rel_req* req);
+int mfvit_vit_backward_rel(const mfvit_vit_cfg* cfg, const mfvit_vit_rel_req* req, const float* params, const void* shadow, void* workspace,
+                           const float* dfeatures, mfvit_stream_t stream);
+
 /* Token-input encoder (cfg->token_input = 1): the GPT of the TransFuser fusion (fuseattention.py:84-212), heads x head_dim with
  * head_dim in {32, 64, 96} (config.py: n_embd 384, n_head 4 -> 96), mlp_dim = block_exp * dim.
  * Parameter arena (f32): pos_emb [tokens][dim], then per block

@@ -17,6 +17,16 @@
 // a_l = diag(c_l) (F_l / 2 + I / 2), c_l = 1 / (s_l / 2 + 1 / 2): each step w = v o c_l, v <- (w F_l + w) / 2.  One workgroup per image,
 // v in LDS, column sums in a fixed order.
 //
+// Relevance kernels (Chefer, Gur & Wolf 2021, the self-attention rule), behind block l's attention backward in the data-gradient chain, from the
+// qkv and lse of the forward and dO = d y_t / d (attention output before proj) (the proj data gradient, [B][T][D] in the activation storage
+// type: f32, bf16, fp16 or split bf16, I32 layout):
+//   dP_h = dO_h V_h^T,  A_l = (1/H) sum_h max(0, P_h o dP_h),  and the cls row v of R = (I + A_{L-1}) ... (I + A_0): v <- v + v A_l, l = L-1 .. 0.
+// Map kernel: one workgroup per (image, 32-query tile), wave w takes the key tiles w, w + 4, ...  Per head, S = q k^T and dP = dO v^T run on
+// v_mfma_f32_32x32x2_f32 with the lane layout of the probability kernel (both operands widened to f32 on load); the heads are summed in
+// registers in head order, so per-head maps never reach memory.  Outputs: A_l into `map` (optional) and the tile's share of the row product,
+// part[b][tile][j] = sum_{i in tile} v[i] A_l[i][j] (optional; rows in register order, then the two lane halves).  Update kernel: v <- v + the
+// tiles' parts in tile order; after block 0 it writes v[1:].  With `first` v is e_0 and is not read.
+//
 // No atomics anywhere: repeated calls return the same bits.
 #include "common.cuh"
 #include "kernels.h"
@@ -205,6 +215,115 @@ __global__ __launch_bounds__(256) void attn_rollout_kernel(const float* __restri
     for (int j = 1 + threadIdx.x; j < Tn; j += blockDim.x) out[(long)b * (Tn - 1) + j - 1] = v[j];
 }
 
+// Relevance map of one block: map [B][T][T] (or NULL) = A_l; part [B][nqt][T] (or NULL) = per query tile, sum over its rows i of v[i] A_l[i][:],
+// with v [B][T] (first: e_0, v not read; part NULL: v must be NULL, it is not read either).  Grid B * nqt, nqt = ceil(T / 32).
+template <typename TQ, typename TD, int NB>
+__global__ __launch_bounds__(256) void attn_rel_kernel(const typename AmStor<TQ>::E* __restrict__ qkv, const float* __restrict__ lse,
+                                                       const typename AmStor<TD>::E* __restrict__ dout, float* __restrict__ map,
+                                                       const float* __restrict__ v, float* __restrict__ part, int Tn, int H, int nqt, float c,
+                                                       int first) {
+    typedef typename AmStor<TQ>::E E;
+    typedef typename AmStor<TD>::E ED;
+    constexpr int HD = 32 * NB, EP = AmStor<TQ>::EP, EPD = AmStor<TD>::EP;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5;
+    const int qt = blockIdx.x % nqt, b = blockIdx.x / nqt;
+    const int q0 = qt * 32;
+    const long hs = (long)H * HD * EP, rs = 3 * hs;                 // storage elements of one of q / k / v of a token, and of all three
+    const long ds = (long)H * HD * EPD;                              // storage elements of a dO row
+    const E* base = qkv + (long)b * Tn * rs;
+    const int qrow = min(q0 + (lane & 31), Tn - 1);                  // (rows past the end: a valid row is read, nothing is stored)
+    const E* qp = base + (long)qrow * rs;
+    const ED* dp = dout + ((long)b * Tn + qrow) * ds;
+    const float* lb = lse + (long)b * H * Tn;
+    const int nkt = (Tn + 31) / 32;
+    float vr[16];                                                    // v of the lane's 16 result rows (0 past T; v is read only with part)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int q = q0 + am_acc_row(r, lane);
+        vr[r] = !part || q >= Tn ? 0.f : first ? (q == 0 ? 1.f : 0.f) : v[(long)b * Tn + q];
+    }
+    for (int kt = wave; kt < nkt; kt += AM_WAVES) {
+        const int key = kt * 32 + (lane & 31);
+        const E* krow = base + (long)min(key, Tn - 1) * rs + hs;
+        const E* vrow = krow + hs;
+        f32x16 a;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) a[r] = 0.f;
+        for (int h = 0; h < H; ++h) {
+            f32x16 s, g;
+            {
+                float qf[16 * NB], kf[16 * NB];
+                am_load_frag<TQ, NB>(qp + (long)h * HD * EP, half, qf);
+                am_load_frag<TQ, NB>(krow + (long)h * HD * EP, half, kf);
+                s = am_scores<NB>(qf, kf);
+            }
+            {
+                float df[16 * NB], vf[16 * NB];
+                am_load_frag<TD, NB>(dp + (long)h * HD * EPD, half, df);
+                am_load_frag<TQ, NB>(vrow + (long)h * HD * EP, half, vf);
+                g = am_scores<NB>(df, vf);
+            }
+            const float* lrow = lb + (long)h * Tn;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float p = exp2f(fmaf(s[r], c, -lrow[min(q0 + am_acc_row(r, lane), Tn - 1)] * 1.4426950408889634f));
+                a[r] += fmaxf(0.f, p * g[r]);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) a[r] = a[r] / (float)H;
+        if (map && key < Tn) {
+            float* o = map + (long)b * Tn * Tn + key;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int q = q0 + am_acc_row(r, lane);
+                if (q < Tn) o[(long)q * Tn] = a[r];
+            }
+        }
+        if (part) {                                                  // (uniform over the grid)
+            float pr = 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) pr = fmaf(vr[r], a[r], pr);
+            pr += __shfl_xor(pr, 32, 64);                            // both halves end with the same bits
+            if (half == 0 && key < Tn) part[((long)b * nqt + qt) * Tn + key] = pr;
+        }
+    }
+}
+
+// v [B][T] <- v + sum over the nqt tiles of part [B][nqt][T], tiles in order (first: v = e_0 before the sum); out [B][T-1] (or NULL) = v[:, 1:]
+__global__ __launch_bounds__(256) void attn_rel_update_kernel(float* __restrict__ v, const float* __restrict__ part, int B, int Tn, int nqt,
+                                                              int first, float* __restrict__ out) {
+    const long n = (long)B * Tn;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const int b = (int)(i / Tn), j = (int)(i % Tn);
+        float acc = first ? (j == 0 ? 1.f : 0.f) : v[i];
+        const float* p = part + (long)b * nqt * Tn + j;
+        for (int t = 0; t < nqt; ++t) acc += p[(long)t * Tn];
+        v[i] = acc;
+        if (out && j > 0) out[(long)b * (Tn - 1) + j - 1] = acc;
+    }
+}
+
+template <typename TQ, typename TD, int NB>
+int launch_rel(const void* qkv, const float* lse, const void* dout, int B, int Tn, int H, float* map, const float* v, float* part, int first,
+               hipStream_t st) {
+    const int nqt = (Tn + 31) / 32;
+    const float c = 1.0f / sqrtf((float)(32 * NB)) * 1.4426950408889634f;   // the forward kernels' scale * log2(e)
+    ProfScope ps(PROF_OTHER, 4.0 * B * H * (double)Tn * Tn * 32 * NB, (double)B * Tn * Tn * 4 * (map ? 1 : 0) + (double)B * nqt * Tn * 4, st);
+    MFVIT_LAUNCH((attn_rel_kernel<TQ, TD, NB>), dim3(B * nqt), dim3(64 * AM_WAVES), 0, st, (const typename AmStor<TQ>::E*)qkv, lse,
+                 (const typename AmStor<TD>::E*)dout, map, v, part, Tn, H, nqt, c, first);
+    MFVIT_CHECK_LAUNCH();
+    return MFVIT_OK;
+}
+template <typename TQ, typename TD>
+int rel_by_hd(const void* qkv, const float* lse, const void* dout, int B, int Tn, int H, int HD, float* map, const float* v, float* part, int first,
+              hipStream_t st) {
+    if (HD == 32) return launch_rel<TQ, TD, 1>(qkv, lse, dout, B, Tn, H, map, v, part, first, st);
+    if (HD == 64) return launch_rel<TQ, TD, 2>(qkv, lse, dout, B, Tn, H, map, v, part, first, st);
+    if (HD == 96) return launch_rel<TQ, TD, 3>(qkv, lse, dout, B, Tn, H, map, v, part, first, st);
+    return MFVIT_ENOSYS;
+}
+
 template <typename T, int NB>
 int launch_probs(const void* qkv, const float* lse, int B, int Tn, int H, int fuse, int rows, float* out, float* sums, hipStream_t st) {
     typedef typename AmStor<T>::E E;
@@ -250,6 +369,30 @@ int attn_rollout(const float* maps, const float* sums, int depth, int B, int Tn,
     if (bytes > 64 * 1024) return MFVIT_ENOSYS;
     ProfScope ps(PROF_OTHER, 2.0 * depth * B * (double)Tn * Tn, 4.0 * depth * B * (double)Tn * Tn, st);
     MFVIT_LAUNCH(attn_rollout_kernel, dim3(B), dim3(256), bytes, st, maps, sums, depth, B, Tn, out);
+    MFVIT_CHECK_LAUNCH();
+    return MFVIT_OK;
+}
+
+int attn_rel_map(int qdt, int ddt, const void* qkv, const float* lse, const void* dout, int B, int Tn, int H, int HD, float* map, const float* v,
+                 float* part, int first, hipStream_t st) {
+    if (!qkv || !lse || !dout || B <= 0 || Tn <= 0 || H <= 0 || (!map && !part) || (part && !first && !v) || (!part && v))
+        return MFVIT_EINVAL;
+    // (qkv tag, dO tag) pairs of the encoder: the qkv of a split-bf16 encoder may be split fp16 (attn_qkv_dtype), its dO stays split bf16
+    if (qdt == MFVIT_F32 && ddt == MFVIT_F32) return rel_by_hd<float, float>(qkv, lse, dout, B, Tn, H, HD, map, v, part, first, st);
+    if (qdt == MFVIT_BF16 && ddt == MFVIT_BF16) return rel_by_hd<bf16, bf16>(qkv, lse, dout, B, Tn, H, HD, map, v, part, first, st);
+    if (qdt == MFVIT_F16 && ddt == MFVIT_F16) return rel_by_hd<f16, f16>(qkv, lse, dout, B, Tn, H, HD, map, v, part, first, st);
+    if (qdt == MFVIT_BF16X3 && ddt == MFVIT_BF16X3) return rel_by_hd<sbf16, sbf16>(qkv, lse, dout, B, Tn, H, HD, map, v, part, first, st);
+    if (qdt == MFVIT_X3F16 && ddt == MFVIT_BF16X3) return rel_by_hd<sf16, sbf16>(qkv, lse, dout, B, Tn, H, HD, map, v, part, first, st);
+    return MFVIT_EINVAL;
+}
+
+int attn_rel_update(float* v, const float* part, int B, int Tn, int first, float* out, hipStream_t st) {
+    if (!v || !part || B <= 0 || Tn < 2) return MFVIT_EINVAL;
+    const int nqt = (Tn + 31) / 32;
+    const long n = (long)B * Tn;
+    const int grid = (n + 255) / 256 < 2048 ? (int)((n + 255) / 256) : 2048;
+    ProfScope ps(PROF_OTHER, (double)n * nqt, (double)n * (nqt + 2) * 4, st);
+    MFVIT_LAUNCH(attn_rel_update_kernel, dim3(grid), dim3(256), 0, st, v, part, B, Tn, nqt, first, out);
     MFVIT_CHECK_LAUNCH();
     return MFVIT_OK;
 }

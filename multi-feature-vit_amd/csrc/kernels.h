@@ -101,4 +101,11 @@ int mask_scale_rows(int dtype, bool f32, const void* src, long lds_, void* dst, 
 int attn_probs(int qdt, const void* qkv, const float* lse, int B, int Tn, int H, int HD, int fuse, int cls_only, float* out, float* sums,
                hipStream_t st);
 int attn_rollout(const float* maps, const float* sums, int depth, int B, int Tn, float* out, hipStream_t st);
+// attention_maps.hip, relevance (Chefer et al. 2021) behind one block's attention backward: from its qkv (tag qdt), lse and dO (the proj data
+// gradient, activation tag ddt), map [B][T][T] (or NULL) = A = mean over heads of max(0, P o dO V^T), and part [B][ceil(T/32)][T] (or NULL) =
+// per 32-query tile the rows' share of v A, v [B][T] (first: e_0, not read).  attn_rel_update: v <- v + the parts (tile order); first: v = e_0
+// before; out [B][T-1] (or NULL) = v[:, 1:].
+int attn_rel_map(int qdt, int ddt, const void* qkv, const float* lse, const void* dout, int B, int Tn, int H, int HD, float* map, const float* v,
+                 float* part, int first, hipStream_t st);
+int attn_rel_update(float* v, const float* part, int B, int Tn, int first, float* out, hipStream_t st);
 }  // namespace mfvit

@@ -413,6 +413,30 @@ static int attn_block_step(const Dims& d, const mfvit_vit_attn_req* r, int l, in
     return MFVIT_OK;
 }
 
+// Relevance (mfvit_vit_backward_rel): validity of a request; its scratch is v [B][T] then the per-tile parts [B][ceil(T/32)][T] (relevance only);
+// and the step behind block l's attention backward - A_l into req->maps (the block's slot among the selected ones) and, for the relevance, the
+// row product and update of v.
+static bool rel_req_ok(const mfvit_vit_cfg* cfg, const mfvit_vit_rel_req* r, Dims& d) {
+    if (!r || !get_dims(cfg, d) || d.tok || !d.save || d.T > 8192) return false;
+    if (d.depth < 64 && (r->blocks >> d.depth) != 0) return false;
+    if ((r->blocks != 0) != (r->maps != nullptr)) return false;
+    return r->blocks != 0 || r->relevance != nullptr;
+}
+static int rel_block_step(const Dims& d, const mfvit_vit_rel_req* r, int l, int qdt, const void* qkv, const float* lse, const void* dout,
+                          hipStream_t st) {
+    const bool sel = (r->blocks >> l) & 1;
+    if (!sel && !r->relevance) return MFVIT_OK;
+    float* map = nullptr;
+    if (sel) map = r->maps + (size_t)__builtin_popcountll(r->blocks & ((1ull << l) - 1)) * d.B * d.T * d.T;
+    // (a maps-only request has 256 bytes of scratch: neither v nor the parts exist then)
+    float* v = r->relevance ? (float*)r->scratch : nullptr;
+    float* part = r->relevance ? v + (size_t)d.B * d.T : nullptr;
+    const int first = l == d.depth - 1;
+    MFVIT_TRY(attn_rel_map(qdt, d.dtype, qkv, lse, dout, d.B, d.T, d.H, d.HD, map, v, part, first, st));
+    if (r->relevance) MFVIT_TRY(attn_rel_update(v, part, d.B, d.T, first, l == 0 ? r->relevance : nullptr, st));
+    return MFVIT_OK;
+}
+
 static int encoder_forward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* dropcfg, const float* params, const void* shadow, const float* img,
                            void* workspace, float* features, mfvit_stream_t stream, bool want_tokens,
                            const mfvit_vit_attn_req* attn = nullptr) {
@@ -625,12 +649,14 @@ static int encoder_forward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* dropc
 
 // Shared backward; dinput (token-input mode only): d loss / d tokens, written by the embedding stage.  dimg (image mode only, stage_lo == -1; the
 // workspace then has mfvit_vit_workspace_bytes_ex(.., 1) bytes): d loss / d image, overwritten.  dparams == NULL (with dimg): the data-gradient
-// chain alone - no weight-gradient GEMM, no split-partial reduce, no bias / LayerNorm column sum, no side stream.
+// chain alone - no weight-gradient GEMM, no split-partial reduce, no bias / LayerNorm column sum, no side stream.  rel (dparams == dimg == NULL,
+// stages depth .. 0): that chain with the relevance step of mfvit_vit_backward_rel behind every block's attention backward; it ends at block 0's
+// step (no attention backward or LN1 backward of block 0).
 static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* dropcfg, const float* params, const void* shadow, void* workspace,
                             const float* dfeatures, float* dparams, float* dinput, float* dimg, int stage_hi, int stage_lo, mfvit_stream_t stream,
-                            bool want_tokens) {
+                            bool want_tokens, const mfvit_vit_rel_req* rel = nullptr) {
     Dims d;
-    if (!get_dims(cfg, dropcfg, d) || !params || !shadow || !workspace || (!dparams && !dimg)) return MFVIT_EINVAL;
+    if (!get_dims(cfg, dropcfg, d) || !params || !shadow || !workspace || (!dparams && !dimg && !rel)) return MFVIT_EINVAL;
     if (!d.save || d.tok != want_tokens) return MFVIT_EINVAL;
     if (stage_hi > d.depth || stage_lo < -1 || stage_lo > stage_hi) return MFVIT_EINVAL;
     if (dimg && (d.tok || stage_lo != -1)) return MFVIT_EINVAL;
@@ -851,12 +877,18 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop
                 if (do_max) { p.omax = domax(l); p.omax_rows = d.T; p.omax_hd = d.HD; }
                 MFVIT_TRY(gemm_nt_tile(d.dtype, EPI_NONE, p, st));
             }
+            if (rel && l == 0) {
+                // the relevance is complete after block 0's step: nothing reads block 0's dqkv or d x_0
+                MFVIT_TRY(rel_block_step(d, rel, l, qdt_bwd, b + W.qkv, (const float*)(b + W.lse), ws + W.dattn, st));
+                continue;
+            }
             if (d.p_attn > 0.f)
                 MFVIT_TRY(attn_bwd_tiled_drop(d.dtype, b + W.qkv, b + W.attn, ws + W.dattn, (const float*)(b + W.lse), dqkv, d.B, d.T, d.H, d.HD,
                                               make_drop(d.p_attn, d.seed, site(l, 2)), st));
             else
             MFVIT_TRY(attn_bwd(qdt_bwd, b + W.qkv, b + W.attn, ws + W.dattn, (const float*)(b + W.lse), dqkv, nullptr,
                                d.B, d.T, d.H, d.HD, st, do_max ? domax(l) : nullptr));
+            if (rel) MFVIT_TRY(rel_block_step(d, rel, l, qdt_bwd, b + W.qkv, (const float*)(b + W.lse), ws + W.dattn, st));
             MFVIT_TRY(fork());                                    // dqkv - and with it every input of this block's weight gradients - is ready
             for (int i = 0; i < ndef; ++i) MFVIT_TRY(gemm_tn(d.dtype, def_tn[i], wst));
             if (wg) {   // dWqkv += dqkv^T y1 ; d qkv_b += column sums of dqkv (ones-fragment MFMA inside the wgrad kernel)
@@ -994,6 +1026,18 @@ int mfvit_vit_forward_attn(const mfvit_vit_cfg* cfg, const mfvit_vit_attn_req* r
     MFVIT_TRY(encoder_forward(cfg, nullptr, params, shadow, img, workspace, features, stream, false, req));
     if (req->rollout) MFVIT_TRY(attn_rollout((const float*)req->scratch, attn_scratch_sums(d, req), d.depth, d.B, d.T, req->rollout, (hipStream_t)stream));
     return MFVIT_OK;
+}
+size_t mfvit_vit_rel_scratch_bytes(const mfvit_vit_cfg* cfg, const mfvit_vit_rel_req* req) {
+    Dims d;
+    if (!rel_req_ok(cfg, req, d)) return 0;
+    return req->relevance ? align256((size_t)d.B * d.T * ((d.T + 31) / 32 + 1) * 4) : 256;
+}
+int mfvit_vit_backward_rel(const mfvit_vit_cfg* cfg, const mfvit_vit_rel_req* req, const float* params, const void* shadow, void* workspace,
+                           const float* dfeatures, mfvit_stream_t stream) {
+    Dims d;
+    if (!rel_req_ok(cfg, req, d) || !req->scratch || !dfeatures || !params || !shadow || !workspace) return MFVIT_EINVAL;
+    ShareScope share(cfg);
+    return encoder_backward(cfg, nullptr, params, shadow, workspace, dfeatures, nullptr, nullptr, nullptr, d.depth, 0, stream, false, req);
 }
 int mfvit_vit_backward(const mfvit_vit_cfg* cfg, const float* params, const void* shadow, void* workspace, const float* dfeatures,
                        float* dparams, int stage_hi, int stage_lo, mfvit_stream_t stream) {

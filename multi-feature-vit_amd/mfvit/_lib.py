@@ -40,6 +40,11 @@ class VitAttnReq(Structure):
 HEAD_FUSION = {None: 0, "mean": 1, "max": 2, "min": 3}     # mfvit_vit_attn_req::fuse
 
 
+class VitRelReq(Structure):
+    """mfvit_vit_rel_req: which relevance maps / cls-row relevance a relevance backward writes (include/mfvit.h)."""
+    _fields_ = [("blocks", c_uint64), ("maps", c_void_p), ("relevance", c_void_p), ("scratch", c_void_p)]
+
+
 class FusionCfg(Structure):
     _fields_ = [("batch", c_int), ("tokens", c_int), ("dim", c_int), ("heads", c_int), ("num_classes", c_int),
                 ("eps_pre", c_float), ("eps_post", c_float)]
@@ -68,6 +73,8 @@ SIGNATURES = {
     "mfvit_vit_backward_ex": (I, [POINTER(VitCfg), POINTER(VitDrop), P, P, P, P, P, P, I, I, P]),
     "mfvit_vit_attn_scratch_bytes": (c_size_t, [POINTER(VitCfg), POINTER(VitAttnReq)]),
     "mfvit_vit_forward_attn": (I, [POINTER(VitCfg), POINTER(VitAttnReq), P, P, P, P, P, P]),
+    "mfvit_vit_rel_scratch_bytes": (c_size_t, [POINTER(VitCfg), POINTER(VitRelReq)]),
+    "mfvit_vit_backward_rel": (I, [POINTER(VitCfg), POINTER(VitRelReq), P, P, P, P, P]),
     "mfvit_gpt_forward": (I, [POINTER(VitCfg), P, P, P, P, P, P]),
     "mfvit_gpt_backward": (I, [POINTER(VitCfg), P, P, P, P, P, P, P]),
     "mfvit_linear_fwd": (I, [I, I, P, L, P, L, P, P, L, P, L, I, I, I, P]),

@@ -14,6 +14,7 @@ layout of include/mfvit.h), so the encoder kernels, the fused optimizers, the EM
 all-reduce all work on contiguous slices.  Gradients come back from the C ABI as one flat arena as well.
 There is no CPU / eager fallback: forward on a non-GPU tensor raises.
 """
+import contextlib
 import ctypes
 import math
 import operator
@@ -43,6 +44,53 @@ def build_2d_sincos_position_embedding(gh, gw, dim, temperature=10000.0):
     out_h = gh_.flatten()[:, None] * omega[None]
     pe = torch.cat([out_w.sin(), out_w.cos(), out_h.sin(), out_h.cos()], dim=1)[None]
     return torch.cat([torch.zeros(1, 1, dim, dtype=torch.float64), pe], dim=1).float()
+
+
+def check_target(target, B, C):
+    """The target class of a relevance call as a (B,) int64 CPU tensor (None stays None: the argmax of the model's output), or ValueError for
+    a bad type, shape or class - before anything is launched.  C: the number of classes (None: not known before the head has run; the
+    upper bound is then checked by resolve_target)."""
+    if target is None:
+        return None
+    if isinstance(target, torch.Tensor):
+        if target.dtype.is_floating_point or target.dtype.is_complex or target.dtype == torch.bool:
+            raise ValueError(f"target must hold integer classes, got dtype {target.dtype}")
+        if tuple(target.shape) != (B,):
+            raise ValueError(f"target tensor must have shape ({B},), got {tuple(target.shape)}")
+        t = target.detach().to("cpu", torch.int64)
+    else:
+        try:
+            if isinstance(target, bool):
+                raise TypeError
+            t = torch.full((B,), operator.index(target), dtype=torch.int64)
+        except TypeError:
+            raise ValueError(f"target must be None, an int or a ({B},) integer tensor, got {target!r}") from None
+    if B and (int(t.min()) < 0 or (C is not None and int(t.max()) >= C)):
+        raise ValueError(f"target class out of range for {C} classes: {t.tolist()}")
+    return t
+
+
+def resolve_target(target, out):
+    """The (B, 1) device index of the scored class: the checked target, or the argmax of out (B, C)."""
+    if target is None:
+        return out.detach().argmax(dim=1, keepdim=True)
+    if target.numel() and int(target.max()) >= out.shape[1]:
+        raise ValueError(f"target class out of range for {out.shape[1]} classes: {target.tolist()}")
+    return target.to(out.device).view(-1, 1)
+
+
+@contextlib.contextmanager
+def eval_modules(*mods):
+    """Every module under mods in evaluation mode for the block (no BatchNorm statistic moves, no dropout); training flags restored after,
+    also on error."""
+    saved = [(m, m.training) for mod in mods if mod is not None for m in mod.modules()]
+    try:
+        for m, _ in saved:
+            m.training = False
+        yield
+    finally:
+        for m, t in saved:
+            m.training = t
 
 
 class _WB(nn.Module):
@@ -612,3 +660,81 @@ class VisionTransformerMoCo(nn.Module):
             raise ValueError(f"head_fusion must be 'mean', 'max' or 'min', got {head_fusion!r}")
         _, roll = self._attn_forward(x, [], _lib.HEAD_FUSION[head_fusion], False, True)
         return roll.view(roll.shape[0], self.img_size[0] // 16, self.img_size[1] // 16)
+
+    # ------------------------------------------------------------------ attention relevance (include/mfvit.h, mfvit_vit_backward_rel)
+    # Chefer, Gur & Wolf 2021 (self-attention rule) for the score y_t = head(features3D(x)[:, 0])[t]: an evaluation forward with saved activations,
+    # d y_t / d features through the head by autograd on a detached leaf copy of the features (the head in eval mode), then the data-gradient chain
+    # with a relevance step behind every block's attention backward.  No dropout site, no seed, no p.grad, no gradient arena; the feature cache
+    # and the module's state are left as they were.
+    def _head_width(self):
+        """Number of outputs of the head, when its modules tell (None otherwise)."""
+        h = self.head
+        for m in reversed(list(h.modules())):
+            for a in ("out_features", "num_features"):
+                v = getattr(m, a, None)
+                if isinstance(v, int) and not isinstance(v, bool):
+                    return v
+        return None
+
+    def _rel_forward(self, x):
+        """Evaluation forward with saved activations: (cfg, workspace, features).  The caller releases the workspace."""
+        img = self._prep_img(x.detach())
+        with torch.no_grad():
+            cfg = self._cfg(img, True)
+            cache = self._feat_cache
+            self._ensure_shadow(cfg)
+            self._feat_cache = cache            # (a rebuilt shadow means new parameters: the cache key no longer matches anyway)
+            ws = self._get_ws(cfg)
+            feats = torch.empty(img.shape[0], self.num_tokens, self.embed_dim, device=img.device, dtype=torch.float32)
+            try:
+                check(lib().mfvit_vit_forward(cfg, ptr(self._arena), ptr(self._shadow), ptr(img), ptr(ws), ptr(feats), stream()),
+                      "mfvit_vit_forward")
+            except BaseException:
+                self._release_ws(ws)
+                raise
+        return cfg, ws, feats
+
+    def _rel_backward(self, cfg, ws, dfeats, blocks, want_rel):
+        """mfvit_vit_backward_rel on the workspace of _rel_forward: ([(B, T, T) map of every block in `blocks`], (B, T-1) relevance or None)."""
+        B, T = cfg.batch, self.num_tokens
+        dev = ws.device
+        dfeats = dfeats.detach().float().contiguous()
+        per = B * T * T
+        with torch.no_grad():
+            maps = torch.empty(len(blocks) * per, device=dev, dtype=torch.float32) if blocks else None
+            rel = torch.empty(B, T - 1, device=dev, dtype=torch.float32) if want_rel else None
+            req = _lib.VitRelReq(sum(1 << l for l in blocks), ptr(maps), ptr(rel), None)
+            nbytes = lib().mfvit_vit_rel_scratch_bytes(cfg, req)
+            if nbytes == 0:
+                raise _lib.MfvitError("invalid relevance request for this encoder configuration")
+            scratch = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+            req.scratch = scratch.data_ptr()
+            check(lib().mfvit_vit_backward_rel(cfg, req, ptr(self._arena), ptr(self._shadow), ptr(ws), ptr(dfeats), stream()),
+                  "mfvit_vit_backward_rel")
+        return [maps[i * per:(i + 1) * per].view(B, T, T) for i in range(len(blocks))], rel
+
+    def _relevance(self, x, target, blocks, want_rel):
+        tgt = check_target(target, int(x.shape[0]) if x.dim() else 0, self._head_width())
+        cfg, ws, feats = self._rel_forward(x)
+        try:
+            f = feats.detach().requires_grad_(True)
+            with torch.enable_grad(), eval_modules(self.head):
+                out = self.forward_head(f)
+                idx = resolve_target(tgt, out)
+                (df,) = torch.autograd.grad(out.gather(1, idx).sum(), f)
+            return self._rel_backward(cfg, ws, df, blocks, want_rel)
+        finally:
+            self._release_ws(ws)
+
+    def attention_relevance(self, x, target=None):
+        """(B, gh, gw) class-specific relevance of the patches (Chefer et al. 2021, include/mfvit.h): the cls row of
+        R = (I + A_{L-1}) ... (I + A_0), A_l = mean over heads of max(0, P o d y_t / d P), for the logit y_t of class `target` (None: the
+        argmax of the head's output per image; an int; or a (B,) integer tensor).  Not normalised: scale it for display."""
+        _, rel = self._relevance(x, target, [], True)
+        return rel.view(rel.shape[0], self.img_size[0] // 16, self.img_size[1] // 16)
+
+    def get_relevance_maps(self, x, target=None, blocks=None):
+        """A_l = mean over heads of max(0, P o d y_t / d P) of the blocks in `blocks` (indices as in get_attention_maps; default: all), one
+        (B, T, T) f32 tensor per block in block order; target as in attention_relevance."""
+        blocks = self._attn_blocks(blocks)
+        return self._relevance(x, target, blocks, False)[0]

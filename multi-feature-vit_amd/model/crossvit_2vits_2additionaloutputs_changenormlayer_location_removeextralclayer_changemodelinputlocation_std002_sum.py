@@ -21,6 +21,7 @@ import torch.nn as nn
 
 from mfvit import _lib
 from mfvit.arena import ParamArena
+from mfvit.encoder import check_target, eval_modules, resolve_target
 from mfvit.fusion import MAX_CROSS_ATTN_DEPTH, FusionFn, FusionSpec, check_fusion_shape
 from model.module import Attention, CrossAttention, FeedForward, PreNorm  # noqa: F401  (same import list as FUS:6)
 
@@ -147,3 +148,42 @@ class Fus_CrossViT(nn.Module):
             return FusionFn.apply(self._spec, cxr_ftrs, enh_ftrs, hc.weight, hc.bias, he.weight, he.bias, *self._spec.live())
         fused, _, _ = FusionFn.apply(self._spec, cxr_ftrs, enh_ftrs, None, None, None, None, *self._spec.live())
         return fused, vit_cxr(img_cxr), vit_enh(img_enh)
+
+    def attention_relevance(self, vit_cxr, vit_enh, img_cxr, img_enh, target=None):
+        """(rel_cxr, rel_enh): the class-specific relevance (Chefer et al. 2021; VisionTransformerMoCo.attention_relevance) of each encoder's
+        patches, (B, gh, gw) each, for the score the reference predicts from, y_t = (fused + x_cxr + x_enh)[t] (MAIN_CA:868-870); target: None
+        (the argmax per image), an int or a (B,) integer tensor.  Each encoder runs an evaluation forward with saved activations; the fusion and
+        the single-stream heads (in eval mode) run on leaf copies of the two feature tensors, and d y_t / d features of each stream feeds that
+        encoder's relevance backward.  The exchange's own cross-attention is not part of the chain.  No p.grad is set.  The two encoders run one
+        after the other on the caller's stream, whatever _two_streams says.  vit_cxr / vit_enh must be the encoders this model was built with
+        (forward takes the features from those): ValueError otherwise."""
+        for vit, bound, name in ((vit_cxr, self.vit_features_cxr, "vit_cxr"), (vit_enh, self.vit_features_enh, "vit_enh")):
+            if getattr(vit, "features3D", None) != bound:
+                raise ValueError(f"{name} is not the encoder this Fus_CrossViT was built with: its relevance would not be the predicting model's")
+        B = int(img_cxr.shape[0])
+        if img_enh is None or int(img_enh.shape[0]) != B:
+            raise ValueError("img_cxr and img_enh must hold the same number of images")
+        tgt = check_target(target, B, self.num_classes)
+        cfg_c, ws_c, f_c = vit_cxr._rel_forward(img_cxr)
+        try:
+            cfg_e, ws_e, f_e = vit_enh._rel_forward(img_enh)
+            try:
+                lc, le = f_c.detach().requires_grad_(True), f_e.detach().requires_grad_(True)
+                with torch.enable_grad(), eval_modules(vit_cxr.head, vit_enh.head):
+                    hc, he = self._plain_head(vit_cxr), self._plain_head(vit_enh)
+                    if hc is not None and he is not None and hc.out_features == self.num_classes == he.out_features:
+                        fused, x_c, x_e = FusionFn.apply(self._spec, lc, le, hc.weight, hc.bias, he.weight, he.bias, *self._spec.live())
+                    else:
+                        fused, _, _ = FusionFn.apply(self._spec, lc, le, None, None, None, None, *self._spec.live())
+                        x_c, x_e = vit_cxr.forward_head(lc), vit_enh.forward_head(le)
+                    out = fused + x_c + x_e
+                    idx = resolve_target(tgt, out)
+                    g_c, g_e = torch.autograd.grad(out.gather(1, idx).sum(), (lc, le))
+                _, r_c = vit_cxr._rel_backward(cfg_c, ws_c, g_c, [], True)
+                _, r_e = vit_enh._rel_backward(cfg_e, ws_e, g_e, [], True)
+            finally:
+                vit_enh._release_ws(ws_e)
+        finally:
+            vit_cxr._release_ws(ws_c)
+        return (r_c.view(B, vit_cxr.img_size[0] // 16, vit_cxr.img_size[1] // 16),
+                r_e.view(B, vit_enh.img_size[0] // 16, vit_enh.img_size[1] // 16))
