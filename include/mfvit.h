@@ -325,6 +325,32 @@ int mfvit_head_bwd(const float* dy, int64_t lddy, const float* x, int64_t ldx, c
  * preds = argmax (MAIN_CA:870). */
 int mfvit_cross_entropy(const float* logits, const int64_t* target, float* loss_mean, float* dlogits, int64_t* preds, int B, int C,
                         mfvit_stream_t stream);
+/* Soft-target cross entropy (mean) for C <= 64 classes with label smoothing and a mixed target (timm's SoftTargetCrossEntropy over
+ * mixup_target; the rest of the DeiT / MoCo-v3 fine-tune recipe next to drop_path_rate):
+ *   y_i = lam_i s(t_i) + (1 - lam_i) s(t_partner_i),   s(t) = (1 - smoothing) onehot(t) + smoothing / C,
+ *   loss_mean[1] = mean_i( - sum_c y_ic log softmax(logits_i)_c ),   dlogits = (softmax - y) / B (or NULL),
+ *   preds = first-maximum argmax (or NULL).
+ * partner (device int32 [B], indices into target) and lam (device f32 [B]) come together; both NULL is a plain, possibly smoothed,
+ * hard target (smoothing 0: mfvit_cross_entropy's loss).  The [B][C] target matrix is never materialised, and the mean is a
+ * fixed-order sum: repeated calls return the same bits.  MFVIT_EINVAL (before any HIP call): exactly one of partner / lam NULL,
+ * C > 64, C < 1, B < 1, smoothing outside [0, 1). */
+int mfvit_cross_entropy_soft(const float* logits, const int64_t* target, const int32_t* partner, const float* lam, float smoothing,
+                             float* loss_mean, float* dlogits, int64_t* preds, int B, int C, mfvit_stream_t stream);
+
+/* Random erasing + Mixup / CutMix of one or two image batches in one launch (timm.data.Mixup after RandomErasing(mode='const');
+ * mfvit.mixup builds the tables).  a, out_a f32 [n][C][H][W]; b, out_b the second stream of the same shape (the enhanced twin of the CXR
+ * image: same partner, coefficient and boxes), or both NULL.  lam: device f32 [n].
+ *   desc : device int32 [n][12]: 0 partner index j in [0, n), 1 mode (0 copy, 1 mixup, 2 cutmix), 2..5 the cut box yl yh xl xh
+ *          (half-open, 0 <= yl <= yh <= H, 0 <= xl <= xh <= W), 6 erase flag, 7..10 the erase box eyl eyh exl exh, 11 zero.
+ * With E(x_k) = sample k with its OWN erase box filled with 0 (the dataset mean after Normalize; erasing runs in the loader, before the
+ * batch is mixed, so the partner is read erased too):
+ *   mode 0: out[i] = E(x_i)      mode 1: out[i] = lam_i E(x_i) + (1 - lam_i) E(x_j), one f32 expression per element
+ *   mode 2: out[i] = E(x_j) inside the cut box, E(x_i) outside
+ * Copy, erase and cutmix elements are moves and zeros (bit-exact).  Box and partner ranges are the caller's contract; reads are clamped to
+ * the batch.  Out of place.  MFVIT_EINVAL (before any HIP call): an output overlapping an input or the other output (out_a == a,
+ * out_b == b included), exactly one of b / out_b NULL, n, C, H or W <= 0, n > 65535, C * H * W > 2^30. */
+int mfvit_batch_mix(const float* a, const float* b, float* out_a, float* out_b, const int32_t* desc, const float* lam, int n, int C, int H,
+                    int W, mfvit_stream_t stream);
 
 /* GPU-side input pipeline (replaces the torchvision / Pillow chain of aihc_utils/image_transform.py:50-84 run by
  * the DataLoader workers, moco/loader.py:121-137): Resize((S,S)) or Resize(S) (bilinear; shorter side S, aspect ratio kept) ->

@@ -98,6 +98,8 @@ SIGNATURES = {
     "mfvit_head_fwd": (I, [P, L, P, P, P, L, I, I, I, I, P]),
     "mfvit_head_bwd": (I, [P, L, P, L, P, P, L, I, P, P, I, I, I, P]),
     "mfvit_cross_entropy": (I, [P, P, P, P, P, I, I, P]),
+    "mfvit_cross_entropy_soft": (I, [P, P, P, P, F, P, P, P, I, I, P]),
+    "mfvit_batch_mix": (I, [P, P, P, P, P, P, I, I, I, I, P]),
     "mfvit_fusion_param_count": (c_size_t, [POINTER(FusionCfg)]),
     "mfvit_fusion_workspace_bytes": (c_size_t, [POINTER(FusionCfg)]),
     "mfvit_fusion_forward": (I, [POINTER(FusionCfg), P, P, P, P, P, P, P, P, P, P, P, P]),

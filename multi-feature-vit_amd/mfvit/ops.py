@@ -343,3 +343,50 @@ def cross_entropy(logits, target, want_grad=True):
     check(lib().mfvit_cross_entropy(ptr(logits), ptr(target), ptr(loss), ptr(dlogits), ptr(preds), B, C, stream()),
           "mfvit_cross_entropy")
     return loss, dlogits, preds
+
+
+def cross_entropy_soft(logits, target, partner=None, lam=None, smoothing=0.0, want_grad=True):
+    """Soft-target cross entropy (mean) over logits [B][C], C <= 64, with the mixed, smoothed target of mfvit_cross_entropy_soft:
+    y_i = lam_i s(t_i) + (1 - lam_i) s(t_partner_i), s(t) = (1 - smoothing) onehot(t) + smoothing / C; partner (int32 [B]) and lam
+    (f32 [B]) come together or not at all.  Returns (loss_mean [1], dlogits or None, preds int64)."""
+    require_cuda(logits, target, partner, lam)
+    if logits.dim() != 2 or logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise _lib.MfvitError("cross_entropy_soft: logits must be a contiguous f32 [B][C] tensor")
+    B, C = logits.shape
+    if target.shape != (B,) or target.dtype != torch.int64 or not target.is_contiguous():
+        raise _lib.MfvitError(f"cross_entropy_soft: target must be a contiguous int64 [{B}] tensor")
+    if (partner is None) != (lam is None):
+        raise _lib.MfvitError("cross_entropy_soft: partner and lam come together")
+    if partner is not None:
+        if partner.shape != (B,) or partner.dtype != torch.int32 or not partner.is_contiguous():
+            raise _lib.MfvitError(f"cross_entropy_soft: partner must be a contiguous int32 [{B}] tensor")
+        if lam.shape != (B,) or lam.dtype != torch.float32 or not lam.is_contiguous():
+            raise _lib.MfvitError(f"cross_entropy_soft: lam must be a contiguous f32 [{B}] tensor")
+    if not 0.0 <= float(smoothing) < 1.0:
+        raise ValueError(f"smoothing must lie in [0, 1), got {smoothing}")
+    loss = torch.empty(1, device=logits.device, dtype=torch.float32)
+    dlogits = torch.empty_like(logits) if want_grad else None
+    preds = torch.empty(B, device=logits.device, dtype=torch.int64)
+    check(lib().mfvit_cross_entropy_soft(ptr(logits), ptr(target), ptr(partner), ptr(lam), float(smoothing), ptr(loss), ptr(dlogits), ptr(preds),
+                                         B, C, stream()), "mfvit_cross_entropy_soft")
+    return loss, dlogits, preds
+
+
+def batch_mix(a, desc, lam, b=None):
+    """Random erasing + Mixup / CutMix of the f32 NCHW batch `a` (and of its twin `b`, with the same partner, coefficient and boxes) in one
+    launch: mfvit_batch_mix.  desc: device int32 [n][12] and lam: device f32 [n] as mfvit.mixup.Mixup.sample_params builds them (ranges are
+    the caller's contract: mfvit.mixup.check_params).  Returns out_a, or (out_a, out_b)."""
+    require_cuda(a, desc, lam, b)
+    if a.dim() != 4 or a.dtype != torch.float32 or not a.is_contiguous():
+        raise _lib.MfvitError("batch_mix: the batch must be a contiguous f32 [n][C][H][W] tensor")
+    if b is not None and (b.shape != a.shape or b.dtype != torch.float32 or not b.is_contiguous()):
+        raise _lib.MfvitError(f"batch_mix: the second stream must be a contiguous f32 tensor of the first one's shape {tuple(a.shape)}, got {tuple(b.shape)}")
+    n, C, H, W = a.shape
+    if desc.shape != (n, 12) or desc.dtype != torch.int32 or not desc.is_contiguous():
+        raise _lib.MfvitError(f"batch_mix: desc must be a contiguous int32 [{n}][12] tensor")
+    if lam.shape != (n,) or lam.dtype != torch.float32 or not lam.is_contiguous():
+        raise _lib.MfvitError(f"batch_mix: lam must be a contiguous f32 [{n}] tensor")
+    out_a = torch.empty_like(a)
+    out_b = torch.empty_like(b) if b is not None else None
+    check(lib().mfvit_batch_mix(ptr(a), ptr(b), ptr(out_a), ptr(out_b), ptr(desc), ptr(lam), n, C, H, W, stream()), "mfvit_batch_mix")
+    return out_a if b is None else (out_a, out_b)
