@@ -506,11 +506,15 @@ int mfvit_bn_bwd_apply(int dtype, const void* dy, const void* x, const void* y, 
 /* F.normalize(x, dim=1) (BLD:165,175) and its backward (f32). */
 int mfvit_l2norm_fwd(const float* x, float* y, float* inv_norm, int n, int C, float eps, mfvit_stream_t stream);
 int mfvit_l2norm_bwd(const float* dy, const float* y, const float* inv_norm, float* dx, int n, int C, mfvit_stream_t stream);
-/* out[r * ldo] = scale * (a[r] . b[r])   (l_pos, BLD:183). */
+/* out[r * ldo] = scale * (a[r] . b[r])   (l_pos, BLD:183).  a, b are dense (n, C); `out` and `ldo` need no alignment: with ldo = 1 + K the
+ * result goes straight into column 0 of the (n, 1 + K) logits and nothing else of them is touched (tests/test_moco_rowops_gpu.py). */
 int mfvit_rowdot(const float* a, const float* b, float* out, int64_t ldo, float scale, int n, int C, mfvit_stream_t stream);
 /* nn.CrossEntropyLoss (mean) over wide rows, e.g. the (n, 1 + 65536) InfoNCE logits (MAIN_MOCO:330,535):
  * loss_mean[1]; optional per-row lse (given: the mean is taken over the rows in a fixed order - the same bits on every run; NULL: one float atomic per
- * row); optional dlogits = (softmax - onehot) / n. */
+ * row); optional dlogits = (softmax - onehot) / n.  Rows are `ld` (logits) / `ldd` (dlogits) floats apart, both >= C; neither the strides nor the
+ * base pointers need any alignment beyond a float's (every row is split into a scalar head, 16-byte body and scalar tail by its own address, and
+ * a gradient row of another phase is written with scalar stores), and only the [row, :C] windows are read or written
+ * (tests/test_moco_rowops_gpu.py pins this down). */
 int mfvit_cross_entropy_rows(const float* logits, int64_t ld, const int64_t* target, float* loss_mean, float* lse, float* dlogits,
                              int64_t ldd, int n, int C, mfvit_stream_t stream);
 /* momentum update over a flat arena: dst = dst * m + src * (1 - m)   (BLD:83-89, one launch instead of ~157 x 3). */

@@ -487,6 +487,30 @@ def golden_lars():
     print("lars.npz")
 
 
+def golden_lars_f64():
+    """The reference's LARS on the CPU in float64 (parameters, gradients and `mu` after every step): pins oracle/ref_optim.py::lars_step to
+    1e-12.  Matrices, a 1-D tensor (no trust ratio, no weight decay), a zero parameter, a gradient of -wd * p (zero update norm)."""
+    from moco.optimizer import LARS
+    shapes = [(40, 30), (37,), (4, 3), (3, 2), (129, 3)]
+    ps = [torch.nn.Parameter(rng_tensor(430 + i, s, dtype=torch.float64)) for i, s in enumerate(shapes)]
+    with torch.no_grad():
+        ps[3].zero_()
+    wd = 2.0 ** -6
+    opt = LARS(ps, lr=0.3, weight_decay=wd, momentum=0.9)
+    d = dict(lr=0.3, weight_decay=wd, momentum=0.9, trust=0.001, n=len(shapes), shapes=np.array([str(s) for s in shapes]))
+    for step in range(3):
+        for i, p in enumerate(ps):
+            p.grad = rng_tensor(440 + 10 * step + i, p.shape, dtype=torch.float64)
+            if step == 1 and i == 2:
+                p.grad = (-wd * p.detach()).clone()
+        opt.step()
+        for i, p in enumerate(ps):
+            d[f"p{i}.step{step}"] = p.detach().numpy().copy()
+            d[f"mu{i}.step{step}"] = opt.state[p]["mu"].numpy().copy()
+    np.savez_compressed(os.path.join(OUT, "lars_f64.npz"), **d)
+    print("lars_f64.npz")
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     torch.set_num_threads(8)
@@ -502,3 +526,4 @@ if __name__ == "__main__":
     golden_moco_forward()
     golden_transfuser()
     golden_lars()
+    golden_lars_f64()
