@@ -539,6 +539,26 @@ int mfvit_sgd_step(const int64_t* table, int nchunks, float lr, float momentum, 
  * cleared by the caller) is set to 1 when any element was inf / nan before the multiplication. */
 int mfvit_amp_unscale(const int64_t* table, int nchunks, float inv_scale, float* found_inf, mfvit_stream_t stream);
 
+/* Gradient-norm clipping over the same chunk tables (additive in ABI 5): the three calls together replace
+ * torch.nn.utils.clip_grad_norm_(parameters, max_norm, norm_type) - its foreach norm, stack, norm, clamp and foreach multiply
+ * (torch/nn/utils/clip_grad.py) - with every sum taken in a fixed order (no float atomics: the same inputs give the same bits).
+ * Only the gradient column and the count of a row are read.  norm_kind: 0 = L2, 1 = inf (max |g|).
+ *
+ * mfvit_grad_norm_partials (torch's `_foreach_norm(grads, norm_type)`): partials[row] = the sum of squares (L2) or max |g| (inf) of the
+ *   row's gradient elements, one float per table row; a NaN element gives a NaN partial for either kind.  The gradients are not
+ *   written.  Several tables (param groups, optimizers) take part in one total by writing to consecutive ranges of one buffer.
+ * mfvit_grad_clip_coef (torch's `vector_norm(stack(norms))`, `clip_coef = max_norm / (total_norm + 1e-6)`, `clamp(max=1.0)`): over
+ *   `nrows` partials, accumulated in double in row order.  row_tensor[row] in [0, ntensors) names the tensor a row belongs to (rows of
+ *   one tensor need not be adjacent).  out2[0] = total norm, out2[1] = min(1, max_norm / (total + 1e-6)), each rounded to float once;
+ *   a NaN total gives a NaN coefficient, an infinite one 0, as torch's formula does.  per_tensor (NULL, or float[ntensors]) receives
+ *   every tensor's norm; row_tensor is read only then and may be NULL otherwise.
+ * mfvit_grad_scale (torch's `_foreach_mul_(grads, clip_coef_clamped)`): g *= *coef over every row; the coefficient is read from
+ *   device memory, and a coefficient of exactly 1.0f leaves the gradients untouched (no memory traffic). */
+int mfvit_grad_norm_partials(const int64_t* table, int nchunks, int norm_kind, float* partials, mfvit_stream_t stream);
+int mfvit_grad_clip_coef(const float* partials, const int32_t* row_tensor, int nrows, int ntensors, int norm_kind, double max_norm,
+                         float* per_tensor, float* out2, mfvit_stream_t stream);
+int mfvit_grad_scale(const int64_t* table, int nchunks, const float* coef, mfvit_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -138,6 +138,155 @@ __global__ __launch_bounds__(256) void amp_unscale_kernel(const long* __restrict
     if (__any(bad) && (threadIdx.x & 63) == 0) *found_inf = 1.0f;
 }
 
+// ---- gradient-norm clipping (torch.nn.utils.clip_grad_norm_): norm pass -> finalize -> scale pass, every sum in a fixed order.
+// One gradient pointer per row, so a row off a 16-byte boundary is not read element by element: `head` (0..3) floats up to the boundary,
+// 16-byte groups behind them, at most 3 floats of tail.
+__device__ __forceinline__ long grad_head(const float* g, long n) {
+    const long h = (long)((16 - ((size_t)g & 15)) & 15) >> 2;
+    return h < n ? h : n;
+}
+// |x| as its bit pattern: non-negative floats order like integers, and every NaN lies above inf - an integer max keeps a NaN where fmaxf drops it
+__device__ __forceinline__ int abs_bits(float x) { return __builtin_bit_cast(int, x) & 0x7fffffff; }
+__device__ __forceinline__ int imax(int a, int b) { return a > b ? a : b; }
+
+// partials[row] = sum g^2 (KIND 0) or max |g| (KIND 1) of the row.  4 bytes of HBM traffic per element, two independent 16-byte loads per thread
+// in flight.  Summation order (KIND 0; the tests' gate is derived from it): thread t takes the head element t into s0, the groups t, t + 512, ...
+// into s0 and t + 256, t + 768, ... into s1, element by element with one fmaf each, the tail element t into s1, then s0 + s1, the 6 shuffle
+// levels of wave_sum and the 4 wave sums in order.  A row of CHUNK = 16,384 elements: at most 8 groups = 32 roundings per accumulator.
+template <int KIND> __global__ __launch_bounds__(256) void grad_norm_kernel(const long* __restrict__ tab, float* __restrict__ partials) {
+    const long* e = tab + (long)blockIdx.x * CH;
+    const float* g = (const float*)e[2];
+    const long n = e[5];
+    const long head = grad_head(g, n);
+    const long n4 = (n - head) >> 2;
+    const float4* g4 = (const float4*)(g + head);
+    const float* tail = g + head + (n4 << 2);
+    const long ntail = n - head - (n4 << 2);
+    const int t = threadIdx.x;
+    __shared__ float sc[4];
+    if (KIND == 0) {
+        float s0 = 0.f, s1 = 0.f;
+        if (t < head) s0 = g[t] * g[t];
+        for (long i = t; i < n4; i += 512) {
+            const long j = i + 256;
+            const bool two = j < n4;
+            const float4 a = g4[i];
+            float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (two) b = g4[j];
+            s0 = fmaf(a.x, a.x, s0); s0 = fmaf(a.y, a.y, s0); s0 = fmaf(a.z, a.z, s0); s0 = fmaf(a.w, a.w, s0);
+            s1 = fmaf(b.x, b.x, s1); s1 = fmaf(b.y, b.y, s1); s1 = fmaf(b.z, b.z, s1); s1 = fmaf(b.w, b.w, s1);
+        }
+        if (t < ntail) s1 = fmaf(tail[t], tail[t], s1);
+        const float s = block_sum<256>(s0 + s1, sc);
+        if (t == 0) partials[blockIdx.x] = s;
+    } else {
+        int m0 = 0, m1 = 0;
+        if (t < head) m0 = abs_bits(g[t]);
+        for (long i = t; i < n4; i += 512) {
+            const long j = i + 256;
+            const bool two = j < n4;
+            const float4 a = g4[i];
+            float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (two) b = g4[j];
+            m0 = imax(imax(m0, abs_bits(a.x)), imax(abs_bits(a.y), imax(abs_bits(a.z), abs_bits(a.w))));
+            m1 = imax(imax(m1, abs_bits(b.x)), imax(abs_bits(b.y), imax(abs_bits(b.z), abs_bits(b.w))));
+        }
+        if (t < ntail) m1 = imax(m1, abs_bits(tail[t]));
+        int m = imax(m0, m1);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) m = imax(m, __shfl_xor(m, o, 64));
+        int* si = (int*)sc;
+        if ((t & 63) == 0) si[t >> 6] = m;
+        __syncthreads();
+        if (t == 0) partials[blockIdx.x] = __builtin_bit_cast(float, imax(imax(si[0], si[1]), imax(si[2], si[3])));
+    }
+}
+
+// One workgroup.  Total: thread t sums the partials t, t + 256, ... in double in row order, then a fixed tree over the 256 threads (inf norm: the
+// integer max of the bit patterns, exact).  Per-tensor norms (optional): thread k owns the tensors k, k + 256, ... and adds the partials of their rows
+// in row order; the rows pass through LDS 256 at a time.
+__global__ __launch_bounds__(256) void grad_clip_coef_kernel(const float* __restrict__ partials, const int* __restrict__ row_tensor, int nrows,
+                                                             int ntensors, int kind, double max_norm, float* __restrict__ per_tensor,
+                                                             float* __restrict__ out2) {
+    const int t = threadIdx.x;
+    __shared__ double red[256];
+    __shared__ float sp[256];
+    __shared__ int st[256];
+    double acc = 0.0;          // non-negative either way; the inf norm carries |g| bit patterns as integers
+    int mx = 0;
+    for (int r = t; r < nrows; r += 256) {
+        acc += (double)partials[r];
+        mx = imax(mx, abs_bits(partials[r]));
+    }
+    if (kind == 0) {
+        red[t] = acc;
+        __syncthreads();
+        for (int o = 128; o > 0; o >>= 1) {
+            if (t < o) red[t] += red[t + o];
+            __syncthreads();
+        }
+    } else {
+        int* ri = (int*)red;
+        ri[t] = mx;
+        __syncthreads();
+        for (int o = 128; o > 0; o >>= 1) {
+            if (t < o) ri[t] = imax(ri[t], ri[t + o]);
+            __syncthreads();
+        }
+    }
+    if (t == 0) {
+        const double total = kind == 0 ? sqrt(red[0]) : (double)__builtin_bit_cast(float, ((int*)red)[0]);
+        const double c = max_norm / (total + 1e-6);
+        out2[0] = (float)total;
+        out2[1] = (float)(c > 1.0 ? 1.0 : c);      // (not fmin: a NaN total must give a NaN coefficient, as torch's clamp does)
+    }
+    if (!per_tensor) return;
+    for (int k0 = 0; k0 < ntensors; k0 += 256) {
+        const int k = k0 + t;
+        double a = 0.0;
+        int m = 0;
+        for (int r0 = 0; r0 < nrows; r0 += 256) {
+            __syncthreads();
+            if (r0 + t < nrows) { sp[t] = partials[r0 + t]; st[t] = row_tensor[r0 + t]; }
+            __syncthreads();
+            const int cnt = nrows - r0 < 256 ? nrows - r0 : 256;
+            for (int r = 0; r < cnt; ++r)
+                if (st[r] == k) { a += (double)sp[r]; m = imax(m, abs_bits(sp[r])); }
+        }
+        if (k < ntensors) per_tensor[k] = kind == 0 ? (float)sqrt(a) : __builtin_bit_cast(float, m);
+    }
+}
+
+// g *= *coef; 8 bytes of HBM traffic per element when the step clips, none when it does not: a coefficient of exactly 1 returns before any access
+__global__ __launch_bounds__(256) void grad_scale_kernel(const long* __restrict__ tab, const float* __restrict__ coef) {
+    const float c = *coef;
+    if (c == 1.0f) return;
+    const long* e = tab + (long)blockIdx.x * CH;
+    float* g = (float*)e[2];
+    const long n = e[5];
+    const long head = grad_head(g, n);
+    const long n4 = (n - head) >> 2;
+    float4* g4 = (float4*)(g + head);
+    float* tail = g + head + (n4 << 2);
+    const long ntail = n - head - (n4 << 2);
+    const int t = threadIdx.x;
+    if (t < head) g[t] *= c;
+    for (long i = t; i < n4; i += 512) {
+        const long j = i + 256;
+        const bool two = j < n4;
+        float4 a = g4[i];
+        float4 b = a;
+        if (two) b = g4[j];
+        a.x *= c; a.y *= c; a.z *= c; a.w *= c;
+        g4[i] = a;
+        if (two) {
+            b.x *= c; b.y *= c; b.z *= c; b.w *= c;
+            g4[j] = b;
+        }
+    }
+    if (t < ntail) tail[t] *= c;
+}
+
 }  // namespace mfvit
 
 using namespace mfvit;
@@ -169,6 +318,30 @@ int mfvit_adam_step(const int64_t* table, int nchunks, float lr, float beta1, fl
 int mfvit_amp_unscale(const int64_t* table, int nchunks, float inv_scale, float* found_inf, mfvit_stream_t stream) {
     if (!table || !found_inf || nchunks <= 0) return MFVIT_EINVAL;
     MFVIT_LAUNCH(amp_unscale_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, (const long*)table, inv_scale, found_inf);
+    MFVIT_CHECK_LAUNCH();
+    return MFVIT_OK;
+}
+int mfvit_grad_norm_partials(const int64_t* table, int nchunks, int norm_kind, float* partials, mfvit_stream_t stream) {
+    if (!table || !partials || nchunks <= 0 || (norm_kind != 0 && norm_kind != 1)) return MFVIT_EINVAL;
+    if (norm_kind == 0)
+        MFVIT_LAUNCH(grad_norm_kernel<0>, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, (const long*)table, partials);
+    else
+        MFVIT_LAUNCH(grad_norm_kernel<1>, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, (const long*)table, partials);
+    MFVIT_CHECK_LAUNCH();
+    return MFVIT_OK;
+}
+int mfvit_grad_clip_coef(const float* partials, const int32_t* row_tensor, int nrows, int ntensors, int norm_kind, double max_norm,
+                         float* per_tensor, float* out2, mfvit_stream_t stream) {
+    if (!partials || !out2 || nrows <= 0 || ntensors <= 0 || (norm_kind != 0 && norm_kind != 1)) return MFVIT_EINVAL;
+    if (per_tensor && !row_tensor) return MFVIT_EINVAL;
+    MFVIT_LAUNCH(grad_clip_coef_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, (const int*)row_tensor, nrows, ntensors, norm_kind,
+                       max_norm, per_tensor, out2);
+    MFVIT_CHECK_LAUNCH();
+    return MFVIT_OK;
+}
+int mfvit_grad_scale(const int64_t* table, int nchunks, const float* coef, mfvit_stream_t stream) {
+    if (!table || !coef || nchunks <= 0) return MFVIT_EINVAL;
+    MFVIT_LAUNCH(grad_scale_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, (const long*)table, coef);
     MFVIT_CHECK_LAUNCH();
     return MFVIT_OK;
 }

@@ -9,7 +9,7 @@ import os
 import torch  # noqa: F401  MUST precede loading libmfvit_hip.so: torch bundles its own libamdhip64.so.7 / libhsa-runtime64;
 #                      whichever copy of that SONAME is mapped first serves the whole process, and mixing the system
 #                      runtime with torch's bundled HSA layer leaves the extension with "no ROCm-capable device"
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int64, c_size_t, c_uint32, c_uint64, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_uint32, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MFVIT_LIB") or os.path.join(_HERE, "libmfvit_hip.so")   # MFVIT_LIB: experiment builds
@@ -54,6 +54,7 @@ P = c_void_p
 I = c_int
 L = c_int64
 F = c_float
+D = c_double
 
 # name -> (restype, argtypes); must list every symbol of include/mfvit.h (tests/test_boundary_cpu.py checks it)
 SIGNATURES = {
@@ -121,6 +122,9 @@ SIGNATURES = {
     "mfvit_adam_step": (I, [P, I, F, F, F, F, F, I, P]),
     "mfvit_sgd_step": (I, [P, I, F, F, F, I, P]),
     "mfvit_amp_unscale": (I, [P, I, F, P, P]),
+    "mfvit_grad_norm_partials": (I, [P, I, I, P, P]),
+    "mfvit_grad_clip_coef": (I, [P, P, I, I, I, D, P, P, P]),
+    "mfvit_grad_scale": (I, [P, I, P, P]),
     "mfvit_prenorm_xattn_forward": (I, [POINTER(FusionCfg), P, P, P, P, P, P]),
     "mfvit_prenorm_xattn_backward": (I, [POINTER(FusionCfg), P, P, P, P, P, P, P, P, P]),
     "mfvit_xattn_forward": (I, [POINTER(FusionCfg), P, P, P, P, P]),

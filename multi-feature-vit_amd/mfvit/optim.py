@@ -9,6 +9,8 @@ State layout = the reference's / torch's, so optimizer state dicts move both way
 The device chunk tables are runtime caches of raw addresses: they live on the optimizer object (never inside ``param_groups``,
 which ``state_dict()`` pickles), are keyed by every address a row holds (parameter, gradient, both state tensors), and are dropped by
 ``load_state_dict``.
+
+``clip_grad_norm_`` / ``grad_norm`` (torch.nn.utils.clip_grad_norm_) run over the same tables: they take the optimizer, not the parameters.
 """
 import torch
 
@@ -108,8 +110,11 @@ class _TableOptimizer(torch.optim.Optimizer):
             host = torch.tensor(rows, dtype=torch.int64).pin_memory()
             if len(tables) >= 8:
                 tables.clear()
-            hit = tables[key] = (host.to(ps[0].device, non_blocking=True), len(ps), host)   # keep the pinned source alive
+            dev = host.to(ps[0].device, non_blocking=True)
+            # (column 0 as int32: the per-row tensor index of mfvit_grad_clip_coef, made on the device from the table just uploaded)
+            hit = tables[key] = (dev, len(ps), host, dev[:, 0].to(torch.int32))   # keep the pinned source alive
         out = (hit[0], hit[1], ps)
+        cache["row_tensor"] = hit[3]     # belongs to `out`: the fast path above hands `out` back only while nothing has changed
         # signature of this call for the fast path: the state dicts of the live parameters (None for a parameter without a gradient)
         sts = [self.state[p] if p.grad is not None else None for p in params]
         sig = []
@@ -145,6 +150,10 @@ class _TableOptimizer(torch.optim.Optimizer):
             if table is None:
                 continue
             check(lib().mfvit_amp_unscale(ptr(table), table.shape[0], float(inv_scale), ptr(found_inf), stream()), "mfvit_amp_unscale")
+
+    def clip_grad_norm_(self, max_norm, norm_type=2.0, error_if_nonfinite=False, per_tensor=False):
+        """``clip_grad_norm_(self, ...)``: one total over every param group of this optimizer."""
+        return clip_grad_norm_(self, max_norm, norm_type, error_if_nonfinite, per_tensor)
 
 
 class LARS(_TableOptimizer):
@@ -269,3 +278,93 @@ class SGD(_TableOptimizer):
             check(lib().mfvit_sgd_step(ptr(table), table.shape[0], float(g["lr"]), float(g["momentum"]), float(g["weight_decay"]), 0,
                                        stream()), "mfvit_sgd_step")
             _bump_versions(live)
+
+
+# ------------------------------------------------------------------------------------------------ gradient-norm clipping
+def _clip_args(optimizers, norm_type):
+    if isinstance(optimizers, _TableOptimizer):
+        opts = [optimizers]
+    else:
+        try:
+            opts = list(optimizers)
+        except TypeError:
+            opts = None
+        if not opts or not all(isinstance(o, _TableOptimizer) for o in opts):
+            raise TypeError("mfvit.optim.clip_grad_norm_ / grad_norm take the optimizer(s) of mfvit.optim, not a parameter iterable: the device "
+                            "chunk tables the kernels stream over live on the optimizer (for bare parameters use torch.nn.utils.clip_grad_norm_)")
+    kind = {2.0: 0, float("inf"): 1}.get(float(norm_type))
+    if kind is None:
+        raise NotImplementedError(f"norm_type {norm_type!r}: the HIP kernels implement the L2 and the inf norm; torch.nn.utils.clip_grad_norm_ "
+                                  "has the other orders")
+    devs = {next(p for g in o.param_groups for p in g["params"]).device for o in opts}
+    if len(devs) != 1:
+        raise ValueError(f"the optimizers of one clip_grad_norm_ / grad_norm call must be on one device, got {sorted(map(str, devs))}")
+    return opts, kind, devs.pop()
+
+
+@torch.no_grad()
+def _grad_norm(optimizers, max_norm, norm_type, error_if_nonfinite, per_tensor, scale):
+    opts, kind, dev = _clip_args(optimizers, norm_type)
+    h, st = lib(), stream()
+    scratch = opts[0]._cache().setdefault("clip", {})      # partials of the last call (sized by row count) and joined row indices
+    part = scratch.get("partials")
+    tabs, rows, nt = [], 0, 0
+    for o in opts:
+        for gi, g in enumerate(o.param_groups):
+            o._pre(gi)                                      # data parallel: this group's exchange is joined before its gradients are read
+            table, n, _ = o._table(gi, g)
+            if table is None:
+                continue
+            nrows = table.shape[0]
+            if part is None or rows + nrows > part.numel():
+                grown = torch.empty(max(1024, rows + nrows, 2 * (0 if part is None else part.numel())), device=dev, dtype=torch.float32)
+                if rows:
+                    grown[:rows].copy_(part[:rows])
+                part = scratch["partials"] = grown
+            check(h.mfvit_grad_norm_partials(ptr(table), nrows, kind, part.data_ptr() + 4 * rows, st), "mfvit_grad_norm_partials")
+            tabs.append((table, o._cache()[gi]["row_tensor"], nt))
+            rows += nrows
+            nt += n
+    if not tabs:
+        zero = torch.zeros((), device=dev, dtype=torch.float32)
+        return (zero, torch.zeros(0, device=dev, dtype=torch.float32)) if per_tensor else zero
+    row_tensor = norms = None
+    if per_tensor:
+        norms = torch.empty(nt, device=dev, dtype=torch.float32)
+        if len(tabs) == 1:
+            row_tensor = tabs[0][1]
+        else:       # tensor indices counted through all tables; joined once per set of tables (the cached tuple keeps them alive: ids stay unique)
+            key = tuple(id(rt) for _, rt, _ in tabs)
+            joined = scratch.setdefault("joined", {})
+            hit = joined.get(key)
+            if hit is None:
+                if len(joined) >= 8:
+                    joined.clear()
+                hit = joined[key] = (torch.cat([rt + base for _, rt, base in tabs]), [rt for _, rt, _ in tabs])
+            row_tensor = hit[0]
+    out = torch.empty(2, device=dev, dtype=torch.float32)       # a fresh pair per call: the caller keeps out[0]
+    check(h.mfvit_grad_clip_coef(ptr(part), ptr(row_tensor), rows, nt, kind, float(max_norm), ptr(norms), ptr(out), st), "mfvit_grad_clip_coef")
+    total = out[0]
+    if error_if_nonfinite and not bool(torch.isfinite(total)):      # the only host synchronisation, as in torch
+        raise RuntimeError(f"The total norm of order {float(norm_type)} for gradients from `parameters` is non-finite, so it cannot be clipped. "
+                           "To disable this error and scale the gradients by the non-finite norm anyway, set `error_if_nonfinite=False`")
+    if scale:
+        coef = out.data_ptr() + 4
+        for table, _, _ in tabs:
+            check(h.mfvit_grad_scale(ptr(table), table.shape[0], coef, st), "mfvit_grad_scale")
+    return (total, norms) if per_tensor else total
+
+
+def clip_grad_norm_(optimizers, max_norm, norm_type=2.0, error_if_nonfinite=False, per_tensor=False):
+    """torch.nn.utils.clip_grad_norm_ over the chunk tables of one optimizer of this module or a sequence of them: ONE total norm over the
+    gradients of every param group of every optimizer given (parameters without a gradient are skipped), then g *= min(1, max_norm / (total + 1e-6)).
+    A norm pass per table (mfvit_grad_norm_partials), one finalize (mfvit_grad_clip_coef) and a scale pass per table (mfvit_grad_scale) that touches
+    no memory when the coefficient is 1; every sum is taken in a fixed order, and nothing waits for the GPU unless `error_if_nonfinite` is set.
+    Returns the total norm as a 0-dim f32 device tensor, with per_tensor=True (total, norms of the parameters that have gradients, in order).
+    norm_type: 2 or inf.  Call it where torch's goes: after backward() - after ``scaler.unscale_(optimizer)`` with a GradScaler - and before step()."""
+    return _grad_norm(optimizers, max_norm, norm_type, error_if_nonfinite, per_tensor, True)
+
+
+def grad_norm(optimizers, norm_type=2.0, per_tensor=False):
+    """The total gradient norm clip_grad_norm_ would return (and the per-tensor norms), for logging: the gradients are not touched."""
+    return _grad_norm(optimizers, float("inf"), norm_type, False, per_tensor, False)
