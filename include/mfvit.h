@@ -374,6 +374,29 @@ int mfvit_input_transform(const uint8_t* src, const int64_t* desc, const int32_t
 int mfvit_input_transform_rect(const uint8_t* src, const int64_t* desc, const int32_t* tables, int n, int S, int out_h, int out_w,
                                const float* mean3, const float* std3, float* out, mfvit_stream_t stream);
 
+/* The MoCo-v3 aug1 / aug2 chains (main_covid_mocov3based_single_img_type_5draws_mocov3structure_mocov2loss_vitsmall.py:388-413; blur:
+ * moco/loader.py:25-34): RandomResizedCrop -> RandomApply(ColorJitter(0.4, 0.4, 0.2, 0.1)) -> RandomGrayscale -> GaussianBlur ->
+ * [Solarize] -> flip -> ToTensor -> Normalize, bit-exact against Pillow (ImageEnhance / ImagingBlend in float32, Image.convert's L and HSV,
+ * ImageFilter.GaussianBlur's three extended box passes per axis, ImageOps.solarize at 128).  src, desc, tables, mean3, std3 as for
+ * mfvit_input_transform, with rotation mode 0, no crop and a zero slot 17: the geometric stage writes the flipped S x S uint8 frame (the
+ * flip commutes with every operation here), and out is float32 [n][3][S][S].
+ *   photo : device int32 [n][16], one descriptor per sample, so every sample of a launch may differ:
+ *           0 the jitter operations in the order they run, one nibble each from bit 0: 0 none, 1 brightness, 2 contrast, 3 saturation, 4 hue
+ *           1 / 2 / 3 the bits of the float32 brightness / contrast / saturation factor (ImageEnhance: 0 + f (v - 0), mean + f (v - mean)
+ *             with mean = int(mean(L) + 0.5) over the image as contrast finds it, L + f (v - L))
+ *           4 the hue shift int(hue * 255) mod 256 added to the 8-bit H of Pillow's HSV
+ *           5 flags: 1 grayscale (L replicated), 2 blur, 4 solarize
+ *           6 / 7 / 8 the box blur of one pass: r = (int)fr, ww = (uint32)(2^24 / (2 fr + 1)), fw = (2^24 - (2 r + 1) ww) / 2 with fr
+ *             Pillow's float32 _gaussian_blur_radius(sigma, 3);  9..15 zero
+ *   max_radius : the largest r of the batch.  The blur tile carries a halo of 3 (r + 1) pixels sized for r <= 1 (sigma <= 2.4494896; the
+ *           reference draws sigma from [0.1, 2]): MFVIT_ENOSYS beyond that, before any HIP call.
+ *   workspace : mfvit_input_photometric_workspace_bytes(n, S) bytes on the device (the uint8 frames and the per-sample L sums; 0 for an
+ *           invalid n / S).  MFVIT_EINVAL: a NULL pointer, n <= 0, n > 65535, S <= 0, S * S > 2^30, max_radius < 0.
+ * Four asynchronous operations on `stream` (a memset and three kernels), no host synchronisation. */
+size_t mfvit_input_photometric_workspace_bytes(int n, int S);
+int mfvit_input_photometric(const uint8_t* src, const int64_t* desc, const int32_t* tables, const int32_t* photo, int n, int S, int max_radius,
+                            void* workspace, const float* mean3, const float* std3, float* out, mfvit_stream_t stream);
+
 /* Epoch metrics on the device (replaces the per-batch .cpu() copies MAIN_CA:886-899 and the scikit-learn calls
  * MAIN_CA:901-911).  scores f32 [n][C] (row stride ld), labels int64 [n].  ACCUMULATES into caller-zeroed uint64 arrays:
  * confusion[t][p] (+ optional preds[n] = first-maximum argmax, as torch.max MAIN_CA:870), and per class c the pair counts of the

@@ -27,9 +27,12 @@ __device__ __forceinline__ int clip8(int v) {
 //              16 source row pitch in bytes (a RandomResizedCrop box is a window of a wider image), 17 resized frame Sh << 32 | Sw
 //              (0: S x S), 18..19 unused
 // table row xx of an axis: [xmin, count, k[0..ksize)]; the x table has Sw rows, the y table Sh rows.  Output window ch x cw.
+// U8: stop at the uint8 image (stage 0 of the photometric chains, photometric.hip): one R | G << 8 | B << 16 dword per pixel into out8
+// [n][ch][cw] instead of the normalised float32 planes.
+template <bool U8>
 __global__ __launch_bounds__(256) void input_transform_kernel(const unsigned char* __restrict__ src, const long long* __restrict__ desc,
                                                               const int* __restrict__ tables, int S, int ch, int cw, float m0, float m1,
-                                                              float m2, float s0, float s1, float s2, float* __restrict__ out) {
+                                                              float m2, float s0, float s1, float s2, float* __restrict__ out, unsigned* __restrict__ out8) {
     const int smp = blockIdx.y;
     const int pix = blockIdx.x * 256 + threadIdx.x;
     const int plane = ch * cw;
@@ -92,6 +95,10 @@ __global__ __launch_bounds__(256) void input_transform_kernel(const unsigned cha
         }
         if (vres) v0 = clip8(a0), v1 = clip8(a1), v2 = clip8(a2);
     }
+    if constexpr (U8) {
+        out8[(long)smp * plane + pix] = (unsigned)v0 | ((unsigned)v1 << 8) | ((unsigned)v2 << 16);
+        return;
+    }
     // ToTensor (uint8 -> float / 255) and Normalize ((x - mean) / std), IEEE f32 like the torch ops they replace
     float* o = out + ((long)smp * 3) * plane + pix;
     o[0] = __fdiv_rn(__fdiv_rn((float)v0, 255.0f) - m0, s0);
@@ -104,8 +111,16 @@ __global__ __launch_bounds__(256) void input_transform_kernel(const unsigned cha
 int input_transform(const unsigned char* src, const long long* desc, const int* tables, int n, int S, int out_h, int out_w,
                     const float* mean, const float* stdv, float* out, hipStream_t st) {
     if (n <= 0 || S <= 0 || out_h <= 0 || out_w <= 0 || (long long)out_h * out_w > (1ll << 30)) return MFVIT_EINVAL;
-    MFVIT_LAUNCH(input_transform_kernel, dim3((out_h * out_w + 255) / 256, n), dim3(256), 0, st, src, desc, tables, S, out_h, out_w, mean[0],
-                 mean[1], mean[2], stdv[0], stdv[1], stdv[2], out);
+    MFVIT_LAUNCH(input_transform_kernel<false>, dim3((out_h * out_w + 255) / 256, n), dim3(256), 0, st, src, desc, tables, S, out_h, out_w, mean[0],
+                 mean[1], mean[2], stdv[0], stdv[1], stdv[2], out, (unsigned*)nullptr);
+    MFVIT_CHECK_LAUNCH();
+    return MFVIT_OK;
+}
+
+int input_transform_u8(const unsigned char* src, const long long* desc, const int* tables, int n, int S, unsigned* frames, hipStream_t st) {
+    if (n <= 0 || n > 65535 || S <= 0 || (long long)S * S > (1ll << 30)) return MFVIT_EINVAL;
+    MFVIT_LAUNCH(input_transform_kernel<true>, dim3((S * S + 255) / 256, n), dim3(256), 0, st, src, desc, tables, S, S, S, 0.0f, 0.0f, 0.0f, 1.0f,
+                 1.0f, 1.0f, (float*)nullptr, frames);
     MFVIT_CHECK_LAUNCH();
     return MFVIT_OK;
 }

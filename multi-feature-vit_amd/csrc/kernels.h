@@ -19,6 +19,11 @@ bool gemm_nt_rowp_supported(int dtype, int repi, const GemmP& p);   // gemm_rowp
 int gemm_nt_rowp(int dtype, int repi, const GemmP& p, hipStream_t st);
 int input_transform(const unsigned char* src, const long long* desc, const int* tables, int n, int S, int out_h, int out_w,
                     const float* mean, const float* stdv, float* out, hipStream_t st);   // input.hip
+int input_transform_u8(const unsigned char* src, const long long* desc, const int* tables, int n, int S, unsigned* frames,
+                       hipStream_t st);   // input.hip: the same gather, stopped at the uint8 S x S frame (R | G << 8 | B << 16 per pixel)
+size_t input_photometric_workspace_bytes(int n, int S);   // photometric.hip
+int input_photometric(const unsigned char* src, const long long* desc, const int* tables, const int* photo, int n, int S, int max_radius,
+                      void* workspace, const float* mean, const float* stdv, float* out, hipStream_t st);
 int eval_counts(const float* scores, long ld, const int64_t* labels, int n, int C, unsigned long long* conf, unsigned long long* u2,
                 unsigned long long* npos, int64_t* preds, hipStream_t st);   // metrics.hip
 int gemm_tn(int dtype, const GemmP& p, hipStream_t st);

@@ -1081,6 +1081,12 @@ int mfvit_input_transform_rect(const uint8_t* src, const int64_t* desc, const in
     if (!src || !desc || !tables || !mean3 || !std3 || !out) return MFVIT_EINVAL;
     return input_transform(src, (const long long*)desc, tables, n, S, out_h, out_w, mean3, std3, out, (hipStream_t)stream);
 }
+size_t mfvit_input_photometric_workspace_bytes(int n, int S) { return input_photometric_workspace_bytes(n, S); }
+int mfvit_input_photometric(const uint8_t* src, const int64_t* desc, const int32_t* tables, const int32_t* photo, int n, int S, int max_radius,
+                            void* workspace, const float* mean3, const float* std3, float* out, mfvit_stream_t stream) {
+    if (!src || !desc || !tables || !photo || !workspace || !mean3 || !std3 || !out) return MFVIT_EINVAL;   // mean3 / std3: HOST pointers
+    return input_photometric(src, (const long long*)desc, tables, photo, n, S, max_radius, workspace, mean3, std3, out, (hipStream_t)stream);
+}
 int mfvit_eval_counts(const float* scores, int64_t ld, const int64_t* labels, int n, int C, uint64_t* confusion, int64_t* preds,
                       uint64_t* u2, uint64_t* npos, mfvit_stream_t stream) {
     if (!scores || !labels || (!confusion && !(u2 && npos))) return MFVIT_EINVAL;

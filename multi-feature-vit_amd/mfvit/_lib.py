@@ -131,6 +131,8 @@ SIGNATURES = {
     "mfvit_xattn_backward": (I, [POINTER(FusionCfg), P, P, P, P, P, P, P]),
     "mfvit_input_transform": (I, [P, P, P, I, I, I, P, P, P, P]),
     "mfvit_input_transform_rect": (I, [P, P, P, I, I, I, I, P, P, P, P]),
+    "mfvit_input_photometric_workspace_bytes": (c_size_t, [I, I]),
+    "mfvit_input_photometric": (I, [P, P, P, P, I, I, I, P, P, P, P, P]),
     "mfvit_eval_counts": (I, [P, L, P, I, I, P, P, P, P, P]),
     "mfvit_prof_enable": (I, [I]),
     "mfvit_set_wgrad_stream": (I, [I]),
