@@ -1,0 +1,166 @@
+// C ABI entry points of include/mfvit.h for the single ops: argument checks, then one launcher call each.  No allocation, no
+// synchronisation: every launch goes to the caller's stream, all memory is caller-owned.
+#include "../../include/mfvit.h"
+#include "kernels.h"
+
+using namespace mfvit;
+
+extern "C" {
+
+int mfvit_input_transform(const uint8_t* src, const int64_t* desc, const int32_t* tables, int n, int S, int crop, const float* mean3,
+                          const float* std3, float* out, mfvit_stream_t stream) {
+    if (!src || !desc || !tables || !mean3 || !std3 || !out) return MFVIT_EINVAL;   // mean3 / std3 are HOST pointers (3 floats each)
+    if (crop > S) return MFVIT_EINVAL;
+    return input_transform(src, (const long long*)desc, tables, n, S, crop, crop, mean3, std3, out, (hipStream_t)stream);
+}
+int mfvit_input_transform_rect(const uint8_t* src, const int64_t* desc, const int32_t* tables, int n, int S, int out_h, int out_w,
+                               const float* mean3, const float* std3, float* out, mfvit_stream_t stream) {
+    if (!src || !desc || !tables || !mean3 || !std3 || !out) return MFVIT_EINVAL;
+    return input_transform(src, (const long long*)desc, tables, n, S, out_h, out_w, mean3, std3, out, (hipStream_t)stream);
+}
+size_t mfvit_input_photometric_workspace_bytes(int n, int S) { return input_photometric_workspace_bytes(n, S); }
+int mfvit_input_photometric(const uint8_t* src, const int64_t* desc, const int32_t* tables, const int32_t* photo, int n, int S, int max_radius,
+                            void* workspace, const float* mean3, const float* std3, float* out, mfvit_stream_t stream) {
+    if (!src || !desc || !tables || !photo || !workspace || !mean3 || !std3 || !out) return MFVIT_EINVAL;   // mean3 / std3: HOST pointers
+    return input_photometric(src, (const long long*)desc, tables, photo, n, S, max_radius, workspace, mean3, std3, out, (hipStream_t)stream);
+}
+int mfvit_eval_counts(const float* scores, int64_t ld, const int64_t* labels, int n, int C, uint64_t* confusion, int64_t* preds,
+                      uint64_t* u2, uint64_t* npos, mfvit_stream_t stream) {
+    if (!scores || !labels || (!confusion && !(u2 && npos))) return MFVIT_EINVAL;
+    return eval_counts(scores, ld, labels, n, C, (unsigned long long*)confusion, (unsigned long long*)u2, (unsigned long long*)npos, preds,
+                       (hipStream_t)stream);
+}
+int mfvit_linear_fwd(int dtype, int epilogue, const void* x, int64_t ldx, const void* w, int64_t ldw, const float* bias, void* y,
+                     int64_t ldy, void* y2, int64_t ldy2, int M, int N, int K, mfvit_stream_t stream) {
+    if (!x || !w || (!y && epilogue != EPI_BIAS_GELU)) return MFVIT_EINVAL;      // GELU: y = NULL skips the saved derivative
+    if (epilogue != EPI_BIAS && epilogue != EPI_BIAS_GELU && epilogue != EPI_NONE && epilogue != EPI_BIAS_X3F16) return MFVIT_EINVAL;
+    if (epilogue == EPI_BIAS_GELU && !y2) return MFVIT_EINVAL;
+    GemmP p = nt(x, ldx, w, ldw, M, N, K);
+    p.bias = bias; p.out0 = y; p.ldo0 = ldy; p.out1 = y2; p.ldo1 = ldy2;
+    return gemm_nt_tile(dtype, epilogue, p, (hipStream_t)stream);
+}
+int mfvit_linear_dgrad_act(int dtype, const void* dy, int64_t lddy, const void* wt, int64_t ldwt, const void* act_grad, int64_t ldg,
+                           void* dx, int64_t lddx, int M, int N, int K, mfvit_stream_t stream) {
+    if (!dy || !wt || !act_grad || !dx) return MFVIT_EINVAL;
+    GemmP p = nt(dy, lddy, wt, ldwt, M, N, K);
+    p.aux = act_grad; p.ldaux = ldg; p.out0 = dx; p.ldo0 = lddx;
+    return gemm_nt_tile(dtype, EPI_GELU_BWD, p, (hipStream_t)stream);
+}
+int mfvit_linear_wgrad(int dtype, const void* dy, int64_t lddy, const void* x, int64_t ldx, float* dw, int64_t lddw, int M, int N, int K,
+                       mfvit_stream_t stream) {
+    if (!dy || !x || !dw) return MFVIT_EINVAL;
+    GemmP p = nt(dy, lddy, x, ldx, M, N, K);
+    p.out0 = dw; p.ldo0 = lddw;
+    return gemm_tn(dtype, p, (hipStream_t)stream);
+}
+int mfvit_linear_wgrad_ws(int dtype, const void* dy, int64_t lddy, const void* x, int64_t ldx, float* dw, int64_t lddw, int M, int N,
+                          int K, float* scratch, mfvit_stream_t stream) {
+    if (!dy || !x || !dw) return MFVIT_EINVAL;
+    GemmP p = nt(dy, lddy, x, ldx, M, N, K);
+    p.out0 = dw; p.ldo0 = lddw;
+    p.cpart = scratch;
+    return gemm_tn(dtype, p, (hipStream_t)stream);
+}
+int mfvit_linear_wgrad_pair(int dtype, const void* dy_a, int64_t lddy_a, const void* x_a, int64_t ldx_a, float* dw_a, int64_t lddw_a, float* dbias_a,
+                            int Na, const void* dy_b, int64_t lddy_b, const void* x_b, int64_t ldx_b, float* dw_b, int64_t lddw_b, int Nb, int M, int K,
+                            mfvit_stream_t stream) {
+    if (!dy_a || !x_a || !dw_a || !dy_b || !x_b || !dw_b) return MFVIT_EINVAL;
+    GemmP a = nt(dy_a, lddy_a, x_a, ldx_a, M, Na, K), b = nt(dy_b, lddy_b, x_b, ldx_b, M, Nb, K);
+    a.out0 = dw_a; a.ldo0 = lddw_a; a.cs0 = dbias_a;
+    b.out0 = dw_b; b.ldo0 = lddw_b;
+    if (!gemm_tn_pair_supported(dtype, a, b)) return MFVIT_ENOSYS;
+    return gemm_tn_glds_pair(dtype, a, b, (hipStream_t)stream);
+}
+int mfvit_linear_res_ln_fwd(int dtype, const void* a, int64_t lda, const void* w, int64_t ldw, const float* bias, const float* res,
+                            int64_t ldres, float* x_out, void* y, int y_f32, const float* gamma, const float* beta, float eps,
+                            float* mean, float* rstd, int M, int K, mfvit_stream_t stream) {
+    return mfvit_linear_res_ln_fwd_ws(dtype, a, lda, w, ldw, bias, res, ldres, x_out, y, y_f32, gamma, beta, eps, mean, rstd, M, K, nullptr, stream);
+}
+int mfvit_linear_res_ln_fwd_ws(int dtype, const void* a, int64_t lda, const void* w, int64_t ldw, const float* bias, const float* res,
+                               int64_t ldres, float* x_out, void* y, int y_f32, const float* gamma, const float* beta, float eps,
+                               float* mean, float* rstd, int M, int K, float* scratch, mfvit_stream_t stream) {
+    if (!a || !w || !y || !gamma || !beta || ((size_t)scratch & 15)) return MFVIT_EINVAL;
+    GemmP p = nt(a, lda, w, ldw, M, 384, K);
+    p.kpart = scratch;
+    p.bias = bias; p.res = res; p.ldres = ldres;
+    p.out0 = x_out; p.ldo0 = 384; p.out1 = y; p.ldo1 = (dtype == MFVIT_BF16X3 && !y_f32) ? 768 : 384; p.y_f32 = y_f32;
+    p.gamma = gamma; p.beta = beta; p.eps = eps; p.mean = mean; p.rstd = rstd;
+    return gemm_nt_row(dtype, REPI_RES_LN, p, (hipStream_t)stream);
+}
+int mfvit_linear_dgrad_ln_bwd(int dtype, const void* dy, int64_t lddy, const void* wt, int64_t ldwt, const float* x, const float* mean,
+                              const float* rstd, const float* gamma, const float* dres, float* dx, void* dx_t, float* dgamma,
+                              float* dbeta, float* dcol, int M, int K, mfvit_stream_t stream) {
+    return mfvit_linear_dgrad_ln_bwd_ws(dtype, dy, lddy, wt, ldwt, x, mean, rstd, gamma, dres, dx, dx_t, dgamma, dbeta, dcol, M, K, nullptr, stream);
+}
+int mfvit_linear_dgrad_ln_bwd_ws(int dtype, const void* dy, int64_t lddy, const void* wt, int64_t ldwt, const float* x, const float* mean,
+                                 const float* rstd, const float* gamma, const float* dres, float* dx, void* dx_t, float* dgamma,
+                                 float* dbeta, float* dcol, int M, int K, float* scratch, mfvit_stream_t stream) {
+    if (!dy || !wt || !x || !mean || !rstd || !gamma || !dx || ((size_t)scratch & 15)) return MFVIT_EINVAL;
+    GemmP p = nt(dy, lddy, wt, ldwt, M, 384, K);
+    p.kpart = scratch;
+    p.aux = x; p.ldaux = 384; p.mean = (float*)mean; p.rstd = (float*)rstd; p.gamma = gamma;
+    p.res = dres; p.ldres = 384;
+    p.out0 = dx; p.ldo0 = 384; p.out1 = dx_t; p.ldo1 = dtype == MFVIT_BF16X3 ? 768 : 384;
+    p.cs0 = dgamma; p.cs1 = dbeta; p.cs2 = dcol;
+    return gemm_nt_row(dtype, REPI_LNBWD_RES, p, (hipStream_t)stream);
+}
+int mfvit_attention_fwd(int dtype, const void* qkv, void* out, float* lse, int B, int T, int H, int head_dim, mfvit_stream_t stream) {
+    if (!qkv || !out || !lse || B <= 0 || T <= 0 || H <= 0) return MFVIT_EINVAL;
+    return attn_fwd(dtype, qkv, out, lse, B, T, H, head_dim, (hipStream_t)stream);
+}
+int mfvit_attention_qkv_dtype(int dtype, int T, int head_dim) { return attn_qkv_dtype(dtype, T, head_dim); }
+int mfvit_attention_bwd(int dtype, const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* dbias_qkv,
+                        int B, int T, int H, int head_dim, mfvit_stream_t stream) {
+    if (!qkv || !out || !dout || !lse || !dqkv || B <= 0 || T <= 0 || H <= 0) return MFVIT_EINVAL;
+    return attn_bwd(dtype, qkv, out, dout, lse, dqkv, dbias_qkv, B, T, H, head_dim, (hipStream_t)stream);
+}
+int mfvit_attention_drop_fwd(int dtype, const void* qkv, void* out, float* lse, int B, int T, int H, int head_dim, float p, uint64_t seed,
+                             uint32_t site, mfvit_stream_t stream) {
+    if (!qkv || !out || !lse || B <= 0 || T <= 0 || H <= 0 || !(p >= 0.f && p < 1.f)) return MFVIT_EINVAL;
+    if (!attn_tiled_supported(dtype, T, head_dim)) return MFVIT_ENOSYS;
+    return attn_fwd_tiled_drop(dtype, qkv, out, lse, B, T, H, head_dim, make_drop(p, seed, site), (hipStream_t)stream);
+}
+int mfvit_attention_drop_bwd(int dtype, const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int B, int T, int H,
+                             int head_dim, float p, uint64_t seed, uint32_t site, mfvit_stream_t stream) {
+    if (!qkv || !out || !dout || !lse || !dqkv || B <= 0 || T <= 0 || H <= 0 || !(p >= 0.f && p < 1.f)) return MFVIT_EINVAL;
+    if (!attn_tiled_supported(dtype, T, head_dim)) return MFVIT_ENOSYS;
+    return attn_bwd_tiled_drop(dtype, qkv, out, dout, lse, dqkv, B, T, H, head_dim, make_drop(p, seed, site), (hipStream_t)stream);
+}
+int mfvit_dropout_mask(float p, uint64_t seed, uint32_t site, int64_t n, uint8_t* keep, mfvit_stream_t stream) {
+    if (!keep || !(p >= 0.f && p < 1.f)) return MFVIT_EINVAL;
+    return dropout_mask(make_drop(p, seed, site), n, keep, (hipStream_t)stream);
+}
+int mfvit_layernorm_fwd(int dtype, const float* x, void* y, int y_f32, const float* gamma, const float* beta, float eps, float* mean,
+                        float* rstd, int rows, int N, mfvit_stream_t stream) {
+    if (!x || !y || !gamma || !beta) return MFVIT_EINVAL;
+    return ln_rows(dtype, N, x, N, nullptr, 0, 0, nullptr, 0, y, (dtype == MFVIT_BF16X3 && !y_f32) ? 2 * N : N, y_f32, gamma, beta, eps, mean, rstd, rows, 1, 0,
+                   0, (hipStream_t)stream);
+}
+int mfvit_layernorm_bwd(int dtype, const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
+                        const float* dres, float* dx, void* dx_t, float* dgamma, float* dbeta, float* dcol, int rows, int N,
+                        mfvit_stream_t stream) {
+    if (!dy || !x || !mean || !rstd || !gamma) return MFVIT_EINVAL;
+    return ln_bwd_rows(dtype, N, dy, N, x, N, mean, rstd, gamma, dres, N, dx, N, dx_t, dtype == MFVIT_BF16X3 ? 2 * N : N, dgamma, dbeta, dcol, nullptr, rows, 1, 0,
+                       (hipStream_t)stream);
+}
+int mfvit_cast_transpose(int dtype, const float* src, void* dst, void* dst_t, int R, int C, mfvit_stream_t stream) {
+    if (!src || R <= 0 || C <= 0) return MFVIT_EINVAL;
+    return cast_transpose(dtype, src, dst, dst_t, R, C, (hipStream_t)stream);
+}
+int mfvit_head_fwd(const float* x, int64_t ldx, const float* w, const float* b, float* y, int64_t ldy, int M, int N, int K, int accumulate,
+                   mfvit_stream_t stream) {
+    if (!x || !w || !y) return MFVIT_EINVAL;
+    return linear_small_fwd(x, ldx, w, b, y, ldy, M, N, K, accumulate, (hipStream_t)stream);
+}
+int mfvit_head_bwd(const float* dy, int64_t lddy, const float* x, int64_t ldx, const float* w, float* dx, int64_t lddx, int dx_accumulate,
+                   float* dw, float* db, int M, int N, int K, mfvit_stream_t stream) {
+    if (!dy || !x || !w) return MFVIT_EINVAL;
+    return linear_small_bwd(dy, lddy, x, ldx, w, dx, lddx, dx_accumulate, dw, db, M, N, K, (hipStream_t)stream);
+}
+int mfvit_cross_entropy(const float* logits, const int64_t* target, float* loss_mean, float* dlogits, int64_t* preds, int B, int C,
+                        mfvit_stream_t stream) {
+    if (!logits || !target || !loss_mean) return MFVIT_EINVAL;
+    return ce_small(logits, (const long*)target, loss_mean, dlogits, (long*)preds, B, C, (hipStream_t)stream);
+}
+
+}  // extern "C"

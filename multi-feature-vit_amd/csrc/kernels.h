@@ -2,6 +2,8 @@
 #pragma once
 #include "gemm.cuh"
 
+#include <string.h>
+
 namespace mfvit {
 
 enum { EPI_BIAS = 0, EPI_BIAS_GELU = 1, EPI_GELU_BWD = 2, EPI_NONE = 3, EPI_BIAS_RELU = 4,    // 4: out0 = relu'(pre), out1 = relu(pre)
@@ -113,4 +115,19 @@ int attn_rollout(const float* maps, const float* sums, int depth, int B, int Tn,
 int attn_rel_map(int qdt, int ddt, const void* qkv, const float* lse, const void* dout, int B, int Tn, int H, int HD, float* map, const float* v,
                  float* part, int first, hipStream_t st);
 int attn_rel_update(float* v, const float* part, int B, int Tn, int first, float* out, hipStream_t st);
+
+// out = A W^T (A: M x K, W: N x K): the operands and the shape, every other field zero
+inline GemmP nt(const void* A, long lda, const void* W, long ldw, int M, int N, int K) {
+    GemmP p;
+    memset(&p, 0, sizeof(p));
+    p.A = A; p.lda = lda; p.W = W; p.ldw = ldw;
+    p.M = M; p.N = N; p.K = K;
+    return p;
+}
 }  // namespace mfvit
+
+#define MFVIT_TRY(expr)            \
+    do {                           \
+        int rc__ = (expr);         \
+        if (rc__ != MFVIT_OK) return rc__; \
+    } while (0)

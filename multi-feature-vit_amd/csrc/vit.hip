@@ -7,7 +7,6 @@
 
 #include <atomic>
 #include <stdlib.h>
-#include <string.h>
 
 using namespace mfvit;
 
@@ -26,12 +25,6 @@ struct ShareScope {
 }  // namespace mfvit
 
 namespace {
-
-// Round 4: the fc1 bias gradient comes from the accumulators of the fc2-dgrad tile epilogue (float atomics on 1536 addresses)
-// instead of the ones-fragment MFMAs of the fc1 weight gradient - those cost that launch 8 % (98.9 vs 91.5 us for the same flops without them: a third
-// more MFMAs on half the waves of a third of its workgroups).  Same box, 0 / 1 / 0 / 1: weight-gradient class 97.8 / 94.3 / 97.4 / 94.8 us per launch, tile
-// class unchanged (93.2 / 93.3 / 93.4 / 93.6), step 27.23 / 27.16 / 27.26 / 27.19 ms.
-constexpr bool fc1b_in_tile() { return true; }
 
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -263,10 +256,109 @@ WsLayout ws_layout(const Dims& d) {
     return W;
 }
 
-GemmP zero_gemm() {
-    GemmP p;
-    memset(&p, 0, sizeof(p));
-    return p;
+// ------------------------------------------------------------------ per-call context of encoder_forward / encoder_backward
+struct EncCtx {
+    const Dims d;
+    const ParamLayout L;
+    const ShadowLayout S;
+    const WsLayout W;
+    char* const ws;
+    const char* const sh;
+    const float* const params;
+    const hipStream_t st;
+    const long D, F;
+    const long e;            // leading dimensions of dtype tensors are in storage elements
+    const bool hw;           // 16-bit / split operands: the forward GEMMs read the weight shadows, f32 reads the arena
+    // only split bf16 (hi + lo = the f32 value to 2^-17) drops the f32 residual-gradient copies; plain bf16 / fp16 keep them: re-rounding the residual
+    // gradient to 8 / 11 mantissa bits at each of the 2 x depth LayerNorm-backward stages departs from the reference's autocast (fp32 residual grads)
+    const bool lean_grad;    // (the unfused row passes read the f32 residual gradient)
+    const float eps;
+    const DropP off = make_drop(0.f, 0, 0);
+
+    EncCtx(const mfvit_vit_cfg* cfg, const Dims& dims, const float* params_, const void* shadow, void* workspace, mfvit_stream_t stream)
+        : d(dims), L(param_layout(dims)), S(shadow_layout(dims)), W(ws_layout(dims)), ws((char*)workspace), sh((const char*)shadow), params(params_),
+          st((hipStream_t)stream), D(dims.D), F(dims.F), e(dims.ep), hw(dims.dtype != MFVIT_F32),
+          lean_grad(dims.dtype == MFVIT_BF16X3 && !dims.unfused), eps(cfg->ln_eps) {}
+
+    // activations are kept per block for a backward (save), in one copy otherwise
+    size_t slot(int l) const { return d.save ? (size_t)l : 0; }
+    float* xbuf(int l) const { return (float*)(ws + W.x0 + slot(l) * W.x_stride); }
+    float* stat(int l) const { return (float*)(ws + W.st0 + slot(l) * W.st_stride); }
+    char* blk(int l) const { return ws + W.blk0 + slot(l) * W.blk_stride; }
+    const float* pblk(int l) const { return params + L.blk0 + (long)l * L.blk_stride; }
+    const char* sblk(int l) const { return sh + S.blk0 + (size_t)l * S.blk_stride; }
+    float* kpart() const { return (float*)(ws + W.kpart); }
+    // the W operand of a forward GEMM
+    const void* weight(const char* shadow_w, const float* arena_w) const { return hw ? (const void*)shadow_w : (const void*)arena_w; }
+    // dropout sites (include/mfvit.h): the GPT's from the cfg, the ViT's from mfvit_vit_drop
+    static unsigned site(int l, int which) { return 16u * (unsigned)l + (unsigned)which; }
+    DropP dpath(int l, int which) const { return make_drop(d.dpr ? d.dpr[l] : 0.f, d.seed, site(l, which)); }   // per sample: keep of row r = sample r / T
+};
+
+struct BranchDrop { DropP drop, dpath; };   // masks of a residual branch: the element dropout and the per-sample drop path
+
+// the plain tile GEMM of the same product: operands, shape and bias, nothing else
+GemmP operands_of(const GemmP& p) {
+    GemmP q = nt(p.A, p.lda, p.W, p.ldw, p.M, p.N, p.K);
+    q.bias = p.bias;
+    return q;
+}
+
+// One "Linear, then residual + LayerNorm" site of the forward.  p: the REPI_RES_LN parameters of the site (kpart included where the site has one).
+// mask: the dropout of the branch and its drop path, NULL for a site whose branch is never masked (the patch embedding).  tag: the profiler tag
+// of the row-complete launches.  The first path that applies:
+//   1. drop path as the only masked branch (the fine-tune recipe: drop_rate = 0, drop_path_rate > 0) stays on the row-complete kernel: its
+//      drop-path epilogue (REPI_RES_LN_DP, gemm_rowp.hip) adds the residual rows (aux) to the sample-scaled branch - where that kernel applies
+//   2. a masked branch: plain GEMM + bias -> scratch, then dropout (element mask x per-sample drop-path factor) + residual + LayerNorm in one row pass
+//   3. unfused: plain GEMM + bias -> scratch, then residual + LayerNorm as one row pass
+//   4. the row-complete GEMM with the residual + LayerNorm epilogue
+int linear_res_ln(const EncCtx& c, const GemmP& p, const BranchDrop* mask, int tag) {
+    const Dims& d = c.d;
+    const long De = c.D * c.e;
+    const bool masked = mask && d.rdrop;
+    if (masked && !(d.p_resid > 0.f) && !d.unfused) {
+        GemmP r = p;
+        r.aux = p.res; r.ldaux = p.ldres; r.res = nullptr; r.ldres = 0;
+        r.drop = mask->dpath; r.drop_tpr = d.T;
+        ProfTag scope(tag);
+        if (gemm_nt_rowp_supported(d.dtype, REPI_RES_LN_DP, r)) return gemm_nt_rowp(d.dtype, REPI_RES_LN_DP, r, c.st);
+    }
+    if (masked || d.unfused) {
+        GemmP q = operands_of(p);
+        q.out0 = c.ws + (masked ? c.W.dtmp : c.W.utmp); q.ldo0 = De;
+        MFVIT_TRY(gemm_nt_tile(d.dtype, EPI_BIAS, q, c.st));
+        if (masked)
+            return drop_add_ln_rows(d.dtype, d.D, q.out0, De, nullptr, 0, nullptr, 0, 0, p.res, p.ldres, mask->drop, mask->dpath, d.T, (float*)p.out0,
+                                    p.ldo0, p.out1, p.ldo1, p.y_f32, p.gamma, p.beta, p.eps, p.mean, p.rstd, p.M, c.st);
+        // a periodic residual (res_mod) is a table indexed by the output row: the row pass takes it as `pos`, with the site's row remap
+        const bool table = p.res_mod != 0;
+        return add_ln_rows(d.dtype, d.D, q.out0, De, table ? p.res : nullptr, table ? p.ldres : 0, table ? p.orow_out : 0, table ? nullptr : p.res,
+                           table ? 0 : p.ldres, p.orow_in, p.orow_out, p.orow_off, (float*)p.out0, p.ldo0, p.out1, p.ldo1, p.y_f32, p.gamma, p.beta,
+                           p.eps, p.mean, p.rstd, p.M, c.st);
+    }
+    ProfTag scope(tag);
+    return gemm_nt_row(d.dtype, REPI_RES_LN, p, c.st);
+}
+
+// One "data-gradient GEMM, then LayerNorm backward + residual gradient + column sums" site of the backward.  p: the product, the LayerNorm input
+// (aux), its statistics and weight, the column-sum targets and kpart.  The residual gradient comes in f32 (res) - or, lean_grad, in the operand
+// type alone (res_t); the result goes to dx (f32, NULL: not kept) and dx_t (operand type).
+// 16-bit modes: the f32 copies were a second 38.7 MB store per launch (14 % of it) read by nobody else but the embedding stage.
+int dgrad_ln_bwd(const EncCtx& c, GemmP p, const float* res, const void* res_t, float* dx, void* dx_t) {
+    const Dims& d = c.d;
+    const long D = c.D, De = c.D * c.e;
+    if (d.unfused) {
+        // plain data-gradient GEMM -> scratch, then the LayerNorm backward + residual-gradient add + column sums as one row pass
+        GemmP q = operands_of(p);
+        q.out0 = c.ws + c.W.utmp; q.ldo0 = De;
+        MFVIT_TRY(gemm_nt_tile(d.dtype, EPI_NONE, q, c.st));
+        return ln_bwd_rows(d.dtype, d.D, nullptr, 0, (const float*)p.aux, p.ldaux, p.mean, p.rstd, p.gamma, res, D, dx, D, dx_t, De, p.cs0, p.cs1,
+                           p.cs2, p.cpart, p.M, 1, 0, c.st, q.out0, De);
+    }
+    if (c.lean_grad) { p.res_t = res_t; p.ldres_t = De; }
+    else { p.res = res; p.ldres = D; }
+    p.out0 = dx; p.ldo0 = D; p.out1 = dx_t; p.ldo1 = De;
+    return gemm_nt_row(d.dtype, REPI_LNBWD_RES, p, c.st);
 }
 
 // Weight-gradient GEMMs are leaves of the backward graph: they CAN run on a second (library-owned, lazily created) HIP stream beside the
@@ -307,12 +399,6 @@ SideStream& side_stream(hipStream_t caller) {
     }
     return x;
 }
-
-#define MFVIT_TRY(expr)            \
-    do {                           \
-        int rc__ = (expr);         \
-        if (rc__ != MFVIT_OK) return rc__; \
-    } while (0)
 
 }  // namespace
 
@@ -443,95 +529,57 @@ static int encoder_forward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* dropc
     Dims d;
     if (!get_dims(cfg, dropcfg, d) || !params || !shadow || !img || !workspace || !features) return MFVIT_EINVAL;
     if (d.tok != want_tokens) return MFVIT_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    const ParamLayout L = param_layout(d);
-    const ShadowLayout S = shadow_layout(d);
-    const WsLayout W = ws_layout(d);
-    char* ws = (char*)workspace;
-    const char* sh = (const char*)shadow;
-    const bool hw = d.dtype != MFVIT_F32;
-    const long D = d.D, F = d.F;
-    const long e = d.ep;   // leading dimensions of dtype tensors are in storage elements
-    const float eps = cfg->ln_eps;
-    auto xbuf = [&](int l) { return (float*)(ws + W.x0 + (d.save ? (size_t)l : 0) * W.x_stride); };
-    auto stat = [&](int l) { return (float*)(ws + W.st0 + (d.save ? (size_t)l : 0) * W.st_stride); };
-    auto blk = [&](int l) { return ws + W.blk0 + (d.save ? (size_t)l : 0) * W.blk_stride; };
-    auto pblk = [&](int l) { return params + L.blk0 + (long)l * L.blk_stride; };
-    auto sblk = [&](int l) { return sh + S.blk0 + (size_t)l * S.blk_stride; };
-
-    // dropout sites (include/mfvit.h): the GPT's from the cfg, the ViT's from mfvit_vit_drop
-    auto site = [](int l, int which) { return 16u * (unsigned)l + (unsigned)which; };
-    const DropP off = make_drop(0.f, 0, 0);
-    auto dpath = [&](int l, int which) { return make_drop(d.dpr ? d.dpr[l] : 0.f, d.seed, site(l, which)); };   // per sample: keep of row r = sample r / T
-    // Drop path as the only masked branch (the fine-tune recipe: drop_rate = 0, drop_path_rate > 0) stays on the row-complete kernel: its drop-path
-    // epilogue (REPI_RES_LN_DP, gemm_rowp.hip) adds the residual rows (aux) to the sample-scaled branch.  p: the REPI_RES_LN parameters of the site.
-    // Returns false (nothing launched) where the kernel does not apply; the row pass below takes the site then.
-    auto rowp_dpath = [&](GemmP p, DropP dp, int& rc) -> bool {
-        if (!d.rdrop || d.p_resid > 0.f || d.unfused) return false;
-        p.aux = p.res; p.ldaux = p.ldres; p.res = nullptr; p.ldres = 0;
-        p.drop = dp; p.drop_tpr = d.T;
-        p.kpart = (float*)(ws + W.kpart);
-        if (!gemm_nt_rowp_supported(d.dtype, REPI_RES_LN_DP, p)) return false;
-        rc = gemm_nt_rowp(d.dtype, REPI_RES_LN_DP, p, st);
-        return true;
-    };
+    const EncCtx c(cfg, d, params, shadow, workspace, stream);
+    const ParamLayout& L = c.L;
+    const ShadowLayout& S = c.S;
+    const WsLayout& W = c.W;
+    char* const ws = c.ws;
+    const hipStream_t st = c.st;
+    const long D = c.D, F = c.F, e = c.e;
+    const float eps = c.eps;
+    // x_0 and LN1_0 -> y1_0: the outputs of every embedding form
+    float* const x0 = c.xbuf(0);
+    char* const y1_0 = c.blk(0) + W.y1;
+    const float* const g0 = c.pblk(0) + L.ln1_w;
+    const float* const b0 = c.pblk(0) + L.ln1_b;
+    float* const mean0 = c.stat(0);
+    float* const rstd0 = c.stat(0) + d.M;
     if (d.tok && d.p_embd > 0.f) {
         // x_0 = drop(tokens + pos_emb) (fuseattention.py:187 `self.drop(self.pos_emb + token_embeddings)`); LN1_0 -> y1_0
         MFVIT_TRY(drop_add_ln_rows(d.dtype, d.D, nullptr, 0, img, D, d.use_pos ? params + L.pos : nullptr, D, d.T, nullptr, 0,
-                                   make_drop(d.p_embd, d.seed, 1), off, 1, xbuf(0), D, blk(0) + W.y1, D * e, 0, pblk(0) + L.ln1_w, pblk(0) + L.ln1_b,
-                                   eps, stat(0), stat(0) + d.M, d.M, st));
+                                   make_drop(d.p_embd, d.seed, 1), c.off, 1, x0, D, y1_0, D * e, 0, g0, b0, eps, mean0, rstd0, d.M, st));
     } else if (d.tok) {
         // token input (fuseattention.py:186-189): x_0 = tokens (+ pos_emb, shared by the batch); LN1_0 -> y1_0.  One row kernel pass.
-        MFVIT_TRY(ln_rows(d.dtype, d.D, img, D, d.use_pos ? params + L.pos : nullptr, D, d.T, xbuf(0), D, blk(0) + W.y1, D * e, 0,
-                          pblk(0) + L.ln1_w, pblk(0) + L.ln1_b, eps, stat(0), stat(0) + d.M, d.M, 1, 0, 0, st));
+        MFVIT_TRY(ln_rows(d.dtype, d.D, img, D, d.use_pos ? params + L.pos : nullptr, D, d.T, x0, D, y1_0, D * e, 0, g0, b0, eps, mean0, rstd0, d.M,
+                          1, 0, 0, st));
     } else {
-    // patch embedding: im2col -> row-complete GEMM (+bias +pos_embed) -> x_0, LN1_0 -> y1_0
-    MFVIT_TRY(im2col16(d.dtype, img, ws + W.patches, d.B, cfg->img_h, cfg->img_w, st));
-    if (d.unfused) {
-        // plain GEMM + bias -> scratch, then one row pass: + pos_embed, the patch rows of image b behind its cls row, LN1_0
-        GemmP q = zero_gemm();
-        q.A = ws + W.patches; q.lda = 768 * e;
-        q.W = hw ? (const void*)(sh + S.pe_w) : (const void*)(params + L.pe_w); q.ldw = 768 * e;
-        q.M = d.Mp; q.N = d.D; q.K = 768;
-        q.bias = params + L.pe_b;
-        q.out0 = ws + W.utmp; q.ldo0 = D * e;
-        MFVIT_TRY(gemm_nt_tile(d.dtype, EPI_BIAS, q, st));
-        MFVIT_TRY(add_ln_rows(d.dtype, d.D, ws + W.utmp, D * e, params + L.pos, D, d.T, nullptr, 0, d.np, d.T, 1, xbuf(0), D, blk(0) + W.y1, D * e, 0,
-                              pblk(0) + L.ln1_w, pblk(0) + L.ln1_b, eps, stat(0), stat(0) + d.M, d.Mp, st));
-    } else {
-        GemmP p = zero_gemm();
-        p.A = ws + W.patches; p.lda = 768 * e;
-        p.W = hw ? (const void*)(sh + S.pe_w) : (const void*)(params + L.pe_w); p.ldw = 768 * e;
-        p.M = d.Mp; p.N = d.D; p.K = 768;
+        // patch embedding: im2col -> GEMM + bias + pos_embed, the patch rows of image b behind its cls row -> x_0, LN1_0 -> y1_0
+        MFVIT_TRY(im2col16(d.dtype, img, ws + W.patches, d.B, cfg->img_h, cfg->img_w, st));
+        GemmP p = nt(ws + W.patches, 768 * e, c.weight(c.sh + S.pe_w, params + L.pe_w), 768 * e, d.Mp, d.D, 768);
         p.bias = params + L.pe_b;
         p.res = params + L.pos; p.ldres = D; p.res_mod = d.np; p.res_off = 1;
         p.orow_in = d.np; p.orow_out = d.T; p.orow_off = 1;
-        p.out0 = xbuf(0); p.ldo0 = D;
-        p.out1 = blk(0) + W.y1; p.ldo1 = D * e;
-        p.gamma = pblk(0) + L.ln1_w; p.beta = pblk(0) + L.ln1_b; p.eps = eps;
-        p.mean = stat(0); p.rstd = stat(0) + d.M;
-        MFVIT_TRY(gemm_nt_row(d.dtype, REPI_RES_LN, p, st));
-    }
-    // cls rows: x_0[b,0] = cls_token + pos_embed[0]; LN1_0
-    MFVIT_TRY(ln_rows(d.dtype, d.D, params + L.cls, 0, params + L.pos, D, 1, xbuf(0), D, blk(0) + W.y1, D * e, 0, pblk(0) + L.ln1_w,
-                      pblk(0) + L.ln1_b, eps, stat(0), stat(0) + d.M, d.B, d.T, 0, 1, st));
-    if (d.p_embd > 0.f)
-        // timm pos_drop: x_0 = drop(cat(cls, patch_embed(x)) + pos_embed), cls rows included; in place, then LN1_0 again
-        MFVIT_TRY(drop_add_ln_rows(d.dtype, d.D, nullptr, 0, xbuf(0), D, nullptr, 0, 0, nullptr, 0, make_drop(d.p_embd, d.seed, 1), off, 1, xbuf(0), D,
-                                   blk(0) + W.y1, D * e, 0, pblk(0) + L.ln1_w, pblk(0) + L.ln1_b, eps, stat(0), stat(0) + d.M, d.M, st));
+        p.out0 = x0; p.ldo0 = D;
+        p.out1 = y1_0; p.ldo1 = D * e;
+        p.gamma = g0; p.beta = b0; p.eps = eps;
+        p.mean = mean0; p.rstd = rstd0;
+        MFVIT_TRY(linear_res_ln(c, p, nullptr, PROF_TAG_NONE));
+        // cls rows: x_0[b,0] = cls_token + pos_embed[0]; LN1_0
+        MFVIT_TRY(ln_rows(d.dtype, d.D, params + L.cls, 0, params + L.pos, D, 1, x0, D, y1_0, D * e, 0, g0, b0, eps, mean0, rstd0, d.B, d.T, 0, 1, st));
+        if (d.p_embd > 0.f)
+            // timm pos_drop: x_0 = drop(cat(cls, patch_embed(x)) + pos_embed), cls rows included; in place, then LN1_0 again
+            MFVIT_TRY(drop_add_ln_rows(d.dtype, d.D, nullptr, 0, x0, D, nullptr, 0, 0, nullptr, 0, make_drop(d.p_embd, d.seed, 1), c.off, 1, x0, D,
+                                       y1_0, D * e, 0, g0, b0, eps, mean0, rstd0, d.M, st));
     }
 
     for (int l = 0; l < d.depth; ++l) {
-        char* b = blk(l);
-        const float* pb = pblk(l);
-        const char* sb = sblk(l);
+        char* b = c.blk(l);
+        const float* pb = c.pblk(l);
+        const char* sb = c.sblk(l);
         // qkv tensor format: split FP16 for the whole-head attention kernels in bf16x3 mode (attention_mfma.hip), the activation dtype otherwise
         const int qdt = d.p_attn > 0.f ? d.dtype : attn_qkv_dtype(d.dtype, d.T, d.HD);
         {   // qkv = y1 Wqkv^T + b
-            GemmP p = zero_gemm();
-            p.A = b + W.y1; p.lda = D * e;
-            p.W = hw ? (const void*)(sb + S.qkv_w) : (const void*)(pb + L.qkv_w); p.ldw = D * e;
-            p.M = d.M; p.N = 3 * d.D; p.K = d.D;
+            GemmP p = nt(b + W.y1, D * e, c.weight(sb + S.qkv_w, pb + L.qkv_w), D * e, d.M, 3 * d.D, d.D);
             p.bias = pb + L.qkv_b;
             p.out0 = b + W.qkv; p.ldo0 = 3 * D * e;
             ProfTag tag(PROF_TAG_MHSA_QKV);
@@ -540,108 +588,51 @@ static int encoder_forward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* dropc
         if (d.p_attn > 0.f) {
             if (!attn_tiled_supported(d.dtype, d.T, d.HD)) return MFVIT_ENOSYS;
             MFVIT_TRY(attn_fwd_tiled_drop(d.dtype, b + W.qkv, b + W.attn, (float*)(b + W.lse), d.B, d.T, d.H, d.HD,
-                                          make_drop(d.p_attn, d.seed, site(l, 2)), st));
+                                          make_drop(d.p_attn, d.seed, c.site(l, 2)), st));
         } else {
             MFVIT_TRY(attn_fwd(qdt, b + W.qkv, b + W.attn, (float*)(b + W.lse), d.B, d.T, d.H, d.HD, st));
         }
         if (attn) MFVIT_TRY(attn_block_step(d, attn, l, qdt, b + W.qkv, (const float*)(b + W.lse), st));
         {   // xmid = x + attn Wproj^T + b ; y2 = LN2(xmid)
-            GemmP p = zero_gemm();
-            p.A = b + W.attn; p.lda = D * e;
-            p.W = hw ? (const void*)(sb + S.proj_w) : (const void*)(pb + L.proj_w); p.ldw = D * e;
-            p.M = d.M; p.N = d.D; p.K = d.D;
+            // (masked: xmid = x + resid_drop(proj(attn)), fuseattention.py:57; timm: x + drop_path(proj_drop(proj(attn))))
+            GemmP p = nt(b + W.attn, D * e, c.weight(sb + S.proj_w, pb + L.proj_w), D * e, d.M, d.D, d.D);
             p.bias = pb + L.proj_b;
-            p.res = xbuf(l); p.ldres = D;
+            p.res = c.xbuf(l); p.ldres = D;
             p.out0 = b + W.xmid; p.ldo0 = D;
             p.out1 = b + W.y2; p.ldo1 = D * e;
             p.gamma = pb + L.ln2_w; p.beta = pb + L.ln2_b; p.eps = eps;
             p.mean = (float*)(b + W.st2); p.rstd = (float*)(b + W.st2) + d.M;
-            int rc = MFVIT_OK;
-            bool done;
-            {
-                ProfTag tag(PROF_TAG_MHSA_PROJ);
-                done = rowp_dpath(p, dpath(l, 6), rc);
-            }
-            if (done) {
-                MFVIT_TRY(rc);
-            } else if (d.rdrop) {
-                // xmid = x + resid_drop(proj(attn)) (fuseattention.py:57; timm: x + drop_path(proj_drop(proj(attn)))): plain GEMM + bias, then
-                // dropout (element mask x per-sample drop-path factor) + residual + LN2 in one row pass
-                GemmP q = zero_gemm();
-                q.A = p.A; q.lda = p.lda; q.W = p.W; q.ldw = p.ldw; q.M = p.M; q.N = p.N; q.K = p.K; q.bias = p.bias;
-                q.out0 = ws + W.dtmp; q.ldo0 = D * e;
-                MFVIT_TRY(gemm_nt_tile(d.dtype, EPI_BIAS, q, st));
-                MFVIT_TRY(drop_add_ln_rows(d.dtype, d.D, ws + W.dtmp, D * e, nullptr, 0, nullptr, 0, 0, xbuf(l), D,
-                                           make_drop(d.p_resid, d.seed, site(l, 3)), dpath(l, 6), d.T, (float*)(b + W.xmid), D, b + W.y2, D * e, 0,
-                                           p.gamma, p.beta,
-                                           eps, p.mean, p.rstd, d.M, st));
-            } else if (d.unfused) {
-                // plain GEMM + bias -> scratch, then residual + LN2 as one row pass
-                GemmP q = zero_gemm();
-                q.A = p.A; q.lda = p.lda; q.W = p.W; q.ldw = p.ldw; q.M = p.M; q.N = p.N; q.K = p.K; q.bias = p.bias;
-                q.out0 = ws + W.utmp; q.ldo0 = D * e;
-                MFVIT_TRY(gemm_nt_tile(d.dtype, EPI_BIAS, q, st));
-                MFVIT_TRY(add_ln_rows(d.dtype, d.D, ws + W.utmp, D * e, nullptr, 0, 0, xbuf(l), D, 0, 0, 0, (float*)(b + W.xmid), D, b + W.y2, D * e, 0,
-                                      p.gamma, p.beta, eps, p.mean, p.rstd, d.M, st));
-            } else {
-                p.kpart = (float*)(ws + W.kpart);
-                ProfTag tag(PROF_TAG_MHSA_PROJ);
-                MFVIT_TRY(gemm_nt_row(d.dtype, REPI_RES_LN, p, st));
-            }
+            p.kpart = c.kpart();
+            const BranchDrop mask = {make_drop(d.p_resid, d.seed, c.site(l, 3)), c.dpath(l, 6)};
+            MFVIT_TRY(linear_res_ln(c, p, &mask, PROF_TAG_MHSA_PROJ));
         }
         {   // hpre = y2 W1^T + b1 ; hact = gelu(hpre)   (training: hact = drop(gelu(hpre)), out0 = gelu'(hpre) * mask - timm Mlp.drop)
-            GemmP p = zero_gemm();
-            p.A = b + W.y2; p.lda = D * e;
-            p.W = hw ? (const void*)(sb + S.fc1_w) : (const void*)(pb + L.fc1_w); p.ldw = D * e;
-            p.M = d.M; p.N = d.F; p.K = d.D;
+            GemmP p = nt(b + W.y2, D * e, c.weight(sb + S.fc1_w, pb + L.fc1_w), D * e, d.M, d.F, d.D);
             p.bias = pb + L.fc1_b;
             p.out0 = d.save ? b + W.hpre : nullptr; p.ldo0 = F;      // act'(pre) in act_grad_type<T> (gemm.hip): F elements per row
             p.out1 = b + W.hact; p.ldo1 = F * e;
-            p.drop = make_drop(d.p_gelu, d.seed, site(l, 5));
+            p.drop = make_drop(d.p_gelu, d.seed, c.site(l, 5));
             MFVIT_TRY(gemm_nt_tile(d.dtype, d.act == 1 ? EPI_BIAS_RELU : (d.p_gelu > 0.f ? EPI_BIAS_GELU_DROP : EPI_BIAS_GELU), p, st));
         }
         {   // x_{l+1} = xmid + hact W2^T + b2 ; y = LN(next norm1 | final norm)
+            // (masked: x_{l+1} = xmid + Dropout(fc2(relu(fc1(y2)))), fuseattention.py:67-72,80; timm: xmid + drop_path(drop(fc2(..))))
             const bool last = l + 1 == d.depth;
-            GemmP p = zero_gemm();
-            p.A = b + W.hact; p.lda = F * e;
-            p.W = hw ? (const void*)(sb + S.fc2_w) : (const void*)(pb + L.fc2_w); p.ldw = F * e;
-            p.M = d.M; p.N = d.D; p.K = d.F;
+            GemmP p = nt(b + W.hact, F * e, c.weight(sb + S.fc2_w, pb + L.fc2_w), F * e, d.M, d.D, d.F);
             p.bias = pb + L.fc2_b;
             p.res = (const float*)(b + W.xmid); p.ldres = D;
-            p.out0 = xbuf(l + 1); p.ldo0 = D;
+            p.out0 = c.xbuf(l + 1); p.ldo0 = D;
             if (last) {
                 p.out1 = features; p.ldo1 = D; p.y_f32 = 1;
                 p.gamma = params + L.norm_w; p.beta = params + L.norm_b;
             } else {
-                p.out1 = blk(l + 1) + W.y1; p.ldo1 = D * e;
-                p.gamma = pblk(l + 1) + L.ln1_w; p.beta = pblk(l + 1) + L.ln1_b;
+                p.out1 = c.blk(l + 1) + W.y1; p.ldo1 = D * e;
+                p.gamma = c.pblk(l + 1) + L.ln1_w; p.beta = c.pblk(l + 1) + L.ln1_b;
             }
             p.eps = eps;
-            p.mean = stat(l + 1); p.rstd = stat(l + 1) + d.M;
-            int rc = MFVIT_OK;
-            if (rowp_dpath(p, dpath(l, 7), rc)) {
-                MFVIT_TRY(rc);
-            } else if (d.rdrop) {
-                // x_{l+1} = xmid + Dropout(fc2(relu(fc1(y2)))) (fuseattention.py:67-72,80; timm: xmid + drop_path(drop(fc2(..))))
-                GemmP q = zero_gemm();
-                q.A = p.A; q.lda = p.lda; q.W = p.W; q.ldw = p.ldw; q.M = p.M; q.N = p.N; q.K = p.K; q.bias = p.bias;
-                q.out0 = ws + W.dtmp; q.ldo0 = D * e;
-                MFVIT_TRY(gemm_nt_tile(d.dtype, EPI_BIAS, q, st));
-                MFVIT_TRY(drop_add_ln_rows(d.dtype, d.D, ws + W.dtmp, D * e, nullptr, 0, nullptr, 0, 0, (const float*)(b + W.xmid), D,
-                                           make_drop(d.p_resid, d.seed, site(l, 4)), dpath(l, 7), d.T, xbuf(l + 1), D, p.out1, p.ldo1, p.y_f32,
-                                           p.gamma, p.beta, eps,
-                                           p.mean, p.rstd, d.M, st));
-            } else if (d.unfused) {
-                GemmP q = zero_gemm();
-                q.A = p.A; q.lda = p.lda; q.W = p.W; q.ldw = p.ldw; q.M = p.M; q.N = p.N; q.K = p.K; q.bias = p.bias;
-                q.out0 = ws + W.utmp; q.ldo0 = D * e;
-                MFVIT_TRY(gemm_nt_tile(d.dtype, EPI_BIAS, q, st));
-                MFVIT_TRY(add_ln_rows(d.dtype, d.D, ws + W.utmp, D * e, nullptr, 0, 0, (const float*)(b + W.xmid), D, 0, 0, 0, xbuf(l + 1), D, p.out1,
-                                      p.ldo1, p.y_f32, p.gamma, p.beta, eps, p.mean, p.rstd, d.M, st));
-            } else {
-                p.kpart = (float*)(ws + W.kpart);
-                MFVIT_TRY(gemm_nt_row(d.dtype, REPI_RES_LN, p, st));
-            }
+            p.mean = c.stat(l + 1); p.rstd = c.stat(l + 1) + d.M;
+            p.kpart = c.kpart();
+            const BranchDrop mask = {make_drop(d.p_resid, d.seed, c.site(l, 4)), c.dpath(l, 7)};
+            MFVIT_TRY(linear_res_ln(c, p, &mask, PROF_TAG_NONE));
         }
     }
     return MFVIT_OK;
@@ -661,20 +652,15 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop
     if (stage_hi > d.depth || stage_lo < -1 || stage_lo > stage_hi) return MFVIT_EINVAL;
     if (dimg && (d.tok || stage_lo != -1)) return MFVIT_EINVAL;
     const bool wg = dparams != nullptr;             // parameter gradients wanted (false: data-gradient-only backward)
-    hipStream_t st = (hipStream_t)stream;
-    const ParamLayout L = param_layout(d);
-    const ShadowLayout S = shadow_layout(d);
-    const WsLayout W = ws_layout(d);
-    char* ws = (char*)workspace;
-    const char* sh = (const char*)shadow;
-    const long D = d.D, F = d.F;
-    const long e = d.ep;   // leading dimensions of dtype tensors are in storage elements
-    auto xbuf = [&](int l) { return (float*)(ws + W.x0 + (size_t)l * W.x_stride); };
-    auto stat = [&](int l) { return (float*)(ws + W.st0 + (size_t)l * W.st_stride); };
-    auto blk = [&](int l) { return ws + W.blk0 + (size_t)l * W.blk_stride; };
-    auto pblk = [&](int l) { return params + L.blk0 + (long)l * L.blk_stride; };
+    const EncCtx c(cfg, d, params, shadow, workspace, stream);
+    const ParamLayout& L = c.L;
+    const ShadowLayout& S = c.S;
+    const WsLayout& W = c.W;
+    char* const ws = c.ws;
+    const hipStream_t st = c.st;
+    const long D = c.D, F = c.F, e = c.e;
+    const bool lean_grad = c.lean_grad;
     auto gblk = [&](int l) { return wg ? dparams + L.blk0 + (long)l * L.blk_stride : nullptr; };
-    auto sblk = [&](int l) { return sh + S.blk0 + (size_t)l * S.blk_stride; };
     float* gx = (float*)(ws + W.gx);
     float* gmid = (float*)(ws + W.gmid);
     float* colscr = (float*)(ws + W.colscratch);
@@ -736,13 +722,7 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop
         return hipStreamWaitEvent(st, ss.done[l & 63], 0) == hipSuccess ? MFVIT_OK : MFVIT_ELAUNCH;
     };
 
-    // only split bf16 (hi + lo = the f32 value to 2^-17) drops the f32 residual-gradient copies; plain bf16 / fp16 keep them: re-rounding the residual
-    // gradient to 8 / 11 mantissa bits at each of the 2 x depth LayerNorm-backward stages departs from the reference's autocast (fp32 residual grads)
-    const bool lean_grad = d.dtype == MFVIT_BF16X3 && !d.unfused;   // (the unfused row passes read the f32 residual gradient)
-    auto site = [](int l, int which) { return 16u * (unsigned)l + (unsigned)which; };
     const bool rdrop = d.rdrop;                     // the bias gradients of proj / fc2 then come from the MASKED dY (wgrad column sums)
-    const DropP off = make_drop(0.f, 0, 0);
-    auto dpath = [&](int l, int which) { return make_drop(d.dpr ? d.dpr[l] : 0.f, d.seed, site(l, which)); };
     // The attention backward's split-fp16 core scales dO (= the proj data gradient) per (image, head) by a power of two from the pair's largest |dO|.  The
     // GEMM that produces dO leaves those maxima behind (GemmP::omax: atomicMax of f32 bits, one slice per block, zeroed here for the blocks of this call), and
     // the attention kernel reads ONE number per pair instead of prefetching the hi parts of all of dO's rows a pair ahead.  MFVIT_DO_MAX=0: the prefetch.
@@ -758,19 +738,16 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop
         if (s == d.depth) {
             // final LayerNorm backward: dfeatures -> gx (grad of x_depth); dcol = d fc2_b of the last block
             if (!dfeatures) return MFVIT_EINVAL;
-            if (wg)
-                MFVIT_TRY(ln_bwd_rows(d.dtype, d.D, dfeatures, D, xbuf(d.depth), D, stat(d.depth), stat(d.depth) + d.M, params + L.norm_w,
-                                      nullptr, 0, gx, D, pp(W.gxT, d.depth - 1), D * e, dparams + L.norm_w, dparams + L.norm_b,
-                                      rdrop ? colscr + D : gblk(d.depth - 1) + L.fc2_b, next_colpart(), d.M, 1, 0, st));
-            else
-                MFVIT_TRY(ln_bwd_rows(d.dtype, d.D, dfeatures, D, xbuf(d.depth), D, stat(d.depth), stat(d.depth) + d.M, params + L.norm_w,
-                                      nullptr, 0, gx, D, pp(W.gxT, d.depth - 1), D * e, nullptr, nullptr, nullptr, nullptr, d.M, 1, 0, st));
+            float* const dcol = !wg ? nullptr : rdrop ? colscr + D : gblk(d.depth - 1) + L.fc2_b;
+            MFVIT_TRY(ln_bwd_rows(d.dtype, d.D, dfeatures, D, c.xbuf(d.depth), D, c.stat(d.depth), c.stat(d.depth) + d.M, params + L.norm_w,
+                                  nullptr, 0, gx, D, pp(W.gxT, d.depth - 1), D * e, wg ? dparams + L.norm_w : nullptr,
+                                  wg ? dparams + L.norm_b : nullptr, dcol, wg ? next_colpart() : nullptr, d.M, 1, 0, st));
         } else if (s >= 0) {
             const int l = s;
-            char* b = blk(l);
-            const float* pb = pblk(l);
+            char* b = c.blk(l);
+            const float* pb = c.pblk(l);
             float* gb = gblk(l);
-            const char* sb = sblk(l);
+            const char* sb = c.sblk(l);
             void* gxT = pp(W.gxT, l);
             void* gmidT = pp(W.gmidT, l);
             void* dhpre = pp(W.dhpre, l);
@@ -788,75 +765,49 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop
             const void* gy2 = gxT;                                // dY of fc2: the residual gradient, masked where the branch was dropped
             if (rdrop) {
                 // (the residual gradient itself passes unscaled: gxT stays the residual operand of the LN2 backward below)
-                MFVIT_TRY(mask_scale_rows(d.dtype, false, gxT, D * e, ws + W.dtmp, D * e, make_drop(d.p_resid, d.seed, site(l, 4)), dpath(l, 7), d.T,
+                MFVIT_TRY(mask_scale_rows(d.dtype, false, gxT, D * e, ws + W.dtmp, D * e, make_drop(d.p_resid, d.seed, c.site(l, 4)), c.dpath(l, 7), d.T,
                                           d.M, d.D, st));
                 gy2 = ws + W.dtmp;
             }
             if (wg) {   // dW2 += gx^T hact
-                GemmP p = zero_gemm();
-                p.A = gy2; p.lda = D * e; p.W = b + W.hact; p.ldw = F * e;
-                p.M = d.M; p.N = d.D; p.K = d.F;
+                GemmP p = nt(gy2, D * e, b + W.hact, F * e, d.M, d.D, d.F);
                 if (rdrop) p.cs0 = gb + L.fc2_b;
                 p.out0 = gb + L.fc2_w; p.ldo0 = F;
                 p.cpart = next_tnpart();                          // split partials: plain stores, reduced in a fixed order at the end of the call
                 MFVIT_TRY(tn_now_or_later(p));
             }
             {   // dhpre = (gx W2) * gelu'(hpre)
-                GemmP p = zero_gemm();
-                p.A = gy2; p.lda = D * e; p.W = sb + S.fc2_t; p.ldw = D * e;
-                p.M = d.M; p.N = d.F; p.K = d.D;
+                GemmP p = nt(gy2, D * e, sb + S.fc2_t, D * e, d.M, d.F, d.D);
                 p.aux = b + W.hpre; p.ldaux = F;
                 p.out0 = dhpre; p.ldo0 = F * e;
-                if (fc1b_in_tile() && wg) { p.cs0 = gb + L.fc1_b; p.cpart = next_colpart(); }   // d fc1_b += column sums of dhpre from the accumulators of this epilogue (partials, fixed-order reduce)
+                if (wg) { p.cs0 = gb + L.fc1_b; p.cpart = next_colpart(); }   // d fc1_b += column sums of dhpre from the accumulators of this epilogue (partials, fixed-order reduce)
                 MFVIT_TRY(gemm_nt_tile(d.dtype, EPI_GELU_BWD, p, st));
             }
             if (wg) {   // dW1 += dhpre^T y2
-                GemmP p = zero_gemm();
-                p.A = dhpre; p.lda = F * e; p.W = b + W.y2; p.ldw = D * e;
-                p.M = d.M; p.N = d.F; p.K = d.D;
-                if (!fc1b_in_tile()) p.cs0 = gb + L.fc1_b;        // d fc1_b += column sums of dhpre (ones-fragment MFMA in the wgrad kernel)
+                GemmP p = nt(dhpre, F * e, b + W.y2, D * e, d.M, d.F, d.D);   // (d fc1_b: from the fc2 data gradient's epilogue, above)
                 p.out0 = gb + L.fc1_w; p.ldo0 = D;
                 p.cpart = next_tnpart();                          // split partials: plain stores, reduced in a fixed order at the end of the call
                 MFVIT_TRY(tn_now_or_later(p));
             }
             {   // gmid = LN2bwd(dhpre W1) + gx ; d ln2_w, d ln2_b, d proj_b
-                GemmP p = zero_gemm();
-                p.A = dhpre; p.lda = F * e; p.W = sb + S.fc1_t; p.ldw = F * e;
-                p.M = d.M; p.N = d.D; p.K = d.F;
+                GemmP p = nt(dhpre, F * e, sb + S.fc1_t, F * e, d.M, d.D, d.F);
                 p.aux = b + W.xmid; p.ldaux = D;
                 p.mean = (float*)(b + W.st2); p.rstd = (float*)(b + W.st2) + d.M;
                 p.gamma = pb + L.ln2_w;
-                // 16-bit modes: the residual gradient travels in the operand-type copy alone (gxT / gmidT: hi + lo = the f32 value to 2^-17);
-                // the f32 copies gx / gmid were a second 38.7 MB store per launch (14 % of it) read by nobody else but the embedding stage
-                if (lean_grad) { p.res_t = gxT; p.ldres_t = D * e; p.out0 = nullptr; }
-                else { p.res = gx; p.ldres = D; p.out0 = gmid; }
-                p.ldo0 = D; p.out1 = gmidT; p.ldo1 = D * e;
+                p.kpart = c.kpart();
                 if (wg) { p.cs0 = gb + L.ln2_w; p.cs1 = gb + L.ln2_b; p.cs2 = rdrop ? colscr + D : gb + L.proj_b; p.cpart = next_colpart(); }
-                if (d.unfused) {
-                    // plain data-gradient GEMM -> scratch, then the LayerNorm backward + residual-gradient add + column sums as one row pass
-                    GemmP q = zero_gemm();
-                    q.A = p.A; q.lda = p.lda; q.W = p.W; q.ldw = p.ldw; q.M = p.M; q.N = p.N; q.K = p.K;
-                    q.out0 = ws + W.utmp; q.ldo0 = D * e;
-                    MFVIT_TRY(gemm_nt_tile(d.dtype, EPI_NONE, q, st));
-                    MFVIT_TRY(ln_bwd_rows(d.dtype, d.D, nullptr, 0, (const float*)(b + W.xmid), D, p.mean, p.rstd, p.gamma, gx, D, gmid, D, gmidT, D * e,
-                                          p.cs0, p.cs1, p.cs2, p.cpart, d.M, 1, 0, st, ws + W.utmp, D * e));
-                } else {
-                    p.kpart = (float*)(ws + W.kpart);
-                    MFVIT_TRY(gemm_nt_row(d.dtype, REPI_LNBWD_RES, p, st));
-                }
+                MFVIT_TRY(dgrad_ln_bwd(c, p, gx, gxT, lean_grad ? nullptr : gmid, gmidT));
             }
             const void* gyp = gmidT;                              // dY of proj
             if (rdrop) {
-                MFVIT_TRY(mask_scale_rows(d.dtype, false, gmidT, D * e, ws + W.dtmp, D * e, make_drop(d.p_resid, d.seed, site(l, 3)), dpath(l, 6), d.T,
+                MFVIT_TRY(mask_scale_rows(d.dtype, false, gmidT, D * e, ws + W.dtmp, D * e, make_drop(d.p_resid, d.seed, c.site(l, 3)), c.dpath(l, 6), d.T,
                                           d.M, d.D, st));
                 gyp = ws + W.dtmp;
             }
-            GemmP pend_proj = zero_gemm();                        // dWproj: launched here, or held back to ride along with dWqkv (one launch for both)
+            GemmP pend_proj = {};                                 // dWproj: launched here, or held back to ride along with dWqkv (one launch for both)
             bool have_pend = false;
             if (wg) {   // dWproj += gmid^T attn
-                GemmP p = zero_gemm();
-                p.A = gyp; p.lda = D * e; p.W = b + W.attn; p.ldw = D * e;
-                p.M = d.M; p.N = d.D; p.K = d.D;
+                GemmP p = nt(gyp, D * e, b + W.attn, D * e, d.M, d.D, d.D);
                 if (rdrop) p.cs0 = gb + L.proj_b;
                 p.out0 = gb + L.proj_w; p.ldo0 = D;
                 p.cpart = next_tnpart();                          // split partials: plain stores, reduced in a fixed order at the end of the call
@@ -870,9 +821,7 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop
                 }
             }
             {   // dattn = gmid Wproj
-                GemmP p = zero_gemm();
-                p.A = gyp; p.lda = D * e; p.W = sb + S.proj_t; p.ldw = D * e;
-                p.M = d.M; p.N = d.D; p.K = d.D;
+                GemmP p = nt(gyp, D * e, sb + S.proj_t, D * e, d.M, d.D, d.D);
                 p.out0 = ws + W.dattn; p.ldo0 = D * e;
                 if (do_max) { p.omax = domax(l); p.omax_rows = d.T; p.omax_hd = d.HD; }
                 MFVIT_TRY(gemm_nt_tile(d.dtype, EPI_NONE, p, st));
@@ -884,7 +833,7 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop
             }
             if (d.p_attn > 0.f)
                 MFVIT_TRY(attn_bwd_tiled_drop(d.dtype, b + W.qkv, b + W.attn, ws + W.dattn, (const float*)(b + W.lse), dqkv, d.B, d.T, d.H, d.HD,
-                                              make_drop(d.p_attn, d.seed, site(l, 2)), st));
+                                              make_drop(d.p_attn, d.seed, c.site(l, 2)), st));
             else
             MFVIT_TRY(attn_bwd(qdt_bwd, b + W.qkv, b + W.attn, ws + W.dattn, (const float*)(b + W.lse), dqkv, nullptr,
                                d.B, d.T, d.H, d.HD, st, do_max ? domax(l) : nullptr));
@@ -892,9 +841,7 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop
             MFVIT_TRY(fork());                                    // dqkv - and with it every input of this block's weight gradients - is ready
             for (int i = 0; i < ndef; ++i) MFVIT_TRY(gemm_tn(d.dtype, def_tn[i], wst));
             if (wg) {   // dWqkv += dqkv^T y1 ; d qkv_b += column sums of dqkv (ones-fragment MFMA inside the wgrad kernel)
-                GemmP p = zero_gemm();
-                p.A = dqkv; p.lda = 3 * D * e; p.W = b + W.y1; p.ldw = D * e;
-                p.M = d.M; p.N = 3 * d.D; p.K = d.D;
+                GemmP p = nt(dqkv, 3 * D * e, b + W.y1, D * e, d.M, 3 * d.D, d.D);
                 p.cs0 = gb + L.qkv_b;
                 p.out0 = gb + L.qkv_w; p.ldo0 = D;
                 p.cpart = next_tnpart();                          // split partials: plain stores, reduced in a fixed order at the end of the call
@@ -915,33 +862,20 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop
             MFVIT_TRY(wait_layer(l + 1));                         // fc2-wgrad of layer l+1 reads the gxT copy written next
             {   // gx = LN1bwd(dqkv Wqkv) + gmid ; d ln1_w, d ln1_b, d fc2_b of block l-1 (or scratch for the embed stage)
                 if (wg && l == 0 && hipMemsetAsync(colscr, 0, 2 * D * sizeof(float), st) != hipSuccess) return MFVIT_ELAUNCH;
-                GemmP p = zero_gemm();
-                p.A = dqkv; p.lda = 3 * D * e; p.W = sb + S.qkv_t; p.ldw = 3 * D * e;
-                p.M = d.M; p.N = d.D; p.K = 3 * d.D;
-                p.aux = xbuf(l); p.ldaux = D;
-                p.mean = stat(l); p.rstd = stat(l) + d.M;
+                GemmP p = nt(dqkv, 3 * D * e, sb + S.qkv_t, 3 * D * e, d.M, d.D, 3 * d.D);
+                p.aux = c.xbuf(l); p.ldaux = D;
+                p.mean = c.stat(l); p.rstd = c.stat(l) + d.M;
                 p.gamma = pb + L.ln1_w;
-                if (lean_grad) { p.res_t = gmidT; p.ldres_t = D * e; p.out0 = l == 0 ? gx : nullptr; }     // (the embedding stage reads gx)
-                else { p.res = gmid; p.ldres = D; p.out0 = gx; }
-                p.ldo0 = D; p.out1 = pp(W.gxT, l - 1); p.ldo1 = D * e;
+                p.kpart = c.kpart();
                 if (wg) { p.cs0 = gb + L.ln1_w; p.cs1 = gb + L.ln1_b; p.cs2 = (l > 0 && !rdrop) ? gblk(l - 1) + L.fc2_b : colscr; p.cpart = next_colpart(); }
-                if (d.unfused) {
-                    GemmP q = zero_gemm();
-                    q.A = p.A; q.lda = p.lda; q.W = p.W; q.ldw = p.ldw; q.M = p.M; q.N = p.N; q.K = p.K;
-                    q.out0 = ws + W.utmp; q.ldo0 = D * e;
-                    MFVIT_TRY(gemm_nt_tile(d.dtype, EPI_NONE, q, st));
-                    MFVIT_TRY(ln_bwd_rows(d.dtype, d.D, nullptr, 0, xbuf(l), D, p.mean, p.rstd, p.gamma, gmid, D, gx, D, pp(W.gxT, l - 1), D * e,
-                                          p.cs0, p.cs1, p.cs2, p.cpart, d.M, 1, 0, st, ws + W.utmp, D * e));
-                } else {
-                    p.kpart = (float*)(ws + W.kpart);
-                    MFVIT_TRY(gemm_nt_row(d.dtype, REPI_LNBWD_RES, p, st));
-                }
+                // (lean_grad keeps the f32 result at block 0 only: the embedding stage reads gx)
+                MFVIT_TRY(dgrad_ln_bwd(c, p, gmid, gmidT, lean_grad && l > 0 ? nullptr : gx, pp(W.gxT, l - 1)));
             }
         } else if (d.tok) {
             MFVIT_TRY(colpart_batch_flush(st));
             // token-input embedding stage: gx = d x_0 = d tokens; d pos_emb = sum over the batch (fuseattention.py:187)
             if (d.p_embd > 0.f)      // d (tokens + pos_emb) = d x_0 * mask / (1 - p)
-                MFVIT_TRY(mask_scale_rows(d.dtype, true, gx, D, gx, D, make_drop(d.p_embd, d.seed, 1), off, 1, d.M, d.D, st));
+                MFVIT_TRY(mask_scale_rows(d.dtype, true, gx, D, gx, D, make_drop(d.p_embd, d.seed, 1), c.off, 1, d.M, d.D, st));
             if (dinput && hipMemcpyAsync(dinput, gx, (size_t)d.M * D * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
                 return MFVIT_ELAUNCH;
             if (d.use_pos) MFVIT_TRY(batch_sum(gx, dparams + L.pos, d.B, (long)d.T * D, st));
@@ -951,7 +885,7 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop
                 // pos_drop: d (cat(cls, patch_embed) + pos_embed) = d x_0 * mask / (1 - p) - the f32 rows (cls, pe_b) and their operand-type copy
                 // (pe_w) - and colscr[0:D] becomes the column sum of the masked rows
                 // (the operand-type copy is cast afresh from the masked f32 rows: no second rounding of the split copy)
-                MFVIT_TRY(mask_scale_rows(d.dtype, true, gx, D, gx, D, make_drop(d.p_embd, d.seed, 1), off, 1, d.M, d.D, st));
+                MFVIT_TRY(mask_scale_rows(d.dtype, true, gx, D, gx, D, make_drop(d.p_embd, d.seed, 1), c.off, 1, d.M, d.D, st));
                 MFVIT_TRY(cast_transpose(d.dtype, gx, pp(W.gxT, -1), nullptr, d.M, d.D, st));
                 if (wg) {
                     if (hipMemsetAsync(colscr, 0, D * sizeof(float), st) != hipSuccess) return MFVIT_ELAUNCH;
@@ -964,10 +898,7 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop
                 // A = the operand-type copy of gx from token row 1 on: B T - 1 rows, the cls rows of images 1 .. B-1 among them (skipped by the epilogue).
                 char* wpeT = ws + W.wpeT;
                 MFVIT_TRY(cast_transpose(d.dtype, params + L.pe_w, nullptr, wpeT, d.D, 768, st));
-                GemmP p = zero_gemm();
-                p.A = (const char*)pp(W.gxT, -1) + (size_t)D * d.es; p.lda = D * e;
-                p.W = wpeT; p.ldw = D * e;
-                p.M = d.M - 1; p.N = 768; p.K = d.D;
+                GemmP p = nt((const char*)pp(W.gxT, -1) + (size_t)D * d.es, D * e, wpeT, D * e, d.M - 1, 768, d.D);
                 p.orow_in = d.np; p.orow_out = d.T;
                 p.out0 = dimg; p.ldo0 = cfg->img_w;
                 MFVIT_TRY(gemm_nt_tile(d.dtype, EPI_COL2IM16, p, st));
@@ -981,9 +912,7 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop
                 MFVIT_TRY(colsum_rows(gx, D, colscr + D, d.B, d.T, 0, d.D, st));
                 MFVIT_TRY(axpy(dparams + L.pe_b, colscr, 1.0f, d.D, st));
                 MFVIT_TRY(axpy(dparams + L.pe_b, colscr + D, -1.0f, d.D, st));
-                GemmP p = zero_gemm();   // d pe_w += gx[patch rows]^T patches
-                p.A = pp(W.gxT, -1); p.lda = D * e; p.W = ws + W.patches; p.ldw = 768 * e;
-                p.M = d.Mp; p.N = d.D; p.K = 768;
+                GemmP p = nt(pp(W.gxT, -1), D * e, ws + W.patches, 768 * e, d.Mp, d.D, 768);   // d pe_w += gx[patch rows]^T patches
                 p.orow_in = d.np; p.orow_out = d.T; p.orow_off = 1;
                 p.out0 = dparams + L.pe_w; p.ldo0 = 768;
                 p.cpart = next_tnpart();
@@ -1067,169 +996,6 @@ int mfvit_gpt_backward(const mfvit_vit_cfg* cfg, const float* params, const void
     ShareScope share(cfg);
     if (!dparams) return MFVIT_EINVAL;
     return encoder_backward(cfg, nullptr, params, shadow, workspace, dout, dparams, dtokens, nullptr, cfg->depth, -1, stream, true);
-}
-
-// ------------------------------------------------------------------------------------------------ single ops
-int mfvit_input_transform(const uint8_t* src, const int64_t* desc, const int32_t* tables, int n, int S, int crop, const float* mean3,
-                          const float* std3, float* out, mfvit_stream_t stream) {
-    if (!src || !desc || !tables || !mean3 || !std3 || !out) return MFVIT_EINVAL;   // mean3 / std3 are HOST pointers (3 floats each)
-    if (crop > S) return MFVIT_EINVAL;
-    return input_transform(src, (const long long*)desc, tables, n, S, crop, crop, mean3, std3, out, (hipStream_t)stream);
-}
-int mfvit_input_transform_rect(const uint8_t* src, const int64_t* desc, const int32_t* tables, int n, int S, int out_h, int out_w,
-                               const float* mean3, const float* std3, float* out, mfvit_stream_t stream) {
-    if (!src || !desc || !tables || !mean3 || !std3 || !out) return MFVIT_EINVAL;
-    return input_transform(src, (const long long*)desc, tables, n, S, out_h, out_w, mean3, std3, out, (hipStream_t)stream);
-}
-size_t mfvit_input_photometric_workspace_bytes(int n, int S) { return input_photometric_workspace_bytes(n, S); }
-int mfvit_input_photometric(const uint8_t* src, const int64_t* desc, const int32_t* tables, const int32_t* photo, int n, int S, int max_radius,
-                            void* workspace, const float* mean3, const float* std3, float* out, mfvit_stream_t stream) {
-    if (!src || !desc || !tables || !photo || !workspace || !mean3 || !std3 || !out) return MFVIT_EINVAL;   // mean3 / std3: HOST pointers
-    return input_photometric(src, (const long long*)desc, tables, photo, n, S, max_radius, workspace, mean3, std3, out, (hipStream_t)stream);
-}
-int mfvit_eval_counts(const float* scores, int64_t ld, const int64_t* labels, int n, int C, uint64_t* confusion, int64_t* preds,
-                      uint64_t* u2, uint64_t* npos, mfvit_stream_t stream) {
-    if (!scores || !labels || (!confusion && !(u2 && npos))) return MFVIT_EINVAL;
-    return eval_counts(scores, ld, labels, n, C, (unsigned long long*)confusion, (unsigned long long*)u2, (unsigned long long*)npos, preds,
-                       (hipStream_t)stream);
-}
-int mfvit_linear_fwd(int dtype, int epilogue, const void* x, int64_t ldx, const void* w, int64_t ldw, const float* bias, void* y,
-                     int64_t ldy, void* y2, int64_t ldy2, int M, int N, int K, mfvit_stream_t stream) {
-    if (!x || !w || (!y && epilogue != EPI_BIAS_GELU)) return MFVIT_EINVAL;      // GELU: y = NULL skips the saved derivative
-    if (epilogue != EPI_BIAS && epilogue != EPI_BIAS_GELU && epilogue != EPI_NONE && epilogue != EPI_BIAS_X3F16) return MFVIT_EINVAL;
-    if (epilogue == EPI_BIAS_GELU && !y2) return MFVIT_EINVAL;
-    GemmP p = zero_gemm();
-    p.A = x; p.lda = ldx; p.W = w; p.ldw = ldw; p.M = M; p.N = N; p.K = K;
-    p.bias = bias; p.out0 = y; p.ldo0 = ldy; p.out1 = y2; p.ldo1 = ldy2;
-    return gemm_nt_tile(dtype, epilogue, p, (hipStream_t)stream);
-}
-int mfvit_linear_dgrad_act(int dtype, const void* dy, int64_t lddy, const void* wt, int64_t ldwt, const void* act_grad, int64_t ldg,
-                           void* dx, int64_t lddx, int M, int N, int K, mfvit_stream_t stream) {
-    if (!dy || !wt || !act_grad || !dx) return MFVIT_EINVAL;
-    GemmP p = zero_gemm();
-    p.A = dy; p.lda = lddy; p.W = wt; p.ldw = ldwt; p.M = M; p.N = N; p.K = K;
-    p.aux = act_grad; p.ldaux = ldg; p.out0 = dx; p.ldo0 = lddx;
-    return gemm_nt_tile(dtype, EPI_GELU_BWD, p, (hipStream_t)stream);
-}
-int mfvit_linear_wgrad(int dtype, const void* dy, int64_t lddy, const void* x, int64_t ldx, float* dw, int64_t lddw, int M, int N, int K,
-                       mfvit_stream_t stream) {
-    if (!dy || !x || !dw) return MFVIT_EINVAL;
-    GemmP p = zero_gemm();
-    p.A = dy; p.lda = lddy; p.W = x; p.ldw = ldx; p.M = M; p.N = N; p.K = K;
-    p.out0 = dw; p.ldo0 = lddw;
-    return gemm_tn(dtype, p, (hipStream_t)stream);
-}
-int mfvit_linear_wgrad_ws(int dtype, const void* dy, int64_t lddy, const void* x, int64_t ldx, float* dw, int64_t lddw, int M, int N,
-                          int K, float* scratch, mfvit_stream_t stream) {
-    if (!dy || !x || !dw) return MFVIT_EINVAL;
-    GemmP p = zero_gemm();
-    p.A = dy; p.lda = lddy; p.W = x; p.ldw = ldx; p.M = M; p.N = N; p.K = K;
-    p.out0 = dw; p.ldo0 = lddw;
-    p.cpart = scratch;
-    return gemm_tn(dtype, p, (hipStream_t)stream);
-}
-int mfvit_linear_wgrad_pair(int dtype, const void* dy_a, int64_t lddy_a, const void* x_a, int64_t ldx_a, float* dw_a, int64_t lddw_a, float* dbias_a,
-                            int Na, const void* dy_b, int64_t lddy_b, const void* x_b, int64_t ldx_b, float* dw_b, int64_t lddw_b, int Nb, int M, int K,
-                            mfvit_stream_t stream) {
-    if (!dy_a || !x_a || !dw_a || !dy_b || !x_b || !dw_b) return MFVIT_EINVAL;
-    GemmP a = zero_gemm(), b = zero_gemm();
-    a.A = dy_a; a.lda = lddy_a; a.W = x_a; a.ldw = ldx_a; a.M = M; a.N = Na; a.K = K; a.out0 = dw_a; a.ldo0 = lddw_a; a.cs0 = dbias_a;
-    b.A = dy_b; b.lda = lddy_b; b.W = x_b; b.ldw = ldx_b; b.M = M; b.N = Nb; b.K = K; b.out0 = dw_b; b.ldo0 = lddw_b;
-    if (!gemm_tn_pair_supported(dtype, a, b)) return MFVIT_ENOSYS;
-    return gemm_tn_glds_pair(dtype, a, b, (hipStream_t)stream);
-}
-int mfvit_linear_res_ln_fwd(int dtype, const void* a, int64_t lda, const void* w, int64_t ldw, const float* bias, const float* res,
-                            int64_t ldres, float* x_out, void* y, int y_f32, const float* gamma, const float* beta, float eps,
-                            float* mean, float* rstd, int M, int K, mfvit_stream_t stream) {
-    return mfvit_linear_res_ln_fwd_ws(dtype, a, lda, w, ldw, bias, res, ldres, x_out, y, y_f32, gamma, beta, eps, mean, rstd, M, K, nullptr, stream);
-}
-int mfvit_linear_res_ln_fwd_ws(int dtype, const void* a, int64_t lda, const void* w, int64_t ldw, const float* bias, const float* res,
-                               int64_t ldres, float* x_out, void* y, int y_f32, const float* gamma, const float* beta, float eps,
-                               float* mean, float* rstd, int M, int K, float* scratch, mfvit_stream_t stream) {
-    if (!a || !w || !y || !gamma || !beta || ((size_t)scratch & 15)) return MFVIT_EINVAL;
-    GemmP p = zero_gemm();
-    p.kpart = scratch;
-    p.A = a; p.lda = lda; p.W = w; p.ldw = ldw; p.M = M; p.N = 384; p.K = K;
-    p.bias = bias; p.res = res; p.ldres = ldres;
-    p.out0 = x_out; p.ldo0 = 384; p.out1 = y; p.ldo1 = (dtype == MFVIT_BF16X3 && !y_f32) ? 768 : 384; p.y_f32 = y_f32;
-    p.gamma = gamma; p.beta = beta; p.eps = eps; p.mean = mean; p.rstd = rstd;
-    return gemm_nt_row(dtype, REPI_RES_LN, p, (hipStream_t)stream);
-}
-int mfvit_linear_dgrad_ln_bwd(int dtype, const void* dy, int64_t lddy, const void* wt, int64_t ldwt, const float* x, const float* mean,
-                              const float* rstd, const float* gamma, const float* dres, float* dx, void* dx_t, float* dgamma,
-                              float* dbeta, float* dcol, int M, int K, mfvit_stream_t stream) {
-    return mfvit_linear_dgrad_ln_bwd_ws(dtype, dy, lddy, wt, ldwt, x, mean, rstd, gamma, dres, dx, dx_t, dgamma, dbeta, dcol, M, K, nullptr, stream);
-}
-int mfvit_linear_dgrad_ln_bwd_ws(int dtype, const void* dy, int64_t lddy, const void* wt, int64_t ldwt, const float* x, const float* mean,
-                                 const float* rstd, const float* gamma, const float* dres, float* dx, void* dx_t, float* dgamma,
-                                 float* dbeta, float* dcol, int M, int K, float* scratch, mfvit_stream_t stream) {
-    if (!dy || !wt || !x || !mean || !rstd || !gamma || !dx || ((size_t)scratch & 15)) return MFVIT_EINVAL;
-    GemmP p = zero_gemm();
-    p.kpart = scratch;
-    p.A = dy; p.lda = lddy; p.W = wt; p.ldw = ldwt; p.M = M; p.N = 384; p.K = K;
-    p.aux = x; p.ldaux = 384; p.mean = (float*)mean; p.rstd = (float*)rstd; p.gamma = gamma;
-    p.res = dres; p.ldres = 384;
-    p.out0 = dx; p.ldo0 = 384; p.out1 = dx_t; p.ldo1 = dtype == MFVIT_BF16X3 ? 768 : 384;
-    p.cs0 = dgamma; p.cs1 = dbeta; p.cs2 = dcol;
-    return gemm_nt_row(dtype, REPI_LNBWD_RES, p, (hipStream_t)stream);
-}
-int mfvit_attention_fwd(int dtype, const void* qkv, void* out, float* lse, int B, int T, int H, int head_dim, mfvit_stream_t stream) {
-    if (!qkv || !out || !lse || B <= 0 || T <= 0 || H <= 0) return MFVIT_EINVAL;
-    return attn_fwd(dtype, qkv, out, lse, B, T, H, head_dim, (hipStream_t)stream);
-}
-int mfvit_attention_qkv_dtype(int dtype, int T, int head_dim) { return attn_qkv_dtype(dtype, T, head_dim); }
-int mfvit_attention_bwd(int dtype, const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* dbias_qkv,
-                        int B, int T, int H, int head_dim, mfvit_stream_t stream) {
-    if (!qkv || !out || !dout || !lse || !dqkv || B <= 0 || T <= 0 || H <= 0) return MFVIT_EINVAL;
-    return attn_bwd(dtype, qkv, out, dout, lse, dqkv, dbias_qkv, B, T, H, head_dim, (hipStream_t)stream);
-}
-int mfvit_attention_drop_fwd(int dtype, const void* qkv, void* out, float* lse, int B, int T, int H, int head_dim, float p, uint64_t seed,
-                             uint32_t site, mfvit_stream_t stream) {
-    if (!qkv || !out || !lse || B <= 0 || T <= 0 || H <= 0 || !(p >= 0.f && p < 1.f)) return MFVIT_EINVAL;
-    if (!attn_tiled_supported(dtype, T, head_dim)) return MFVIT_ENOSYS;
-    return attn_fwd_tiled_drop(dtype, qkv, out, lse, B, T, H, head_dim, make_drop(p, seed, site), (hipStream_t)stream);
-}
-int mfvit_attention_drop_bwd(int dtype, const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int B, int T, int H,
-                             int head_dim, float p, uint64_t seed, uint32_t site, mfvit_stream_t stream) {
-    if (!qkv || !out || !dout || !lse || !dqkv || B <= 0 || T <= 0 || H <= 0 || !(p >= 0.f && p < 1.f)) return MFVIT_EINVAL;
-    if (!attn_tiled_supported(dtype, T, head_dim)) return MFVIT_ENOSYS;
-    return attn_bwd_tiled_drop(dtype, qkv, out, dout, lse, dqkv, B, T, H, head_dim, make_drop(p, seed, site), (hipStream_t)stream);
-}
-int mfvit_dropout_mask(float p, uint64_t seed, uint32_t site, int64_t n, uint8_t* keep, mfvit_stream_t stream) {
-    if (!keep || !(p >= 0.f && p < 1.f)) return MFVIT_EINVAL;
-    return dropout_mask(make_drop(p, seed, site), n, keep, (hipStream_t)stream);
-}
-int mfvit_layernorm_fwd(int dtype, const float* x, void* y, int y_f32, const float* gamma, const float* beta, float eps, float* mean,
-                        float* rstd, int rows, int N, mfvit_stream_t stream) {
-    if (!x || !y || !gamma || !beta) return MFVIT_EINVAL;
-    return ln_rows(dtype, N, x, N, nullptr, 0, 0, nullptr, 0, y, (dtype == MFVIT_BF16X3 && !y_f32) ? 2 * N : N, y_f32, gamma, beta, eps, mean, rstd, rows, 1, 0,
-                   0, (hipStream_t)stream);
-}
-int mfvit_layernorm_bwd(int dtype, const float* dy, const float* x, const float* mean, const float* rstd, const float* gamma,
-                        const float* dres, float* dx, void* dx_t, float* dgamma, float* dbeta, float* dcol, int rows, int N,
-                        mfvit_stream_t stream) {
-    if (!dy || !x || !mean || !rstd || !gamma) return MFVIT_EINVAL;
-    return ln_bwd_rows(dtype, N, dy, N, x, N, mean, rstd, gamma, dres, N, dx, N, dx_t, dtype == MFVIT_BF16X3 ? 2 * N : N, dgamma, dbeta, dcol, nullptr, rows, 1, 0,
-                       (hipStream_t)stream);
-}
-int mfvit_cast_transpose(int dtype, const float* src, void* dst, void* dst_t, int R, int C, mfvit_stream_t stream) {
-    if (!src || R <= 0 || C <= 0) return MFVIT_EINVAL;
-    return cast_transpose(dtype, src, dst, dst_t, R, C, (hipStream_t)stream);
-}
-int mfvit_head_fwd(const float* x, int64_t ldx, const float* w, const float* b, float* y, int64_t ldy, int M, int N, int K, int accumulate,
-                   mfvit_stream_t stream) {
-    if (!x || !w || !y) return MFVIT_EINVAL;
-    return linear_small_fwd(x, ldx, w, b, y, ldy, M, N, K, accumulate, (hipStream_t)stream);
-}
-int mfvit_head_bwd(const float* dy, int64_t lddy, const float* x, int64_t ldx, const float* w, float* dx, int64_t lddx, int dx_accumulate,
-                   float* dw, float* db, int M, int N, int K, mfvit_stream_t stream) {
-    if (!dy || !x || !w) return MFVIT_EINVAL;
-    return linear_small_bwd(dy, lddy, x, ldx, w, dx, lddx, dx_accumulate, dw, db, M, N, K, (hipStream_t)stream);
-}
-int mfvit_cross_entropy(const float* logits, const int64_t* target, float* loss_mean, float* dlogits, int64_t* preds, int B, int C,
-                        mfvit_stream_t stream) {
-    if (!logits || !target || !loss_mean) return MFVIT_EINVAL;
-    return ce_small(logits, (const long*)target, loss_mean, dlogits, (long*)preds, B, C, (hipStream_t)stream);
 }
 
 }  // extern "C"

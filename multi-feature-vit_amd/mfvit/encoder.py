@@ -520,15 +520,9 @@ class VisionTransformerMoCo(nn.Module):
         hook = on_stage_done or getattr(self, "_grad_stage_hook", None)
 
         def bwd(hi, lo):
-            if dimg is not None and lo == -1:     # (the call that runs the embedding stage also writes the image gradient)
-                check(lib().mfvit_vit_backward_ex(cfg, drop, ptr(self._arena), ptr(self._shadow), ptr(ws), ptr(dfeats), ptr(gflat), ptr(dimg),
-                                                  hi, lo, stream()), "mfvit_vit_backward_ex")
-            elif drop is None:
-                check(lib().mfvit_vit_backward(cfg, ptr(self._arena), ptr(self._shadow), ptr(ws), ptr(dfeats), ptr(gflat), hi, lo, stream()),
-                      "mfvit_vit_backward")
-            else:
-                check(lib().mfvit_vit_backward_drop(cfg, drop, ptr(self._arena), ptr(self._shadow), ptr(ws), ptr(dfeats), ptr(gflat), hi, lo,
-                                                    stream()), "mfvit_vit_backward_drop")
+            # (drop = NULL, dimg = NULL: exactly mfvit_vit_backward; the call that runs the embedding stage also writes the image gradient)
+            check(lib().mfvit_vit_backward_ex(cfg, drop, ptr(self._arena), ptr(self._shadow), ptr(ws), ptr(dfeats), ptr(gflat),
+                                              ptr(dimg) if lo == -1 else None, hi, lo, stream()), "mfvit_vit_backward_ex")
         if hook is None:
             bwd(self.depth, -1)
         else:
