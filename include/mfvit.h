@@ -463,6 +463,53 @@ int mfvit_fusion_ex_backward(const mfvit_fusion_cfg* cfg, int cross_attn_depth, 
                              const float* dx_cxr, const float* dx_enh, float* dparams, float* df_cxr, float* df_enh, float* dhw_cxr,
                              float* dhb_cxr, float* dhw_enh, float* dhb_enh, mfvit_stream_t stream);
 
+/* Attention maps of the exchange (additive in ABI 5).  In exchange layer `layer` (0 .. cross_attn_depth - 1) the cls token of one stream is the
+ * only query; its keys are row j = 0: its own pre-normed cls token, rows j = 1 .. T-1: the OTHER stream's pre-normed patch tokens of the layer's
+ * input, row by row.  Direction d = 0 is the CXR cls query (block [0], reads ENH patches), d = 1 the ENH cls query (block [2], reads CXR patches);
+ * heads in the order of the rows of wq / wk / wv.
+ *
+ * mfvit_fusion_ex_attention, after a mfvit_fusion_ex_forward (or mfvit_fusion_forward: depth 1, pool_mean 0) with the same cfg / depth / pool on
+ * `workspace`: the softmax probabilities a^d_h[j] exactly as that forward normalised them (one copy kernel, nothing is recomputed).
+ *   fuse  0: out [2][B][heads][T] (every row sums to 1);  1 / 2 / 3: mean / max / min over ALL heads, out [2][B][T].  max / min are not
+ *         renormalised: a max-fused row sums to more than 1, a min-fused row to less.
+ *
+ * mfvit_fusion_ex_grad_attention, after a mfvit_fusion_ex_backward (or mfvit_fusion_backward) on that workspace, with the params / f_cxr / f_enh
+ * of the forward: the gradient-weighted map of the score y the backward differentiated (dfused, dx_* = d y / d outputs),
+ *   da^d_h[j] = d y / d a^d_h[j] = z_j . du^d_h,    abar[d][b][j] = (1 / heads) sum_h max(0, a^d_h[j] da^d_h[j]),    abar [2][B][T],
+ * z_j the pre-normed key row (re-derived from the layer's input rows and the row statistics of the forward), du = d y / d u_h as the backward left
+ * it; the heads are summed in head order (in one workgroup per (sample, direction), also across the chunks of 3 heads the exchange runs in).
+ * What it reads of the workspace - the probabilities, the row statistics and du - is written by the forward, or by the backward's du GEMM, and by
+ * nothing after: mfvit_fusion_ex_backward leaves all three intact, and both calls may be repeated.  Neither call writes the workspace.
+ * No atomics: repeated calls return the same bits.
+ * MFVIT_EINVAL (before any HIP call): a NULL pointer, layer outside 0 .. cross_attn_depth - 1, fuse outside 0 - 3, T > 8192, and the checks of
+ * mfvit_fusion_ex_forward.  With no such call the other entry points run exactly the launches they ran before. */
+int mfvit_fusion_ex_attention(const mfvit_fusion_cfg* cfg, int cross_attn_depth, int pool_mean, const void* workspace, int layer, int fuse,
+                              float* out, mfvit_stream_t stream);
+int mfvit_fusion_ex_grad_attention(const mfvit_fusion_cfg* cfg, int cross_attn_depth, int pool_mean, const float* params, const float* f_cxr,
+                                   const float* f_enh, const void* workspace, int layer, float* abar, mfvit_stream_t stream);
+
+/* Cross-stream relevance of a two-stream model with ONE exchange layer and cls pooling (additive in ABI 5; Chefer, Gur & Wolf 2021, the
+ * self-attention rule inside each encoder, the co-attention rule across the exchange), all for the same score y.  Per image and stream s in
+ * {c (cxr), e (enh)}, with A^s_l the encoder's relevance maps (mfvit_vit_backward_rel, every block: maps_s [depth_s][B][T][T]) and abar as above:
+ *   R_s = (I + A^s_{L-1}) ... (I + A^s_0),  r_s = R_s[0, :],  n_s = R_s 1 - 1,
+ *   Rbar_s[j, :] = (R_s[j, :] - e_j) / n_s[j] + e_j   (e_j where n_s[j] <= 0),
+ *   direction 0:  w = (0, abar[0][1:]),  what[j] = w[j] / n_e[j]  (0 where n_e[j] <= 0),
+ *     rel_cc = (1 + abar[0][0]) r_c[1:]                             cxr cls -> cxr patches
+ *     rel_ce = Rbar_c[0,0] (what R_e - what + w)[1:]                cxr cls -> enh patches (= Rbar_c[0,0] w Rbar_e)
+ *   direction 1, symmetric: rel_ee, rel_ec.
+ *   out4 [4][B][T-1] = rel_cc | rel_ce | rel_ec | rel_ee  (patch order; not normalised).  The CXR image's total is rel_cc + rel_ec, the ENH
+ *   image's rel_ee + rel_ce.
+ * One workgroup per (image, stream), its vectors in LDS (T <= 8192): n_s as a column chain over blocks 0 .. L-1, then r_s and what R_s as two
+ * row chains over blocks L-1 .. 0 in one read of the maps; a second, elementwise launch applies the other stream's Rbar[0,0].  Every vector is
+ * carried as its difference from the chain's start, so n_s and r_s[0] - 1 are sums of non-negative terms.  The maps are read twice
+ * (8 (depth_c + depth_e) B T^2 bytes of traffic).
+ *   scratch  mfvit_bimodal_relevance_scratch_bytes(B, T) bytes (the two streams' Rbar[0,0], [2][B])
+ * No atomics: repeated calls return the same bits.  MFVIT_EINVAL (before any HIP call), and 0 bytes of scratch, for B <= 0, T < 2, T > 8192;
+ * mfvit_bimodal_relevance also for a depth <= 0 or a NULL pointer. */
+size_t mfvit_bimodal_relevance_scratch_bytes(int B, int T);
+int mfvit_bimodal_relevance(int B, int T, int depth_c, int depth_e, const float* maps_c, const float* maps_e, const float* abar, float* out4,
+                            void* scratch, mfvit_stream_t stream);
+
 /* Stand-alone PreNorm(CrossAttention) (MOD:15-21,108-137): out[b] = proj(attn(LN_1e-5([x_own[b,0] ; x_oth[b,1:]]))) -> (B, dim).
  * params = one block [norm.weight, norm.bias, fn.wq.weight, fn.wk.weight, fn.wv.weight, fn.proj.weight, fn.proj.bias]
  * (4 D^2 + 3 D floats).  x_own == x_oth reproduces PreNorm(dim, CrossAttention(...))(x) exactly.  cfg: batch, tokens, dim,

@@ -827,6 +827,80 @@ __global__ __launch_bounds__(XW * 64) void x_rows_bwd_kernel(const float* __rest
     }
 }
 
+// ------------------------------------------------------------------ exchange maps (mfvit_fusion_ex_attention / _grad_attention)
+// The exchange's softmax probabilities as x_stream_fwd left them in FusWs::a [2][B][nh][T]: per head (fuse 0, out [2][B][nh][T]) or fused over
+// ALL nh heads in head order (1 mean | 2 max | 3 min, out [2][B][T]).  One thread per output element.
+__global__ __launch_bounds__(256) void x_attn_map_kernel(const float* __restrict__ a, int nh, int T, long n, int fuse, float* __restrict__ out) {
+    const long i = blockIdx.x * 256L + threadIdx.x;
+    if (i >= n) return;
+    if (fuse == 0) { out[i] = a[i]; return; }
+    const long sb = i / T;
+    const int t = (int)(i - sb * T);
+    const float* p = a + sb * nh * T + t;
+    float f = p[0];
+    for (int h = 1; h < nh; ++h) {
+        const float v = p[(long)h * T];
+        f = fuse == 1 ? f + v : fuse == 2 ? fmaxf(f, v) : fminf(f, v);
+    }
+    out[i] = fuse == 1 ? f / (float)nh : f;
+}
+
+// Gradient-weighted exchange map after the backward: da_h[t] = z_t . du_h (the first phase of x_stream_bwd_kernel), then
+//   Abar[dir][b][t] = (1 / nh) sum_h max(0, a_h[t] da_h[t]),  the heads summed in head order.
+// One workgroup per (sample, direction), a wave per row; more than NH = 3 heads: the chunks of 3 run one after the other INSIDE the workgroup (the
+// mean crosses them), every chunk re-deriving z_t from the row and its statistics (the rows come from L2 after the first chunk).
+// LDS: st[2][T] | acc[T]; row t of acc is only ever touched by the wave that owns the row.
+template <int XW, int D>
+__global__ __launch_bounds__(XW * 64) void x_grad_map_kernel(const float* __restrict__ fc, const float* __restrict__ fe,
+                                                         const float* __restrict__ params, FusLayout L, int B, int T, int nh,
+                                                         const float* __restrict__ a_in, const float* __restrict__ st_in,
+                                                         const float* __restrict__ du, float* __restrict__ abar) {
+    constexpr int NPL = D / 64;
+    extern __shared__ __attribute__((aligned(16))) float xs[];
+    float* st = xs;
+    float* acc = st + 2 * T;
+    const int b = blockIdx.x, dir = blockIdx.y, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const long sb = (long)dir * B + b;
+    const float* own = (dir == 0 ? fc : fe) + (long)b * T * D;
+    const float* oth = (dir == 0 ? fe : fc) + (long)b * T * D;
+    float g[NPL], be[NPL];
+#pragma unroll
+    for (int i = 0; i < NPL; ++i) {
+        g[i] = L.no_norm ? 1.f : params[L.ca[dir] + L.n_w + lane + 64 * i];
+        be[i] = L.no_norm ? 0.f : params[L.ca[dir] + L.n_b + lane + 64 * i];
+    }
+    for (int q = threadIdx.x; q < 2 * T; q += XW * 64) st[q] = st_in[sb * 2 * T + q];
+    __syncthreads();
+    for (int h0 = 0; h0 < nh; h0 += NH) {
+        float duv[NH][NPL];
+#pragma unroll
+        for (int h = 0; h < NH; ++h)
+#pragma unroll
+            for (int i = 0; i < NPL; ++i) duv[h][i] = du[(sb * nh + h0 + h) * D + lane + 64 * i];
+        for (int t = w; t < T; t += XW) {
+            const float* row = t == 0 ? own : oth + (long)t * D;
+            const float mu = st[t], rs = st[T + t];
+            float d0 = 0.f, d1 = 0.f, d2 = 0.f;
+#pragma unroll
+            for (int i = 0; i < NPL; ++i) {
+                const float z = (row[lane + 64 * i] - mu) * rs * g[i] + be[i];
+                d0 = fmaf(z, duv[0][i], d0); d1 = fmaf(z, duv[1][i], d1); d2 = fmaf(z, duv[2][i], d2);
+            }
+            d0 = wave_sum(d0); d1 = wave_sum(d1); d2 = wave_sum(d2);
+            if (lane == 0) {
+                const float* ap = a_in + (sb * nh + h0) * T + t;
+                float s = h0 == 0 ? 0.f : acc[t];
+                s += fmaxf(0.f, ap[0] * d0);
+                s += fmaxf(0.f, ap[T] * d1);
+                s += fmaxf(0.f, ap[2 * T] * d2);
+                acc[t] = s;
+            }
+        }
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < T; t += XW * 64) abar[sb * T + t] = acc[t] / (float)nh;
+}
+
 GemmP zg() { GemmP p; memset(&p, 0, sizeof(p)); return p; }
 
 // waves per workgroup of the streaming passes: the same bytes in flight per CU at both widths (a D = 768 row is twice a D = 384 row; the
@@ -1226,6 +1300,69 @@ int mfvit_fusion_ex_backward(const mfvit_fusion_cfg* cfg, int cross_attn_depth, 
     return FUS_BY_DIM(cfg->dim, fusion_full_backward)(cfg, cross_attn_depth, pool_mean, params, f_cxr, f_enh, hw_cxr, hw_enh, (float*)workspace,
                                                       dfused, dx_cxr, dx_enh, dparams, df_cxr, df_enh, dhw_cxr, dhb_cxr, dhw_enh, dhb_enh,
                                                       (hipStream_t)stream);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ exchange maps
+constexpr int MAX_MAP_TOKENS = 8192;   // as the rollout / relevance chains (include/mfvit.h)
+
+// the FusWs of exchange layer `layer` inside the workspace of a (cross_attn_depth, pool_mean) model: the workspace itself on the one-layer
+// cls path, the layer's slab on the full-row path
+static const float* fus_layer_ws(const mfvit_fusion_cfg* cfg, int depth, int pool_mean, const void* workspace, int layer) {
+    const float* ws = (const float*)workspace;
+    if (!fus_full(depth, pool_mean)) return ws;
+    return ws + layer * fus_ex_ws(cfg->batch, cfg->tokens, cfg->num_classes, cfg->dim, cfg->heads, depth).slab;
+}
+
+template <int D>
+static int fusion_grad_map(const mfvit_fusion_cfg* cfg, int depth, int pool_mean, const float* params, const float* f_cxr, const float* f_enh,
+                           const float* ws, int layer, float* abar, hipStream_t st) {
+    const int B = cfg->batch, T = cfg->tokens, C = cfg->num_classes, nh = cfg->heads;
+    const FusWs W = fus_ws(B, T, C, D, nh);
+    const float* wl = fus_layer_ws(cfg, depth, pool_mean, ws, layer);
+    const FusLayout L = fus_full(depth, pool_mean) ? fus_layer_layout(D, C, depth, layer) : fus_layout(D, C);
+    // the layer's input rows, as fusion_full_forward / _backward take them: the features, or the rows of the layer below
+    const float* xc = layer == 0 ? f_cxr : fus_layer_ws(cfg, depth, pool_mean, ws, layer - 1) + fus_ex_ws(B, T, C, D, nh, depth).Y;
+    const float* xe = layer == 0 ? f_enh : xc + (long)B * T * D;
+    // What this reads of the workspace and who wrote it last: a, st - x_stream_fwd (the forward; the backward only reads them); du - the
+    // "du_h = do_h Wv_h" GEMM of xattn_core_backward, which nothing after it writes (x_stream_bwd / x_stream_dz read it; dkq, dz0p, dqv, dz0q, pd,
+    // ds and the full-row path's dx / pr / pbp are regions of their own in fus_ws / fus_ex_ws).
+    const size_t lds = (size_t)3 * T * 4;
+    static PerDeviceOnce attr;
+    max_lds((x_grad_map_kernel<XW_BWD, D>), attr);
+    ProfScope ps(PROF_OTHER, 2.0 * 2 * B * (double)T * D * nh, 2.0 * B * T * D * 4 * (nh / NH), st);
+    MFVIT_LAUNCH((x_grad_map_kernel<XW_BWD, D>), dim3(B, 2), dim3(XW_BWD * 64), lds, st, xc, xe, params, L, B, T, nh, wl + W.a, wl + W.st,
+                 wl + W.du, abar);
+    MFVIT_CHECK_LAUNCH();
+    return MFVIT_OK;
+}
+
+extern "C" {
+
+int mfvit_fusion_ex_attention(const mfvit_fusion_cfg* cfg, int cross_attn_depth, int pool_mean, const void* workspace, int layer, int fuse,
+                              float* out, mfvit_stream_t stream) {
+    if (!fus_ex_ok(cfg, cross_attn_depth, pool_mean) || !workspace || !out || layer < 0 || layer >= cross_attn_depth || fuse < 0 || fuse > 3 ||
+        cfg->tokens > MAX_MAP_TOKENS)
+        return MFVIT_EINVAL;
+    const int B = cfg->batch, T = cfg->tokens, nh = cfg->heads;
+    const FusWs W = fus_ws(B, T, cfg->num_classes, cfg->dim, nh);
+    const float* wl = fus_layer_ws(cfg, cross_attn_depth, pool_mean, workspace, layer);
+    const long n = 2L * B * (fuse ? 1 : nh) * T;
+    hipStream_t st = (hipStream_t)stream;
+    ProfScope ps(PROF_OTHER, 0, (2.0 * B * nh * T + (double)n) * 4, st);
+    MFVIT_LAUNCH(x_attn_map_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, wl + W.a, nh, T, n, fuse, out);
+    MFVIT_CHECK_LAUNCH();
+    return MFVIT_OK;
+}
+
+int mfvit_fusion_ex_grad_attention(const mfvit_fusion_cfg* cfg, int cross_attn_depth, int pool_mean, const float* params, const float* f_cxr,
+                                   const float* f_enh, const void* workspace, int layer, float* abar, mfvit_stream_t stream) {
+    if (!fus_ex_ok(cfg, cross_attn_depth, pool_mean) || !params || !f_cxr || !f_enh || !workspace || !abar || layer < 0 ||
+        layer >= cross_attn_depth || cfg->tokens > MAX_MAP_TOKENS)
+        return MFVIT_EINVAL;
+    return FUS_BY_DIM(cfg->dim, fusion_grad_map)(cfg, cross_attn_depth, pool_mean, params, f_cxr, f_enh, (const float*)workspace, layer, abar,
+                                                 (hipStream_t)stream);
 }
 
 }  // extern "C"

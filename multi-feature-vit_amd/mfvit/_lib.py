@@ -108,6 +108,10 @@ SIGNATURES = {
     "mfvit_fusion_ex_workspace_bytes": (c_size_t, [POINTER(FusionCfg), I, I]),
     "mfvit_fusion_ex_forward": (I, [POINTER(FusionCfg), I, I, P, P, P, P, P, P, P, P, P, P, P, P]),
     "mfvit_fusion_ex_backward": (I, [POINTER(FusionCfg), I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "mfvit_fusion_ex_attention": (I, [POINTER(FusionCfg), I, I, P, I, I, P, P]),
+    "mfvit_fusion_ex_grad_attention": (I, [POINTER(FusionCfg), I, I, P, P, P, P, I, P, P]),
+    "mfvit_bimodal_relevance_scratch_bytes": (c_size_t, [I, I]),
+    "mfvit_bimodal_relevance": (I, [I, I, I, I, P, P, P, P, P, P]),
     "mfvit_bn_stats": (I, [I, P, I, I, P, P, P]),
     "mfvit_bn_combine": (I, [P, P, P, I, I, F, F, P, P, P, P, P]),
     "mfvit_bn_apply": (I, [I, P, P, P, P, P, I, P, I, I, P]),

@@ -124,3 +124,86 @@ class FusionFn(torch.autograd.Function):
                                              ptr(dhw_e), ptr(dhb_e), stream()), "mfvit_fusion_ex_backward")
         ctx.ws = None
         return (None, df_c, df_e, dhw_c, dhb_c, dhw_e, dhb_e) + tuple(spec.grad_views(gflat, off))
+
+
+class ExchangeRun:
+    """One mfvit_fusion_ex_forward called directly (no autograd node, so FusionFn runs what it always ran) whose workspace stays alive for the
+    exchange-map calls of include/mfvit.h: attention() after the forward, grad_attention() after backward().  heads: the backbones' plain
+    classifier heads (hw_c, hb_c, hw_e, hb_e) or None, as FusionFn takes them."""
+
+    def __init__(self, spec, f_cxr, f_enh, heads=None):
+        _lib.require_cuda(f_cxr, f_enh)
+        B, T, D = f_cxr.shape
+        if D != spec.dim:
+            raise _lib.MfvitError(f"fusion built for dim {spec.dim}, features have {D}")
+        self.spec = spec
+        self.flat, _ = spec.tail(spec.arena.ensure())
+        L = spec.depth
+        C = (self.flat.numel() - L * (8 * D * D + 10 * D)) // (2 * (D + 1))
+        self.cfg = cfg = fusion_cfg(B, T, C, D, spec.heads)
+        if lib().mfvit_fusion_ex_param_count(cfg, L, spec.pool_mean) != self.flat.numel():
+            raise _lib.MfvitError("fusion parameter arena does not match the C ABI layout")
+        self.f_cxr, self.f_enh = f_cxr.detach().contiguous().float(), f_enh.detach().contiguous().float()
+        dev = self.f_cxr.device
+        self.ws = torch.empty(lib().mfvit_fusion_ex_workspace_bytes(cfg, L, spec.pool_mean), device=dev, dtype=torch.uint8)
+        self.fused = torch.empty(B, C, device=dev, dtype=torch.float32)
+        self.heads = heads
+        self.x_c = torch.empty_like(self.fused) if heads is not None else None
+        self.x_e = torch.empty_like(self.fused) if heads is not None else None
+        hw_c, hb_c, hw_e, hb_e = heads if heads is not None else (None,) * 4
+        check(lib().mfvit_fusion_ex_forward(cfg, L, spec.pool_mean, ptr(self.flat), ptr(self.f_cxr), ptr(self.f_enh), ptr(hw_c), ptr(hb_c),
+                                            ptr(hw_e), ptr(hb_e), ptr(self.ws), ptr(self.fused), ptr(self.x_c), ptr(self.x_e), stream()),
+              "mfvit_fusion_ex_forward")
+
+    def attention(self, layer, fuse):
+        """(2, B, heads, T), or (2, B, T) fused over the heads (fuse 1 mean | 2 max | 3 min): the softmax probabilities of exchange layer `layer`."""
+        cfg = self.cfg
+        shape = (2, cfg.batch, cfg.tokens) if fuse else (2, cfg.batch, cfg.heads, cfg.tokens)
+        out = torch.empty(shape, device=self.ws.device, dtype=torch.float32)
+        check(lib().mfvit_fusion_ex_attention(cfg, self.spec.depth, self.spec.pool_mean, ptr(self.ws), layer, fuse, ptr(out), stream()),
+              "mfvit_fusion_ex_attention")
+        return out
+
+    def backward(self, dfused, dx_c=None, dx_e=None, need_df=False):
+        """mfvit_fusion_ex_backward of (dfused, dx_c, dx_e) into a scratch parameter-gradient buffer that is dropped (the C ABI accumulates into
+        one; no p.grad, no view of it leaves this call).  Returns (d / d f_cxr, d / d f_enh), or (None, None) without need_df."""
+        spec, cfg = self.spec, self.cfg
+        gflat = torch.zeros_like(self.flat)
+        df_c = torch.empty_like(self.f_cxr) if need_df else None
+        df_e = torch.empty_like(self.f_enh) if need_df else None
+        have = self.heads is not None and dx_c is not None and dx_e is not None
+        hw_c, _, hw_e, _ = self.heads if have else (None,) * 4
+        dfused = dfused.contiguous().float()
+        dx_c = dx_c.contiguous().float() if have else None
+        dx_e = dx_e.contiguous().float() if have else None
+        check(lib().mfvit_fusion_ex_backward(cfg, spec.depth, spec.pool_mean, ptr(self.flat), ptr(self.f_cxr), ptr(self.f_enh), ptr(hw_c),
+                                             ptr(hw_e), ptr(self.ws), ptr(dfused), ptr(dx_c), ptr(dx_e), ptr(gflat), ptr(df_c), ptr(df_e),
+                                             None, None, None, None, stream()), "mfvit_fusion_ex_backward")
+        return df_c, df_e
+
+    def grad_attention(self, layer):
+        """(2, B, T): abar of exchange layer `layer` for the score the last backward() differentiated."""
+        cfg = self.cfg
+        abar = torch.empty(2, cfg.batch, cfg.tokens, device=self.ws.device, dtype=torch.float32)
+        check(lib().mfvit_fusion_ex_grad_attention(cfg, self.spec.depth, self.spec.pool_mean, ptr(self.flat), ptr(self.f_cxr), ptr(self.f_enh),
+                                                   ptr(self.ws), layer, ptr(abar), stream()), "mfvit_fusion_ex_grad_attention")
+        return abar
+
+
+def bimodal_relevance(maps_c, maps_e, abar):
+    """mfvit_bimodal_relevance: maps_s (L_s, B, T, T) contiguous f32 relevance maps of each encoder, abar (2, B, T) -> (4, B, T-1) =
+    rel_cc | rel_ce | rel_ec | rel_ee."""
+    _lib.require_cuda(maps_c, maps_e, abar)
+    Lc, B, T, _ = maps_c.shape
+    Le = maps_e.shape[0]
+    if tuple(maps_c.shape[1:]) != (B, T, T) or tuple(maps_e.shape[1:]) != (B, T, T) or tuple(abar.shape) != (2, B, T):
+        raise _lib.MfvitError(f"bimodal relevance: maps {tuple(maps_c.shape)} / {tuple(maps_e.shape)} and abar {tuple(abar.shape)} do not agree")
+    maps_c, maps_e, abar = maps_c.contiguous().float(), maps_e.contiguous().float(), abar.contiguous().float()
+    nbytes = lib().mfvit_bimodal_relevance_scratch_bytes(B, T)
+    if nbytes == 0:
+        raise _lib.MfvitError(f"bimodal relevance is built for 2 .. 8192 tokens, got {T}")
+    scratch = torch.empty(nbytes, device=abar.device, dtype=torch.uint8)
+    out = torch.empty(4, B, T - 1, device=abar.device, dtype=torch.float32)
+    check(lib().mfvit_bimodal_relevance(B, T, Lc, Le, ptr(maps_c), ptr(maps_e), ptr(abar), ptr(out), ptr(scratch), stream()),
+          "mfvit_bimodal_relevance")
+    return out

@@ -22,7 +22,7 @@ import torch.nn as nn
 from mfvit import _lib
 from mfvit.arena import ParamArena
 from mfvit.encoder import check_target, eval_modules, resolve_target
-from mfvit.fusion import MAX_CROSS_ATTN_DEPTH, FusionFn, FusionSpec, check_fusion_shape
+from mfvit.fusion import MAX_CROSS_ATTN_DEPTH, ExchangeRun, FusionFn, FusionSpec, bimodal_relevance, check_fusion_shape
 from model.module import Attention, CrossAttention, FeedForward, PreNorm  # noqa: F401  (same import list as FUS:6)
 
 
@@ -154,7 +154,7 @@ class Fus_CrossViT(nn.Module):
         patches, (B, gh, gw) each, for the score the reference predicts from, y_t = (fused + x_cxr + x_enh)[t] (MAIN_CA:868-870); target: None
         (the argmax per image), an int or a (B,) integer tensor.  Each encoder runs an evaluation forward with saved activations; the fusion and
         the single-stream heads (in eval mode) run on leaf copies of the two feature tensors, and d y_t / d features of each stream feeds that
-        encoder's relevance backward.  The exchange's own cross-attention is not part of the chain.  No p.grad is set.  The two encoders run one
+        encoder's relevance backward.  The exchange's own cross-attention is not part of the chain (cross_relevance is the form that has it).  No p.grad is set.  The two encoders run one
         after the other on the caller's stream, whatever _two_streams says.  vit_cxr / vit_enh must be the encoders this model was built with
         (forward takes the features from those): ValueError otherwise."""
         for vit, bound, name in ((vit_cxr, self.vit_features_cxr, "vit_cxr"), (vit_enh, self.vit_features_enh, "vit_enh")):
@@ -187,3 +187,130 @@ class Fus_CrossViT(nn.Module):
             vit_cxr._release_ws(ws_c)
         return (r_c.view(B, vit_cxr.img_size[0] // 16, vit_cxr.img_size[1] // 16),
                 r_e.view(B, vit_enh.img_size[0] // 16, vit_enh.img_size[1] // 16))
+
+    # ------------------------------------------------------------------ the exchange's own maps (include/mfvit.h, mfvit_fusion_ex_attention ..)
+    # Key row 0 of an exchange map is the query's own cls token, rows 1 .. T-1 the OTHER stream's patch tokens, row by row; "cxr" is the direction
+    # whose query is the CXR cls token.  All three calls run evaluation forwards of the encoders (no dropout site, no seed), call the fusion
+    # library directly on a workspace of their own (forward() and its autograd node run what they always ran), set no p.grad, allocate no
+    # gradient arena and leave the training flags, the RNG states and the encoders' feature caches as they were.
+    def _check_pair(self, vit_cxr, vit_enh, img_cxr, img_enh):
+        for vit, bound, name in ((vit_cxr, self.vit_features_cxr, "vit_cxr"), (vit_enh, self.vit_features_enh, "vit_enh")):
+            if getattr(vit, "features3D", None) != bound:
+                raise ValueError(f"{name} is not the encoder this Fus_CrossViT was built with: its maps would not be the predicting model's")
+        B = int(img_cxr.shape[0])
+        if img_enh is None or int(img_enh.shape[0]) != B:
+            raise ValueError("img_cxr and img_enh must hold the same number of images")
+        return B
+
+    def _check_one_layer_cls(self, what):
+        if self._spec.depth != 1 or self._spec.pool_mean:
+            raise NotImplementedError(f"{what} is defined for cross_attn_depth == 1 and pool == 'cls' (got depth {self._spec.depth}, "
+                                      f"pool {self.pool!r}); get_exchange_attention works at any depth and pooling")
+
+    @staticmethod
+    def _eval_features(vit, img):
+        """features3D of an evaluation forward without saved activations, the feature cache left alone."""
+        img = vit._prep_img(img.detach())
+        with torch.no_grad():
+            cfg = vit._cfg(img, False)
+            cache = vit._feat_cache
+            vit._ensure_shadow(cfg)
+            vit._feat_cache = cache
+            ws = vit._get_ws(cfg)
+            feats = torch.empty(img.shape[0], vit.num_tokens, vit.embed_dim, device=img.device, dtype=torch.float32)
+            try:
+                _lib.check(_lib.lib().mfvit_vit_forward(cfg, _lib.ptr(vit._arena), _lib.ptr(vit._shadow), _lib.ptr(img), _lib.ptr(ws),
+                                                        _lib.ptr(feats), _lib.stream()), "mfvit_vit_forward")
+            finally:
+                vit._release_ws(ws)
+        return feats
+
+    def _scored_exchange(self, vit_cxr, vit_enh, f_c, f_e, tgt, need_df):
+        """The exchange forward on (f_c, f_e) and the backward of y_t = (fused + x_cxr + x_enh)[t]: (run, d y_t / d f_c, d y_t / d f_e)."""
+        hc, he = self._plain_head(vit_cxr), self._plain_head(vit_enh)
+        fused_heads = hc is not None and he is not None and hc.out_features == self.num_classes == he.out_features
+        with torch.no_grad():
+            run = ExchangeRun(self._spec, f_c, f_e, (hc.weight, hc.bias, he.weight, he.bias) if fused_heads else None)
+        if fused_heads:
+            with torch.no_grad():
+                idx = resolve_target(tgt, run.fused + run.x_c + run.x_e)
+                hot = torch.zeros_like(run.fused).scatter_(1, idx, 1.0)
+                g_c, g_e = run.backward(hot, hot, hot, need_df)
+            return run, g_c, g_e
+        lc, le = run.f_cxr.detach().requires_grad_(True), run.f_enh.detach().requires_grad_(True)
+        with torch.enable_grad(), eval_modules(vit_cxr.head, vit_enh.head):
+            x = vit_cxr.forward_head(lc) + vit_enh.forward_head(le)
+            idx = resolve_target(tgt, run.fused + x.detach())
+            h_c, h_e = torch.autograd.grad(x.gather(1, idx).sum(), (lc, le)) if need_df else (None, None)
+        with torch.no_grad():
+            hot = torch.zeros_like(run.fused).scatter_(1, idx, 1.0)
+            g_c, g_e = run.backward(hot, None, None, need_df)
+            if need_df:
+                g_c, g_e = g_c + h_c, g_e + h_e
+        return run, g_c, g_e
+
+    def get_exchange_attention(self, vit_cxr, vit_enh, img_cxr, img_enh, head_fusion=None):
+        """[(a_cxr, a_enh) for every exchange layer of the live encoder]: the softmax probabilities of the cls queries exactly as the forward
+        normalised them, (B, heads, T) each, or (B, T) fused over the heads with head_fusion 'mean' | 'max' | 'min' (max / min are not
+        renormalised: a max-fused row sums to more than 1, a min-fused row to less).  Any cross_attn_depth, either pool."""
+        self._check_pair(vit_cxr, vit_enh, img_cxr, img_enh)
+        if head_fusion not in _lib.HEAD_FUSION:
+            raise ValueError(f"head_fusion must be None, 'mean', 'max' or 'min', got {head_fusion!r}")
+        fuse = _lib.HEAD_FUSION[head_fusion]
+        with torch.no_grad():
+            run = ExchangeRun(self._spec, self._eval_features(vit_cxr, img_cxr), self._eval_features(vit_enh, img_enh))
+            try:
+                out = [run.attention(l, fuse) for l in range(self._spec.depth)]
+            finally:
+                run.ws = None
+        return [(a[0], a[1]) for a in out]
+
+    def exchange_relevance(self, vit_cxr, vit_enh, img_cxr, img_enh, target=None):
+        """(Abar_cxr, Abar_enh), (B, T) each: the gradient-weighted exchange map Abar[j] = mean over heads of max(0, a_h[j] d y_t / d a_h[j]) for
+        the score of attention_relevance, y_t = (fused + x_cxr + x_enh)[t]; target as there.  cross_attn_depth == 1, pool == 'cls'."""
+        B = self._check_pair(vit_cxr, vit_enh, img_cxr, img_enh)
+        tgt = check_target(target, B, self.num_classes)
+        self._check_one_layer_cls("exchange_relevance")
+        run, _, _ = self._scored_exchange(vit_cxr, vit_enh, self._eval_features(vit_cxr, img_cxr), self._eval_features(vit_enh, img_enh), tgt, False)
+        try:
+            with torch.no_grad():
+                abar = run.grad_attention(0)
+        finally:
+            run.ws = None
+        return abar[0], abar[1]
+
+    def cross_relevance(self, vit_cxr, vit_enh, img_cxr, img_enh, target=None):
+        """(rel_cc, rel_ce, rel_ec, rel_ee), (B, gh, gw) each, not normalised: the relevance of each image's patches for y_t THROUGH the exchange
+        (Chefer et al. 2021, self-attention rule inside the encoders, co-attention rule across the exchange; include/mfvit.h,
+        mfvit_bimodal_relevance).  rel_cc / rel_ce: what the CXR cls token draws from the CXR / ENH patches, rel_ee / rel_ec likewise for the
+        ENH cls token; the CXR image's total is rel_cc + rel_ec, the ENH image's rel_ee + rel_ce.  Keeps every block's (B, T, T) relevance
+        map of both encoders while it runs: 4 (L_cxr + L_enh) B T^2 bytes.  cross_attn_depth == 1, pool == 'cls'."""
+        B = self._check_pair(vit_cxr, vit_enh, img_cxr, img_enh)
+        tgt = check_target(target, B, self.num_classes)
+        self._check_one_layer_cls("cross_relevance")
+        if vit_cxr.num_tokens != vit_enh.num_tokens:
+            raise ValueError("the two encoders must produce the same number of tokens")
+        cfg_c, ws_c, f_c = vit_cxr._rel_forward(img_cxr)
+        try:
+            cfg_e, ws_e, f_e = vit_enh._rel_forward(img_enh)
+            try:
+                run, g_c, g_e = self._scored_exchange(vit_cxr, vit_enh, f_c, f_e, tgt, True)
+                try:
+                    with torch.no_grad():
+                        abar = run.grad_attention(0)
+                finally:
+                    run.ws = None
+                m_c, _ = vit_cxr._rel_backward(cfg_c, ws_c, g_c, list(range(vit_cxr.depth)), False)
+                m_e, _ = vit_enh._rel_backward(cfg_e, ws_e, g_e, list(range(vit_enh.depth)), False)
+            finally:
+                vit_enh._release_ws(ws_e)
+        finally:
+            vit_cxr._release_ws(ws_c)
+
+        def stacked(ms):    # (the maps of one call are slices of one buffer, block after block)
+            base = ms[0]._base
+            return base.view(len(ms), *ms[0].shape) if base is not None and base.numel() == len(ms) * ms[0].numel() else torch.stack(ms)
+        with torch.no_grad():
+            out = bimodal_relevance(stacked(m_c), stacked(m_e), abar)
+        gc, ge = (vit_cxr.img_size[0] // 16, vit_cxr.img_size[1] // 16), (vit_enh.img_size[0] // 16, vit_enh.img_size[1] // 16)
+        return out[0].view(B, *gc), out[1].view(B, *ge), out[2].view(B, *gc), out[3].view(B, *ge)
