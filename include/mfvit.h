@@ -406,6 +406,36 @@ int mfvit_input_photometric(const uint8_t* src, const int64_t* desc, const int32
 int mfvit_eval_counts(const float* scores, int64_t ld, const int64_t* labels, int n, int C, uint64_t* confusion, int64_t* preds,
                       uint64_t* u2, uint64_t* npos, mfvit_stream_t stream);
 
+/* The perturbation test for patch-relevance maps (Chefer, Gur & Wolf 2021 section 4, positive / negative perturbation; Petsiuk et al. 2018,
+ * deletion / insertion; mfvit.perturb drives it): rank the patches, mask them a fraction at a time, score the model's output again.  Three
+ * launches, one each, asynchronous on `stream`.
+ *
+ * mfvit_patch_rank: rel f32 [B][P] (row stride ld) -> rank int32 [B][P], the position of patch i when the patches of image b are ordered
+ * most relevant first, by a total order that depends on the values and the indices only:
+ *   rank[i] = #{j : rel[j] > rel[i], or rel[j] == rel[i] and j < i}.
+ * NaN counts as below every number, -inf included, NaNs among themselves by index; -0.0 == +0.0 is a tie.  That is the inverse permutation
+ * of np.argsort(-rel, kind="stable") - NOT of torch.argsort(descending=True, stable=True), which puts NaN first.  Exact (integers).
+ * P <= 8192, the token limit.  MFVIT_EINVAL (before any HIP call): a NULL pointer, B <= 0, B > 65535, P <= 0, P > 8192, ld < P. */
+int mfvit_patch_rank(const float* rel, int64_t ld, int32_t* rank, int B, int P, mfvit_stream_t stream);
+/* mfvit_patch_perturb: img f32 [B][C][H][W], rank int32 [B][P] with P = (H / 16) (W / 16), patches row by row as the encoder numbers its
+ * tokens, steps device int32 [S][2] (half-open rank ranges lo_s, hi_s), fill device f32 [C] -> out f32 [S][B][C][H][W]:
+ *   out[s][b][c][y][x] = fill[c] if lo_s <= rank[b][(y / 16) (W / 16) + x / 16] < hi_s, else img[b][c][y][x].
+ * Every element is a move or the fill value (bit-exact).  With k patches to remove: positive perturbation (most relevant first) is
+ * [0, k), negative (least relevant first) [P - k, P), insertion (only the top k visible) [k, P).  The range values (0 <= lo <= hi <= P)
+ * and the rank values are the caller's contract; they only enter comparisons.  Out of place.  MFVIT_EINVAL (before any HIP call): a NULL
+ * pointer, H or W not a positive multiple of 16, P > 8192, B, C or S <= 0, B > 65535, S > 65535, C * H * W > 2^30, out overlapping img. */
+int mfvit_patch_perturb(const float* img, const int32_t* rank, const int32_t* steps, const float* fill, float* out, int B, int C, int H,
+                        int W, int S, mfvit_stream_t stream);
+/* mfvit_perturb_score: logits f32 [S][B][C] (row stride ld, row s * B + b), target int64 [B].  ACCUMULATES into caller-zeroed correct
+ * uint64 [S], sums f64 [S][2] and nonfinite uint64 [S]: per step the number of images whose first-maximum argmax (as torch.max, like
+ * mfvit_eval_counts) equals the target, the sum of the target's softmax probability (computed in double from the f32 logits,
+ * max-subtracted) in sums[s][0] and the sum of the target's raw logit in sums[s][1].  A row with a non-finite logit counts as wrong, adds 0
+ * to both sums and 1 to nonfinite[s].  One workgroup per step and a fixed-order sum (every thread walks its images in index order, then a
+ * fixed tree): called batch after batch, it gives the same bits on every run.  A target outside [0, C) is the caller's contract (such a
+ * row is wrong and adds 0; nothing outside the row is read).  MFVIT_EINVAL (before any HIP call): a NULL pointer, S, B or C <= 0, ld < C. */
+int mfvit_perturb_score(const float* logits, int64_t ld, const int64_t* target, int S, int B, int C, uint64_t* correct, double* sums,
+                        uint64_t* nonfinite, mfvit_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Two-stream fusion: bidirectional cls<->patch cross-attention exchange + heads (f32).
  * Replaces PreNorm / CrossAttention (MOD:15-21,108-137), MultiScaleTransformerEncoder.forward (FUS:35-65) and

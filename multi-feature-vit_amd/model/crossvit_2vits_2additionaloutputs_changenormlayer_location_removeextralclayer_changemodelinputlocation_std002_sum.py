@@ -314,3 +314,41 @@ class Fus_CrossViT(nn.Module):
             out = bimodal_relevance(stacked(m_c), stacked(m_e), abar)
         gc, ge = (vit_cxr.img_size[0] // 16, vit_cxr.img_size[1] // 16), (vit_enh.img_size[0] // 16, vit_enh.img_size[1] // 16)
         return out[0].view(B, *gc), out[1].view(B, *ge), out[2].view(B, *gc), out[3].view(B, *ge)
+
+    # ------------------------------------------------------------------ the perturbation test (mfvit.perturb; include/mfvit.h, mfvit_patch_rank ..)
+    def perturbation_test(self, vit_cxr, vit_enh, img_cxr, img_enh, maps, target=None, fractions=None, mode="positive", fill=None,
+                          max_batch=None, meter=None, return_logits=False, ks=None):
+        """mfvit.perturb.perturbation_test for the two-stream model, scored on fused + x_cxr + x_enh (MAIN_CA:868), the score of
+        attention_relevance: meter, or (meter, logits (S, B, classes)) with return_logits.  maps = (m_cxr, m_enh), each (B, gh, gw) or (B, P)
+        for its own image; either may be None: that stream stays intact at every step - the stream-ablation curve.  Each stream has its own
+        patch count (k_s = int(P * fractions[s]) per stream; the meter's fractions are those of the first perturbed stream) and its own fill:
+        fill = None or (fill_cxr, fill_enh), each as perturb_patches takes it.  target, mode, max_batch (images per stream and forward),
+        meter, ks as there.  Runs this model's ordinary forward under no_grad, everything in evaluation mode; training flags, RNG states, the
+        encoders' feature caches and p.grad stay as they were."""
+        from mfvit import perturb
+        B = self._check_pair(vit_cxr, vit_enh, img_cxr, img_enh)
+        if not isinstance(maps, (tuple, list)) or len(maps) != 2 or (maps[0] is None and maps[1] is None):
+            raise ValueError("maps must be (m_cxr, m_enh), at least one of them a relevance map")
+        if fill is not None and (not isinstance(fill, (tuple, list)) or len(fill) != 2):
+            raise ValueError("fill must be None or (fill_cxr, fill_enh)")
+        fills = (None, None) if fill is None else fill
+        plans = [perturb._plan(img, m, fractions, ks, mode, max_batch, what)
+                 for img, m, what in ((img_cxr, maps[0], "perturbation_test (cxr)"), (img_enh, maps[1], "perturbation_test (enh)"))]
+        tgt = check_target(target, B, self.num_classes)
+        lead = plans[0] if maps[0] is not None else plans[1]
+        meter = perturb._meter_for(meter, lead[2], lead[1])
+        _lib.require_cuda(img_cxr, img_enh, maps[0], maps[1])
+
+        def forward(xs):
+            fused, x_c, x_e = self(vit_cxr, vit_enh, xs[0], xs[1])
+            return fused + x_c + x_e
+        saved = [(v, v._feat_cache, getattr(v, "_grad_arena_lent", False)) for v in (vit_cxr, vit_enh)]
+        try:
+            with torch.no_grad(), eval_modules(self, vit_cxr, vit_enh):
+                streams = [(img, None if m is None else perturb.patch_rank(m), perturb.ranges_for(P, counts, mode), f)
+                           for img, m, (_, P, counts), f in zip((img_cxr, img_enh), maps, plans, fills)]
+                logits = perturb.run_steps(forward, streams, len(lead[2]), B, max_batch, tgt, meter, mode == "insertion")
+        finally:
+            for v, cache, lent in saved:
+                v._feat_cache, v._grad_arena_lent = cache, lent
+        return (meter, logits) if return_logits else meter
