@@ -436,6 +436,47 @@ int mfvit_patch_perturb(const float* img, const int32_t* rank, const int32_t* st
 int mfvit_perturb_score(const float* logits, int64_t ld, const int64_t* target, int S, int B, int C, uint64_t* correct, double* sums,
                         uint64_t* nonfinite, mfvit_stream_t stream);
 
+/* Gradient attribution (integrated gradients, SmoothGrad, saliency; mfvit.attribution drives it; additive in ABI 5): everything around the
+ * model's forward and its data-gradient-only backward (mfvit_vit_backward_ex with dparams = NULL).  Three launches, one each, asynchronous on
+ * `stream`; no atomics, every sum in a fixed order: the same bits on every run.  16-byte accesses where every image pointer is 16-byte
+ * aligned (and hw % 4 == 0), a scalar path otherwise.
+ *
+ * mfvit_attr_inputs: x f32 [B][C][hw]; base f32 [C] (base_full = 0: one constant per channel) or [B][C][hw] (base_full = 1); alpha device
+ * f32 [S]; sigma device f32 [B] or NULL; seed device uint64 [1] (read only when sigma is given) -> out f32 [S][B][C][hw]:
+ *   v = base                               where alpha_s == 0          (a move: bit-exact)
+ *   v = x                                  where alpha_s == 1          (a move: bit-exact)
+ *   v = fmaf(alpha_s, x - base, base)      otherwise (the difference rounded to f32 first)
+ *   out[s][b][e] = v, or fmaf(sigma_b, z, v) when sigma is given, e the element index inside the image.
+ * z is a standard normal from a counter hash of (seed, gs = s0 + s, b, e); nothing is stored.  With lowbias32 the multiply-xorshift hash of
+ * the dropout masks (x ^= x >> 16, x *= 0x7feb352d, x ^= x >> 15, x *= 0x846ca68b, x ^= x >> 16) and lowbias32b the same form with the
+ * constants 0x21f0aaad, 0x735a2d97 and a last shift of 15:
+ *   k   = lowbias32(lo32(seed) ^ lowbias32(hi32(seed) + 0x9E3779B9 * (gs + 1)));   key = lowbias32(k + 0x85EBCA6B * (b + 1))
+ *   h1  = lowbias32(e ^ key);   h2 = lowbias32b(e ^ key)
+ *   u1  = ((float)(h1 >> 8) + 0.5f) * 2^-24   (f32 arithmetic: in (0, 1], never 0);   u2 = (float)(h2 >> 8) * 2^-24   (in [0, 1))
+ *   z   = sqrtf(-2 logf(u1)) * cospif(2 u2)   (the accurate device functions; every product rounded to f32).
+ * s0 is the global index of the call's first sample: the noise of sample gs is the same however the samples are grouped into calls.
+ * x = 0, base = 0, alpha = 1, sigma = 1 exports z itself.  Out of place.  MFVIT_EINVAL (before any HIP call): x, base, alpha or out NULL,
+ * sigma without seed, S, B, C or hw <= 0, S > 65535, B > 65535, s0 < 0 or > 2^30, C * hw > 2^30, out overlapping x or a full base. */
+int mfvit_attr_inputs(const float* x, const float* base, int base_full, const float* alpha, const float* sigma, const uint64_t* seed, int s0,
+                      float* out, int S, int B, int C, int64_t hw, mfvit_stream_t stream);
+/* mfvit_attr_accumulate: g f32 [k][B][n] (the image gradients of the group just run), w device f32 [k], acc f32 [B][n], zeroed by the caller
+ * before the first group:  acc[b][i] += sum_s w_s g[s][b][i]^power, s ascending, one rounding per step: power 1 is a = fmaf(w_s, g, a);
+ * power 2 is a = (float)fma(w_s g, g, a) evaluated in double, where w_s g is exact, so that the square enters unrounded.
+ * MFVIT_EINVAL (before any HIP call): a NULL pointer, k, B or n <= 0, k > 65535, B > 65535, n > 2^30, power not 1 or 2, acc overlapping g. */
+int mfvit_attr_accumulate(const float* g, const float* w, float* acc, int k, int B, int64_t n, int power, mfvit_stream_t stream);
+/* mfvit_attr_finish: acc f32 [B][C][H][W]; with times_input x f32 [B][C][H][W] and base as in mfvit_attr_inputs (both unread otherwise) ->
+ * pixels f32 [B][H][W] (or NULL), patches f32 [B][H / 16][W / 16], total f64 [B], all OVERWRITTEN:
+ *   t_c    = acc_c * (x_c - base_c) (the difference, then the product, each rounded to f32), or acc_c without times_input
+ *   pixel  = f(t_0) + f(t_1) + ..  in channel order, f the identity or fabsf (absval)
+ *   patch  = the 256 pixels of a 16 x 16 patch: groups of four pixels of a row (a0 + a1) + (a2 + a3), the four groups of a patch row
+ *            (q0 + q1) + (q2 + q3), then the 16 rows pairwise, ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)) plus the same of r8 .. r15:
+ *            eight additions deep
+ *   total  = the sum of the SIGNED t_c of the image (also with absval) in double: per thread in visiting order, then a fixed tree.
+ * One workgroup per image: no output has two writers.  MFVIT_EINVAL (before any HIP call): acc, patches or total NULL, times_input without
+ * x or base, H or W not a positive multiple of 16, B or C <= 0, C * H * W > 2^30, pixels overlapping an input. */
+int mfvit_attr_finish(const float* acc, const float* x, const float* base, int base_full, int times_input, int absval, float* pixels,
+                      float* patches, double* total, int B, int C, int H, int W, mfvit_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Two-stream fusion: bidirectional cls<->patch cross-attention exchange + heads (f32).
  * Replaces PreNorm / CrossAttention (MOD:15-21,108-137), MultiScaleTransformerEncoder.forward (FUS:35-65) and

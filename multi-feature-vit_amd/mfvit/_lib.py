@@ -141,6 +141,9 @@ SIGNATURES = {
     "mfvit_patch_rank": (I, [P, L, P, I, I, P]),
     "mfvit_patch_perturb": (I, [P, P, P, P, P, I, I, I, I, I, P]),
     "mfvit_perturb_score": (I, [P, L, P, I, I, I, P, P, P, P]),
+    "mfvit_attr_inputs": (I, [P, P, I, P, P, P, I, P, I, I, I, L, P]),
+    "mfvit_attr_accumulate": (I, [P, P, P, I, I, L, I, P]),
+    "mfvit_attr_finish": (I, [P, P, P, I, I, I, P, P, P, I, I, I, I, P]),
     "mfvit_prof_enable": (I, [I]),
     "mfvit_set_wgrad_stream": (I, [I]),
     "mfvit_set_stream_share": (I, [I]),

@@ -352,3 +352,47 @@ class Fus_CrossViT(nn.Module):
             for v, cache, lent in saved:
                 v._feat_cache, v._grad_arena_lent = cache, lent
         return (meter, logits) if return_logits else meter
+
+    # ------------------------------------------------------------------ gradient attribution (mfvit.attribution; include/mfvit.h, mfvit_attr_inputs ..)
+    # The three methods of mfvit.attribution for the score of attention_relevance, y_t = (fused + x_cxr + x_enh)[t] (MAIN_CA:868), along the JOINT path
+    # of both images: ((res_cxr, res_enh), stream_share).  baselines = (baseline_cxr, baseline_enh), each as integrated_gradients takes it;
+    # streams = 'both' | 'cxr' | 'enh': with one stream the other image stays at its input at every step (a plain evaluation forward) and its
+    # result is None.  stream_share = total_cxr / (total_cxr + total_enh), (B,) float64 on the device, NaN where the denominator is 0; for
+    # integrated gradients the results' delta is the completeness gap of both totals together.  The encoders run one after the other on the
+    # caller's stream; each attributed one runs its data-gradient-only backward.  Same contract as attention_relevance and perturbation_test: no
+    # p.grad, no gradient arena, training flags, feature caches and RNG states (but for one drawn seed) as they were.
+    def _attribution(self, method, vit_cxr, vit_enh, img_cxr, img_enh, target, kw):
+        from mfvit import attribution
+        self._check_pair(vit_cxr, vit_enh, img_cxr, img_enh)
+
+        def out_of(f_c, f_e):
+            hc, he = self._plain_head(vit_cxr), self._plain_head(vit_enh)
+            if hc is not None and he is not None and hc.out_features == self.num_classes == he.out_features:
+                fused, x_c, x_e = FusionFn.apply(self._spec, f_c, f_e, hc.weight, hc.bias, he.weight, he.bias, *self._spec.live())
+            else:
+                fused, _, _ = FusionFn.apply(self._spec, f_c, f_e, None, None, None, None, *self._spec.live())
+                x_c, x_e = vit_cxr.forward_head(f_c), vit_enh.forward_head(f_e)
+            return fused + x_c + x_e
+        return attribution.two_stream(method, (vit_cxr, vit_enh), (img_cxr, img_enh), out_of, self.num_classes, (self, vit_cxr, vit_enh),
+                                      target=target, **kw)
+
+    def integrated_gradients(self, vit_cxr, vit_enh, img_cxr, img_enh, target=None, baselines=(None, None), streams="both", steps=20,
+                             rule="trapezoid", score="logit", sign="signed", noise=None, max_batch=None, return_pixels=False):
+        """mfvit.attribution.integrated_gradients for the two-stream model: see above."""
+        return self._attribution("integrated_gradients", vit_cxr, vit_enh, img_cxr, img_enh, target,
+                                 dict(baselines=baselines, streams=streams, steps=steps, rule=rule, score=score, sign=sign, noise=noise,
+                                      max_batch=max_batch, return_pixels=return_pixels))
+
+    def smoothgrad(self, vit_cxr, vit_enh, img_cxr, img_enh, target=None, streams="both", noise_level=0.15, samples=25, squared=False, seed=None,
+                   times_input=False, score="logit", sign="signed", max_batch=None, return_pixels=False):
+        """mfvit.attribution.smoothgrad for the two-stream model (stream i draws its noise from seed + i): see above."""
+        return self._attribution("smoothgrad", vit_cxr, vit_enh, img_cxr, img_enh, target,
+                                 dict(streams=streams, noise_level=noise_level, samples=samples, squared=squared, seed=seed, times_input=times_input,
+                                      score=score, sign=sign, max_batch=max_batch, return_pixels=return_pixels))
+
+    def saliency(self, vit_cxr, vit_enh, img_cxr, img_enh, target=None, streams="both", times_input=False, score="logit", sign="signed",
+                 max_batch=None, return_pixels=False):
+        """mfvit.attribution.saliency for the two-stream model: see above."""
+        return self._attribution("saliency", vit_cxr, vit_enh, img_cxr, img_enh, target,
+                                 dict(streams=streams, times_input=times_input, score=score, sign=sign, max_batch=max_batch,
+                                      return_pixels=return_pixels))
