@@ -321,8 +321,11 @@ int mfvit_head_fwd(const float* x, int64_t ldx, const float* w, const float* b, 
                    mfvit_stream_t stream);
 int mfvit_head_bwd(const float* dy, int64_t lddy, const float* x, int64_t ldx, const float* w, float* dx, int64_t lddx, int dx_accumulate,
                    float* dw, float* db, int M, int N, int K, mfvit_stream_t stream);
-/* nn.CrossEntropyLoss (mean) for C <= 64 classes (MAIN_CA:873, MAIN_SS:714): loss_mean[1], dlogits = dloss/dlogits,
- * preds = argmax (MAIN_CA:870). */
+/* First maximum.  Wherever this header says "first-maximum argmax" or "as torch.max" (mfvit_cross_entropy, mfvit_cross_entropy_soft,
+ * mfvit_eval_counts), the index of a row is torch.max(x, 1)[1] / np.argmax: the first NaN of the row if it holds one, otherwise the first of
+ * its largest values (+0.0 and -0.0 are equal).  Rows [1, nan, 3], [nan, 2, 1], [3, 1, nan], [2, 5, 5] give 1, 0, 2, 1. */
+/* nn.CrossEntropyLoss (mean) for C <= 64 classes (MAIN_CA:873, MAIN_SS:714): loss_mean[1] (a fixed-order sum: the same bits on every run),
+ * dlogits = dloss/dlogits (or NULL), preds = first-maximum argmax (MAIN_CA:870; or NULL).  MFVIT_EINVAL (before any HIP call): C > 64, C < 1. */
 int mfvit_cross_entropy(const float* logits, const int64_t* target, float* loss_mean, float* dlogits, int64_t* preds, int B, int C,
                         mfvit_stream_t stream);
 /* Soft-target cross entropy (mean) for C <= 64 classes with label smoothing and a mixed target (timm's SoftTargetCrossEntropy over
@@ -402,7 +405,9 @@ int mfvit_input_photometric(const uint8_t* src, const int64_t* desc, const int32
  * confusion[t][p] (+ optional preds[n] = first-maximum argmax, as torch.max MAIN_CA:870), and per class c the pair counts of the
  * one-vs-rest ROC AUC: u2[c] = 2 #{(pos, neg): s_pos > s_neg} + #{s_pos == s_neg}, npos[c] = #{label == c}; AUC_c = u2 /
  * (2 npos (n - npos)) = the trapezoid area of sklearn's roc_curve.  The pair counts are over THIS call's n samples (call it
- * once on the whole epoch's scores); the confusion matrix may be accumulated batch by batch.  Either half may be NULL. */
+ * once on the whole epoch's scores); the confusion matrix may be accumulated batch by batch.  Either half may be NULL (preds is written by
+ * the confusion half).  Labels are compared as 64-bit integers: one outside [0, C) is in no row of the confusion matrix and is a negative
+ * of every class, as label_binarize makes it. */
 int mfvit_eval_counts(const float* scores, int64_t ld, const int64_t* labels, int n, int C, uint64_t* confusion, int64_t* preds,
                       uint64_t* u2, uint64_t* npos, mfvit_stream_t stream);
 
@@ -631,7 +636,8 @@ const char* mfvit_prof_class_name(int cls);
 /* BatchNorm1d over the batch axis of x[n][C] (BLD:62-78; SyncBatchNorm semantics, MAIN_MOCO:297):
  *   mfvit_bn_stats   : rank-local per-column mean and M2 = sum (x - mean)^2
  *   mfvit_bn_combine : merge W (mean, M2, count) triples (all_gathered by the host) -> global mean, invstd; updates the
- *                      running statistics (momentum, unbiased variance) when given
+ *                      running statistics (momentum, unbiased variance; the biased one when the global count is 1) when given.  A rank
+ *                      with count 0 is skipped, whatever its mean and M2 hold (an empty rank of SyncBatchNorm)
  *   mfvit_bn_apply   : y = (x - mean) * invstd [* gamma + beta] [-> ReLU]   (gamma == NULL: affine=False) */
 int mfvit_bn_stats(int dtype, const void* x, int n, int C, float* mean, float* m2, mfvit_stream_t stream);
 int mfvit_bn_combine(const float* means, const float* m2s, const float* counts, int W, int C, float eps, float momentum, float* mean,

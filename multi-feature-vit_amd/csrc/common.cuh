@@ -207,6 +207,9 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
+// One step of the first-maximum scan of include/mfvit.h ("First maximum"): does v, met after the running best, replace it?  A larger value does, and
+// the first NaN does (as torch.max / np.argmax: the first NaN wins, otherwise the first maximum); once best is NaN nothing replaces it.
+__device__ __forceinline__ bool first_max_takes(float v, float best) { return v > best || (v != v && best == best); }
 // The wave's maximum of NON-NEGATIVE values as a scalar, without LDS permutes: four DPP steps inside the rows of 16 lanes, then the four rows by readlane.
 __device__ __forceinline__ float wave_max_nonneg_dpp(float v) {
     auto dpp = [](float x, auto ctrl) __attribute__((always_inline)) {

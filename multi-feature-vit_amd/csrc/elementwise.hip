@@ -569,7 +569,7 @@ int linear_small_bwd(const float* dy, long lddy, const float* x, long ldx, const
 // --------------------------------------------------------------------------------------- small-C cross entropy
 // nn.CrossEntropyLoss (mean) over logits [B][C], C <= 64: one thread per sample, ONE block (samples strided over its 1,024 threads); the mean is a fixed-order
 // sum (per-thread sequences, wave sums, the 16 wave totals in order): the same bits on every run (round 6: one float atomic per wave before).
-// Writes dlogits = (softmax - onehot) / B and preds (argmax, first maximum like torch.max).
+// Writes dlogits = (softmax - onehot) / B and preds (argmax, first maximum like torch.max: first_max_takes).
 __global__ __launch_bounds__(1024) void ce_small_kernel(const float* __restrict__ logits, const long* __restrict__ target, float* __restrict__ loss_mean,
                                                         float* __restrict__ dlogits, long* __restrict__ preds, int B, int C) {
     __shared__ float red[16];
@@ -578,7 +578,7 @@ __global__ __launch_bounds__(1024) void ce_small_kernel(const float* __restrict_
         const float* z = logits + (long)b * C;
         float m = z[0];
         int am = 0;
-        for (int c = 1; c < C; ++c) if (z[c] > m) { m = z[c]; am = c; }
+        for (int c = 1; c < C; ++c) if (first_max_takes(z[c], m)) { m = z[c]; am = c; }
         float s = 0.f;
         for (int c = 0; c < C; ++c) s += __expf(z[c] - m);
         const float lse = m + __logf(s);

@@ -8,7 +8,7 @@ namespace mfvit {
 
 namespace {
 
-// conf[t][p] += 1 for every sample (first maximum wins, like torch.max / np.argmax); preds optional
+// conf[t][p] += 1 for every sample (first maximum wins, the first NaN before it, like torch.max / np.argmax); preds optional
 __global__ __launch_bounds__(256) void confusion_kernel(const float* __restrict__ scores, long ld, const int64_t* __restrict__ labels, int n,
                                                         int C, unsigned long long* __restrict__ conf, int64_t* __restrict__ preds) {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -18,11 +18,11 @@ __global__ __launch_bounds__(256) void confusion_kernel(const float* __restrict_
     float bv = s[0];
     for (int c = 1; c < C; ++c) {
         const float v = s[c];
-        if (v > bv) { bv = v; best = c; }
+        if (first_max_takes(v, bv)) { bv = v; best = c; }
     }
     if (preds) preds[i] = best;
-    const int t = (int)labels[i];
-    if (t >= 0 && t < C) atomicAdd(conf + (long)t * C + best, 1ull);
+    const int64_t t = labels[i];                                    // all 64 bits, as auc_pairs_kernel compares them: 2^32 + 1 is no class
+    if (t >= 0 && t < C) atomicAdd(conf + t * C + best, 1ull);
 }
 
 // One-vs-rest ROC AUC of class c = blockIdx.y, as exact integers: for every positive i (label == c) count the negatives j with a

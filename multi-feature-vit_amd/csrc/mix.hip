@@ -116,7 +116,7 @@ __global__ __launch_bounds__(1024) void ce_soft_kernel(const float* __restrict__
         const float* z = logits + (long)b * C;
         float m = z[0];
         int am = 0;
-        for (int c = 1; c < C; ++c) if (z[c] > m) { m = z[c]; am = c; }
+        for (int c = 1; c < C; ++c) if (first_max_takes(z[c], m)) { m = z[c]; am = c; }
         float s = 0.f;
         for (int c = 0; c < C; ++c) s += expf(z[c] - m);
         const float ls = logf(s), inv = 1.f / s;

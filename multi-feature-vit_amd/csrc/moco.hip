@@ -124,7 +124,9 @@ __global__ __launch_bounds__(256) void bn_combine_kernel(const float* __restrict
     if (c >= C) return;
     float N = 0.f, mu = 0.f, M2 = 0.f;
     for (int w = 0; w < W; ++w) {
-        const float nb = counts[w], mb = means[(long)w * C + c], qb = m2s[(long)w * C + c];
+        const float nb = counts[w];
+        if (!(nb > 0.f)) continue;                                      // an empty rank contributes nothing (its mean and M2 are not read), as SyncBatchNorm
+        const float mb = means[(long)w * C + c], qb = m2s[(long)w * C + c];
         const float Nn = N + nb, d = mb - mu;
         mu += d * nb / Nn;
         M2 += qb + d * d * N * nb / Nn;

@@ -260,3 +260,181 @@ def test_adam_gate_separates_the_right_split_from_index_bugs():
     print(f"adam split: float32 restatement at most {worst:.2f} of the gate; mutations reached {reached}")
     assert all(v > 0 for v in reached.values()), reached
     assert paths == {0, 1, 2, 3}, paths                                 # vector single, vector pair, tail, scalar fallback
+
+
+# ------------------------------------------------------------------------------------------------ 3. the BatchNorm entry points (tests/test_bn_edges_gpu.py)
+@pytest.mark.parametrize("relu", [False, True], ids=["plain", "relu"])
+@pytest.mark.parametrize("affine", [True, False], ids=["affine", "noaffine"])
+@pytest.mark.parametrize("n,C", [(1, 3), (2, 1), (17, 5), (33, 68)])
+def test_bn_restatements_are_F_batch_norm_and_its_autograd_in_training(n, C, affine, relu):
+    x = rng_tensor(40 + n + C, (n, C), scale=2.0, dtype=torch.float64) + 0.5
+    x[:, 0] = ref_moco.BN_CONST                                          # a constant column: var = 0
+    x.requires_grad_(True)
+    dy = rng_tensor(41 + n + C, (n, C), dtype=torch.float64)
+    w = (1 + 0.1 * rng_tensor(42 + C, (C,), dtype=torch.float64)).requires_grad_(True) if affine else None
+    b = (0.1 * rng_tensor(43 + C, (C,), dtype=torch.float64)).requires_grad_(True) if affine else None
+    rm0, rv0 = rng_tensor(44 + C, (C,), dtype=torch.float64), rng_tensor(45 + C, (C,), dtype=torch.float64).abs() + 0.5
+    for eps, mom in ((1e-5, 0.1), (1e-3, 0.37)):
+        for t in (x, w, b):
+            if t is not None:
+                t.grad = None
+        rm, rv = rm0.clone(), rv0.clone()
+        if n > 1:
+            y = F.batch_norm(x, rm, rv, w, b, training=True, momentum=mom, eps=eps)
+        else:                      # torch refuses one value per channel in training; SyncBatchNorm's arithmetic at N = 1 is var = 0, biased in the running variance
+            y = (x - x.detach()) / (0.0 + eps) ** 0.5 * (w if affine else 1.0) + (b if affine else 0.0)
+            rm, rv = (1 - mom) * rm + mom * x.detach()[0], (1 - mom) * rv
+        out = torch.relu(y) if relu else y
+        out.backward(dy)
+        xd = x.detach()
+        mean_p, m2_p = ref_moco.bn_stats(xd)
+        mean, invstd, r_rm, r_rv = ref_moco.bn_combine(mean_p[None], m2_p[None], torch.tensor([float(n)]), eps, mom, rm0, rv0)
+        assert rel(mean, xd.mean(0)) < PIN and rel(r_rm, rm) < PIN and rel(r_rv, rv) < PIN
+        wd, bd = (w.detach(), b.detach()) if affine else (None, None)
+        r_y = ref_moco.bn_apply(xd, mean, invstd, wd, bd, relu)
+        assert rel(r_y, out) < PIN
+        s1, s2 = ref_moco.bn_bwd_sums(dy, xd, r_y, mean, invstd, relu)
+        dx = ref_moco.bn_bwd_apply(dy, xd, r_y, mean, invstd, wd, relu, s1, s2, 1.0 / n)
+        if n > 1:
+            assert rel(dx, x.grad) < 1e-9                                # (the constant column: differences of terms invstd = 1 / sqrt(eps) larger)
+            if affine:
+                assert rel(s1, b.grad) < PIN and rel(s2, w.grad) < PIN
+        else:
+            assert not bool(dx.any())
+
+
+@pytest.mark.parametrize("affine", [True, False], ids=["affine", "noaffine"])
+def test_bn_restatements_are_F_batch_norm_and_its_autograd_in_eval(affine):
+    """eval mode as mfvit/mlp.py runs it: mean = running mean, invstd = rsqrt(running var + eps), and the sums of the backward zeroed."""
+    n, C, eps = 9, 6, 1e-5
+    x = rng_tensor(50, (n, C), dtype=torch.float64).requires_grad_(True)
+    dy = rng_tensor(51, (n, C), dtype=torch.float64)
+    w = (1 + 0.1 * rng_tensor(52, (C,), dtype=torch.float64)) if affine else None
+    b = 0.1 * rng_tensor(53, (C,), dtype=torch.float64) if affine else None
+    rm, rv = rng_tensor(54, (C,), dtype=torch.float64), rng_tensor(55, (C,), dtype=torch.float64).abs() + 0.5
+    y = torch.relu(F.batch_norm(x, rm, rv, w, b, training=False, eps=eps))
+    y.backward(dy)
+    invstd = 1.0 / torch.sqrt(rv + eps)
+    r_y = ref_moco.bn_apply(x.detach(), rm, invstd, w, b, True)
+    zero = torch.zeros(C, dtype=torch.float64)
+    assert rel(r_y, y) < PIN
+    assert rel(ref_moco.bn_bwd_apply(dy, x.detach(), r_y, rm, invstd, w, True, zero, zero, 1.0 / n), x.grad) < PIN
+
+
+def test_bn_relu_mask_passes_positive_values_only():
+    y = torch.tensor([[1.0, 0.0, -0.0, -2.0, float("nan"), 1e-30]])
+    assert ref_moco.bn_masked(torch.ones(1, 6), y, True).tolist() == [[1.0, 0.0, 0.0, 0.0, 0.0, 1.0]]
+    assert ref_moco.bn_masked(torch.ones(1, 6), y, False).tolist() == [[1.0] * 6]
+    for prec in ref_moco.BN_DTYPES:                                      # the hand-built y of the case matrix holds all five kinds
+        yh = ref_moco.bn_case_inputs(prec, 5, 7, "plain")[2].float()
+        assert bool((yh > 0).any()) and bool((yh < 0).any()) and bool(torch.isnan(yh).any())
+        zeros = yh[yh == 0]
+        assert bool(torch.signbit(zeros).any()) and not bool(torch.signbit(zeros).all())
+
+
+def test_bn_combine_restatement_is_the_statistics_of_the_concatenated_batch_and_skips_empty_ranks():
+    C = 5
+    for name, counts in ref_moco.BN_COMBINE_COUNTS.items():
+        g = torch.Generator().manual_seed(len(counts))
+        parts = [torch.randn(k, C, generator=g, dtype=torch.float64) * 3 + w for w, k in enumerate(counts)]
+        st = [ref_moco.bn_stats(p) for p in parts]
+        means, m2s, cnt = torch.stack([s[0] for s in st]), torch.stack([s[1] for s in st]), torch.tensor(counts, dtype=torch.float64)
+        allx = torch.cat(parts)
+        rm, rv = torch.zeros(C, dtype=torch.float64), torch.ones(C, dtype=torch.float64)
+        F.batch_norm(allx, rm, rv, training=True, momentum=0.37, eps=1e-3)
+        want = (allx.mean(0), 1.0 / torch.sqrt(allx.var(0, unbiased=False) + 1e-3), rm, rv)
+        got = ref_moco.bn_combine(means, m2s, cnt, 1e-3, 0.37, torch.zeros(C), torch.ones(C))
+        assert all(rel(a, b) < PIN for a, b in zip(got, want)), name
+        # the rank-by-rank statement of the same (bn_chan_combine) agrees
+        chan = ref_moco.bn_chan_combine(torch.cat([torch.cat([m, q, k[None]]) for m, q, k in zip(means, m2s, cnt)]), C, 1e-3)
+        assert rel(chan[0], got[0]) < PIN and rel(chan[2], got[1]) < PIN
+        for pos in (0, len(counts) // 2, len(counts)):                   # an empty rank with garbage in it changes nothing, wherever it stands
+            m9 = torch.cat([means[:pos], torch.full((1, C), 1e30, dtype=torch.float64), means[pos:]])
+            q9 = torch.cat([m2s[:pos], torch.full((1, C), 7.0, dtype=torch.float64), m2s[pos:]])
+            k9 = torch.cat([cnt[:pos], torch.zeros(1, dtype=torch.float64), cnt[pos:]])
+            again = ref_moco.bn_combine(m9, q9, k9, 1e-3, 0.37, torch.zeros(C), torch.ones(C))
+            assert all(torch.equal(a, b) for a, b in zip(again, got)), (name, pos)
+            f32 = ref_moco.bn_combine_f32(m9, q9, k9, 1e-3)
+            assert all(torch.equal(a, b) for a, b in zip(f32, ref_moco.bn_combine_f32(means, m2s, cnt, 1e-3))), (name, pos)
+
+
+def test_bn_float32_floors_stay_under_a_quarter_of_the_gates():
+    """The float32 restatements of the two-pass statistics and of the combine over the case matrix of tests/test_bn_edges_gpu.py, against float64: what
+    float32 itself costs, before any kernel.  A quarter of the gate at most, or the input is badly chosen; the figures stand above the gates there."""
+    gpu = _gpu_test_module("test_bn_edges_gpu")
+    assert gpu.STAT_GATE <= 5e-5 and gpu.COMBINE_GATE <= 2e-5
+    assert all(gpu.OUT_GATE[p] <= t for p, t in (("f32", 5e-5), ("fp16", 2e-3), ("bf16", 1.6e-2)))
+    for prec, dt in ref_moco.BN_DTYPES.items():
+        floor, col, one_pass, out, dx_floor, dx2_own, dx2_terms = 0.0, 0.0, float("inf"), 0.0, 0.0, 0.0, 0.0
+        for C in ref_moco.BN_C:
+            for n in ref_moco.BN_N:
+                for family in ("plain", "edge"):
+                    x, dy, y, gamma, beta = ref_moco.bn_case_inputs(prec, n, C, family)
+                    (mu, q), (r_mu, r_q) = ref_moco.bn_stats_f32(x), ref_moco.bn_stats(x)
+                    floor = max(floor, rel(mu, r_mu), rel(q, r_q))
+                    if family == "edge" and C > 1 and n > 1:               # the mean >> std column on its own scale, and what one pass would give
+                        col = max(col, float((mu[1] - r_mu[1]).abs() / r_mu[1].abs()), float((q[1] - r_q[1]).abs() / r_q[1].clamp_min(1e-30)))
+                        if n >= 15:
+                            q1 = ref_moco.bn_stats_f32(x, one_pass=True)[1]
+                            one_pass = min(one_pass, float((q1[1] - r_q[1]).abs() / r_q[1]))
+                    r_mean, r_is, _, _ = ref_moco.bn_combine(r_mu[None], r_q[None], torch.tensor([float(n)]))
+                    r_y = ref_moco.bn_apply(x, r_mean, r_is, gamma, beta, True)
+                    if float(r_y.abs().max()) > 0:
+                        out = max(out, rel(r_y.to(dt), r_y))
+                    # dx in float32 from float32-rounded statistics and sums, before the rounding to the element type
+                    m32, i32 = r_mean.float(), r_is.float()
+                    s1, s2 = (t.float() for t in ref_moco.bn_bwd_sums(dy, x, y, m32, i32, True))
+                    args = (dy, x, y, m32, i32, gamma, True, s1, s2, float(np.float32(1.0 / n)))
+                    r_dx, dx32 = ref_moco.bn_bwd_apply(*args), ref_moco.bn_bwd_apply_f32(*args)
+                    if n == 2:
+                        dx2_own = max(dx2_own, rel(dx32, r_dx))
+                        dx2_terms = max(dx2_terms, float((dx32.double() - r_dx).abs().max()) / max(ref_moco.bn_bwd_apply_terms(*args), 1e-30))
+                    elif n > 2:
+                        dx_floor = max(dx_floor, rel(dx32, r_dx))
+        print(f"bn statistics[{prec}]: float32 two-pass restatement vs float64 max {floor:.2e}; mean >> std column (ratio {ref_moco.BN_RATIO[prec]:g}) "
+              f"{col:.2e} on its own scale, one pass at least {one_pass:.2e} (gate {gpu.STAT_GATE:.0e}); y rounded to {prec} {out:.2e} (gate {gpu.OUT_GATE[prec]:.0e})")
+        print(f"bn dx[{prec}] in float32, before its rounding to {prec}: n >= 15 max {dx_floor:.2e}; n = 2 {dx2_own:.2e} of its own size (it vanishes identically), "
+              f"{dx2_terms:.2e} of its terms")
+        # the mean >> std column stays under a quarter of the gate; the whole matrix under the gate and under a quarter of the ceiling (the kernels
+        # are no less exact than this restatement, so a gate of 4 x what they measure cannot be 4 x this floor as well)
+        assert col < gpu.STAT_GATE / 4 and floor < min(gpu.STAT_GATE, 5e-5 / 4)
+        assert max(dx_floor, dx2_terms) < 5e-5 / 4 < dx2_own
+        assert out < gpu.OUT_GATE[prec] / 4 or prec != "f32"               # (the 16-bit outputs: their rounding IS the error; see OUT_GATE)
+        if prec == "f32":
+            assert one_pass > 10 * gpu.STAT_GATE                           # the second pass earns its keep: one pass is told apart by the gate
+    worst = 0.0
+    for C in (1, 5, 256, 257, 1028):
+        for counts in ref_moco.BN_COMBINE_COUNTS.values():
+            means, m2s, cnt = ref_moco.bn_combine_inputs(C, counts)
+            for eps in (1e-5, 1e-3):
+                mu, invstd, unb = ref_moco.bn_combine_f32(means, m2s, cnt, eps)
+                r = ref_moco.bn_combine(means, m2s, cnt, eps, 0.1, torch.zeros(C), torch.zeros(C))
+                worst = max(worst, rel(mu, r[0]), rel(invstd, r[1]), rel(0.1 * unb.double(), r[3]))
+    print(f"bn combine: float32 rank-by-rank restatement vs float64 max {worst:.2e} (gate {gpu.COMBINE_GATE:.0e})")
+    assert worst < min(gpu.COMBINE_GATE, 2e-5 / 4)                         # (the kernel measures what this restatement does: the gate is 4 x this floor)
+
+
+# ------------------------------------------------------------------------------------------------ 4. the small cross entropies (tests/test_ce_small_gpu.py)
+def test_ce_small_float32_floor_and_case_matrix():
+    """ce_small_kernel restated in float32 with exact exp / log over the case matrix of tests/test_ce_small_gpu.py, by that test's own measures: the
+    floor of CE_SMALL_GATE.  And the matrix holds what it says: targets in column 0 and C - 1, tie rows whose first maximum is column C // 3,
+    saturated rows with a tiny loss beside rows with a large one."""
+    gpu = _gpu_test_module("test_ce_small_gpu")
+    assert all(v <= 2e-5 for v in gpu.CE_SMALL_GATE.values())
+    floor = dict(loss=0.0, dlogits=0.0)
+    for C in ref_moco.CE_SMALL_C:
+        for B in ref_moco.CE_SMALL_B:
+            for scale in ref_moco.CE_SMALL_SCALES:
+                z, t = ref_moco.ce_small_case(B, C, scale)
+                zd = z.double().requires_grad_(True)
+                rows = F.cross_entropy(zd, t, reduction="none")
+                rows.mean().backward()
+                if B > 1:
+                    assert int(t[0]) == 0 and int(t[-1]) == C - 1 and int(z.max(1)[1][1]) == C // 3 and (C == 1 or float(z[1, C // 3]) == float(z[1, C - 1]))
+                if scale > 1 and C > 2 and B > 1000:
+                    assert float(rows.detach().min()) < 1e-6 and float(rows.detach().max()) > 50.0
+                loss, d = ref_moco.ce_small_f32(z, t)
+                e = gpu.errors(loss, d, float(rows.detach().mean()), zd.grad, float(rows.detach().max()), scale, B)
+                floor = {k: max(floor[k], e[k]) for k in floor}
+    print(f"small cross entropy: float32 restatement vs float64 max loss {floor['loss']:.2e} dlogits {floor['dlogits']:.2e} (gates {gpu.CE_SMALL_GATE})")
+    assert all(v < min(gpu.CE_SMALL_GATE[k], 2e-5 / 4) for k, v in floor.items())
