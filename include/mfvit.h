@@ -488,13 +488,20 @@ int mfvit_attr_finish(const float* acc, const float* x, const float* base, int b
  * Fus_CrossViT.forward (FUS:126-157).  dim 384 or 768 (vit_small / vit_base), heads 3, 6 or 12 (head_dim = dim / heads); any other
  * value gives MFVIT_EINVAL / 0 bytes.  mfvit_fusion_* run one exchange layer with pool='cls'; the mfvit_fusion_ex_* entry points below
  * add cross_attn_depth and pool='mean'.
+ * Ranges: batch >= 1 (no upper limit), num_classes 1 .. 64, tokens 2 .. T_max(dim, heads).  T_max is set by the 160 KB of LDS a streaming
+ * pass may request - per (sample, direction) the rows' statistics, scores and score gradients of all heads stay in LDS:
+ *   backward          32 T + 160 dim bytes                                     (every head count)
+ *   token gradient    4 (max(2 heads dim + 2 heads T, 16 dim) + 2 T) bytes     (heads 6 and 12 only)
+ *   T_max:  dim 384: heads 3: 3200, 6: 2596, 12: 1220        dim 768: heads 3: 1280, 6: 1280, 12: 866
+ * (vit_base at 384 x 384 pixels, tokens 577, fits at every head count.)  A larger token count is refused like any other value outside the
+ * ranges: MFVIT_EINVAL before any HIP call from every entry point of this section, 0 from the *_param_count / *_workspace_bytes queries.
  * ------------------------------------------------------------------------------------------------------------ */
 typedef struct mfvit_fusion_cfg {
-    int batch;
-    int tokens;       /* 1 + patches (197 at 224^2) */
+    int batch;        /* >= 1 */
+    int tokens;       /* 1 + patches (197 at 224^2): 2 .. T_max(dim, heads), see above */
     int dim;          /* 384 or 768 */
     int heads;        /* 3 (FUS:75), 6 or 12 -> head_dim = dim / heads */
-    int num_classes;  /* 3 */
+    int num_classes;  /* 1 .. 64 (3 in the reference) */
     float eps_pre;    /* 1e-5: PreNorm's nn.LayerNorm default (MOD:18) */
     float eps_post;   /* 1e-6: FUS:26,31 */
 } mfvit_fusion_cfg;

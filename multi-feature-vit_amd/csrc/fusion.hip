@@ -84,6 +84,12 @@ FusWs fus_ws(int B, int T, int C, int D, int NH) {
 }
 
 // ---------------------------------------------------------------------------------------------- kernels
+// Mean of a row from its sum: a true division.  sum * (1.f / D) carries the rounding of 1 / D, and with that product contracted into the
+// subtraction x - mean (an fma) the error survives even where sum / D is exact: an exactly constant row came out as
+// beta - 2^-26 x rstd gamma instead of beta (1.5e-5 gamma under the post-norm's eps of 1e-6), which the next layer's LayerNorm of that row
+// (spread 0.05) turned into 3e-4 (tests/test_fusion_edges_gpu.py, the constant_row case on the full-row path).
+template <int D> __device__ __forceinline__ float row_mean(float sum) { return sum / (float)D; }
+
 // z0[dir][b] = LN_pre(own cls row); one wave per (b, dir)
 template <int D>
 __global__ __launch_bounds__(64) void x_cls_ln_kernel(const float* __restrict__ fc, const float* __restrict__ fe,
@@ -103,7 +109,7 @@ __global__ __launch_bounds__(64) void x_cls_ln_kernel(const float* __restrict__ 
         if (lane == 0) { st0[((long)dir * B + b) * 2] = 0.f; st0[((long)dir * B + b) * 2 + 1] = 1.f; }
         return;
     }
-    const float mu = wave_sum(s) * (1.f / D);
+    const float mu = row_mean<D>(wave_sum(s));
     float q = 0.f;
 #pragma unroll
     for (int i = 0; i < NPL; ++i) { const float d = v[i] - mu; q += d * d; }
@@ -146,7 +152,7 @@ __global__ __launch_bounds__(XW * 64) void x_stream_fwd_kernel(const float* __re
         float v[NPL], s = 0.f;
 #pragma unroll
         for (int i = 0; i < NPL; ++i) { v[i] = row[lane + 64 * i]; s += v[i]; }
-        const float mu = L.no_norm ? 0.f : wave_sum(s) * (1.f / D);
+        const float mu = L.no_norm ? 0.f : row_mean<D>(wave_sum(s));
         float q = 0.f;
 #pragma unroll
         for (int i = 0; i < NPL; ++i) { v[i] -= mu; q += v[i] * v[i]; }
@@ -231,7 +237,7 @@ __global__ __launch_bounds__(128) void x_finish_fwd_kernel(const float* __restri
     float c0[NPL], v[NPL], s = 0.f;
 #pragma unroll
     for (int i = 0; i < NPL; ++i) { c0[i] = cls[lane + 64 * i]; v[i] = c0[i] + op[lane + 64 * i]; s += v[i]; }
-    const float mu = wave_sum(s) * (1.f / D);
+    const float mu = row_mean<D>(wave_sum(s));
     float q = 0.f;
 #pragma unroll
     for (int i = 0; i < NPL; ++i) { v[i] -= mu; q += v[i] * v[i]; }
@@ -614,7 +620,7 @@ __global__ __launch_bounds__(XW * 64) void x_rows_fwd_kernel(const float* __rest
             v[i] = own[(long)t * D + lane + 64 * i] + (t == 0 ? outp[sb * D + lane + 64 * i] : 0.f);
             s += v[i];
         }
-        const float mu = wave_sum(s) * (1.f / D);
+        const float mu = row_mean<D>(wave_sum(s));
         float q = 0.f;
 #pragma unroll
         for (int i = 0; i < NPL; ++i) { v[i] -= mu; q += v[i] * v[i]; }
@@ -911,9 +917,22 @@ constexpr int MAX_XDEPTH = 16;   // cross_attn_depth accepted by the _ex entry p
 #define FUS_TRY(expr) do { int rc__ = (expr); if (rc__ != MFVIT_OK) return rc__; } while (0)
 #define FUS_BY_DIM(dim, CALL) ((dim) == 384 ? CALL<384> : CALL<768>)
 
+// Dynamic LDS (bytes) of the streaming passes, one helper per launch: the launch requests exactly this, and fus_ok refuses a token count whose
+// passes would need more than the FUS_MAX_LDS they may request (max_lds) - before any HIP call, instead of a launch error in mid-call.
+constexpr size_t FUS_MAX_LDS = 160 * 1024;
+size_t lds_stream_fwd(int D, int T) { return (size_t)(5L * T + (long)(D == 384 ? xw_fwd<384>() : xw_fwd<768>()) * NH * D) * 4; }
+size_t lds_stream_bwd(int D, int T) { return (size_t)(8L * T + (long)XW_BWD * 5 * D) * 4; }
+size_t lds_stream_dz(int D, int T, int nh) {   // (the layout x_stream_dz_kernel derives for itself)
+    const long big = 2L * nh * D + 2L * nh * T, redn = (long)XW_DZ * 2 * D;
+    return (size_t)((big > redn ? big : redn) + 2L * T) * 4;
+}
+bool fus_lds_ok(int D, int T, int nh) {
+    return lds_stream_fwd(D, T) <= FUS_MAX_LDS && lds_stream_bwd(D, T) <= FUS_MAX_LDS && (nh == NH || lds_stream_dz(D, T, nh) <= FUS_MAX_LDS);
+}
+
 bool fus_ok(const mfvit_fusion_cfg* c) {
     return c && c->batch > 0 && c->tokens > 1 && (c->dim == 384 || c->dim == 768) && (c->heads == 3 || c->heads == 6 || c->heads == 12) &&
-           c->num_classes > 0 && c->num_classes <= 64;
+           c->num_classes > 0 && c->num_classes <= 64 && fus_lds_ok(c->dim, c->tokens, c->heads);
 }
 bool fus_ex_ok(const mfvit_fusion_cfg* c, int depth, int pool_mean) {
     return fus_ok(c) && depth >= 1 && depth <= MAX_XDEPTH && (pool_mean == 0 || pool_mean == 1);
@@ -958,7 +977,7 @@ FusExWs fus_ex_ws(int B, int T, int C, int D, int NH, int depth) {
 }
 
 template <typename K> void max_lds(K* kern, PerDeviceOnce& once) {
-    if (once.first()) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (once.first()) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FUS_MAX_LDS);
 }
 
 }  // namespace
@@ -993,7 +1012,7 @@ static int xattn_core_forward(int ndir, int nh, const FusLayout& L, const FusWs&
     }
     {
         constexpr int XW = xw_fwd<D>();
-        const size_t lds = (size_t)(5 * T + XW * NH * D) * 4;
+        const size_t lds = lds_stream_fwd(D, T);
         static PerDeviceOnce attr1, attrc;
         ProfScope ps(PROF_XATTN_FWD, 0, 2.0 * B * T * D * 4 * 2 * (nh / NH), st);
         if (nh == NH) {
@@ -1032,6 +1051,12 @@ static int fus_prenorm_job(int D, int dir, const FusLayout& L, const FusWs& W, f
     return colpart_reduce(ws + W.pd + (long)dir * 2 * B * 2 * D, 2 * B, D, 2, dparams + L.ca[dir] + L.n_w, dparams + L.ca[dir] + L.n_b, nullptr, st);
 }
 
+// A weight gradient of the exchange, dW += A^T X over the batch rows (f32, plain operands), on gemm_small.hip's kernel at EVERY batch: one
+// workgroup per 32 x 32 output tile sums all rows in a fixed order and adds the total into dparams once.  gemm_tn hands more than 512 rows to the
+// 128 x 128 tile kernel, which splits the rows over several workgroups and - batch addressing (nb > 1) leaves it no partial scratch - adds them by
+// float atomics in arrival order; in one split it would be 9 to 36 workgroups walking every row, where this is 144 and more.
+static int fus_wgrad(const GemmP& p, hipStream_t st) { return gemm_tn_small(p, st); }
+
 // backward of xattn_core_forward: consumes ws.dout (= d outp) and ws.dqp (cls gradient that bypasses the attention)
 template <int D>
 static int xattn_core_backward(int ndir, int nh, const FusLayout& L, const FusWs& W, const float* params, const float* f_cxr,
@@ -1044,7 +1069,7 @@ static int xattn_core_backward(int ndir, int nh, const FusLayout& L, const FusWs
         p.A = ws + W.dout; p.lda = D; p.W = ws + W.o; p.ldw = D; p.M = B; p.N = D; p.K = D;
         p.out0 = dparams + L.ca[0] + L.wp; p.ldo0 = D;
         p.nb = ndir; p.nbi = 1; p.sAo = (long)B * D; p.sWo = (long)B * D; p.sOo = L.ca_stride;
-        FUS_TRY(gemm_tn(MFVIT_F32, p, st));
+        FUS_TRY(fus_wgrad(p, st));
     }
     {   // do = dout Wp   (W operand = WpT)
         GemmP p = zg();
@@ -1058,7 +1083,7 @@ static int xattn_core_backward(int ndir, int nh, const FusLayout& L, const FusWs
         p.A = ws + W.dob; p.lda = D; p.W = ws + W.u; p.ldw = nh * D; p.M = B; p.N = DH; p.K = D;
         p.out0 = dparams + L.ca[0] + L.wv; p.ldo0 = D;
         p.nb = ndir * nh; p.nbi = nh; p.sAo = (long)B * D; p.sAi = DH; p.sWo = (long)B * nh * D; p.sWi = D; p.sOo = L.ca_stride; p.sOi = (long)DH * D;
-        FUS_TRY(gemm_tn(MFVIT_F32, p, st));
+        FUS_TRY(fus_wgrad(p, st));
     }
     {   // du_h = do_h Wv_h   (W operand = WvT[:, h*DH ..])
         GemmP p = zg();
@@ -1068,7 +1093,7 @@ static int xattn_core_backward(int ndir, int nh, const FusLayout& L, const FusWs
         FUS_TRY(gemm_nt_tile(MFVIT_F32, EPI_NONE, p, st));
     }
     {
-        const size_t lds = (size_t)(8 * T + XW_BWD * 5 * D) * 4;
+        const size_t lds = lds_stream_bwd(D, T);
         static PerDeviceOnce attr1, attrc, attrz;
         ProfScope ps(PROF_XATTN_BWD, 0, 2.0 * B * T * D * 4 * 3 * (nh == NH ? 1 : nh / NH + 1), st);
         if (nh == NH) {
@@ -1081,8 +1106,7 @@ static int xattn_core_backward(int ndir, int nh, const FusLayout& L, const FusWs
             MFVIT_LAUNCH((x_stream_bwd_kernel<XW_BWD, D, true>), dim3(B, ndir, nh / NH), dim3(XW_BWD * 64), lds, st, f_cxr, f_enh, params, L, scale,
                                B, T, ws + W.kq, ws + W.a, ws + W.st, ws + W.du, ws + W.dkq, ws + W.dz0p, ws + W.pd, df_cxr, df_enh, ws + W.ds);
             MFVIT_CHECK_LAUNCH();
-            const long big = 2L * nh * D + 2L * nh * T, redn = (long)XW_DZ * 2 * D;
-            const size_t ldz = (size_t)((big > redn ? big : redn) + 2L * T) * 4;
+            const size_t ldz = lds_stream_dz(D, T, nh);
             max_lds((x_stream_dz_kernel<XW_DZ, D>), attrz);
             MFVIT_LAUNCH((x_stream_dz_kernel<XW_DZ, D>), dim3(B, ndir), dim3(XW_DZ * 64), ldz, st, f_cxr, f_enh, params, L, scale, B, T, nh,
                                ws + W.kq, ws + W.a, ws + W.st, ws + W.du, ws + W.ds, ws + W.dz0p, ws + W.pd, df_cxr, df_enh);
@@ -1094,7 +1118,7 @@ static int xattn_core_backward(int ndir, int nh, const FusLayout& L, const FusWs
         p.A = ws + W.qv; p.lda = D; p.W = ws + W.dkq; p.ldw = nh * D; p.M = B; p.N = DH; p.K = D;
         p.out0 = dparams + L.ca[0] + L.wk; p.ldo0 = D;
         p.nb = ndir * nh; p.nbi = nh; p.sAo = (long)B * D; p.sAi = DH; p.sWo = (long)B * nh * D; p.sWi = D; p.sOo = L.ca_stride; p.sOi = (long)DH * D;
-        FUS_TRY(gemm_tn(MFVIT_F32, p, st));
+        FUS_TRY(fus_wgrad(p, st));
     }
     {   // dqv_h = dkq_h Wk_h^T
         GemmP p = zg();
@@ -1108,7 +1132,7 @@ static int xattn_core_backward(int ndir, int nh, const FusLayout& L, const FusWs
         p.A = ws + W.dqv; p.lda = D; p.W = ws + W.z0; p.ldw = D; p.M = B; p.N = D; p.K = D;
         p.out0 = dparams + L.ca[0] + L.wq; p.ldo0 = D;
         p.nb = ndir; p.nbi = 1; p.sAo = (long)B * D; p.sWo = (long)B * D; p.sOo = L.ca_stride;
-        FUS_TRY(gemm_tn(MFVIT_F32, p, st));
+        FUS_TRY(fus_wgrad(p, st));
     }
     {   // dz0q = dqv Wq   (W operand = WqT)
         GemmP p = zg();

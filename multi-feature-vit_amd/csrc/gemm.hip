@@ -1296,7 +1296,7 @@ int gemm_nt_tile(int dtype, int epi, const GemmP& p, hipStream_t st) {
         if (rc != MFVIT_OK) return rc;
         return colpart_reduce(p.cpart, (p.M + 127) / 128, p.N, 1, p.cs0, nullptr, nullptr, st);
     }
-    if (gemm_nt_small_supported(dtype, epi, p)) return gemm_nt_small(epi, p, st);   // gemm_small.hip: f32, M <= 512
+    if (gemm_nt_small_supported(dtype, epi, p)) return gemm_nt_small(epi, p, st);   // gemm_small.hip: f32, M <= 512 - and any M where N % 128 != 0 (no tile kernel takes that)
     switch (epi) {
         case EPI_BIAS: return tile_by_dtype<EPI_BIAS>(dtype, p, st);
         case EPI_BIAS_GELU: return tile_by_dtype<EPI_BIAS_GELU>(dtype, p, st);

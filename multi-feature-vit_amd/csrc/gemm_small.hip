@@ -7,7 +7,8 @@
 // added through LDS.  M = 128, N = K = 384, two directions: 96 workgroups x 48 MFMAs per wave.
 //   * NT (y = x W^T + b): a lane loads 16 contiguous bytes of its row (k .. k+3 for lanes 0 - 31, k+4 .. k+7 for lanes 32 - 63) of both
 //     operands and feeds four MFMAs; which k an MFMA's two lane halves hold is free as long as both operands agree.
-//   * TN (dW[n][k] += sum_m dy[m][n] x[m][k], float atomics like gemm_tn_kernel): 4-byte loads, 128 bytes contiguous per half-wave.
+//   * TN (dW[n][k] += sum_m dy[m][n] x[m][k]): 4-byte loads, 128 bytes contiguous per half-wave.  No splits: the workgroup sums every row of its
+//     tile in a fixed order and adds the total to dW with ONE atomic per element, so the result is the same bits on every run, at any M.
 // Same GemmP batch addressing as the tile kernels (apply_batch); no epilogue beyond the bias.
 #include "gemm.cuh"
 #include "kernels.h"
@@ -17,7 +18,7 @@ namespace mfvit {
 
 namespace {
 
-constexpr int SM_MAX_ROWS = 512;          // above that the 128 x 128 tiles fill the chip better
+constexpr int SM_MAX_ROWS = 512;          // above that the 128 x 128 tiles fill the chip better - where they can take the shape at all
 
 __device__ __forceinline__ f32x16 mma_f32(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
 
@@ -152,7 +153,10 @@ bool small_switch() { return true; }   // (round 4 A/B: 27 - 36 us -> 6 - 9 us p
 
 bool gemm_nt_small_supported(int dtype, int epi, const GemmP& p) {
     if (dtype != MFVIT_F32 || (epi != EPI_NONE && epi != EPI_BIAS) || !plain(p) || !small_switch()) return false;
-    if (p.M <= 0 || p.M > SM_MAX_ROWS || p.K % 32 || p.lda % 4 || p.ldw % 4) return false;
+    if (p.M <= 0 || p.K % 32 || p.lda % 4 || p.ldw % 4) return false;
+    // more rows than SM_MAX_ROWS stay here when launch_tile<float> (gemm.hip: N % 128 == 0) has no kernel for the shape: the per-head products of
+    // the exchange at head_dim 32 / 64 (N = head_dim) would otherwise be refused at batch > 512
+    if (p.M > SM_MAX_ROWS && p.N % 128 == 0) return false;
     if ((((uintptr_t)p.A | (uintptr_t)p.W) & 15) || ((p.sAo | p.sAi | p.sWo | p.sWi) & 3)) return false;
     return epi == EPI_NONE || p.bias != nullptr;
 }
@@ -172,6 +176,7 @@ int gemm_nt_small(int epi, GemmP p, hipStream_t st) {
 }
 
 bool gemm_tn_small_supported(int dtype, const GemmP& p) {
+    // (what gemm_tn sends here.  The kernel itself takes any M: the exchange's weight gradients call gemm_tn_small directly at every batch, fusion.hip::fus_wgrad)
     return dtype == MFVIT_F32 && plain(p) && !p.bias && small_switch() && p.M > 0 && p.M <= SM_MAX_ROWS;
 }
 int gemm_tn_small(GemmP p, hipStream_t st) {

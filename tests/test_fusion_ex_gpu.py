@@ -9,6 +9,7 @@ import torch
 
 from conftest import check_sampled, rng_tensor
 from oracle import ref_fusion, ref_vit
+from oracle.ref_fusion import fus_ex_fused as ref_fus_forward
 
 pytestmark = pytest.mark.gpu
 FUS_MOD = ("model.crossvit_2vits_2additionaloutputs_changenormlayer_location_removeextralclayer_"
@@ -127,23 +128,6 @@ def test_standalone_exchange_against_reference_golden(golden, case):
     check_grad(g, "d.xl", xl.grad)
     for n, p in enc.named_parameters():
         check_grad(g, "d." + n, p.grad)
-
-
-def ref_fus_forward(p, fc, fe, heads, L, pool, M):
-    """Fus_CrossViT.forward (FUS:126-157) from features, float64, on oracle.ref_fusion.cross_attention / oracle.ref_vit.layer_norm."""
-    ln = ref_vit.layer_norm
-    xs, xl = fc, fe
-    for l in range(L):
-        P = f"multi_scale_transformers.{M - 1}.cross_attn_layers.{l}."
-        sc, x_small, lc, x_large = xs[:, :1], xs[:, 1:], xl[:, :1], xl[:, 1:]
-        y = ln(torch.cat((lc, x_small), 1), p[P + "2.norm.weight"], p[P + "2.norm.bias"], 1e-5)
-        xl_n = ln(torch.cat((lc + ref_fusion.cross_attention(p, P + "2.fn.", y, heads), x_large), 1), p[P + "1.weight"], p[P + "1.bias"], 1e-6)
-        y = ln(torch.cat((sc, x_large), 1), p[P + "0.norm.weight"], p[P + "0.norm.bias"], 1e-5)
-        xs_n = ln(torch.cat((sc + ref_fusion.cross_attention(p, P + "0.fn.", y, heads), x_small), 1), p[P + "3.weight"], p[P + "3.bias"], 1e-6)
-        xs, xl = xs_n, xl_n
-    cf, ef = fc + xs, fe + xl
-    cc, ec = (cf.mean(1), ef.mean(1)) if pool == "mean" else (cf[:, 0], ef[:, 0])
-    return (cc @ p["mlp_head_cxr.0.weight"].t() + p["mlp_head_cxr.0.bias"]) + (ec @ p["mlp_head_enh.0.weight"].t() + p["mlp_head_enh.0.bias"])
 
 
 def vit_base_ca(precision, L=1, pool="cls", M=1, heads=3, seed=1801):
