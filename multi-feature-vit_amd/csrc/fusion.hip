@@ -907,25 +907,24 @@ __global__ __launch_bounds__(XW * 64) void x_grad_map_kernel(const float* __rest
     for (int t = threadIdx.x; t < T; t += XW * 64) abar[sb * T + t] = acc[t] / (float)nh;
 }
 
-GemmP zg() { GemmP p; memset(&p, 0, sizeof(p)); return p; }
-
 // waves per workgroup of the streaming passes: the same bytes in flight per CU at both widths (a D = 768 row is twice a D = 384 row; the
 // backward holds ~100 registers per lane at D = 384, ~180 at D = 768)
 template <int D> constexpr int xw_fwd() { return D == 384 ? 16 : 8; }
 constexpr int XW_BWD = 8, XW_DZ = 8, XW_ROWS = 8;
 constexpr int MAX_XDEPTH = 16;   // cross_attn_depth accepted by the _ex entry points
-#define FUS_TRY(expr) do { int rc__ = (expr); if (rc__ != MFVIT_OK) return rc__; } while (0)
 #define FUS_BY_DIM(dim, CALL) ((dim) == 384 ? CALL<384> : CALL<768>)
 
 // Dynamic LDS (bytes) of the streaming passes, one helper per launch: the launch requests exactly this, and fus_ok refuses a token count whose
 // passes would need more than the FUS_MAX_LDS they may request (max_lds) - before any HIP call, instead of a launch error in mid-call.
 constexpr size_t FUS_MAX_LDS = 160 * 1024;
-size_t lds_stream_fwd(int D, int T) { return (size_t)(5L * T + (long)(D == 384 ? xw_fwd<384>() : xw_fwd<768>()) * NH * D) * 4; }
+template <int D> size_t lds_stream_fwd_of(int T) { return (size_t)(5L * T + (long)xw_fwd<D>() * NH * D) * 4; }
+size_t lds_stream_fwd(int D, int T) { return FUS_BY_DIM(D, lds_stream_fwd_of)(T); }
 size_t lds_stream_bwd(int D, int T) { return (size_t)(8L * T + (long)XW_BWD * 5 * D) * 4; }
 size_t lds_stream_dz(int D, int T, int nh) {   // (the layout x_stream_dz_kernel derives for itself)
     const long big = 2L * nh * D + 2L * nh * T, redn = (long)XW_DZ * 2 * D;
     return (size_t)((big > redn ? big : redn) + 2L * T) * 4;
 }
+size_t lds_grad_map(int T) { return (size_t)3 * T * 4; }   // x_grad_map_kernel: the rows' statistics and the map (tokens <= MAX_MAP_TOKENS)
 bool fus_lds_ok(int D, int T, int nh) {
     return lds_stream_fwd(D, T) <= FUS_MAX_LDS && lds_stream_bwd(D, T) <= FUS_MAX_LDS && (nh == NH || lds_stream_dz(D, T, nh) <= FUS_MAX_LDS);
 }
@@ -940,14 +939,14 @@ bool fus_ex_ok(const mfvit_fusion_cfg* c, int depth, int pool_mean) {
 // the full-row path: every row of every layer's post-LN is live (the default cls / one-layer form needs row 0 only)
 bool fus_full(int depth, int pool_mean) { return depth > 1 || pool_mean; }
 
-// layer l of an arena of `depth` exchange layers followed by the two heads: layer l is the block of fus_layout at l (8 D^2 + 10 D floats)
-FusLayout fus_layer_layout(int D, int C, int depth, int l) {
+// An arena of `depth` exchange layers followed by the two heads, as layer 0 sees it.  A layer is the block of fus_layout (FUS_LAYER floats);
+// layer l is layer 0 moved up by l of them (FusCtx::layer).  depth = 1 is fus_layout itself, field for field.
+long fus_layer_floats(int D) { return 8L * D * D + 10L * D; }
+FusLayout fus_arena_layout(int D, int C, int depth) {
     FusLayout L = fus_layout(D, C);
-    const long lay = 8L * D * D + 10L * D;
-    for (int dir = 0; dir < 2; ++dir) { L.ca[dir] += l * lay; L.post[dir] += l * lay; }
-    L.head[0] = depth * lay;
+    L.head[0] = depth * fus_layer_floats(D);
     L.head[1] = L.head[0] + (long)C * D + C;
-    L.total = depth * lay + 2 * ((long)C * D + C);
+    L.total = depth * fus_layer_floats(D) + 2 * ((long)C * D + C);
     return L;
 }
 
@@ -980,36 +979,140 @@ template <typename K> void max_lds(K* kern, PerDeviceOnce& once) {
     if (once.first()) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)FUS_MAX_LDS);
 }
 
+// ------------------------------------------------------------------------------------------------ per-call context of the entry points
+// the caller's tensors (include/mfvit.h); whatever a call does not have stays NULL
+struct FusHeads { const float *w_cxr, *b_cxr, *w_enh, *b_enh; };   // the backbones' own classifier heads (the biases: forward only)
+struct FusOut { float *fused, *x_cxr, *x_enh; };
+struct FusGradIn { const float *dfused, *dx_cxr, *dx_enh; };
+struct FusGradOut { float *df_cxr, *df_enh, *dhw_cxr, *dhb_cxr, *dhw_enh, *dhb_enh; };
+
+// one exchange layer as its kernels see it
+struct FusLayer {
+    FusLayout L;            // parameter offsets of the layer's blocks (and of the heads behind the last layer)
+    float* ws;              // its FusWs (full-row path: its slab, the FusExWs offsets up to `slab` included)
+    const float *xc, *xe;   // its input rows: the features, or the rows of the layer below
+    const float* dY;        // backward of the full-row path: the gradient of its output rows (NULL: the top layer) ...
+    float *dxc, *dxe;       // ... and, every backward, of its input rows: the caller's df_* at layer 0
+};
+
+struct FusCtx {
+    int B, T, C, D, nh, DH;
+    int ndir;               // 2: the model; 1: a stand-alone block (mfvit_prenorm_xattn_* / mfvit_xattn_*)
+    int depth, pool_mean;
+    float scale, eps_pre, eps_post;
+    hipStream_t st;
+    const float* params;
+    float* dparams;
+    const float *f_cxr, *f_enh;
+    float* ws;
+    FusLayout L0;           // layer 0
+    FusWs W;
+    FusExWs E;              // full-row path only (all zero otherwise: layer 0 is the workspace itself)
+    FusHeads heads;
+    FusOut out;
+    FusGradIn gin;
+    FusGradOut gout;
+
+    // the one place that knows where a layer's parameters, workspace, input rows and row gradients are
+    FusLayer layer(int l) const {
+        const long btd = (long)B * T * D;
+        FusLayer v;
+        v.L = L0;
+        for (int dir = 0; dir < 2; ++dir) { v.L.ca[dir] += l * fus_layer_floats(D); v.L.post[dir] += l * fus_layer_floats(D); }
+        v.ws = ws + l * E.slab;
+        v.xc = l == 0 ? f_cxr : ws + (l - 1) * E.slab + E.Y;
+        v.xe = l == 0 ? f_enh : v.xc + btd;
+        v.dY = l == depth - 1 ? nullptr : ws + E.dx + ((l + 1) & 1) * 2 * btd;
+        v.dxc = l == 0 ? gout.df_cxr : ws + E.dx + (l & 1) * 2 * btd;
+        v.dxe = l == 0 ? gout.df_enh : v.dxc + btd;
+        return v;
+    }
+};
+
+// L0: fus_arena_layout of the model, one_block_layout of a stand-alone block.  The entry point adds the tensors only it has (heads, out, gin, gout).
+FusCtx fus_ctx(const mfvit_fusion_cfg* cfg, int ndir, int depth, int pool_mean, const FusLayout& L0, const float* params, float* dparams,
+               const float* f_cxr, const float* f_enh, void* workspace, mfvit_stream_t stream) {
+    FusCtx c = {};
+    c.B = cfg->batch; c.T = cfg->tokens; c.C = cfg->num_classes; c.D = cfg->dim; c.nh = cfg->heads; c.DH = c.D / c.nh;
+    c.ndir = ndir; c.depth = depth; c.pool_mean = pool_mean;
+    c.scale = 1.0f / sqrtf((float)c.DH); c.eps_pre = cfg->eps_pre; c.eps_post = cfg->eps_post;
+    c.st = (hipStream_t)stream;
+    c.params = params; c.dparams = dparams; c.f_cxr = f_cxr; c.f_enh = f_enh; c.ws = (float*)workspace;
+    c.L0 = L0;
+    c.W = fus_ws(c.B, c.T, c.C, c.D, c.nh);
+    if (fus_full(depth, pool_mean)) c.E = fus_ex_ws(c.B, c.T, c.C, c.D, c.nh, depth);
+    return c;
+}
+FusCtx fus_model_ctx(const mfvit_fusion_cfg* cfg, int depth, int pool_mean, const float* params, float* dparams, const float* f_cxr,
+                     const float* f_enh, void* workspace, mfvit_stream_t stream) {
+    return fus_ctx(cfg, 2, depth, pool_mean, fus_arena_layout(cfg->dim, cfg->num_classes, depth), params, dparams, f_cxr, f_enh, workspace, stream);
+}
+
+// ------------------------------------------------------------------------------------------------ the batched f32 products of one layer
+// One operand: its address for direction 0 (head 0), its leading dimension and the steps to the next direction and to the next head (floats).
+// The five operand kinds below are the only place where a stride of this file's GEMMs is computed.
+struct XOpnd { const float* p; long ld, s_dir, s_head; };
+enum { WT_Q = 0, WT_K = 1, WT_V = 2, WT_P = 3 };   // the transposed copies in FusWs::wT
+
+struct XGemm {
+    const FusCtx& c;
+    const FusLayer& v;
+
+    // [dir][B][D] rows of the workspace; head h: the columns h DH ..
+    XOpnd rows(long off) const { return {v.ws + off, c.D, (long)c.B * c.D, c.DH}; }
+    // [dir][B][nh][D] head rows of the workspace
+    XOpnd head_rows(long off) const { return {v.ws + off, (long)c.nh * c.D, (long)c.B * c.nh * c.D, c.D}; }
+    // a D x D weight of block `dir` of the arena (or proj.bias, as the bias of per_dir) and its place in the gradient arena; head h: the rows h DH ..
+    XOpnd weight(long off) const { return {c.params + v.L.ca[0] + off, c.D, v.L.ca_stride, (long)c.DH * c.D}; }
+    XOpnd dweight(long off) const { return {c.dparams + v.L.ca[0] + off, c.D, v.L.ca_stride, (long)c.DH * c.D}; }
+    // the transposed copy wT[dir][k]; head h: the columns h DH ..
+    XOpnd weightT(int k) const { return {v.ws + c.W.wT + (long)k * c.D * c.D, c.D, 4L * c.D * c.D, c.DH}; }
+
+    // The three batch shapes, M = B rows each: out = a w^T (gemm_nt_tile), or the weight gradient out += a^T w (fus_wgrad).
+    // one product per direction (N = K = D)
+    GemmP per_dir(XOpnd a, XOpnd w, XOpnd out, XOpnd bias = {}) const {
+        GemmP p = batch(a, w, out, c.D, c.D, false);
+        p.bias = bias.p; p.sBo = bias.s_dir;
+        return p;
+    }
+    // one per (direction, head), the head slicing the contraction: K = DH, the columns of a
+    GemmP per_head_k(XOpnd a, XOpnd w, XOpnd out) const { return batch(a, w, out, c.D, c.DH, true); }
+    // one per (direction, head), the head slicing the output: N = DH, the columns of out (the rows of a weight gradient)
+    GemmP per_head_n(XOpnd a, XOpnd w, XOpnd out) const { return batch(a, w, out, c.DH, c.D, true); }
+
+    GemmP batch(XOpnd a, XOpnd w, XOpnd out, int N, int K, bool by_head) const {
+        GemmP p = nt(a.p, a.ld, w.p, w.ld, c.B, N, K);
+        p.out0 = const_cast<float*>(out.p); p.ldo0 = out.ld;   // (an output is rows of the workspace or a dweight: writable)
+        p.nb = c.ndir * (by_head ? c.nh : 1); p.nbi = by_head ? c.nh : 1;
+        p.sAo = a.s_dir; p.sWo = w.s_dir; p.sOo = out.s_dir;
+        if (by_head) { p.sAi = a.s_head; p.sWi = w.s_head; p.sOi = out.s_head; }
+        return p;
+    }
+};
+
 }  // namespace
 
-// PreNorm -> CrossAttention of `ndir` directions up to the projection output outp[dir][b][D] (MOD:20,123-137)
+// PreNorm -> CrossAttention of c.ndir directions up to the projection output outp[dir][b][D] (MOD:20,123-137)
 template <int D>
-static int xattn_core_forward(int ndir, int nh, const FusLayout& L, const FusWs& W, const float* params, const float* f_cxr,
-                              const float* f_enh, float* ws, int B, int T, float eps_pre, hipStream_t st) {
-    const int DH = D / nh;
-    const float scale = 1.0f / sqrtf((float)DH);
+static int xattn_core_forward(const FusCtx& c, const FusLayer& v) {
+    const FusLayout& L = v.L;
+    const FusWs& W = c.W;
+    float* const ws = v.ws;
+    const int B = c.B, T = c.T, nh = c.nh, ndir = c.ndir;
+    const hipStream_t st = c.st;
+    const XGemm g{c, v};
     // transposed copies of wq, wk, wv, wp (used by kq here and by the backward)
     for (int dir = 0; dir < ndir; ++dir) {
         const long offs[4] = {L.wq, L.wk, L.wv, L.wp};
         for (int k = 0; k < 4; ++k)
-            FUS_TRY(cast_transpose(MFVIT_F32, params + L.ca[dir] + offs[k], nullptr, ws + W.wT + ((long)dir * 4 + k) * D * D, D, D, st));
+            MFVIT_TRY(cast_transpose(MFVIT_F32, c.params + L.ca[dir] + offs[k], nullptr, ws + W.wT + ((long)dir * 4 + k) * D * D, D, D, st));
     }
-    MFVIT_LAUNCH(x_cls_ln_kernel<D>, dim3(B, ndir), dim3(64), 0, st, f_cxr, f_enh, params, L, eps_pre, B, T, ws + W.z0, ws + W.st0);
+    MFVIT_LAUNCH(x_cls_ln_kernel<D>, dim3(B, ndir), dim3(64), 0, st, v.xc, v.xe, c.params, L, c.eps_pre, B, T, ws + W.z0, ws + W.st0);
     MFVIT_CHECK_LAUNCH();
-    {   // qv = z0 Wq^T
-        GemmP p = zg();
-        p.A = ws + W.z0; p.lda = D; p.W = params + L.ca[0] + L.wq; p.ldw = D; p.M = B; p.N = D; p.K = D;
-        p.out0 = ws + W.qv; p.ldo0 = D;
-        p.nb = ndir; p.nbi = 1; p.sAo = (long)B * D; p.sWo = L.ca_stride; p.sOo = (long)B * D;
-        FUS_TRY(gemm_nt_tile(MFVIT_F32, EPI_NONE, p, st));
-    }
-    {   // kq_h = qv_h Wk_h  (W operand = WkT[:, h*DH ..])
-        GemmP p = zg();
-        p.A = ws + W.qv; p.lda = D; p.W = ws + W.wT + 1L * D * D; p.ldw = D; p.M = B; p.N = D; p.K = DH;
-        p.out0 = ws + W.kq; p.ldo0 = nh * D;
-        p.nb = ndir * nh; p.nbi = nh; p.sAo = (long)B * D; p.sAi = DH; p.sWo = 4L * D * D; p.sWi = DH; p.sOo = (long)B * nh * D; p.sOi = D;
-        FUS_TRY(gemm_nt_tile(MFVIT_F32, EPI_NONE, p, st));
-    }
+    // qv = z0 Wq^T
+    MFVIT_TRY(gemm_nt_tile(MFVIT_F32, EPI_NONE, g.per_dir(g.rows(W.z0), g.weight(L.wq), g.rows(W.qv)), st));
+    // kq_h = qv_h Wk_h  (W operand = WkT[:, h*DH ..])
+    MFVIT_TRY(gemm_nt_tile(MFVIT_F32, EPI_NONE, g.per_head_k(g.rows(W.qv), g.weightT(WT_K), g.head_rows(W.kq)), st));
     {
         constexpr int XW = xw_fwd<D>();
         const size_t lds = lds_stream_fwd(D, T);
@@ -1017,38 +1120,36 @@ static int xattn_core_forward(int ndir, int nh, const FusLayout& L, const FusWs&
         ProfScope ps(PROF_XATTN_FWD, 0, 2.0 * B * T * D * 4 * 2 * (nh / NH), st);
         if (nh == NH) {
             max_lds((x_stream_fwd_kernel<XW, D, false>), attr1);
-            MFVIT_LAUNCH((x_stream_fwd_kernel<XW, D, false>), dim3(B, ndir), dim3(XW * 64), lds, st, f_cxr, f_enh, params, L, eps_pre, scale, B, T,
+            MFVIT_LAUNCH((x_stream_fwd_kernel<XW, D, false>), dim3(B, ndir), dim3(XW * 64), lds, st, v.xc, v.xe, c.params, L, c.eps_pre, c.scale, B, T,
                                ws + W.kq, ws + W.u, ws + W.a, ws + W.st);
         } else {
             max_lds((x_stream_fwd_kernel<XW, D, true>), attrc);
-            MFVIT_LAUNCH((x_stream_fwd_kernel<XW, D, true>), dim3(B, ndir, nh / NH), dim3(XW * 64), lds, st, f_cxr, f_enh, params, L, eps_pre, scale,
+            MFVIT_LAUNCH((x_stream_fwd_kernel<XW, D, true>), dim3(B, ndir, nh / NH), dim3(XW * 64), lds, st, v.xc, v.xe, c.params, L, c.eps_pre, c.scale,
                                B, T, ws + W.kq, ws + W.u, ws + W.a, ws + W.st);
         }
         MFVIT_CHECK_LAUNCH();
     }
-    {   // o_h = u_h Wv_h^T
-        GemmP p = zg();
-        p.A = ws + W.u; p.lda = nh * D; p.W = params + L.ca[0] + L.wv; p.ldw = D; p.M = B; p.N = DH; p.K = D;
-        p.out0 = ws + W.o; p.ldo0 = D;
-        p.nb = ndir * nh; p.nbi = nh; p.sAo = (long)B * nh * D; p.sAi = D; p.sWo = L.ca_stride; p.sWi = (long)DH * D; p.sOo = (long)B * D; p.sOi = DH;
-        FUS_TRY(gemm_nt_tile(MFVIT_F32, EPI_NONE, p, st));
-    }
-    {   // outp = o Wp^T + bp
-        GemmP p = zg();
-        p.A = ws + W.o; p.lda = D; p.W = params + L.ca[0] + L.wp; p.ldw = D; p.M = B; p.N = D; p.K = D;
-        p.bias = params + L.ca[0] + L.bp;
-        p.out0 = ws + W.outp; p.ldo0 = D;
-        p.nb = ndir; p.nbi = 1; p.sAo = (long)B * D; p.sWo = L.ca_stride; p.sOo = (long)B * D; p.sBo = L.ca_stride;
-        FUS_TRY(gemm_nt_tile(MFVIT_F32, EPI_BIAS, p, st));
-    }
+    // o_h = u_h Wv_h^T
+    MFVIT_TRY(gemm_nt_tile(MFVIT_F32, EPI_NONE, g.per_head_n(g.head_rows(W.u), g.weight(L.wv), g.rows(W.o)), st));
+    // outp = o Wp^T + bp
+    MFVIT_TRY(gemm_nt_tile(MFVIT_F32, EPI_BIAS, g.per_dir(g.rows(W.o), g.weight(L.wp), g.rows(W.outp), g.weight(L.bp)), st));
     return MFVIT_OK;
 }
 
 // d pre-norm weight | bias of direction `dir` += the sum over its 2 B partial rows (x_stream_bwd / x_stream_dz: token rows 1 ..,
 // x_row0_bwd: the cls row), fixed order
-static int fus_prenorm_job(int D, int dir, const FusLayout& L, const FusWs& W, float* ws, int B, float* dparams, hipStream_t st) {
-    if (L.no_norm) return MFVIT_OK;
-    return colpart_reduce(ws + W.pd + (long)dir * 2 * B * 2 * D, 2 * B, D, 2, dparams + L.ca[dir] + L.n_w, dparams + L.ca[dir] + L.n_b, nullptr, st);
+static int fus_prenorm_job(const FusCtx& c, const FusLayer& v, int dir) {
+    if (v.L.no_norm) return MFVIT_OK;
+    float* dn = c.dparams + v.L.ca[dir];
+    return colpart_reduce(v.ws + c.W.pd + (long)dir * 2 * c.B * 2 * c.D, 2 * c.B, c.D, 2, dn + v.L.n_w, dn + v.L.n_b, nullptr, c.st);
+}
+// d head weight | bias of direction `dir` - and of that stream's backbone head, where the caller has one - += the sums over the B partial rows
+// that x_finish_bwd / x_head_bwd left in pb, pc of layer v (the top layer)
+static int fus_head_job(const FusCtx& c, const FusLayer& v, int dir) {
+    const int B = c.B, C = c.C, D = c.D;
+    float* dhw = c.dparams + v.L.head[dir];
+    MFVIT_TRY(colpart_reduce(v.ws + c.W.pb + (long)dir * B * 2 * C * D, B, C * D, 2, dhw, dir == 0 ? c.gout.dhw_cxr : c.gout.dhw_enh, nullptr, c.st));
+    return colpart_reduce(v.ws + c.W.pc + (long)dir * B * 2 * C, B, C, 2, dhw + (long)C * D, dir == 0 ? c.gout.dhb_cxr : c.gout.dhb_enh, nullptr, c.st);
 }
 
 // A weight gradient of the exchange, dW += A^T X over the batch rows (f32, plain operands), on gemm_small.hip's kernel at EVERY batch: one
@@ -1057,215 +1158,146 @@ static int fus_prenorm_job(int D, int dir, const FusLayout& L, const FusWs& W, f
 // float atomics in arrival order; in one split it would be 9 to 36 workgroups walking every row, where this is 144 and more.
 static int fus_wgrad(const GemmP& p, hipStream_t st) { return gemm_tn_small(p, st); }
 
-// backward of xattn_core_forward: consumes ws.dout (= d outp) and ws.dqp (cls gradient that bypasses the attention)
+// backward of xattn_core_forward: consumes ws.dout (= d outp) and ws.dqp (cls gradient that bypasses the attention); the gradient of the
+// layer's input rows goes to v.dxc / v.dxe (NULL: not wanted)
 template <int D>
-static int xattn_core_backward(int ndir, int nh, const FusLayout& L, const FusWs& W, const float* params, const float* f_cxr,
-                               const float* f_enh, float* ws, int B, int T, float* dparams, float* df_cxr, float* df_enh, hipStream_t st) {
-    const int DH = D / nh;
-    const float scale = 1.0f / sqrtf((float)DH);
-    const float* wT = ws + W.wT;
-    {   // dWp += dout^T o
-        GemmP p = zg();
-        p.A = ws + W.dout; p.lda = D; p.W = ws + W.o; p.ldw = D; p.M = B; p.N = D; p.K = D;
-        p.out0 = dparams + L.ca[0] + L.wp; p.ldo0 = D;
-        p.nb = ndir; p.nbi = 1; p.sAo = (long)B * D; p.sWo = (long)B * D; p.sOo = L.ca_stride;
-        FUS_TRY(fus_wgrad(p, st));
-    }
-    {   // do = dout Wp   (W operand = WpT)
-        GemmP p = zg();
-        p.A = ws + W.dout; p.lda = D; p.W = wT + 3L * D * D; p.ldw = D; p.M = B; p.N = D; p.K = D;
-        p.out0 = ws + W.dob; p.ldo0 = D;
-        p.nb = ndir; p.nbi = 1; p.sAo = (long)B * D; p.sWo = 4L * D * D; p.sOo = (long)B * D;
-        FUS_TRY(gemm_nt_tile(MFVIT_F32, EPI_NONE, p, st));
-    }
-    {   // dWv_h += do_h^T u_h
-        GemmP p = zg();
-        p.A = ws + W.dob; p.lda = D; p.W = ws + W.u; p.ldw = nh * D; p.M = B; p.N = DH; p.K = D;
-        p.out0 = dparams + L.ca[0] + L.wv; p.ldo0 = D;
-        p.nb = ndir * nh; p.nbi = nh; p.sAo = (long)B * D; p.sAi = DH; p.sWo = (long)B * nh * D; p.sWi = D; p.sOo = L.ca_stride; p.sOi = (long)DH * D;
-        FUS_TRY(fus_wgrad(p, st));
-    }
-    {   // du_h = do_h Wv_h   (W operand = WvT[:, h*DH ..])
-        GemmP p = zg();
-        p.A = ws + W.dob; p.lda = D; p.W = wT + 2L * D * D; p.ldw = D; p.M = B; p.N = D; p.K = DH;
-        p.out0 = ws + W.du; p.ldo0 = nh * D;
-        p.nb = ndir * nh; p.nbi = nh; p.sAo = (long)B * D; p.sAi = DH; p.sWo = 4L * D * D; p.sWi = DH; p.sOo = (long)B * nh * D; p.sOi = D;
-        FUS_TRY(gemm_nt_tile(MFVIT_F32, EPI_NONE, p, st));
-    }
+static int xattn_core_backward(const FusCtx& c, const FusLayer& v) {
+    const FusLayout& L = v.L;
+    const FusWs& W = c.W;
+    float* const ws = v.ws;
+    const int B = c.B, T = c.T, nh = c.nh, ndir = c.ndir;
+    const hipStream_t st = c.st;
+    const XGemm g{c, v};
+    // dWp += dout^T o
+    MFVIT_TRY(fus_wgrad(g.per_dir(g.rows(W.dout), g.rows(W.o), g.dweight(L.wp)), st));
+    // do = dout Wp   (W operand = WpT)
+    MFVIT_TRY(gemm_nt_tile(MFVIT_F32, EPI_NONE, g.per_dir(g.rows(W.dout), g.weightT(WT_P), g.rows(W.dob)), st));
+    // dWv_h += do_h^T u_h
+    MFVIT_TRY(fus_wgrad(g.per_head_n(g.rows(W.dob), g.head_rows(W.u), g.dweight(L.wv)), st));
+    // du_h = do_h Wv_h   (W operand = WvT[:, h*DH ..])
+    MFVIT_TRY(gemm_nt_tile(MFVIT_F32, EPI_NONE, g.per_head_k(g.rows(W.dob), g.weightT(WT_V), g.head_rows(W.du)), st));
     {
         const size_t lds = lds_stream_bwd(D, T);
         static PerDeviceOnce attr1, attrc, attrz;
         ProfScope ps(PROF_XATTN_BWD, 0, 2.0 * B * T * D * 4 * 3 * (nh == NH ? 1 : nh / NH + 1), st);
         if (nh == NH) {
             max_lds((x_stream_bwd_kernel<XW_BWD, D, false>), attr1);
-            MFVIT_LAUNCH((x_stream_bwd_kernel<XW_BWD, D, false>), dim3(B, ndir), dim3(XW_BWD * 64), lds, st, f_cxr, f_enh, params, L, scale, B, T,
-                               ws + W.kq, ws + W.a, ws + W.st, ws + W.du, ws + W.dkq, ws + W.dz0p, ws + W.pd, df_cxr, df_enh, nullptr);
+            MFVIT_LAUNCH((x_stream_bwd_kernel<XW_BWD, D, false>), dim3(B, ndir), dim3(XW_BWD * 64), lds, st, v.xc, v.xe, c.params, L, c.scale, B, T,
+                               ws + W.kq, ws + W.a, ws + W.st, ws + W.du, ws + W.dkq, ws + W.dz0p, ws + W.pd, v.dxc, v.dxe, nullptr);
             MFVIT_CHECK_LAUNCH();
         } else {   // heads in chunks of 3 (dkq, ds), then the token gradient over all heads
             max_lds((x_stream_bwd_kernel<XW_BWD, D, true>), attrc);
-            MFVIT_LAUNCH((x_stream_bwd_kernel<XW_BWD, D, true>), dim3(B, ndir, nh / NH), dim3(XW_BWD * 64), lds, st, f_cxr, f_enh, params, L, scale,
-                               B, T, ws + W.kq, ws + W.a, ws + W.st, ws + W.du, ws + W.dkq, ws + W.dz0p, ws + W.pd, df_cxr, df_enh, ws + W.ds);
+            MFVIT_LAUNCH((x_stream_bwd_kernel<XW_BWD, D, true>), dim3(B, ndir, nh / NH), dim3(XW_BWD * 64), lds, st, v.xc, v.xe, c.params, L, c.scale,
+                               B, T, ws + W.kq, ws + W.a, ws + W.st, ws + W.du, ws + W.dkq, ws + W.dz0p, ws + W.pd, v.dxc, v.dxe, ws + W.ds);
             MFVIT_CHECK_LAUNCH();
             const size_t ldz = lds_stream_dz(D, T, nh);
             max_lds((x_stream_dz_kernel<XW_DZ, D>), attrz);
-            MFVIT_LAUNCH((x_stream_dz_kernel<XW_DZ, D>), dim3(B, ndir), dim3(XW_DZ * 64), ldz, st, f_cxr, f_enh, params, L, scale, B, T, nh,
-                               ws + W.kq, ws + W.a, ws + W.st, ws + W.du, ws + W.ds, ws + W.dz0p, ws + W.pd, df_cxr, df_enh);
+            MFVIT_LAUNCH((x_stream_dz_kernel<XW_DZ, D>), dim3(B, ndir), dim3(XW_DZ * 64), ldz, st, v.xc, v.xe, c.params, L, c.scale, B, T, nh,
+                               ws + W.kq, ws + W.a, ws + W.st, ws + W.du, ws + W.ds, ws + W.dz0p, ws + W.pd, v.dxc, v.dxe);
             MFVIT_CHECK_LAUNCH();
         }
     }
-    {   // dWk_h += qv_h^T dkq_h
-        GemmP p = zg();
-        p.A = ws + W.qv; p.lda = D; p.W = ws + W.dkq; p.ldw = nh * D; p.M = B; p.N = DH; p.K = D;
-        p.out0 = dparams + L.ca[0] + L.wk; p.ldo0 = D;
-        p.nb = ndir * nh; p.nbi = nh; p.sAo = (long)B * D; p.sAi = DH; p.sWo = (long)B * nh * D; p.sWi = D; p.sOo = L.ca_stride; p.sOi = (long)DH * D;
-        FUS_TRY(fus_wgrad(p, st));
-    }
-    {   // dqv_h = dkq_h Wk_h^T
-        GemmP p = zg();
-        p.A = ws + W.dkq; p.lda = nh * D; p.W = params + L.ca[0] + L.wk; p.ldw = D; p.M = B; p.N = DH; p.K = D;
-        p.out0 = ws + W.dqv; p.ldo0 = D;
-        p.nb = ndir * nh; p.nbi = nh; p.sAo = (long)B * nh * D; p.sAi = D; p.sWo = L.ca_stride; p.sWi = (long)DH * D; p.sOo = (long)B * D; p.sOi = DH;
-        FUS_TRY(gemm_nt_tile(MFVIT_F32, EPI_NONE, p, st));
-    }
-    {   // dWq += dqv^T z0
-        GemmP p = zg();
-        p.A = ws + W.dqv; p.lda = D; p.W = ws + W.z0; p.ldw = D; p.M = B; p.N = D; p.K = D;
-        p.out0 = dparams + L.ca[0] + L.wq; p.ldo0 = D;
-        p.nb = ndir; p.nbi = 1; p.sAo = (long)B * D; p.sWo = (long)B * D; p.sOo = L.ca_stride;
-        FUS_TRY(fus_wgrad(p, st));
-    }
-    {   // dz0q = dqv Wq   (W operand = WqT)
-        GemmP p = zg();
-        p.A = ws + W.dqv; p.lda = D; p.W = wT; p.ldw = D; p.M = B; p.N = D; p.K = D;
-        p.out0 = ws + W.dz0q; p.ldo0 = D;
-        p.nb = ndir; p.nbi = 1; p.sAo = (long)B * D; p.sWo = 4L * D * D; p.sOo = (long)B * D;
-        FUS_TRY(gemm_nt_tile(MFVIT_F32, EPI_NONE, p, st));
-    }
-    MFVIT_LAUNCH(x_row0_bwd_kernel<D>, dim3(B), dim3(64 * ndir), 0, st, f_cxr, f_enh, params, L, B, T, ws + W.st0, ws + W.dz0p, ws + W.dz0q,
-                       ws + W.dqp, ws + W.pd, df_cxr, df_enh);
+    // dWk_h += qv_h^T dkq_h
+    MFVIT_TRY(fus_wgrad(g.per_head_n(g.rows(W.qv), g.head_rows(W.dkq), g.dweight(L.wk)), st));
+    // dqv_h = dkq_h Wk_h^T
+    MFVIT_TRY(gemm_nt_tile(MFVIT_F32, EPI_NONE, g.per_head_n(g.head_rows(W.dkq), g.weight(L.wk), g.rows(W.dqv)), st));
+    // dWq += dqv^T z0
+    MFVIT_TRY(fus_wgrad(g.per_dir(g.rows(W.dqv), g.rows(W.z0), g.dweight(L.wq)), st));
+    // dz0q = dqv Wq   (W operand = WqT)
+    MFVIT_TRY(gemm_nt_tile(MFVIT_F32, EPI_NONE, g.per_dir(g.rows(W.dqv), g.weightT(WT_Q), g.rows(W.dz0q)), st));
+    MFVIT_LAUNCH(x_row0_bwd_kernel<D>, dim3(B), dim3(64 * ndir), 0, st, v.xc, v.xe, c.params, L, B, T, ws + W.st0, ws + W.dz0p, ws + W.dz0q,
+                       ws + W.dqp, ws + W.pd, v.dxc, v.dxe);
     MFVIT_CHECK_LAUNCH();
     return MFVIT_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ Fus_CrossViT, one exchange layer, cls pooling
 template <int D>
-static int fusion_forward(const mfvit_fusion_cfg* cfg, const float* params, const float* f_cxr, const float* f_enh, const float* hw_cxr,
-                          const float* hb_cxr, const float* hw_enh, const float* hb_enh, float* ws, float* fused, float* x_cxr, float* x_enh,
-                          hipStream_t st) {
-    const int B = cfg->batch, T = cfg->tokens, C = cfg->num_classes;
-    const FusLayout L = fus_layout(D, C);
-    const FusWs W = fus_ws(B, T, C, D, cfg->heads);
-    FUS_TRY(xattn_core_forward<D>(2, cfg->heads, L, W, params, f_cxr, f_enh, ws, B, T, cfg->eps_pre, st));
-    MFVIT_LAUNCH(x_finish_fwd_kernel<D>, dim3(B), dim3(128), 0, st, f_cxr, f_enh, params, L, cfg->eps_post, B, T, C, ws + W.outp,
-                       ws + W.fus, ws + W.stc, hw_cxr, hb_cxr, hw_enh, hb_enh, fused, x_cxr, x_enh);
+static int fusion_forward(const FusCtx& c) {
+    const FusLayer v = c.layer(0);
+    const FusWs& W = c.W;
+    MFVIT_TRY(xattn_core_forward<D>(c, v));
+    MFVIT_LAUNCH(x_finish_fwd_kernel<D>, dim3(c.B), dim3(128), 0, c.st, v.xc, v.xe, c.params, v.L, c.eps_post, c.B, c.T, c.C, v.ws + W.outp,
+                       v.ws + W.fus, v.ws + W.stc, c.heads.w_cxr, c.heads.b_cxr, c.heads.w_enh, c.heads.b_enh, c.out.fused, c.out.x_cxr, c.out.x_enh);
     MFVIT_CHECK_LAUNCH();
     return MFVIT_OK;
 }
 
 template <int D>
-static int fusion_backward(const mfvit_fusion_cfg* cfg, const float* params, const float* f_cxr, const float* f_enh, const float* hw_cxr,
-                           const float* hw_enh, float* ws, const float* dfused, const float* dx_cxr, const float* dx_enh, float* dparams,
-                           float* df_cxr, float* df_enh, float* dhw_cxr, float* dhb_cxr, float* dhw_enh, float* dhb_enh, hipStream_t st) {
-    const int B = cfg->batch, T = cfg->tokens, C = cfg->num_classes;
-    const FusLayout L = fus_layout(D, C);
-    const FusWs W = fus_ws(B, T, C, D, cfg->heads);
-    MFVIT_LAUNCH(x_finish_bwd_kernel<D>, dim3(B), dim3(128), 0, st, f_cxr, f_enh, params, L, B, T, C, ws + W.outp, ws + W.fus,
-                       ws + W.stc, hw_cxr, hw_enh, dfused, dx_cxr, dx_enh, dparams, dhw_cxr, dhb_cxr, dhw_enh, dhb_enh, ws + W.dout,
-                       ws + W.dqp, ws + W.pa, ws + W.pb, ws + W.pc);
+static int fusion_backward(const FusCtx& c) {
+    const FusLayer v = c.layer(0);
+    const FusLayout& L = v.L;
+    const FusWs& W = c.W;
+    float* const ws = v.ws;
+    float* const dparams = c.dparams;
+    const int B = c.B;
+    MFVIT_LAUNCH(x_finish_bwd_kernel<D>, dim3(B), dim3(128), 0, c.st, v.xc, v.xe, c.params, L, B, c.T, c.C, ws + W.outp, ws + W.fus,
+                       ws + W.stc, c.heads.w_cxr, c.heads.w_enh, c.gin.dfused, c.gin.dx_cxr, c.gin.dx_enh, dparams, c.gout.dhw_cxr, c.gout.dhb_cxr,
+                       c.gout.dhw_enh, c.gout.dhb_enh, ws + W.dout, ws + W.dqp, ws + W.pa, ws + W.pb, ws + W.pc);
     MFVIT_CHECK_LAUNCH();
-    FUS_TRY(xattn_core_backward<D>(2, cfg->heads, L, W, params, f_cxr, f_enh, ws, B, T, dparams, df_cxr, df_enh, st));
+    MFVIT_TRY(xattn_core_backward<D>(c, v));
     // the batch sums of the small gradients, every one in a fixed order (one launch)
-    ColpartBatch batch;
-    ColpartBatch* prev = colpart_batch_begin(&batch);
-    int rc = MFVIT_OK;
-    for (int dir = 0; dir < 2 && rc == MFVIT_OK; ++dir) {
-        float* dhw = dparams + L.head[dir];
+    ColpartScope batch;
+    for (int dir = 0; dir < 2; ++dir) {
         float* dg = dparams + L.post[dir];
-        rc = colpart_reduce(ws + W.pa + (long)dir * B * 3 * D, B, D, 3, dg, dg + D, dparams + L.ca[dir] + L.bp, st);
-        if (rc == MFVIT_OK) rc = colpart_reduce(ws + W.pb + (long)dir * B * 2 * C * D, B, C * D, 2, dhw, dir == 0 ? dhw_cxr : dhw_enh, nullptr, st);
-        if (rc == MFVIT_OK) rc = colpart_reduce(ws + W.pc + (long)dir * B * 2 * C, B, C, 2, dhw + (long)C * D, dir == 0 ? dhb_cxr : dhb_enh, nullptr, st);
-        if (rc == MFVIT_OK) rc = fus_prenorm_job(D, dir, L, W, ws, B, dparams, st);
+        MFVIT_TRY(colpart_reduce(ws + W.pa + (long)dir * B * 3 * D, B, D, 3, dg, dg + D, dparams + L.ca[dir] + L.bp, c.st));
+        MFVIT_TRY(fus_head_job(c, v, dir));
+        MFVIT_TRY(fus_prenorm_job(c, v, dir));
     }
-    if (rc == MFVIT_OK) rc = colpart_batch_flush(st);
-    colpart_batch_begin(prev);
-    return rc;
+    return colpart_batch_flush(c.st);
 }
 
 // ------------------------------------------------------------------------------------------------ Fus_CrossViT, full-row path
 template <int D>
-static int fusion_full_forward(const mfvit_fusion_cfg* cfg, int depth, int pool_mean, const float* params, const float* f_cxr,
-                               const float* f_enh, const float* hw_cxr, const float* hb_cxr, const float* hw_enh, const float* hb_enh, float* ws,
-                               float* fused, float* x_cxr, float* x_enh, hipStream_t st) {
-    const int B = cfg->batch, T = cfg->tokens, C = cfg->num_classes, nh = cfg->heads;
-    const FusWs W = fus_ws(B, T, C, D, nh);
-    const FusExWs E = fus_ex_ws(B, T, C, D, nh, depth);
-    const long btd = (long)B * T * D;
-    for (int l = 0; l < depth; ++l) {
-        const FusLayout L = fus_layer_layout(D, C, depth, l);
-        float* wl = ws + l * E.slab;
-        const float* xc = l == 0 ? f_cxr : ws + (l - 1) * E.slab + E.Y;
-        const float* xe = l == 0 ? f_enh : xc + btd;
-        FUS_TRY(xattn_core_forward<D>(2, nh, L, W, params, xc, xe, wl, B, T, cfg->eps_pre, st));
-        const int pool = l < depth - 1 ? 0 : (pool_mean ? 2 : 1);
-        MFVIT_LAUNCH((x_rows_fwd_kernel<XW_ROWS, D>), dim3(B, 2), dim3(XW_ROWS * 64), 0, st, xc, xe, f_cxr, f_enh, params, L, cfg->eps_post, B, T,
-                           wl + W.outp, wl + E.Y, wl + E.yst, pool, ws + E.fusv);
+static int fusion_full_forward(const FusCtx& c) {
+    const FusWs& W = c.W;
+    const FusExWs& E = c.E;
+    const int B = c.B, T = c.T;
+    for (int l = 0; l < c.depth; ++l) {
+        const FusLayer v = c.layer(l);
+        MFVIT_TRY(xattn_core_forward<D>(c, v));
+        const int pool = l < c.depth - 1 ? 0 : (c.pool_mean ? 2 : 1);
+        MFVIT_LAUNCH((x_rows_fwd_kernel<XW_ROWS, D>), dim3(B, 2), dim3(XW_ROWS * 64), 0, c.st, v.xc, v.xe, c.f_cxr, c.f_enh, c.params, v.L, c.eps_post,
+                           B, T, v.ws + W.outp, v.ws + E.Y, v.ws + E.yst, pool, c.ws + E.fusv);
         MFVIT_CHECK_LAUNCH();
     }
-    MFVIT_LAUNCH(x_head_fwd_kernel<D>, dim3(B), dim3(128), 0, st, f_cxr, f_enh, params, fus_layer_layout(D, C, depth, depth - 1), B, T, C,
-                       ws + E.fusv, hw_cxr, hb_cxr, hw_enh, hb_enh, fused, x_cxr, x_enh);
+    MFVIT_LAUNCH(x_head_fwd_kernel<D>, dim3(B), dim3(128), 0, c.st, c.f_cxr, c.f_enh, c.params, c.layer(c.depth - 1).L, B, T, c.C, c.ws + E.fusv,
+                       c.heads.w_cxr, c.heads.b_cxr, c.heads.w_enh, c.heads.b_enh, c.out.fused, c.out.x_cxr, c.out.x_enh);
     MFVIT_CHECK_LAUNCH();
     return MFVIT_OK;
 }
 
 template <int D>
-static int fusion_full_backward(const mfvit_fusion_cfg* cfg, int depth, int pool_mean, const float* params, const float* f_cxr,
-                                const float* f_enh, const float* hw_cxr, const float* hw_enh, float* ws, const float* dfused,
-                                const float* dx_cxr, const float* dx_enh, float* dparams, float* df_cxr, float* df_enh, float* dhw_cxr,
-                                float* dhb_cxr, float* dhw_enh, float* dhb_enh, hipStream_t st) {
-    const int B = cfg->batch, T = cfg->tokens, C = cfg->num_classes, nh = cfg->heads;
-    const FusWs W = fus_ws(B, T, C, D, nh);
-    const FusExWs E = fus_ex_ws(B, T, C, D, nh, depth);
-    const long btd = (long)B * T * D;
-    const FusLayout Lt = fus_layer_layout(D, C, depth, depth - 1);
-    float* wt = ws + (depth - 1) * E.slab;
-    MFVIT_LAUNCH(x_head_bwd_kernel<D>, dim3(B), dim3(128), 0, st, f_cxr, f_enh, params, Lt, B, T, C, pool_mean, ws + E.fusv, hw_cxr, hw_enh,
-                       dfused, dx_cxr, dx_enh, ws + E.ev, ws + E.bb, wt + W.pb, wt + W.pc);
+static int fusion_full_backward(const FusCtx& c) {
+    const FusWs& W = c.W;
+    const FusExWs& E = c.E;
+    const int B = c.B, T = c.T;
+    float* const dparams = c.dparams;
+    const FusLayer top = c.layer(c.depth - 1);
+    MFVIT_LAUNCH(x_head_bwd_kernel<D>, dim3(B), dim3(128), 0, c.st, c.f_cxr, c.f_enh, c.params, top.L, B, T, c.C, c.pool_mean, c.ws + E.fusv,
+                       c.heads.w_cxr, c.heads.w_enh, c.gin.dfused, c.gin.dx_cxr, c.gin.dx_enh, c.ws + E.ev, c.ws + E.bb, top.ws + W.pb, top.ws + W.pc);
     MFVIT_CHECK_LAUNCH();
-    ColpartBatch batch;
-    ColpartBatch* prev = colpart_batch_begin(&batch);
-    int rc = MFVIT_OK;
-    for (int l = depth - 1; l >= 0 && rc == MFVIT_OK; --l) {
-        const FusLayout L = fus_layer_layout(D, C, depth, l);
-        float* wl = ws + l * E.slab;
-        const float* xc = l == 0 ? f_cxr : ws + (l - 1) * E.slab + E.Y;
-        const float* xe = l == 0 ? f_enh : xc + btd;
-        const bool top = l == depth - 1;
-        const float* dY = top ? nullptr : ws + E.dx + ((l + 1) & 1) * 2 * btd;        // the gradient of this layer's output rows
-        float* dxc = l > 0 ? ws + E.dx + (l & 1) * 2 * btd : df_cxr;                  // ... and of its input rows
-        float* dxe = l > 0 ? dxc + btd : df_enh;
-        MFVIT_LAUNCH(x_post0_bwd_kernel<D>, dim3(B), dim3(128), 0, st, xc, xe, params, L, B, T, wl + W.outp, wl + E.yst, dY, ws + E.ev, ws + E.bb,
-                           l == 0 ? 1 : 0, wl + W.dout, wl + W.dqp, wl + E.pr, wl + E.pbp);
+    ColpartScope batch;
+    for (int l = c.depth - 1; l >= 0; --l) {
+        const FusLayer v = c.layer(l);
+        const FusLayout& L = v.L;
+        MFVIT_LAUNCH(x_post0_bwd_kernel<D>, dim3(B), dim3(128), 0, c.st, v.xc, v.xe, c.params, L, B, T, v.ws + W.outp, v.ws + E.yst, v.dY, c.ws + E.ev,
+                           c.ws + E.bb, l == 0 ? 1 : 0, v.ws + W.dout, v.ws + W.dqp, v.ws + E.pr, v.ws + E.pbp);
         MFVIT_CHECK_LAUNCH();
-        rc = xattn_core_backward<D>(2, nh, L, W, params, xc, xe, wl, B, T, dparams, dxc, dxe, st);
-        if (rc != MFVIT_OK) break;
-        const int mode = top ? (pool_mean ? 1 : 2) : 0;
-        MFVIT_LAUNCH((x_rows_bwd_kernel<XW_ROWS, D>), dim3(B, 2), dim3(XW_ROWS * 64), 0, st, xc, xe, params, L, B, T, wl + E.yst, dY, ws + E.ev, mode,
-                           l == 0 && pool_mean ? 1 : 0, dxc, dxe, wl + E.pr);
+        MFVIT_TRY(xattn_core_backward<D>(c, v));
+        const int mode = l == c.depth - 1 ? (c.pool_mean ? 1 : 2) : 0;
+        MFVIT_LAUNCH((x_rows_bwd_kernel<XW_ROWS, D>), dim3(B, 2), dim3(XW_ROWS * 64), 0, c.st, v.xc, v.xe, c.params, L, B, T, v.ws + E.yst, v.dY,
+                           c.ws + E.ev, mode, l == 0 && c.pool_mean ? 1 : 0, v.dxc, v.dxe, v.ws + E.pr);
         MFVIT_CHECK_LAUNCH();
-        for (int dir = 0; dir < 2 && rc == MFVIT_OK; ++dir) {
-            rc = colpart_reduce(wl + E.pr + (long)dir * 2 * B * 2 * D, 2 * B, D, 2, dparams + L.post[dir], dparams + L.post[dir] + D, nullptr, st);
-            if (rc == MFVIT_OK) rc = colpart_reduce(wl + E.pbp + (long)dir * B * D, B, D, 1, dparams + L.ca[dir] + L.bp, nullptr, nullptr, st);
-            if (rc == MFVIT_OK) rc = fus_prenorm_job(D, dir, L, W, wl, B, dparams, st);
+        for (int dir = 0; dir < 2; ++dir) {
+            float* dg = dparams + L.post[dir];
+            MFVIT_TRY(colpart_reduce(v.ws + E.pr + (long)dir * 2 * B * 2 * D, 2 * B, D, 2, dg, dg + D, nullptr, c.st));
+            MFVIT_TRY(colpart_reduce(v.ws + E.pbp + (long)dir * B * D, B, D, 1, dparams + L.ca[dir] + L.bp, nullptr, nullptr, c.st));
+            MFVIT_TRY(fus_prenorm_job(c, v, dir));
         }
     }
-    for (int dir = 0; dir < 2 && rc == MFVIT_OK; ++dir) {
-        float* dhw = dparams + Lt.head[dir];
-        rc = colpart_reduce(wt + W.pb + (long)dir * B * 2 * C * D, B, C * D, 2, dhw, dir == 0 ? dhw_cxr : dhw_enh, nullptr, st);
-        if (rc == MFVIT_OK) rc = colpart_reduce(wt + W.pc + (long)dir * B * 2 * C, B, C, 2, dhw + (long)C * D, dir == 0 ? dhb_cxr : dhb_enh, nullptr, st);
-    }
-    if (rc == MFVIT_OK) rc = colpart_batch_flush(st);
-    colpart_batch_begin(prev);
-    return rc;
+    for (int dir = 0; dir < 2; ++dir) MFVIT_TRY(fus_head_job(c, top, dir));
+    return colpart_batch_flush(c.st);
 }
 
 extern "C" {
@@ -1279,8 +1311,10 @@ int mfvit_fusion_forward(const mfvit_fusion_cfg* cfg, const float* params, const
                          const float* hb_cxr, const float* hw_enh, const float* hb_enh, void* workspace, float* fused, float* x_cxr,
                          float* x_enh, mfvit_stream_t stream) {
     if (!fus_ok(cfg) || !params || !f_cxr || !f_enh || !workspace || !fused) return MFVIT_EINVAL;
-    return FUS_BY_DIM(cfg->dim, fusion_forward)(cfg, params, f_cxr, f_enh, hw_cxr, hb_cxr, hw_enh, hb_enh, (float*)workspace, fused, x_cxr,
-                                                x_enh, (hipStream_t)stream);
+    FusCtx c = fus_model_ctx(cfg, 1, 0, params, nullptr, f_cxr, f_enh, workspace, stream);
+    c.heads = {hw_cxr, hb_cxr, hw_enh, hb_enh};
+    c.out = {fused, x_cxr, x_enh};
+    return FUS_BY_DIM(cfg->dim, fusion_forward)(c);
 }
 
 int mfvit_fusion_backward(const mfvit_fusion_cfg* cfg, const float* params, const float* f_cxr, const float* f_enh, const float* hw_cxr,
@@ -1289,12 +1323,15 @@ int mfvit_fusion_backward(const mfvit_fusion_cfg* cfg, const float* params, cons
                           mfvit_stream_t stream) {
     if (!fus_ok(cfg) || !params || !f_cxr || !f_enh || !workspace || !dparams) return MFVIT_EINVAL;
     if ((df_cxr == nullptr) != (df_enh == nullptr)) return MFVIT_EINVAL;
-    return FUS_BY_DIM(cfg->dim, fusion_backward)(cfg, params, f_cxr, f_enh, hw_cxr, hw_enh, (float*)workspace, dfused, dx_cxr, dx_enh, dparams,
-                                                 df_cxr, df_enh, dhw_cxr, dhb_cxr, dhw_enh, dhb_enh, (hipStream_t)stream);
+    FusCtx c = fus_model_ctx(cfg, 1, 0, params, dparams, f_cxr, f_enh, workspace, stream);
+    c.heads = {hw_cxr, nullptr, hw_enh, nullptr};
+    c.gin = {dfused, dx_cxr, dx_enh};
+    c.gout = {df_cxr, df_enh, dhw_cxr, dhb_cxr, dhw_enh, dhb_enh};
+    return FUS_BY_DIM(cfg->dim, fusion_backward)(c);
 }
 
 size_t mfvit_fusion_ex_param_count(const mfvit_fusion_cfg* cfg, int cross_attn_depth, int pool_mean) {
-    return fus_ex_ok(cfg, cross_attn_depth, pool_mean) ? (size_t)fus_layer_layout(cfg->dim, cfg->num_classes, cross_attn_depth, 0).total : 0;
+    return fus_ex_ok(cfg, cross_attn_depth, pool_mean) ? (size_t)fus_arena_layout(cfg->dim, cfg->num_classes, cross_attn_depth).total : 0;
 }
 size_t mfvit_fusion_ex_workspace_bytes(const mfvit_fusion_cfg* cfg, int cross_attn_depth, int pool_mean) {
     if (!fus_ex_ok(cfg, cross_attn_depth, pool_mean)) return 0;
@@ -1308,8 +1345,10 @@ int mfvit_fusion_ex_forward(const mfvit_fusion_cfg* cfg, int cross_attn_depth, i
     if (!fus_ex_ok(cfg, cross_attn_depth, pool_mean) || !params || !f_cxr || !f_enh || !workspace || !fused) return MFVIT_EINVAL;
     if (!fus_full(cross_attn_depth, pool_mean))
         return mfvit_fusion_forward(cfg, params, f_cxr, f_enh, hw_cxr, hb_cxr, hw_enh, hb_enh, workspace, fused, x_cxr, x_enh, stream);
-    return FUS_BY_DIM(cfg->dim, fusion_full_forward)(cfg, cross_attn_depth, pool_mean, params, f_cxr, f_enh, hw_cxr, hb_cxr, hw_enh, hb_enh,
-                                                     (float*)workspace, fused, x_cxr, x_enh, (hipStream_t)stream);
+    FusCtx c = fus_model_ctx(cfg, cross_attn_depth, pool_mean, params, nullptr, f_cxr, f_enh, workspace, stream);
+    c.heads = {hw_cxr, hb_cxr, hw_enh, hb_enh};
+    c.out = {fused, x_cxr, x_enh};
+    return FUS_BY_DIM(cfg->dim, fusion_full_forward)(c);
 }
 
 int mfvit_fusion_ex_backward(const mfvit_fusion_cfg* cfg, int cross_attn_depth, int pool_mean, const float* params, const float* f_cxr,
@@ -1321,9 +1360,11 @@ int mfvit_fusion_ex_backward(const mfvit_fusion_cfg* cfg, int cross_attn_depth, 
     if (!fus_full(cross_attn_depth, pool_mean))
         return mfvit_fusion_backward(cfg, params, f_cxr, f_enh, hw_cxr, hw_enh, workspace, dfused, dx_cxr, dx_enh, dparams, df_cxr, df_enh,
                                      dhw_cxr, dhb_cxr, dhw_enh, dhb_enh, stream);
-    return FUS_BY_DIM(cfg->dim, fusion_full_backward)(cfg, cross_attn_depth, pool_mean, params, f_cxr, f_enh, hw_cxr, hw_enh, (float*)workspace,
-                                                      dfused, dx_cxr, dx_enh, dparams, df_cxr, df_enh, dhw_cxr, dhb_cxr, dhw_enh, dhb_enh,
-                                                      (hipStream_t)stream);
+    FusCtx c = fus_model_ctx(cfg, cross_attn_depth, pool_mean, params, dparams, f_cxr, f_enh, workspace, stream);
+    c.heads = {hw_cxr, nullptr, hw_enh, nullptr};
+    c.gin = {dfused, dx_cxr, dx_enh};
+    c.gout = {df_cxr, df_enh, dhw_cxr, dhb_cxr, dhw_enh, dhb_enh};
+    return FUS_BY_DIM(cfg->dim, fusion_full_backward)(c);
 }
 
 }  // extern "C"
@@ -1331,33 +1372,19 @@ int mfvit_fusion_ex_backward(const mfvit_fusion_cfg* cfg, int cross_attn_depth, 
 // ------------------------------------------------------------------------------------------------ exchange maps
 constexpr int MAX_MAP_TOKENS = 8192;   // as the rollout / relevance chains (include/mfvit.h)
 
-// the FusWs of exchange layer `layer` inside the workspace of a (cross_attn_depth, pool_mean) model: the workspace itself on the one-layer
-// cls path, the layer's slab on the full-row path
-static const float* fus_layer_ws(const mfvit_fusion_cfg* cfg, int depth, int pool_mean, const void* workspace, int layer) {
-    const float* ws = (const float*)workspace;
-    if (!fus_full(depth, pool_mean)) return ws;
-    return ws + layer * fus_ex_ws(cfg->batch, cfg->tokens, cfg->num_classes, cfg->dim, cfg->heads, depth).slab;
-}
-
 template <int D>
-static int fusion_grad_map(const mfvit_fusion_cfg* cfg, int depth, int pool_mean, const float* params, const float* f_cxr, const float* f_enh,
-                           const float* ws, int layer, float* abar, hipStream_t st) {
-    const int B = cfg->batch, T = cfg->tokens, C = cfg->num_classes, nh = cfg->heads;
-    const FusWs W = fus_ws(B, T, C, D, nh);
-    const float* wl = fus_layer_ws(cfg, depth, pool_mean, ws, layer);
-    const FusLayout L = fus_full(depth, pool_mean) ? fus_layer_layout(D, C, depth, layer) : fus_layout(D, C);
-    // the layer's input rows, as fusion_full_forward / _backward take them: the features, or the rows of the layer below
-    const float* xc = layer == 0 ? f_cxr : fus_layer_ws(cfg, depth, pool_mean, ws, layer - 1) + fus_ex_ws(B, T, C, D, nh, depth).Y;
-    const float* xe = layer == 0 ? f_enh : xc + (long)B * T * D;
+static int fusion_grad_map(const FusCtx& c, int layer, float* abar) {
+    const FusLayer v = c.layer(layer);
+    const FusWs& W = c.W;
+    const int B = c.B, T = c.T, nh = c.nh;
     // What this reads of the workspace and who wrote it last: a, st - x_stream_fwd (the forward; the backward only reads them); du - the
     // "du_h = do_h Wv_h" GEMM of xattn_core_backward, which nothing after it writes (x_stream_bwd / x_stream_dz read it; dkq, dz0p, dqv, dz0q, pd,
     // ds and the full-row path's dx / pr / pbp are regions of their own in fus_ws / fus_ex_ws).
-    const size_t lds = (size_t)3 * T * 4;
     static PerDeviceOnce attr;
     max_lds((x_grad_map_kernel<XW_BWD, D>), attr);
-    ProfScope ps(PROF_OTHER, 2.0 * 2 * B * (double)T * D * nh, 2.0 * B * T * D * 4 * (nh / NH), st);
-    MFVIT_LAUNCH((x_grad_map_kernel<XW_BWD, D>), dim3(B, 2), dim3(XW_BWD * 64), lds, st, xc, xe, params, L, B, T, nh, wl + W.a, wl + W.st,
-                 wl + W.du, abar);
+    ProfScope ps(PROF_OTHER, 2.0 * 2 * B * (double)T * D * nh, 2.0 * B * T * D * 4 * (nh / NH), c.st);
+    MFVIT_LAUNCH((x_grad_map_kernel<XW_BWD, D>), dim3(B, 2), dim3(XW_BWD * 64), lds_grad_map(T), c.st, v.xc, v.xe, c.params, v.L, B, T, nh,
+                 v.ws + W.a, v.ws + W.st, v.ws + W.du, abar);
     MFVIT_CHECK_LAUNCH();
     return MFVIT_OK;
 }
@@ -1369,13 +1396,11 @@ int mfvit_fusion_ex_attention(const mfvit_fusion_cfg* cfg, int cross_attn_depth,
     if (!fus_ex_ok(cfg, cross_attn_depth, pool_mean) || !workspace || !out || layer < 0 || layer >= cross_attn_depth || fuse < 0 || fuse > 3 ||
         cfg->tokens > MAX_MAP_TOKENS)
         return MFVIT_EINVAL;
-    const int B = cfg->batch, T = cfg->tokens, nh = cfg->heads;
-    const FusWs W = fus_ws(B, T, cfg->num_classes, cfg->dim, nh);
-    const float* wl = fus_layer_ws(cfg, cross_attn_depth, pool_mean, workspace, layer);
-    const long n = 2L * B * (fuse ? 1 : nh) * T;
-    hipStream_t st = (hipStream_t)stream;
-    ProfScope ps(PROF_OTHER, 0, (2.0 * B * nh * T + (double)n) * 4, st);
-    MFVIT_LAUNCH(x_attn_map_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, wl + W.a, nh, T, n, fuse, out);
+    // (the maps only read the workspace)
+    const FusCtx c = fus_model_ctx(cfg, cross_attn_depth, pool_mean, nullptr, nullptr, nullptr, nullptr, const_cast<void*>(workspace), stream);
+    const long n = 2L * c.B * (fuse ? 1 : c.nh) * c.T;
+    ProfScope ps(PROF_OTHER, 0, (2.0 * c.B * c.nh * c.T + (double)n) * 4, c.st);
+    MFVIT_LAUNCH(x_attn_map_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c.st, c.layer(layer).ws + c.W.a, c.nh, c.T, n, fuse, out);
     MFVIT_CHECK_LAUNCH();
     return MFVIT_OK;
 }
@@ -1385,8 +1410,8 @@ int mfvit_fusion_ex_grad_attention(const mfvit_fusion_cfg* cfg, int cross_attn_d
     if (!fus_ex_ok(cfg, cross_attn_depth, pool_mean) || !params || !f_cxr || !f_enh || !workspace || !abar || layer < 0 ||
         layer >= cross_attn_depth || cfg->tokens > MAX_MAP_TOKENS)
         return MFVIT_EINVAL;
-    return FUS_BY_DIM(cfg->dim, fusion_grad_map)(cfg, cross_attn_depth, pool_mean, params, f_cxr, f_enh, (const float*)workspace, layer, abar,
-                                                 (hipStream_t)stream);
+    const FusCtx c = fus_model_ctx(cfg, cross_attn_depth, pool_mean, params, nullptr, f_cxr, f_enh, const_cast<void*>(workspace), stream);
+    return FUS_BY_DIM(cfg->dim, fusion_grad_map)(c, layer, abar);
 }
 
 }  // extern "C"
@@ -1405,43 +1430,45 @@ static FusLayout one_block_layout(const mfvit_fusion_cfg* cfg, bool bare) {
     L.no_norm = bare ? 1 : 0;
     return L;
 }
+// one direction, one layer: x_own's cls row attends x_oth's patches
+static FusCtx one_block_ctx(const mfvit_fusion_cfg* cfg, bool bare, const float* params, float* dparams, const float* x_own, const float* x_oth,
+                            void* workspace, mfvit_stream_t stream) {
+    return fus_ctx(cfg, 1, 1, 0, one_block_layout(cfg, bare), params, dparams, x_own, x_oth, workspace, stream);
+}
 template <int D>
-static int xattn_one_forward_t(const mfvit_fusion_cfg* cfg, bool bare, const float* params, const float* x_own, const float* x_oth,
-                               float* ws, float* out, hipStream_t st) {
-    const int B = cfg->batch, T = cfg->tokens;
-    const FusLayout L = one_block_layout(cfg, bare);
-    const FusWs W = fus_ws(B, T, cfg->num_classes, D, cfg->heads);
-    FUS_TRY(xattn_core_forward<D>(1, cfg->heads, L, W, params, x_own, x_oth, ws, B, T, cfg->eps_pre, st));
-    MFVIT_LAUNCH(x_copy_out_kernel, dim3((unsigned)(((long)B * D + 255) / 256)), dim3(256), 0, st, ws + W.outp, out, (long)B * D);
+static int xattn_one_forward_t(const FusCtx& c, float* out) {
+    const FusLayer v = c.layer(0);
+    const long n = (long)c.B * D;
+    MFVIT_TRY(xattn_core_forward<D>(c, v));
+    MFVIT_LAUNCH(x_copy_out_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c.st, v.ws + c.W.outp, out, n);
     MFVIT_CHECK_LAUNCH();
     return MFVIT_OK;
 }
 static int xattn_one_forward(const mfvit_fusion_cfg* cfg, bool bare, const float* params, const float* x_own, const float* x_oth,
                              void* workspace, float* out, mfvit_stream_t stream) {
     if (!fus_ok(cfg) || !params || !x_own || !x_oth || !workspace || !out) return MFVIT_EINVAL;
-    return FUS_BY_DIM(cfg->dim, xattn_one_forward_t)(cfg, bare, params, x_own, x_oth, (float*)workspace, out, (hipStream_t)stream);
+    return FUS_BY_DIM(cfg->dim, xattn_one_forward_t)(one_block_ctx(cfg, bare, params, nullptr, x_own, x_oth, workspace, stream), out);
 }
 
 template <int D>
-static int xattn_one_backward_t(const mfvit_fusion_cfg* cfg, bool bare, const float* params, const float* x_own, const float* x_oth,
-                                float* ws, const float* dout, float* dparams, float* dx_own, float* dx_oth, hipStream_t st) {
-    const int B = cfg->batch, T = cfg->tokens;
-    const FusLayout L = one_block_layout(cfg, bare);
-    const FusWs W = fus_ws(B, T, cfg->num_classes, D, cfg->heads);
-    MFVIT_LAUNCH(x_copy_out_kernel, dim3((unsigned)(((long)B * D + 255) / 256)), dim3(256), 0, st, dout, ws + W.dout, (long)B * D);
+static int xattn_one_backward_t(const FusCtx& c, const float* dout) {
+    const FusLayer v = c.layer(0);
+    const long n = (long)c.B * D;
+    MFVIT_LAUNCH(x_copy_out_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c.st, dout, v.ws + c.W.dout, n);
     MFVIT_CHECK_LAUNCH();
-    if (hipMemsetAsync(ws + W.dqp, 0, sizeof(float) * B * D, st) != hipSuccess) return MFVIT_ELAUNCH;
+    if (hipMemsetAsync(v.ws + c.W.dqp, 0, sizeof(float) * n, c.st) != hipSuccess) return MFVIT_ELAUNCH;
     // d proj.bias = column sums of dout (x_finish_bwd does this in the fused model)
-    FUS_TRY(colsum_rows(dout, D, dparams + L.ca[0] + L.bp, B, 1, 0, D, st));
-    FUS_TRY(xattn_core_backward<D>(1, cfg->heads, L, W, params, x_own, x_oth, ws, B, T, dparams, dx_own, dx_oth, st));
-    return fus_prenorm_job(D, 0, L, W, ws, B, dparams, st);
+    MFVIT_TRY(colsum_rows(dout, D, c.dparams + v.L.ca[0] + v.L.bp, c.B, 1, 0, D, c.st));
+    MFVIT_TRY(xattn_core_backward<D>(c, v));
+    return fus_prenorm_job(c, v, 0);
 }
 static int xattn_one_backward(const mfvit_fusion_cfg* cfg, bool bare, const float* params, const float* x_own, const float* x_oth,
                               void* workspace, const float* dout, float* dparams, float* dx_own, float* dx_oth, mfvit_stream_t stream) {
     if (!fus_ok(cfg) || !params || !x_own || !x_oth || !workspace || !dout || !dparams) return MFVIT_EINVAL;
     if ((dx_own == nullptr) != (dx_oth == nullptr)) return MFVIT_EINVAL;
-    return FUS_BY_DIM(cfg->dim, xattn_one_backward_t)(cfg, bare, params, x_own, x_oth, (float*)workspace, dout, dparams, dx_own, dx_oth,
-                                                      (hipStream_t)stream);
+    FusCtx c = one_block_ctx(cfg, bare, params, dparams, x_own, x_oth, workspace, stream);
+    c.gout.df_cxr = dx_own; c.gout.df_enh = dx_oth;
+    return FUS_BY_DIM(cfg->dim, xattn_one_backward_t)(c, dout);
 }
 
 extern "C" {

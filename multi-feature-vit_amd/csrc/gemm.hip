@@ -1232,7 +1232,6 @@ __global__ __launch_bounds__(64 * CPR_SUB) void colpart_reduce_kernel(const floa
         if (d) atomicAdd(d + c % ncols, s);
     }
 }
-#define MFVIT_TRY_RC(expr) do { int rc__ = (expr); if (rc__ != MFVIT_OK) return rc__; } while (0)
 // The same for a BATCH of partial buffers in one launch (blockIdx.z = job): the encoder backward gives every row-kernel launch of a call its
 // own partial buffer and reduces them all at the end of the call - one launch instead of 25 (round 3: 50 launches of 4.4 us + their
 // boundaries per step).
@@ -1266,7 +1265,7 @@ int colpart_batch_flush(hipStream_t st) {
 }
 int colpart_reduce(const float* part, int G, int ncols, int nq, float* d0, float* d1, float* d2, hipStream_t st) {
     if (ColpartBatch* b = g_colpart_batch) {                  // deferred: reduced by colpart_batch_flush (every job has its OWN partial buffer)
-        if (b->n == ColpartBatch::MAXJ) MFVIT_TRY_RC(colpart_batch_flush(st));
+        if (b->n == ColpartBatch::MAXJ) MFVIT_TRY(colpart_batch_flush(st));
         ColpartJob& j = b->job[b->n++];
         j.part = part; j.G = G; j.ncols = ncols; j.nq = nq; j.d[0] = d0; j.d[1] = d1; j.d[2] = d2;
         return MFVIT_OK;

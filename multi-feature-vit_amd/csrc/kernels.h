@@ -42,6 +42,17 @@ struct ColpartJob { const float* part; float* d[3]; int G, ncols, nq; };
 struct ColpartBatch { static constexpr int MAXJ = 48; int n; ColpartJob job[MAXJ]; };
 ColpartBatch* colpart_batch_begin(ColpartBatch* b);
 int colpart_batch_flush(hipStream_t st);
+// The bracket as a scope: queues this thread's colpart_reduce calls in a batch of its own and puts the previous batch back on EVERY way out
+// (an early return on an error included: the thread-local pointer never outlives the batch).  Flushing stays explicit.  on = false: no bracket.
+struct ColpartScope {
+    ColpartBatch batch;
+    ColpartBatch* prev = nullptr;
+    const bool on;
+    explicit ColpartScope(bool on_ = true) : on(on_) { if (on) prev = colpart_batch_begin(&batch); }
+    ~ColpartScope() { if (on) colpart_batch_begin(prev); }
+    ColpartScope(const ColpartScope&) = delete;
+    ColpartScope& operator=(const ColpartScope&) = delete;
+};
 bool gemm_tn_pair_supported(int dtype, const GemmP& a, const GemmP& b);   // gemm_tn2.hip: two weight gradients in one launch
 int gemm_tn_glds_pair(int dtype, GemmP a, const GemmP& b, hipStream_t st);
 // out[n][k] += sum over the splits of part[s * stride + n * K + k]  (fixed order: deterministic).  Between tnpart_batch_begin(&batch) and
@@ -52,6 +63,15 @@ struct TnPartJob { const float* part; float* out; long stride, ldo; int splits, 
 struct TnPartBatch { static constexpr int MAXJ = 56; int n; long total4; TnPartJob job[MAXJ]; };
 TnPartBatch* tnpart_batch_begin(TnPartBatch* b);
 int tnpart_batch_flush(hipStream_t st);
+struct TnPartScope {   // the same scope for the split partials (see ColpartScope)
+    TnPartBatch batch;
+    TnPartBatch* prev = nullptr;
+    const bool on;
+    explicit TnPartScope(bool on_ = true) : on(on_) { if (on) prev = tnpart_batch_begin(&batch); }
+    ~TnPartScope() { if (on) tnpart_batch_begin(prev); }
+    TnPartScope(const TnPartScope&) = delete;
+    TnPartScope& operator=(const TnPartScope&) = delete;
+};
 
 int attn_fwd_exact(int dtype, const void* qkv, void* out, float* lse, int B, int Tn, int H, int HD, hipStream_t st);
 int attn_bwd_exact(int dtype, const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* dbias, int B, int Tn,

@@ -668,12 +668,7 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop
     // stage, which reads a sum, and at the end of the call); with residual dropout (intermediate sums are consumed at once) nothing is deferred
     int colpart_used = 0;
     auto next_colpart = [&]() { return (float*)(ws + W.colpart + (size_t)(colpart_used++ % (3 * d.depth + 2)) * W.colpart_stride); };
-    ColpartBatch cbatch;
-    struct BatchScope {
-        ColpartBatch* prev; bool on;
-        BatchScope(ColpartBatch* b, bool on_) : on(on_) { if (on) prev = colpart_batch_begin(b); }
-        ~BatchScope() { if (on) colpart_batch_begin(prev); }
-    } batch_scope(&cbatch, !d.rdrop);
+    ColpartScope colpart_scope(!d.rdrop);
     // split partials of the weight-gradient GEMMs through scratch - plain stores, every launch into its OWN slot - and ONE batched reduce launch at
     // the end of every BLOCK that adds the splits in a fixed order: dW is the same bits on every run (the float atomics it replaces add in whatever
     // order the workgroups finish).  Round 3 measured the same idea with a reduce launch behind EVERY gradient as a loss (77.2 -> 80.8 us per
@@ -684,12 +679,7 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop
     auto next_tnpart = [&]() -> float* {       // (more launches than slots between two flushes: float atomics for the rest - never a slot still in use)
         return tn_used < TN_SLOTS ? (float*)(ws + W.tnpart + (size_t)(tn_used++) * W.tnpart_stride) : nullptr;
     };
-    TnPartBatch tbatch;
-    struct TnScope {
-        TnPartBatch* prev;
-        TnScope(TnPartBatch* b) : prev(tnpart_batch_begin(b)) {}
-        ~TnScope() { tnpart_batch_begin(prev); }
-    } tn_scope(&tbatch);
+    TnPartScope tnpart_scope;
     // dY buffers by layer parity (the embed stage counts as layer -1 -> parity 1)
     auto pp = [&](size_t off, int l) { return (void*)(ws + off + (size_t)(l & 1) * W.pp_stride); };
     // (side_wanted, below, decides whether the side stream of this caller stream is looked up - and created - at all)
