@@ -411,6 +411,42 @@ int mfvit_input_photometric(const uint8_t* src, const int64_t* desc, const int32
 int mfvit_eval_counts(const float* scores, int64_t ld, const int64_t* labels, int n, int C, uint64_t* confusion, int64_t* preds,
                       uint64_t* u2, uint64_t* npos, mfvit_stream_t stream);
 
+/* Bootstrap replicates and DeLong components of the epoch metrics (mfvit.evalstats drives them; additive in ABI 5).  They replace the host
+ * loop a user puts around MAIN_CA:886-911 / MAIN_SS:797-821 to get an interval for the AUC: R resamples, each three scikit-learn calls or
+ * one O(n^2) mfvit_eval_counts.  Here every (model, class) column is ordered once and a replicate costs O(n) per column.
+ *
+ * scores f32 [M][n][C]: M score sets over the same n samples, row stride ld, model stride model_stride (in floats; unread for M = 1);
+ * labels int64 [n], compared in 64 bits.  1 <= n <= 32768, 1 <= C <= 64, 1 <= M <= 8.  Every output element is OVERWRITTEN (no caller
+ * zeroing) and all of them are integers: the same bits on every call.
+ *   psi2(a, b) = 2 [a > b] + [a == b] as float compares: a NaN on either side gives 0, -0.0 == +0.0 (mfvit_eval_counts' pair rule);
+ *   pred_m(i)  = the first maximum of row i of model m (see "First maximum").
+ * Replicate r draws n samples with replacement; w_r[i] is how often sample i was drawn.  Replicate 0 is the sample itself (w_0 = 1).  For
+ * r >= 1, with lowbias32 the hash of the dropout masks:
+ *   key_r = lowbias32(lo32(seed) ^ lowbias32(hi32(seed) + 0x9E3779B9 * (r + 1)));   draw k = 0 .. n - 1 picks (lowbias32(k ^ key_r) * n) >> 32
+ * (a 64-bit product).  stratified = 1: order the samples stably by stratum (label 0, 1, .., C - 1, then every label outside [0, C) as one
+ * last stratum) into a list L; the draw for position q of L, whose stratum holds n_s samples from off_s on, picks
+ * L[off_s + ((lowbias32(q ^ key_r) * n_s) >> 32)]: every stratum keeps its size.  Replicates are absolute: a call computes r = r0 .. r0 + R - 1,
+ * so a result does not depend on how the caller chunks R.
+ *   conf[r][m][t][p] = sum_i w_r[i] [label_i == t] [pred_m(i) == p]                      (uint64 [R][M][C][C]; outside labels add nothing)
+ *   u2[r][m][c]      = sum_{i: label_i == c} sum_{j: label_j != c} w_r[i] w_r[j] psi2(s_m[i][c], s_m[j][c])        (uint64 [R][M][C])
+ *   npos[r][c]       = sum_{label_i == c} w_r[i]                                         (uint64 [R][C]);  AUC = u2 / (2 npos (n - npos)).
+ * At r = 0 these are mfvit_eval_counts' numbers.  conf may be NULL, or u2 and npos may both be NULL.
+ * work: mfvit_boot_work_bytes(n, C, M, R) bytes on the device, 16-byte aligned (0 for an invalid shape or R < 1); its contents before and
+ * after a call mean nothing.  MFVIT_EINVAL (before any HIP call): scores, labels or work NULL, n, C or M outside the limits, ld < C,
+ * M > 1 with model_stride < (n - 1) ld + C, R < 1, r0 < 0, r0 + R > 2^31, stratified not 0 or 1, work_bytes too small, nothing to compute,
+ * only one of u2 / npos. */
+size_t mfvit_boot_work_bytes(int n, int C, int M, int64_t R);
+int mfvit_boot_counts(const float* scores, int64_t ld, int64_t model_stride, const int64_t* labels, int n, int C, int M, uint64_t seed, int64_t r0,
+                      int64_t R, int stratified, void* work, size_t work_bytes, uint64_t* conf, uint64_t* u2, uint64_t* npos, mfvit_stream_t stream);
+/* mfvit_delong_counts: the structural components of DeLong, DeLong & Clarke-Pearson (1988) on the sample itself, as integers:
+ *   v2[m][c][i] = sum_{j: label_j != c} psi2(s_m[i][c], s_m[j][c])  where label_i == c,
+ *                 sum_{j: label_j == c} psi2(s_m[j][c], s_m[i][c])  otherwise                          (int32 [M][C][n]; may be NULL)
+ *   pos_xy[c][m][m'] = sum_{label_i == c} v2[m][c][i] v2[m'][c][i];  neg_xy the same sum over the other samples   (uint64 [C][M][M])
+ *   u2[m][c] = sum_{label_i == c} v2[m][c][i] (uint64 [M][C]);  npos[c] (uint64 [C]).
+ * work: mfvit_boot_work_bytes(n, C, M, 1) bytes.  MFVIT_EINVAL as above, and for a NULL pos_xy, neg_xy, u2 or npos. */
+int mfvit_delong_counts(const float* scores, int64_t ld, int64_t model_stride, const int64_t* labels, int n, int C, int M, void* work,
+                        size_t work_bytes, int32_t* v2, uint64_t* pos_xy, uint64_t* neg_xy, uint64_t* u2, uint64_t* npos, mfvit_stream_t stream);
+
 /* The perturbation test for patch-relevance maps (Chefer, Gur & Wolf 2021 section 4, positive / negative perturbation; Petsiuk et al. 2018,
  * deletion / insertion; mfvit.perturb drives it): rank the patches, mask them a fraction at a time, score the model's output again.  Three
  * launches, one each, asynchronous on `stream`.

@@ -30,6 +30,17 @@ int mfvit_eval_counts(const float* scores, int64_t ld, const int64_t* labels, in
     return eval_counts(scores, ld, labels, n, C, (unsigned long long*)confusion, (unsigned long long*)u2, (unsigned long long*)npos, preds,
                        (hipStream_t)stream);
 }
+size_t mfvit_boot_work_bytes(int n, int C, int M, int64_t R) { return boot_work_bytes(n, C, M, R); }
+int mfvit_boot_counts(const float* scores, int64_t ld, int64_t model_stride, const int64_t* labels, int n, int C, int M, uint64_t seed, int64_t r0,
+                      int64_t R, int stratified, void* work, size_t work_bytes, uint64_t* conf, uint64_t* u2, uint64_t* npos, mfvit_stream_t stream) {
+    return boot_counts(scores, ld, model_stride, labels, n, C, M, seed, r0, R, stratified, work, work_bytes, (unsigned long long*)conf,
+                       (unsigned long long*)u2, (unsigned long long*)npos, (hipStream_t)stream);
+}
+int mfvit_delong_counts(const float* scores, int64_t ld, int64_t model_stride, const int64_t* labels, int n, int C, int M, void* work,
+                        size_t work_bytes, int32_t* v2, uint64_t* pos_xy, uint64_t* neg_xy, uint64_t* u2, uint64_t* npos, mfvit_stream_t stream) {
+    return delong_counts(scores, ld, model_stride, labels, n, C, M, work, work_bytes, v2, (unsigned long long*)pos_xy, (unsigned long long*)neg_xy,
+                         (unsigned long long*)u2, (unsigned long long*)npos, (hipStream_t)stream);
+}
 int mfvit_linear_fwd(int dtype, int epilogue, const void* x, int64_t ldx, const void* w, int64_t ldw, const float* bias, void* y,
                      int64_t ldy, void* y2, int64_t ldy2, int M, int N, int K, mfvit_stream_t stream) {
     if (!x || !w || (!y && epilogue != EPI_BIAS_GELU)) return MFVIT_EINVAL;      // GELU: y = NULL skips the saved derivative

@@ -28,6 +28,14 @@ int input_photometric(const unsigned char* src, const long long* desc, const int
                       void* workspace, const float* mean, const float* stdv, float* out, hipStream_t st);
 int eval_counts(const float* scores, long ld, const int64_t* labels, int n, int C, unsigned long long* conf, unsigned long long* u2,
                 unsigned long long* npos, int64_t* preds, hipStream_t st);   // metrics.hip
+// evalstats.hip: bootstrap replicates (r0 .. r0 + R - 1, replicate 0 the sample itself) and DeLong components of the epoch metrics, what a host loop
+// of R scikit-learn calls around MAIN_CA:886-911 / MAIN_SS:797-821 would compute; scores f32 [M][n][C] (row stride ld, model stride ms)
+size_t boot_work_bytes(int n, int C, int M, long long R);
+int boot_counts(const float* scores, long ld, long ms, const int64_t* labels, int n, int C, int M, unsigned long long seed, long long r0, long long R,
+                int stratified, void* work, size_t work_bytes, unsigned long long* conf, unsigned long long* u2, unsigned long long* npos,
+                hipStream_t st);
+int delong_counts(const float* scores, long ld, long ms, const int64_t* labels, int n, int C, int M, void* work, size_t work_bytes, int* v2,
+                  unsigned long long* pos_xy, unsigned long long* neg_xy, unsigned long long* u2, unsigned long long* npos, hipStream_t st);
 int gemm_tn(int dtype, const GemmP& p, hipStream_t st);
 bool gemm_nt_small_supported(int dtype, int epi, const GemmP& p);   // gemm_small.hip: f32, a handful of rows (the fusion module's per-sample rows)
 int gemm_nt_small(int epi, GemmP p, hipStream_t st);

@@ -138,6 +138,9 @@ SIGNATURES = {
     "mfvit_input_photometric_workspace_bytes": (c_size_t, [I, I]),
     "mfvit_input_photometric": (I, [P, P, P, P, I, I, I, P, P, P, P, P]),
     "mfvit_eval_counts": (I, [P, L, P, I, I, P, P, P, P, P]),
+    "mfvit_boot_work_bytes": (c_size_t, [I, I, I, L]),
+    "mfvit_boot_counts": (I, [P, L, L, P, I, I, I, c_uint64, L, L, I, P, c_size_t, P, P, P, P]),
+    "mfvit_delong_counts": (I, [P, L, L, P, I, I, I, P, c_size_t, P, P, P, P, P, P]),
     "mfvit_patch_rank": (I, [P, L, P, I, I, P]),
     "mfvit_patch_perturb": (I, [P, P, P, P, P, I, I, I, I, I, P]),
     "mfvit_perturb_score": (I, [P, L, P, I, I, I, P, P, P, P]),

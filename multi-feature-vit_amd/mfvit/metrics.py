@@ -69,3 +69,18 @@ class EpochMeter:
         self.confusion = conf
         self.auc_per_class = auc
         return loss_sum / n, float(auc.mean()), float(conf.diag().sum()) / n
+
+    def _epoch(self):
+        return torch.cat(self._scores, 0).contiguous(), torch.cat(self._labels, 0).contiguous()
+
+    def bootstrap_ci(self, n_boot=2000, level=0.95, seed=0, stratified=False):
+        """Bootstrap percentile intervals of the epoch's metrics (mfvit.evalstats.bootstrap_ci with one score set, named "0")."""
+        from . import evalstats
+        scores, labels = self._epoch()
+        return evalstats.bootstrap_ci(scores, labels, n_boot, level, seed, stratified)
+
+    def delong(self, level=0.95):
+        """DeLong variance and normal interval of the epoch's per-class AUC (mfvit.evalstats.delong with one score set)."""
+        from . import evalstats
+        scores, labels = self._epoch()
+        return evalstats.delong(scores, labels, level)
