@@ -447,6 +447,59 @@ int mfvit_boot_counts(const float* scores, int64_t ld, int64_t model_stride, con
 int mfvit_delong_counts(const float* scores, int64_t ld, int64_t model_stride, const int64_t* labels, int n, int C, int M, void* work,
                         size_t work_bytes, int32_t* v2, uint64_t* pos_xy, uint64_t* neg_xy, uint64_t* u2, uint64_t* npos, mfvit_stream_t stream);
 
+/* ROC / precision-recall curves, operating points and calibration of the epoch scores (mfvit.evalstats drives them; additive in ABI 5).  They
+ * replace fpr, tpr, thresholds = metrics.roc_curve(...) per class (MAIN_CA:904-907) and the host loops a study puts around it for "sensitivity
+ * at 95 % specificity" with an interval.  scores, labels, the limits on n, C, M and the work buffer are mfvit_boot_counts'; every output element
+ * is OVERWRITTEN; the counts are integers and every floating sum has a fixed order: the same bits on every call.
+ *
+ * mfvit_curve_counts: per column (m, c) the distinct score values that are numbers, largest first, one entry per tie group (-0.0 and +0.0 are one
+ * group; a float compare decides, denormals keep their order):
+ *   thr[m][c][k]  = the group's score, as the FIRST sample of the group in index order holds it (so +0.0 or -0.0, whichever comes first)
+ *   tp[m][c][k]   = #{i: label_i == c, s_m[i][c] >= thr},  fp[m][c][k] = #{i: label_i != c, s_m[i][c] >= thr}      (f32, uint32, uint32 [M][C][n])
+ *   nthr[m][c]    = the number of valid entries (int32 [M][C]); entries k >= nthr hold thr = NaN, tp = fp = 0
+ *   nnan[m][c]    = #{i: s_m[i][c] is NaN} (int32 [M][C]);   npos[c] = #{label_i == c} (uint64 [C]).
+ * A NaN score is above no threshold (mfvit_eval_counts' "in no pair" rule) and still counts in npos / n - npos; a label outside [0, C) is a
+ * negative of every class.  For a column without NaN, fp, tp and thr are sklearn's _binary_clf_curve (fps, tps, thresholds).
+ * work: mfvit_boot_work_bytes(n, C, M, 1) bytes.  MFVIT_EINVAL (before any HIP call): as mfvit_boot_counts for scores, labels, the shape, the
+ * strides and work, and for a NULL output.
+ *
+ * mfvit_boot_points: operating points of the replicates r = r0 .. r0 + R - 1, with mfvit_boot_counts' weights w_r for the same (seed, r,
+ * stratified); replicate 0 is the sample itself.  With P_r = sum_{label_i == c} w_r[i] (NaN-scored samples included) and N_r = n - P_r, and for a
+ * threshold t: TP_r(t) = sum_{label_i == c, s >= t} w_r[i], FP_r(t) the same over label_i != c (NaN is >= nothing).  The candidate thresholds are
+ * the SAMPLE's distinct number scores (the thr of mfvit_curve_counts, whatever the replicate's weights) and one above everything (TP = FP = 0,
+ * reported as +inf).  requests: DEVICE int32 [Q][3] = (kind, a, b), 1 <= Q <= 64:
+ *   kind 0  the LOWEST candidate with FP_r <= floor(a N_r / b)        (0 <= a <= b, 1 <= b <= 2^20; the product in 64 bits)
+ *   kind 1  the HIGHEST candidate with TP_r >= ceil(a P_r / b)        (same a, b).  Positives with NaN scores can put that out of reach of
+ *           every candidate; then the lowest candidate is taken (all numbers predicted positive).  Without NaN the lowest always qualifies.
+ *   kind 2  a holds the bits of a float tau: the samples with s >= tau as a float compare (NaN tau: none); b is not read.
+ *   tp, fp [r][m][c][q] = TP_r, FP_r at the chosen threshold (uint32 [R][M][C][Q]);  thr [r][m][c][q] = the score of the lowest tie group
+ *   included, by curve_counts' rule, or +inf when none is (f32);  npos[r][c] = P_r (uint64 [R][C], mfvit_boot_counts' npos).
+ * A request whose kind is not 0, 1 or 2, or whose a, b break the bounds, yields tp = fp = 0 and thr = NaN (the requests live on the device and are
+ * not inspected on the host).  One workgroup per (replicate, column): both weighted prefixes in one LDS word per place, a request is a bisection.
+ * work: mfvit_boot_work_bytes(n, C, M, R) bytes.  MFVIT_EINVAL (before any HIP call): as mfvit_boot_counts for scores, labels, the shape, the
+ * strides, work, R, r0 and stratified; Q < 1 or Q > 64; requests or an output NULL.
+ *
+ * mfvit_calib_sums: calibration of logits f32 [M][n][C] (strides as scores) at Kt temperatures in one launch.  temps: HOST f32 [Kt], each finite
+ * and > 0; NB equal-width confidence bins.  Per row, in double from the f32 logits, with beta = 1 / (double)T, mx the row's maximum and
+ * d_c = (double)z_c - (double)mx:  den = sum_c exp(beta d_c) (c ascending),  p_c = exp(beta d_c) / den,  top = the first maximum (independent
+ * of T),  conf = 1 / den = p_top,  bin = min(NB - 1, max(0, (int)ceil(conf NB) - 1)): the bins (lo, hi] of Guo et al. 2017.
+ *   bin_n, bin_hit [m][k][b] = rows in the bin, and those with top == label                           (uint64 [M][Kt][NB])
+ *   bin_conf [m][k][b]       = the sum of conf over the bin's rows                                      (f64 [M][Kt][NB])
+ *   sums [m][k][0..2]        = sum of -log p_y = log(den) - beta d_y;  sum of the Brier terms sum_c (p_c - [c == y])^2;
+ *                              d NLL / d beta = sum of (sum_c p_c d_c - d_y)                            (f64 [M][Kt][3])
+ *   skipped [m]              = rows with a non-finite logit or a label outside [0, C): they add nothing anywhere else  (uint64 [M])
+ * One workgroup per (model, temperature); every thread adds its rows in index order, then a fixed tree; the bin counters are integer atomics in
+ * LDS, the bins' double sums per-thread partials added in thread order (no float atomics).  1 <= Kt <= 16, 1 <= NB <= 64.
+ * MFVIT_EINVAL (before any HIP call): a NULL pointer, n, C or M outside the limits, ld < C, M > 1 with model_stride < (n - 1) ld + C, Kt or NB
+ * outside their limits, a temperature that is not finite or not > 0. */
+int mfvit_curve_counts(const float* scores, int64_t ld, int64_t model_stride, const int64_t* labels, int n, int C, int M, void* work,
+                       size_t work_bytes, float* thr, uint32_t* tp, uint32_t* fp, int32_t* nthr, int32_t* nnan, uint64_t* npos, mfvit_stream_t stream);
+int mfvit_boot_points(const float* scores, int64_t ld, int64_t model_stride, const int64_t* labels, int n, int C, int M, uint64_t seed, int64_t r0,
+                      int64_t R, int stratified, const int32_t* requests, int Q, void* work, size_t work_bytes, uint32_t* tp, uint32_t* fp, float* thr,
+                      uint64_t* npos, mfvit_stream_t stream);
+int mfvit_calib_sums(const float* logits, int64_t ld, int64_t model_stride, const int64_t* labels, int n, int C, int M, const float* temps, int Kt,
+                     int NB, uint64_t* bin_n, uint64_t* bin_hit, double* bin_conf, double* sums, uint64_t* skipped, mfvit_stream_t stream);
+
 /* The perturbation test for patch-relevance maps (Chefer, Gur & Wolf 2021 section 4, positive / negative perturbation; Petsiuk et al. 2018,
  * deletion / insertion; mfvit.perturb drives it): rank the patches, mask them a fraction at a time, score the model's output again.  Three
  * launches, one each, asynchronous on `stream`.

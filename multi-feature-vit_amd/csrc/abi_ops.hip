@@ -41,6 +41,22 @@ int mfvit_delong_counts(const float* scores, int64_t ld, int64_t model_stride, c
     return delong_counts(scores, ld, model_stride, labels, n, C, M, work, work_bytes, v2, (unsigned long long*)pos_xy, (unsigned long long*)neg_xy,
                          (unsigned long long*)u2, (unsigned long long*)npos, (hipStream_t)stream);
 }
+int mfvit_curve_counts(const float* scores, int64_t ld, int64_t model_stride, const int64_t* labels, int n, int C, int M, void* work,
+                       size_t work_bytes, float* thr, uint32_t* tp, uint32_t* fp, int32_t* nthr, int32_t* nnan, uint64_t* npos, mfvit_stream_t stream) {
+    return curve_counts(scores, ld, model_stride, labels, n, C, M, work, work_bytes, thr, tp, fp, nthr, nnan, (unsigned long long*)npos,
+                        (hipStream_t)stream);
+}
+int mfvit_boot_points(const float* scores, int64_t ld, int64_t model_stride, const int64_t* labels, int n, int C, int M, uint64_t seed, int64_t r0,
+                      int64_t R, int stratified, const int32_t* requests, int Q, void* work, size_t work_bytes, uint32_t* tp, uint32_t* fp, float* thr,
+                      uint64_t* npos, mfvit_stream_t stream) {
+    return boot_points(scores, ld, model_stride, labels, n, C, M, seed, r0, R, stratified, requests, Q, work, work_bytes, tp, fp, thr,
+                       (unsigned long long*)npos, (hipStream_t)stream);
+}
+int mfvit_calib_sums(const float* logits, int64_t ld, int64_t model_stride, const int64_t* labels, int n, int C, int M, const float* temps, int Kt,
+                     int NB, uint64_t* bin_n, uint64_t* bin_hit, double* bin_conf, double* sums, uint64_t* skipped, mfvit_stream_t stream) {
+    return calib_sums(logits, ld, model_stride, labels, n, C, M, temps, Kt, NB, (unsigned long long*)bin_n, (unsigned long long*)bin_hit, bin_conf, sums,
+                      (unsigned long long*)skipped, (hipStream_t)stream);
+}
 int mfvit_linear_fwd(int dtype, int epilogue, const void* x, int64_t ldx, const void* w, int64_t ldw, const float* bias, void* y,
                      int64_t ldy, void* y2, int64_t ldy2, int M, int N, int K, mfvit_stream_t stream) {
     if (!x || !w || (!y && epilogue != EPI_BIAS_GELU)) return MFVIT_EINVAL;      // GELU: y = NULL skips the saved derivative

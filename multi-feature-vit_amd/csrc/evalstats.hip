@@ -15,6 +15,13 @@
 //                      the places minus the negatives' prefix.
 //   conf_kernel        one workgroup per replicate: M C^2 counters in LDS.
 //   moments_kernel     pos_xy / neg_xy of the DeLong covariance: exact sums of products of v2.
+// The curve itself, operating points and calibration (mfvit_curve_counts, mfvit_boot_points, mfvit_calib_sums) sit on the same ordered columns:
+//   curve_kernel       one workgroup per column: per tie group of numbers, largest first, its score and the positives / negatives at or above it
+//                      (sklearn's _binary_clf_curve as integers).
+//   points_kernel      one workgroup per (replicate, column), as scan_kernel: the positives' and the negatives' weighted prefixes share one LDS word
+//                      per place (16 bits each), and a request (a cap on FP, a floor on TP, or a threshold) is a bisection on them.
+//   calib_kernel       one workgroup per (model, temperature): softmax in double per row, bin counters by integer LDS atomics, the double sums as
+//                      per-thread partials added in a fixed order.
 #include "common.cuh"
 #include "kernels.h"
 
@@ -248,6 +255,245 @@ __global__ __launch_bounds__(MOM_T) void moments_kernel(const int* __restrict__ 
     }
 }
 
+// ---------------------------------------------------------------------------------------------------- curves, operating points, calibration
+// Siblings of scan_kernel on the same ordered columns.  A weighted prefix is at most n = 32768 < 2^16, so ONE LDS word per place holds two inclusive
+// prefixes (low and high half; neither half can carry into the other) - the 4 n bytes scan_kernel takes for one.
+constexpr int PTS_MAXQ = 64, CAL_MAXK = 16, CAL_MAXB = 64, CAL_T = 256;
+
+// incl[p] = sum of value(q) over the places q <= p (both halves at once); every thread gets the total.  The tiles and the order of scan_kernel.
+template <typename F>
+__device__ __forceinline__ unsigned packed_prefix(int n, unsigned* incl, unsigned* wtot, F value) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    unsigned carry = 0;
+    for (int p0 = 0; p0 < n; p0 += SCAN_T) {
+        const int p = p0 + tid;
+        unsigned x = p < n ? value(p) : 0u;
+        for (int o = 1; o < 64; o <<= 1) {
+            const unsigned y = __shfl_up(x, o, 64);
+            if (lane >= o) x += y;
+        }
+        if (lane == 63) wtot[wave] = x;
+        __syncthreads();
+        unsigned below = 0, total = 0;
+        for (int v = 0; v < SCAN_T / 64; ++v) {
+            const unsigned t = wtot[v];
+            below += v < wave ? t : 0u;
+            total += t;
+        }
+        if (p < n) incl[p] = carry + below + x;
+        carry += total;
+        __syncthreads();
+    }
+    return carry;
+}
+
+// One workgroup per column; dynamic LDS: n words, low half the prefix of the positives that are numbers, high half the prefix of the tie groups' first
+// places.  The group whose first place is gs holds the samples at or above its score from place gs on: tp = positives there, fp = (n - gs) - tp (NaN
+// keys sort first).  Entry k counts the groups from the top; ent[gs] is the group's first sample in index order, whose score is the one reported.
+__global__ __launch_bounds__(SCAN_T) void curve_kernel(const float* __restrict__ scores, long ld, long ms, const unsigned* __restrict__ ent,
+                                                       const unsigned* __restrict__ grp, int n, int C, float* __restrict__ thr, unsigned* __restrict__ tp,
+                                                       unsigned* __restrict__ fp, int* __restrict__ nthr, int* __restrict__ nnan,
+                                                       unsigned long long* __restrict__ npos) {
+    extern __shared__ unsigned incl[];
+    __shared__ unsigned wtot[SCAN_T / 64];
+    __shared__ unsigned allpos;
+    const int tid = threadIdx.x, col = blockIdx.x, m = col / C, c = col - m * C;
+    const unsigned* e_ = ent + (long)col * n;
+    const unsigned* g_ = grp + (long)col * n;
+    const float* s = scores + (long)m * ms + c;
+    if (tid == 0) allpos = 0u;
+    __syncthreads();
+    unsigned mypos = 0;
+    const unsigned total = packed_prefix(n, incl, wtot, [&](int p) -> unsigned {
+        const unsigned e = e_[p];
+        mypos += (e & ENT_POS) ? 1u : 0u;
+        if (e & ENT_NAN) return 0u;
+        return ((e & ENT_POS) ? 1u : 0u) | ((g_[p] & 0xffffu) == (unsigned)p ? 0x10000u : 0u);
+    });
+    if (mypos) atomicAdd(&allpos, mypos);                               // an integer: any order gives the same bits
+    const unsigned G = total >> 16, ptot = total & 0xffffu;
+    const long o = (long)col * n;
+    for (int p = tid; p < n; p += SCAN_T) {
+        const unsigned e = e_[p];
+        if ((e & ENT_NAN) || (g_[p] & 0xffffu) != (unsigned)p) continue;
+        const unsigned k = G - (incl[p] >> 16);                         // groups above this one
+        const unsigned t = ptot - (p ? incl[p - 1] & 0xffffu : 0u);
+        thr[o + k] = s[(long)(e & ENT_IDX) * ld];
+        tp[o + k] = t;
+        fp[o + k] = (unsigned)(n - p) - t;
+    }
+    for (int k = (int)G + tid; k < n; k += SCAN_T) {                    // past the last group: every output element is written
+        thr[o + k] = __uint_as_float(0x7fc00000u);
+        tp[o + k] = 0u;
+        fp[o + k] = 0u;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        nthr[col] = (int)G;
+        nnan[col] = (e_[0] & ENT_NAN) ? (int)(g_[0] >> 16) : 0;
+        if (m == 0) npos[c] = allpos;
+    }
+}
+
+// blockIdx.x = rl * K + col; dynamic LDS: n words, low half the prefix of the positives' weights, high half the negatives', numbers only.
+// A threshold is a place q in [nn, n] that starts a tie group (nn: the NaN keys, q = n: above everything): tp = P' - exclP(q), fp = N' - exclN(q),
+// both monotone in q - thread t < Q answers request t by a bisection on its half of the words.
+__global__ __launch_bounds__(SCAN_T) void points_kernel(const float* __restrict__ scores, long ld, long ms, const unsigned* __restrict__ ent,
+                                                        const unsigned* __restrict__ grp, const unsigned short* __restrict__ w, int npad, int n, int C,
+                                                        int K, const int* __restrict__ req, int Q, unsigned* __restrict__ tp, unsigned* __restrict__ fp,
+                                                        float* __restrict__ thr, unsigned long long* __restrict__ npos) {
+    extern __shared__ unsigned incl[];
+    __shared__ unsigned wtot[SCAN_T / 64];
+    __shared__ unsigned allpos;
+    const int tid = threadIdx.x, col = blockIdx.x % K, rl = blockIdx.x / K, m = col / C, c = col - m * C;
+    const unsigned* e_ = ent + (long)col * n;
+    const unsigned* g_ = grp + (long)col * n;
+    const unsigned short* w_ = w + (long)rl * npad;
+    const float* s = scores + (long)m * ms + c;
+    if (tid == 0) allpos = 0u;
+    __syncthreads();
+    unsigned mypos = 0;
+    const unsigned total = packed_prefix(n, incl, wtot, [&](int p) -> unsigned {
+        const unsigned e = e_[p], wv = w_[e & ENT_IDX];
+        if (e & ENT_POS) mypos += wv;
+        if (e & ENT_NAN) return 0u;
+        return (e & ENT_POS) ? wv : wv << 16;
+    });
+    if (mypos) atomicAdd(&allpos, mypos);
+    __syncthreads();
+    const long long P = allpos, N = n - P, pn = total & 0xffffu, nn_ = total >> 16;      // P, N: NaN-scored samples included; pn, nn_: numbers only
+    if (tid < Q) {
+        const int kind = req[3 * tid], a = req[3 * tid + 1], b = req[3 * tid + 2];
+        const int nan0 = (e_[0] & ENT_NAN) ? (int)(g_[0] >> 16) : 0;
+        auto exclP = [&](int q) -> long long { return q ? (long long)(incl[q - 1] & 0xffffu) : 0ll; };
+        auto exclN = [&](int q) -> long long { return q ? (long long)(incl[q - 1] >> 16) : 0ll; };
+        const bool frac_ok = a >= 0 && b >= 1 && a <= b && b <= (1 << 20);
+        int q = -1;
+        if (kind == 0 && frac_ok) {                                     // the lowest threshold with fp <= floor(a N / b)
+            const long long need = nn_ - (long long)a * N / b;
+            int lo = nan0, hi = n;                                      // exclN(n) = N' >= need: the search always ends on a place that qualifies
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (exclN(mid) >= need) hi = mid; else lo = mid + 1;
+            }
+            q = lo;
+            if (q < n && (g_[q] & 0xffffu) != (unsigned)q) q = (int)(g_[q] >> 16);       // inside a group: its start does not qualify, the next start does
+        } else if (kind == 1 && frac_ok) {                              // the highest threshold with tp >= ceil(a P / b)
+            const long long lim = pn - ((long long)a * P + b - 1) / b;
+            if (lim < 0) {
+                q = nan0;                                               // out of reach (positives with NaN scores): the lowest boundary
+            } else {
+                int lo = nan0, hi = n;                                  // exclP(nan0) = 0 <= lim
+                while (lo < hi) {
+                    const int mid = (lo + hi + 1) >> 1;
+                    if (exclP(mid) <= lim) lo = mid; else hi = mid - 1;
+                }
+                q = lo < n ? (int)(g_[lo] & 0xffffu) : n;
+            }
+        } else if (kind == 2) {                                         // score >= tau, on the order's integer keys
+            const unsigned kt = score_key(__int_as_float(a));
+            q = n;
+            if (kt != 1u) {
+                int lo = nan0, hi = n;
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (score_key(s[(long)(e_[mid] & ENT_IDX) * ld]) >= kt) hi = mid; else lo = mid + 1;
+                }
+                q = lo;
+            }
+        }
+        const long o = ((long)rl * K + col) * Q + tid;
+        if (q < 0) {                                                    // not a request
+            tp[o] = 0u; fp[o] = 0u; thr[o] = __uint_as_float(0x7fc00000u);
+        } else {
+            tp[o] = (unsigned)(pn - exclP(q));
+            fp[o] = (unsigned)(nn_ - exclN(q));
+            thr[o] = q < n ? s[(long)(e_[q] & ENT_IDX) * ld] : __uint_as_float(0x7f800000u);
+        }
+    }
+    if (tid == 0 && col < C) npos[(long)rl * C + col] = allpos;
+}
+
+struct CalTemps { float t[CAL_MAXK]; };
+
+// blockIdx.x = m * Kt + kt.  Dynamic LDS only (a 16-byte aligned base): part f64 [NB][CAL_T], red f64 [3][CAL_T], cn, ch u32 [CAL_MAXB], sk u32.
+// Every thread walks its rows in index order; a bin's confidence sum is the thread's own partial (no float atomics), then lanes add their four
+// partials in thread order and the wave a fixed tree; the three sums take the tree of perturb_score_kernel.
+__global__ __launch_bounds__(CAL_T) void calib_kernel(const float* __restrict__ logits, long ld, long ms, const int64_t* __restrict__ labels, int n, int C,
+                                                      CalTemps temps, int Kt, int NB, unsigned long long* __restrict__ bin_n,
+                                                      unsigned long long* __restrict__ bin_hit, double* __restrict__ bin_conf, double* __restrict__ sums,
+                                                      unsigned long long* __restrict__ skipped) {
+    extern __shared__ __attribute__((aligned(16))) double part[];
+    double* red = part + NB * CAL_T;
+    unsigned* cn = (unsigned*)(red + 3 * CAL_T);
+    unsigned* ch = cn + CAL_MAXB;
+    unsigned* sk = ch + CAL_MAXB;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int m = blockIdx.x / Kt, kt = blockIdx.x - m * Kt;
+    const double beta = 1.0 / (double)temps.t[kt];
+    for (int i = tid; i < NB * CAL_T; i += CAL_T) part[i] = 0.0;
+    if (tid < CAL_MAXB) { cn[tid] = 0u; ch[tid] = 0u; }
+    if (tid == 0) *sk = 0u;
+    __syncthreads();
+    double snll = 0.0, sbr = 0.0, sdb = 0.0;
+    unsigned nskip = 0;
+    for (int i = tid; i < n; i += CAL_T) {
+        const float* z = logits + (long)m * ms + (long)i * ld;
+        float mx = z[0];
+        int am = 0;
+        bool finite = isfinite(mx);
+        for (int k = 1; k < C; ++k) {
+            const float v = z[k];
+            finite = finite && isfinite(v);
+            if (v > mx) { mx = v; am = k; }                             // finite rows: the first maximum
+        }
+        const int64_t t = labels[i];
+        if (!finite || t < 0 || t >= C) { ++nskip; continue; }
+        double den = 0.0;
+        for (int k = 0; k < C; ++k) den += exp(beta * ((double)z[k] - (double)mx));
+        const double dt = (double)z[t] - (double)mx;
+        double ez = 0.0, br = 0.0;
+        for (int k = 0; k < C; ++k) {
+            const double d = (double)z[k] - (double)mx, p = exp(beta * d) / den, e = p - (k == (int)t ? 1.0 : 0.0);
+            ez += p * d;
+            br += e * e;
+        }
+        const double conf = 1.0 / den;                                  // the top label's term is exp(0) = 1
+        snll += log(den) - beta * dt;
+        sbr += br;
+        sdb += ez - dt;
+        const int bin = min(NB - 1, max(0, (int)ceil(conf * (double)NB) - 1));
+        atomicAdd(cn + bin, 1u);
+        if (am == (int)t) atomicAdd(ch + bin, 1u);
+        part[bin * CAL_T + tid] += conf;
+    }
+    if (nskip) atomicAdd(sk, nskip);
+    red[tid] = snll; red[CAL_T + tid] = sbr; red[2 * CAL_T + tid] = sdb;
+    __syncthreads();
+    for (int o = CAL_T / 2; o > 0; o >>= 1) {
+        if (tid < o) {
+            red[tid] += red[tid + o]; red[CAL_T + tid] += red[CAL_T + tid + o]; red[2 * CAL_T + tid] += red[2 * CAL_T + tid + o];
+        }
+        __syncthreads();
+    }
+    const long ob = (long)blockIdx.x * NB;
+    for (int b = wave; b < NB; b += CAL_T / 64) {
+        const double* pb = part + b * CAL_T;
+        double v = ((pb[lane] + pb[lane + 64]) + pb[lane + 128]) + pb[lane + 192];
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+        if (lane == 0) bin_conf[ob + b] = v;
+    }
+    for (int b = tid; b < NB; b += CAL_T) { bin_n[ob + b] = cn[b]; bin_hit[ob + b] = ch[b]; }
+    if (tid == 0) {
+        sums[3 * (long)blockIdx.x] = red[0];
+        sums[3 * (long)blockIdx.x + 1] = red[CAL_T];
+        sums[3 * (long)blockIdx.x + 2] = red[2 * CAL_T];
+        if (kt == 0) skipped[m] = *sk;
+    }
+}
+
+size_t calib_lds_bytes(int NB) { return ((size_t)NB * CAL_T + 3 * CAL_T) * 8 + (2 * CAL_MAXB + 4) * 4; }
+
 size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // the scratch buffer: ent, grp u32 [K + 1][n] | preds8 u8 [M][n] | lab8 u8 [n] | then w u16 [R][npad] (bootstrap) or v2 i32 [K][n] (DeLong)
@@ -286,7 +532,10 @@ int allow_big_lds() {
     if (hipFuncSetAttribute((const void*)scan_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, big) != hipSuccess ||
         hipFuncSetAttribute((const void*)scan_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, big) != hipSuccess ||
         hipFuncSetAttribute((const void*)conf_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * BOOT_MAXM * BOOT_MAXC * BOOT_MAXC) != hipSuccess ||
-        hipFuncSetAttribute((const void*)weights_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * BOOT_MAXN) != hipSuccess)
+        hipFuncSetAttribute((const void*)weights_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * BOOT_MAXN) != hipSuccess ||
+        hipFuncSetAttribute((const void*)curve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, big) != hipSuccess ||
+        hipFuncSetAttribute((const void*)points_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, big) != hipSuccess ||
+        hipFuncSetAttribute((const void*)calib_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)calib_lds_bytes(CAL_MAXB)) != hipSuccess)
         return MFVIT_ELAUNCH;
     return MFVIT_OK;
 }
@@ -362,6 +611,71 @@ int delong_counts(const float* scores, long ld, long ms, const int64_t* labels, 
     MFVIT_LAUNCH(scan_kernel<true>, dim3(K), dim3(SCAN_T), (size_t)n * 4, st, ent, grp, (const unsigned short*)nullptr, L.npad, n, C, K, u2, npos, v2w, v2);
     MFVIT_CHECK_LAUNCH();
     MFVIT_LAUNCH(moments_kernel, dim3(M * M, C), dim3(MOM_T), 0, st, v2w, labels, n, C, M, pos_xy, neg_xy);
+    MFVIT_CHECK_LAUNCH();
+    return MFVIT_OK;
+}
+
+int curve_counts(const float* scores, long ld, long ms, const int64_t* labels, int n, int C, int M, void* work, size_t work_bytes, float* thr,
+                 unsigned* tp, unsigned* fp, int* nthr, int* nnan, unsigned long long* npos, hipStream_t st) {
+    if (!scores_ok(scores, ld, ms, labels, n, C, M, work) || !thr || !tp || !fp || !nthr || !nnan || !npos) return MFVIT_EINVAL;
+    const BootWork L = boot_layout(n, C, M, 1);
+    if (work_bytes < L.total) return MFVIT_EINVAL;
+    MFVIT_TRY(allow_big_lds());
+    char* wk = (char*)work;
+    unsigned* ent = (unsigned*)(wk + L.ent);
+    unsigned* grp = (unsigned*)(wk + L.grp);
+    const int K = M * C;
+    MFVIT_LAUNCH(order_kernel, dim3((n + ORD_T - 1) / ORD_T, K), dim3(ORD_T), 0, st, scores, ld, ms, labels, n, C, K, 0, ent, grp);
+    MFVIT_CHECK_LAUNCH();
+    MFVIT_LAUNCH(curve_kernel, dim3(K), dim3(SCAN_T), (size_t)n * 4, st, scores, ld, ms, ent, grp, n, C, thr, tp, fp, nthr, nnan, npos);
+    MFVIT_CHECK_LAUNCH();
+    return MFVIT_OK;
+}
+
+int boot_points(const float* scores, long ld, long ms, const int64_t* labels, int n, int C, int M, unsigned long long seed, long long r0, long long R,
+                int stratified, const int* req, int Q, void* work, size_t work_bytes, unsigned* tp, unsigned* fp, float* thr, unsigned long long* npos,
+                hipStream_t st) {
+    if (!scores_ok(scores, ld, ms, labels, n, C, M, work) || !req || !tp || !fp || !thr || !npos) return MFVIT_EINVAL;
+    if (R < 1 || r0 < 0 || r0 + R > (1ll << 31) || (stratified != 0 && stratified != 1) || Q < 1 || Q > PTS_MAXQ) return MFVIT_EINVAL;
+    const BootWork L = boot_layout(n, C, M, R);
+    if (work_bytes < L.total) return MFVIT_EINVAL;
+    MFVIT_TRY(allow_big_lds());
+    char* wk = (char*)work;
+    unsigned* ent = (unsigned*)(wk + L.ent);
+    unsigned* grp = (unsigned*)(wk + L.grp);
+    unsigned short* w = (unsigned short*)(wk + L.tail);
+    const int K = M * C;
+    MFVIT_LAUNCH(order_kernel, dim3((n + ORD_T - 1) / ORD_T, K + (stratified ? 1 : 0)), dim3(ORD_T), 0, st, scores, ld, ms, labels, n, C, K, 0, ent, grp);
+    MFVIT_CHECK_LAUNCH();
+    const unsigned* sent = stratified ? ent + (long)K * n : nullptr;
+    const unsigned* sgrp = stratified ? grp + (long)K * n : nullptr;
+    const long long step = 1 << 16;                                     // replicates per launch, as boot_counts
+    for (long long rb = 0; rb < R; rb += step) {
+        const int rn = (int)(R - rb < step ? R - rb : step);
+        unsigned short* wr = w + rb * L.npad;
+        MFVIT_LAUNCH(weights_kernel, dim3(rn), dim3(W_T), (size_t)L.npad * 2, st, n, L.npad, (unsigned)seed, (unsigned)(seed >> 32), (unsigned)(r0 + rb),
+                     sent, sgrp, wr);
+        MFVIT_CHECK_LAUNCH();
+        const long long ob = rb * K * Q;
+        MFVIT_LAUNCH(points_kernel, dim3((unsigned)(rn * K)), dim3(SCAN_T), (size_t)n * 4, st, scores, ld, ms, ent, grp, wr, L.npad, n, C, K, req, Q,
+                     tp + ob, fp + ob, thr + ob, npos + rb * C);
+        MFVIT_CHECK_LAUNCH();
+    }
+    return MFVIT_OK;
+}
+
+int calib_sums(const float* logits, long ld, long ms, const int64_t* labels, int n, int C, int M, const float* temps, int Kt, int NB,
+               unsigned long long* bin_n, unsigned long long* bin_hit, double* bin_conf, double* sums, unsigned long long* skipped, hipStream_t st) {
+    if (!logits || !labels || !temps || !bin_n || !bin_hit || !bin_conf || !sums || !skipped || !boot_shape_ok(n, C, M)) return MFVIT_EINVAL;
+    if (ld < C || (M > 1 && ms < (long)(n - 1) * ld + C) || Kt < 1 || Kt > CAL_MAXK || NB < 1 || NB > CAL_MAXB) return MFVIT_EINVAL;
+    CalTemps t = {};
+    for (int k = 0; k < Kt; ++k) {
+        if (!(temps[k] > 0.f) || !std::isfinite(temps[k])) return MFVIT_EINVAL;
+        t.t[k] = temps[k];
+    }
+    MFVIT_TRY(allow_big_lds());
+    MFVIT_LAUNCH(calib_kernel, dim3(M * Kt), dim3(CAL_T), calib_lds_bytes(NB), st, logits, ld, ms, labels, n, C, t, Kt, NB, bin_n, bin_hit, bin_conf, sums,
+                 skipped);
     MFVIT_CHECK_LAUNCH();
     return MFVIT_OK;
 }

@@ -36,6 +36,15 @@ int boot_counts(const float* scores, long ld, long ms, const int64_t* labels, in
                 hipStream_t st);
 int delong_counts(const float* scores, long ld, long ms, const int64_t* labels, int n, int C, int M, void* work, size_t work_bytes, int* v2,
                   unsigned long long* pos_xy, unsigned long long* neg_xy, unsigned long long* u2, unsigned long long* npos, hipStream_t st);
+// evalstats.hip, on the same ordered columns: the ROC / PR curve of the sample as integer counts, operating points of bootstrap replicates, and
+// calibration sums of logits at several temperatures (temps: a HOST pointer)
+int curve_counts(const float* scores, long ld, long ms, const int64_t* labels, int n, int C, int M, void* work, size_t work_bytes, float* thr,
+                 unsigned* tp, unsigned* fp, int* nthr, int* nnan, unsigned long long* npos, hipStream_t st);
+int boot_points(const float* scores, long ld, long ms, const int64_t* labels, int n, int C, int M, unsigned long long seed, long long r0, long long R,
+                int stratified, const int* req, int Q, void* work, size_t work_bytes, unsigned* tp, unsigned* fp, float* thr, unsigned long long* npos,
+                hipStream_t st);
+int calib_sums(const float* logits, long ld, long ms, const int64_t* labels, int n, int C, int M, const float* temps, int Kt, int NB,
+               unsigned long long* bin_n, unsigned long long* bin_hit, double* bin_conf, double* sums, unsigned long long* skipped, hipStream_t st);
 int gemm_tn(int dtype, const GemmP& p, hipStream_t st);
 bool gemm_nt_small_supported(int dtype, int epi, const GemmP& p);   // gemm_small.hip: f32, a handful of rows (the fusion module's per-sample rows)
 int gemm_nt_small(int epi, GemmP p, hipStream_t st);

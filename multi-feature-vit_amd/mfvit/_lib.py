@@ -141,6 +141,9 @@ SIGNATURES = {
     "mfvit_boot_work_bytes": (c_size_t, [I, I, I, L]),
     "mfvit_boot_counts": (I, [P, L, L, P, I, I, I, c_uint64, L, L, I, P, c_size_t, P, P, P, P]),
     "mfvit_delong_counts": (I, [P, L, L, P, I, I, I, P, c_size_t, P, P, P, P, P, P]),
+    "mfvit_curve_counts": (I, [P, L, L, P, I, I, I, P, c_size_t, P, P, P, P, P, P, P]),
+    "mfvit_boot_points": (I, [P, L, L, P, I, I, I, c_uint64, L, L, I, P, I, P, c_size_t, P, P, P, P, P]),
+    "mfvit_calib_sums": (I, [P, L, L, P, I, I, I, P, I, I, P, P, P, P, P, P]),
     "mfvit_patch_rank": (I, [P, L, P, I, I, P]),
     "mfvit_patch_perturb": (I, [P, P, P, P, P, I, I, I, I, I, P]),
     "mfvit_perturb_score": (I, [P, L, P, I, I, I, P, P, P, P]),

@@ -84,3 +84,24 @@ class EpochMeter:
         from . import evalstats
         scores, labels = self._epoch()
         return evalstats.delong(scores, labels, level)
+
+    def roc_curve(self, drop_intermediate=True):
+        """Per class (fpr, tpr, thresholds) of the epoch's outputs taken as scores, as compute() takes them: what MAIN_CA:904-907 gets from
+        metrics.roc_curve (mfvit.evalstats.roc_curve)."""
+        from . import evalstats
+        scores, labels = self._epoch()
+        return evalstats.roc_curve(scores, labels, drop_intermediate)
+
+    def operating_points(self, at, n_boot=2000, level=0.95, seed=0, stratified=False):
+        """Sensitivity / specificity / PPV / NPV at the operating points `at` with bootstrap intervals, the outputs taken as scores
+        (mfvit.evalstats.operating_points with one score set, named "0")."""
+        from . import evalstats
+        scores, labels = self._epoch()
+        return evalstats.operating_points(scores, labels, at, n_boot, level, seed, stratified)
+
+    def calibration(self, temperature=1.0, n_bins=15):
+        """ECE, MCE, Brier score, NLL and the reliability diagram of softmax(outputs / temperature): here the stored outputs are logits
+        (mfvit.evalstats.calibration)."""
+        from . import evalstats
+        scores, labels = self._epoch()
+        return evalstats.calibration(scores, labels, temperature, n_bins)
