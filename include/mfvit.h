@@ -226,6 +226,74 @@ size_t mfvit_vit_rel_scratch_bytes(const mfvit_vit_cfg* cfg, const mfvit_vit_rel
 int mfvit_vit_backward_rel(const mfvit_vit_cfg* cfg, const mfvit_vit_rel_req* req, const float* params, const void* shadow, void* workspace,
                            const float* dfeatures, mfvit_stream_t stream);
 
+/* Low-rank adapters (LoRA, Hu et al. 2021) of the image encoder's Linear weights.  Additive: five new entry points and two structs, nothing
+ * existing changes its signature, layout, launches or results, so the ABI number stays 5.
+ *
+ * An adapted Linear with frozen weight W [N][K] and adapters A [r][K], B [N][r] (f32, dense rows) runs on the MERGED weight
+ *   W_eff = W + s B A        (s: the caller's scale, alpha / r or alpha / sqrt(r)),
+ * so no forward kernel changes, and its backward is the exact chain rule through W_eff:
+ *   dW_eff = dY^T X,   dB = s dW_eff A^T,   dA = s B^T dW_eff.
+ *
+ * mfvit_lora_merge: out[n][k] = w[n][k] + scale * sum_j b[n][j] a[j][k]   (w: row stride ldw, out: row stride ldo, floats).
+ *   All arithmetic f32; acc = fmaf(b[n][j], a[j][k], acc) for j = 0 .. r-1 from acc = 0, then ONE multiply by scale and ONE add to w: the
+ *   forward error is at most (r + 2) 2^-24 (|w| + |scale| sum_j |b a|).  An update that is exactly zero (b = 0) returns the bits of w.
+ *   out == w (same pointer, same stride) is allowed: the in-place permanent merge.  Any other overlap of out with an input is undefined.
+ * mfvit_lora_grad: da[j][k] = scale * sum_n b[n][j] dw[n][k]  ([r][K] dense),  db[n][j] = scale * sum_k dw[n][k] a[j][k]  ([N][r] dense);
+ *   dw: row stride lddw.  Outputs are OVERWRITTEN.  Fixed summation orders (da: 16 interleaved row sequences n = i, i + 16, .., added
+ *   0 .. 15; db: 64 interleaved sequences of 16-byte pieces, then an xor butterfly), no atomics: repeated calls return the same bits.
+ * Domain of both - anything else is MFVIT_EINVAL before any HIP call: every pointer non-NULL; 1 <= r <= 64; N >= 1; K >= 4 and K % 4 == 0;
+ *   row strides >= K and multiples of 4; w / dw, a, out / da 16-byte aligned (the kernels move 16 bytes along k). */
+int mfvit_lora_merge(const float* w, long ldw, const float* a, const float* b, float scale, float* out, long ldo, int N, int K, int r,
+                     mfvit_stream_t stream);
+int mfvit_lora_grad(const float* dw, long lddw, const float* a, const float* b, float scale, float* da, float* db, int N, int K, int r,
+                    mfvit_stream_t stream);
+
+/* Adapters on the encoder.  Targets: the three row blocks of the fused attn.qkv.weight [3 dim][dim] (q, k, v: each its own A [r][dim],
+ * B [dim][r]), attn.proj.weight, mlp.fc1.weight (A [r][dim], B [mlp_dim][r]) and mlp.fc2.weight (A [r][mlp_dim], B [dim][r]). */
+#define MFVIT_LORA_Q 0
+#define MFVIT_LORA_K 1
+#define MFVIT_LORA_V 2
+#define MFVIT_LORA_PROJ 3
+#define MFVIT_LORA_FC1 4
+#define MFVIT_LORA_FC2 5
+typedef struct mfvit_lora_item {
+    int block;          /* 0 .. cfg->depth - 1 */
+    int target;         /* MFVIT_LORA_* */
+    const float* a;     /* device, [rank][K] */
+    const float* b;     /* device, [N][rank] */
+    float* da;          /* device, [rank][K]: overwritten by the backward entries; not read by mfvit_vit_prepare_shadow_lora (may be NULL there) */
+    float* db;          /* device, [N][rank]: likewise */
+} mfvit_lora_item;
+typedef struct mfvit_lora_req {
+    int rank;           /* 1 .. 64, one rank for all items */
+    float scale;        /* s */
+    int n;              /* number of items (HOST array): 1 .. 6 depth, no (block, target) twice */
+    const mfvit_lora_item* items;
+} mfvit_lora_req;
+/* mfvit_vit_prepare_shadow_lora: eff_params (mfvit_vit_param_count floats, must not overlap params) = params with every adapted weight
+ *   replaced by its W_eff - one device copy of the arena and one batched merge launch (64 items per launch) - then the weight shadow of
+ *   eff_params as mfvit_vit_prepare_shadow builds it.  The forward and backward entry points then take eff_params as `params`: the f32 mode
+ *   reads weights from the arena, so the merged weights are what every kernel sees, not only the 16-bit shadows.  Every cfg->dtype is accepted
+ *   here; whether a plain 16-bit shadow resolves a small update is the caller's concern (mfvit.lora refuses 'bf16' / 'fp16').
+ * mfvit_vit_backward_lora: the data-gradient chain of mfvit_vit_backward_ex(.., dparams = NULL, ..) plus, in every block that has items,
+ *   the weight-gradient GEMMs of the adapted Linears ONLY (the fused qkv gradient when any of q / k / v is adapted) - no bias, LayerNorm or
+ *   cls column sum, no gradient of a Linear without adapters or of the embedding stage, no side stream.  dW_eff goes through the usual split
+ *   partials and their fixed-order reduce into dw_scratch (mfvit_vit_param_count floats in the gradient-arena layout; the call zeroes the slices
+ *   it uses, the rest is not touched), then one batched mfvit_lora_grad launch (64 items per launch) overwrites every item's da / db.
+ *   params = the eff_params of mfvit_vit_prepare_shadow_lora.  dimg: as in mfvit_vit_backward_ex, or NULL - then stage_lo is raised to the
+ *   lowest block with an item, and that block's LN1 data-gradient GEMM, whose result nobody reads, is not launched.  stage_hi = cfg->depth.
+ * mfvit_vit_lora_grad: the batched contraction alone, on the adapted dW slices of a gradient arena that mfvit_vit_backward(_ex / _drop)
+ *   has filled (adapters beside trainable base parameters: the full backward, then this; correct and slower than the selective entry).
+ * MFVIT_EINVAL (before any HIP call): token-input mode; req NULL, n < 1 or an item outside the ranges above, twice, or with a NULL a / b
+ *   (da / db: the two backward entries); rank outside 1 .. 64; a NULL eff_params / dw_scratch / dparams; stage_hi != cfg->depth; and the checks of
+ *   mfvit_vit_prepare_shadow / mfvit_vit_backward_ex.  With no such call the other entry points run exactly the launches they ran before. */
+int mfvit_vit_prepare_shadow_lora(const mfvit_vit_cfg* cfg, const float* params, const mfvit_lora_req* req, float* eff_params, void* shadow,
+                                  mfvit_stream_t stream);
+int mfvit_vit_backward_lora(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, const float* params, const void* shadow, void* workspace,
+                            const float* dfeatures, const mfvit_lora_req* req, float* dw_scratch, float* dimg, int stage_hi, int stage_lo,
+                            mfvit_stream_t stream);
+int mfvit_vit_lora_grad(const mfvit_vit_cfg* cfg, const mfvit_lora_req* req, const float* dparams, mfvit_stream_t stream);
+
 /* Token-input encoder (cfg->token_input = 1): the GPT of the TransFuser fusion (fuseattention.py:84-212), heads x head_dim with
  * head_dim in {32, 64, 96} (config.py: n_embd 384, n_head 4 -> 96), mlp_dim = block_exp * dim.
  * Parameter arena (f32): pos_emb [tokens][dim], then per block

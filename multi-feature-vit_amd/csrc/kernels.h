@@ -153,6 +153,16 @@ int attn_rel_map(int qdt, int ddt, const void* qkv, const float* lse, const void
                  float* part, int first, hipStream_t st);
 int attn_rel_update(float* v, const float* part, int B, int Tn, int first, float* out, hipStream_t st);
 
+// lora.hip: low-rank adapters.  One (Linear, adapter) pair of a batched launch; the table rides in the kernel arguments.
+//   merge: o0[n][k] (row stride ldo) = w[n][k] (row stride ldw) + scale * sum_j b[n][j] a[j][k]        (a: [r][K], b: [N][r], both dense)
+//   grad:  w = dW [N][K] (row stride ldw);  o0 = dA [r][K] = scale * b^T dW,  o1 = dB [N][r] = scale * dW a^T   (ldo unused)
+struct LoraPair { const float* w; const float* a; const float* b; float* o0; float* o1; int N, K, ldw, ldo; };
+constexpr int LORA_MAXP = 64;      // pairs per launch (56 bytes each: the table stays inside 4 KB of kernel arguments); longer tables take more launches
+struct LoraBatch { int n, r; float scale; LoraPair pair[LORA_MAXP]; };
+bool lora_pair_ok(const LoraPair& p, int r, bool grad);
+int lora_merge_batch(const LoraPair* pairs, int n, int r, float scale, hipStream_t st);   // MFVIT_EINVAL before any launch when a pair is outside the domain
+int lora_grad_batch(const LoraPair* pairs, int n, int r, float scale, hipStream_t st);
+
 // out = A W^T (A: M x K, W: N x K): the operands and the shape, every other field zero
 inline GemmP nt(const void* A, long lda, const void* W, long ldw, int M, int N, int K) {
     GemmP p;

@@ -473,6 +473,58 @@ int mfvit_vit_prepare_shadow(const mfvit_vit_cfg* cfg, const float* params, void
 
 }  // extern "C"
 
+// Low-rank adapters (include/mfvit.h, mfvit_lora_req): the checked request of one call.  mask[l]: bit t = block l has an item for target t.
+struct LoraPlan {
+    const mfvit_lora_req* req;
+    unsigned char mask[256];
+    int lowest;            // lowest block with an item
+    float* dw;             // mfvit_vit_backward_lora: the dW_eff scratch in the gradient-arena layout
+};
+enum { LORA_QKV = 7, LORA_PROJ = 8, LORA_FC1 = 16, LORA_FC2 = 32 };
+static bool lora_plan(const Dims& d, const mfvit_lora_req* r, bool grads, LoraPlan& pl) {
+    if (!r || d.tok || d.depth > 256 || r->rank < 1 || r->rank > 64 || r->n < 1 || r->n > 6 * d.depth || !r->items) return false;
+    memset(pl.mask, 0, sizeof(pl.mask));
+    pl.req = r;
+    pl.lowest = d.depth;
+    pl.dw = nullptr;
+    for (int i = 0; i < r->n; ++i) {
+        const mfvit_lora_item& it = r->items[i];
+        if (it.block < 0 || it.block >= d.depth || it.target < 0 || it.target > MFVIT_LORA_FC2) return false;
+        if (!it.a || !it.b || (grads && (!it.da || !it.db))) return false;
+        if (pl.mask[it.block] & (1 << it.target)) return false;
+        pl.mask[it.block] |= (unsigned char)(1 << it.target);
+        pl.lowest = it.block < pl.lowest ? it.block : pl.lowest;
+    }
+    return true;
+}
+// The (weight, adapter) pair of item `it` over an arena-layout buffer `base` (the parameters, or a gradient arena); out: the merge's target arena
+static LoraPair lora_pair(const Dims& d, const ParamLayout& L, const mfvit_lora_item& it, const float* base, float* out, bool grad) {
+    const long D = d.D, F = d.F;
+    long off = L.blk0 + (long)it.block * L.blk_stride;
+    int N = d.D, K = d.D;
+    if (it.target <= MFVIT_LORA_V) off += L.qkv_w + (long)it.target * D * D;
+    else if (it.target == MFVIT_LORA_PROJ) off += L.proj_w;
+    else if (it.target == MFVIT_LORA_FC1) { off += L.fc1_w; N = d.F; }
+    else { off += L.fc2_w; K = d.F; }
+    (void)F;
+    LoraPair p = {base + off, it.a, it.b, grad ? it.da : out + off, grad ? it.db : nullptr, N, K, K, K};
+    return p;
+}
+// merge (grad = false: base = params, out = the effective arena) or gradient contraction (grad = true: base = a gradient arena) of every item:
+// all pairs are checked before the first launch
+static int lora_run(const Dims& d, const mfvit_lora_req* r, const float* base, float* out, bool grad, hipStream_t st) {
+    const ParamLayout L = param_layout(d);
+    for (int i = 0; i < r->n; ++i)
+        if (!lora_pair_ok(lora_pair(d, L, r->items[i], base, out, grad), r->rank, grad)) return MFVIT_EINVAL;
+    LoraPair chunk[LORA_MAXP];
+    for (int i0 = 0; i0 < r->n; i0 += LORA_MAXP) {
+        const int m = r->n - i0 < LORA_MAXP ? r->n - i0 : LORA_MAXP;
+        for (int i = 0; i < m; ++i) chunk[i] = lora_pair(d, L, r->items[i0 + i], base, out, grad);
+        MFVIT_TRY(grad ? lora_grad_batch(chunk, m, r->rank, r->scale, st) : lora_merge_batch(chunk, m, r->rank, r->scale, st));
+    }
+    return MFVIT_OK;
+}
+
 // Shared forward of the two front ends: ViT-S/16 (img = (B,3,H,W) image, patch embedding + cls token) and the token-input GPT
 // (img = (B,T,dim) tokens, + pos_emb).  Everything behind x_0 / LN1_0 is the same pre-LN block stack.
 // Attention maps (mfvit_vit_forward_attn): validity of a request, and the optional per-block step behind block l's attention forward - its
@@ -642,12 +694,14 @@ static int encoder_forward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* dropc
 // workspace then has mfvit_vit_workspace_bytes_ex(.., 1) bytes): d loss / d image, overwritten.  dparams == NULL (with dimg): the data-gradient
 // chain alone - no weight-gradient GEMM, no split-partial reduce, no bias / LayerNorm column sum, no side stream.  rel (dparams == dimg == NULL,
 // stages depth .. 0): that chain with the relevance step of mfvit_vit_backward_rel behind every block's attention backward; it ends at block 0's
-// step (no attention backward or LN1 backward of block 0).
+// step (no attention backward or LN1 backward of block 0).  lora (dparams == NULL; mfvit_vit_backward_lora): that chain plus the weight-gradient
+// GEMMs of the adapted Linears into lora->dw, the split-partial reduce of each block and, at the end, the batched contraction to dA / dB; without
+// dimg the chain ends behind the weight gradients of the lowest adapted block.
 static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* dropcfg, const float* params, const void* shadow, void* workspace,
                             const float* dfeatures, float* dparams, float* dinput, float* dimg, int stage_hi, int stage_lo, mfvit_stream_t stream,
-                            bool want_tokens, const mfvit_vit_rel_req* rel = nullptr) {
+                            bool want_tokens, const mfvit_vit_rel_req* rel = nullptr, const LoraPlan* lora = nullptr) {
     Dims d;
-    if (!get_dims(cfg, dropcfg, d) || !params || !shadow || !workspace || (!dparams && !dimg && !rel)) return MFVIT_EINVAL;
+    if (!get_dims(cfg, dropcfg, d) || !params || !shadow || !workspace || (!dparams && !dimg && !rel && !lora)) return MFVIT_EINVAL;
     if (!d.save || d.tok != want_tokens) return MFVIT_EINVAL;
     if (stage_hi > d.depth || stage_lo < -1 || stage_lo > stage_hi) return MFVIT_EINVAL;
     if (dimg && (d.tok || stage_lo != -1)) return MFVIT_EINVAL;
@@ -660,7 +714,13 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop
     const hipStream_t st = c.st;
     const long D = c.D, F = c.F, e = c.e;
     const bool lean_grad = c.lean_grad;
-    auto gblk = [&](int l) { return wg ? dparams + L.blk0 + (long)l * L.blk_stride : nullptr; };
+    float* const gbase = wg ? dparams : (lora ? lora->dw : nullptr);     // where weight gradients go: the gradient arena, or the adapters' dW_eff scratch
+    auto gblk = [&](int l) { return gbase ? gbase + L.blk0 + (long)l * L.blk_stride : nullptr; };
+    // the adapted Linears of block l whose weight gradient this call forms although wg is off (zeroed first: the GEMMs and the reduce accumulate)
+    auto lora_wants = [&](int l, int bits, long off, long count) -> int {
+        if (wg || !lora || !(lora->mask[l] & bits)) return 0;
+        return hipMemsetAsync(gblk(l) + off, 0, (size_t)count * sizeof(float), st) == hipSuccess ? 1 : -1;
+    };
     float* gx = (float*)(ws + W.gx);
     float* gmid = (float*)(ws + W.gmid);
     float* colscr = (float*)(ws + W.colscratch);
@@ -759,9 +819,12 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop
                                           d.M, d.D, st));
                 gy2 = ws + W.dtmp;
             }
-            if (wg) {   // dW2 += gx^T hact
+            const int w_fc2 = lora_wants(l, LORA_FC2, L.fc2_w, D * F), w_fc1 = lora_wants(l, LORA_FC1, L.fc1_w, F * D),
+                      w_proj = lora_wants(l, LORA_PROJ, L.proj_w, D * D), w_qkv = lora_wants(l, LORA_QKV, L.qkv_w, 3 * D * D);
+            if (w_fc2 < 0 || w_fc1 < 0 || w_proj < 0 || w_qkv < 0) return MFVIT_ELAUNCH;
+            if (wg || w_fc2) {   // dW2 += gx^T hact
                 GemmP p = nt(gy2, D * e, b + W.hact, F * e, d.M, d.D, d.F);
-                if (rdrop) p.cs0 = gb + L.fc2_b;
+                if (rdrop && wg) p.cs0 = gb + L.fc2_b;
                 p.out0 = gb + L.fc2_w; p.ldo0 = F;
                 p.cpart = next_tnpart();                          // split partials: plain stores, reduced in a fixed order at the end of the call
                 MFVIT_TRY(tn_now_or_later(p));
@@ -773,7 +836,7 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop
                 if (wg) { p.cs0 = gb + L.fc1_b; p.cpart = next_colpart(); }   // d fc1_b += column sums of dhpre from the accumulators of this epilogue (partials, fixed-order reduce)
                 MFVIT_TRY(gemm_nt_tile(d.dtype, EPI_GELU_BWD, p, st));
             }
-            if (wg) {   // dW1 += dhpre^T y2
+            if (wg || w_fc1) {   // dW1 += dhpre^T y2
                 GemmP p = nt(dhpre, F * e, b + W.y2, D * e, d.M, d.F, d.D);   // (d fc1_b: from the fc2 data gradient's epilogue, above)
                 p.out0 = gb + L.fc1_w; p.ldo0 = D;
                 p.cpart = next_tnpart();                          // split partials: plain stores, reduced in a fixed order at the end of the call
@@ -796,9 +859,9 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop
             }
             GemmP pend_proj = {};                                 // dWproj: launched here, or held back to ride along with dWqkv (one launch for both)
             bool have_pend = false;
-            if (wg) {   // dWproj += gmid^T attn
+            if (wg || w_proj) {   // dWproj += gmid^T attn
                 GemmP p = nt(gyp, D * e, b + W.attn, D * e, d.M, d.D, d.D);
-                if (rdrop) p.cs0 = gb + L.proj_b;
+                if (rdrop && wg) p.cs0 = gb + L.proj_b;
                 p.out0 = gb + L.proj_w; p.ldo0 = D;
                 p.cpart = next_tnpart();                          // split partials: plain stores, reduced in a fixed order at the end of the call
                 // held back by default when the weight gradients run on the caller's stream (nothing to overlap: one launch less is a pure gain,
@@ -830,9 +893,9 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop
             if (rel) MFVIT_TRY(rel_block_step(d, rel, l, qdt_bwd, b + W.qkv, (const float*)(b + W.lse), ws + W.dattn, st));
             MFVIT_TRY(fork());                                    // dqkv - and with it every input of this block's weight gradients - is ready
             for (int i = 0; i < ndef; ++i) MFVIT_TRY(gemm_tn(d.dtype, def_tn[i], wst));
-            if (wg) {   // dWqkv += dqkv^T y1 ; d qkv_b += column sums of dqkv (ones-fragment MFMA inside the wgrad kernel)
+            if (wg || w_qkv) {   // dWqkv += dqkv^T y1 ; d qkv_b += column sums of dqkv (ones-fragment MFMA inside the wgrad kernel)
                 GemmP p = nt(dqkv, 3 * D * e, b + W.y1, D * e, d.M, 3 * d.D, d.D);
-                p.cs0 = gb + L.qkv_b;
+                if (wg) p.cs0 = gb + L.qkv_b;
                 p.out0 = gb + L.qkv_w; p.ldo0 = D;
                 p.cpart = next_tnpart();                          // split partials: plain stores, reduced in a fixed order at the end of the call
                 // dWproj rides along when the LDS-DMA kernel takes both (same rows, same K = 384: 27 + 9 tiles x 7 splits = 252 workgroups): the
@@ -845,11 +908,14 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop
                     if (have_pend) MFVIT_TRY(gemm_tn(d.dtype, pend_proj, wst));
                     MFVIT_TRY(gemm_tn(d.dtype, p, wst));
                 }
+            } else if (have_pend) {
+                MFVIT_TRY(gemm_tn(d.dtype, pend_proj, wst));      // (adapters on proj without any on q / k / v)
             }
             MFVIT_TRY(tnpart_batch_flush(wst));                   // dW += this block's split partials, splits in a fixed order; the slots are free again
             tn_used = 0;
             if (use_side && hipEventRecord(ss.done[l & 63], ss.s) != hipSuccess) return MFVIT_ELAUNCH;
             MFVIT_TRY(wait_layer(l + 1));                         // fc2-wgrad of layer l+1 reads the gxT copy written next
+            if (lora && !dimg && l == stage_lo) continue;         // adapters only: nobody reads d x of the lowest adapted block
             {   // gx = LN1bwd(dqkv Wqkv) + gmid ; d ln1_w, d ln1_b, d fc2_b of block l-1 (or scratch for the embed stage)
                 if (wg && l == 0 && hipMemsetAsync(colscr, 0, 2 * D * sizeof(float), st) != hipSuccess) return MFVIT_ELAUNCH;
                 GemmP p = nt(dqkv, 3 * D * e, sb + S.qkv_t, 3 * D * e, d.M, d.D, 3 * d.D);
@@ -913,6 +979,7 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop
     }
     MFVIT_TRY(colpart_batch_flush(st));
     MFVIT_TRY(tnpart_batch_flush(wst));     // dW += the split partials still pending (the patch embedding's), splits in a fixed order
+    if (lora) MFVIT_TRY(lora_run(d, lora->req, lora->dw, nullptr, true, st));   // dA, dB of every item from the dW_eff slices
     if (use_side) {   // join: everything the side stream did is ordered before whatever the caller queues next
         if (hipEventRecord(ss.end, ss.s) != hipSuccess || hipStreamWaitEvent(st, ss.end, 0) != hipSuccess) return MFVIT_ELAUNCH;
     }
@@ -974,6 +1041,43 @@ int mfvit_vit_backward_drop(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop
     if (!drop || !dparams) return MFVIT_EINVAL;
     ShareScope share(cfg);
     return encoder_backward(cfg, drop, params, shadow, workspace, dfeatures, dparams, nullptr, nullptr, stage_hi, stage_lo, stream, false);
+}
+int mfvit_vit_prepare_shadow_lora(const mfvit_vit_cfg* cfg, const float* params, const mfvit_lora_req* req, float* eff_params, void* shadow,
+                                  mfvit_stream_t stream) {
+    Dims d;
+    LoraPlan pl;
+    if (!get_dims(cfg, d) || !params || !shadow || !eff_params || !lora_plan(d, req, false, pl)) return MFVIT_EINVAL;
+    const size_t total = (size_t)param_layout(d).total;
+    if ((eff_params <= params && params < eff_params + total) || (params <= eff_params && eff_params < params + total)) return MFVIT_EINVAL;
+    const ParamLayout L = param_layout(d);
+    for (int i = 0; i < req->n; ++i)
+        if (!lora_pair_ok(lora_pair(d, L, req->items[i], params, eff_params, false), req->rank, false)) return MFVIT_EINVAL;
+    if (hipMemcpyAsync(eff_params, params, total * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return MFVIT_ELAUNCH;
+    MFVIT_TRY(lora_run(d, req, params, eff_params, false, (hipStream_t)stream));
+    return mfvit_vit_prepare_shadow(cfg, eff_params, shadow, stream);
+}
+int mfvit_vit_backward_lora(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, const float* params, const void* shadow, void* workspace,
+                            const float* dfeatures, const mfvit_lora_req* req, float* dw_scratch, float* dimg, int stage_hi, int stage_lo,
+                            mfvit_stream_t stream) {
+    Dims d;
+    LoraPlan pl;
+    if (!get_dims(cfg, drop, d) || !dw_scratch || !dfeatures || !lora_plan(d, req, true, pl)) return MFVIT_EINVAL;
+    if (stage_hi != d.depth || stage_lo > pl.lowest || stage_lo < -1 || (dimg && stage_lo != -1)) return MFVIT_EINVAL;
+    pl.dw = dw_scratch;
+    {   // every contraction checked before the first launch of the chain
+        const ParamLayout L = param_layout(d);
+        for (int i = 0; i < req->n; ++i)
+            if (!lora_pair_ok(lora_pair(d, L, req->items[i], dw_scratch, nullptr, true), req->rank, true)) return MFVIT_EINVAL;
+    }
+    ShareScope share(cfg);
+    return encoder_backward(cfg, drop, params, shadow, workspace, dfeatures, nullptr, nullptr, dimg, stage_hi, dimg ? -1 : pl.lowest, stream, false,
+                            nullptr, &pl);
+}
+int mfvit_vit_lora_grad(const mfvit_vit_cfg* cfg, const mfvit_lora_req* req, const float* dparams, mfvit_stream_t stream) {
+    Dims d;
+    LoraPlan pl;
+    if (!get_dims(cfg, d) || !dparams || !lora_plan(d, req, true, pl)) return MFVIT_EINVAL;
+    return lora_run(d, req, dparams, nullptr, true, (hipStream_t)stream);
 }
 int mfvit_gpt_forward(const mfvit_vit_cfg* cfg, const float* params, const void* shadow, const float* tokens, void* workspace, float* out,
                       mfvit_stream_t stream) {

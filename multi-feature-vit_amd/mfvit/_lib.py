@@ -45,6 +45,16 @@ class VitRelReq(Structure):
     _fields_ = [("blocks", c_uint64), ("maps", c_void_p), ("relevance", c_void_p), ("scratch", c_void_p)]
 
 
+class LoraItem(Structure):
+    """mfvit_lora_item: one (block, target) adapter pair of a request (include/mfvit.h)."""
+    _fields_ = [("block", c_int), ("target", c_int), ("a", c_void_p), ("b", c_void_p), ("da", c_void_p), ("db", c_void_p)]
+
+
+class LoraReq(Structure):
+    """mfvit_lora_req: rank, scale and the host array of items."""
+    _fields_ = [("rank", c_int), ("scale", c_float), ("n", c_int), ("items", POINTER(LoraItem))]
+
+
 class FusionCfg(Structure):
     _fields_ = [("batch", c_int), ("tokens", c_int), ("dim", c_int), ("heads", c_int), ("num_classes", c_int),
                 ("eps_pre", c_float), ("eps_post", c_float)]
@@ -76,6 +86,11 @@ SIGNATURES = {
     "mfvit_vit_forward_attn": (I, [POINTER(VitCfg), POINTER(VitAttnReq), P, P, P, P, P, P]),
     "mfvit_vit_rel_scratch_bytes": (c_size_t, [POINTER(VitCfg), POINTER(VitRelReq)]),
     "mfvit_vit_backward_rel": (I, [POINTER(VitCfg), POINTER(VitRelReq), P, P, P, P, P]),
+    "mfvit_lora_merge": (I, [P, L, P, P, F, P, L, I, I, I, P]),
+    "mfvit_lora_grad": (I, [P, L, P, P, F, P, P, I, I, I, P]),
+    "mfvit_vit_prepare_shadow_lora": (I, [POINTER(VitCfg), P, POINTER(LoraReq), P, P, P]),
+    "mfvit_vit_backward_lora": (I, [POINTER(VitCfg), POINTER(VitDrop), P, P, P, P, POINTER(LoraReq), P, P, I, I, P]),
+    "mfvit_vit_lora_grad": (I, [POINTER(VitCfg), POINTER(LoraReq), P, P]),
     "mfvit_gpt_forward": (I, [POINTER(VitCfg), P, P, P, P, P, P]),
     "mfvit_gpt_backward": (I, [POINTER(VitCfg), P, P, P, P, P, P, P]),
     "mfvit_linear_fwd": (I, [I, I, P, L, P, L, P, P, L, P, L, I, I, I, P]),

@@ -172,7 +172,7 @@ def _eval_features(vit, img):
         ws = vit._get_ws(cfg)
         feats = torch.empty(img.shape[0], vit.num_tokens, vit.embed_dim, device=img.device, dtype=torch.float32)
         try:
-            check(lib().mfvit_vit_forward(cfg, ptr(vit._arena), ptr(vit._shadow), ptr(img), ptr(ws), ptr(feats), stream()), "mfvit_vit_forward")
+            check(lib().mfvit_vit_forward(cfg, ptr(vit._kernel_params()), ptr(vit._shadow), ptr(img), ptr(ws), ptr(feats), stream()), "mfvit_vit_forward")
         finally:
             vit._release_ws(ws)
     return feats
@@ -190,7 +190,7 @@ def _saved_forward(vit, img):
         ws = vit._get_ws(cfg, None, want_dimg=True)
         feats = torch.empty(img.shape[0], vit.num_tokens, vit.embed_dim, device=img.device, dtype=torch.float32)
         try:
-            check(lib().mfvit_vit_forward(cfg, ptr(vit._arena), ptr(vit._shadow), ptr(img), ptr(ws), ptr(feats), stream()), "mfvit_vit_forward")
+            check(lib().mfvit_vit_forward(cfg, ptr(vit._kernel_params()), ptr(vit._shadow), ptr(img), ptr(ws), ptr(feats), stream()), "mfvit_vit_forward")
         except BaseException:
             vit._release_ws(ws)
             raise

@@ -85,6 +85,9 @@ class GradSync:
         import os
         if bucket_layers is None:
             bucket_layers = int(os.environ.get("MFVIT_GRAD_BUCKET_LAYERS", "4"))
+        if getattr(vit, "_lora", None) is not None:
+            raise NotImplementedError("GradSync on a model with LoRA adapters (mfvit.lora): the adapters' gradients are not part of the flat "
+                                      "gradient arena that is exchanged - merge_lora / remove_lora first, or reduce them yourself")
         vit._grad_bucket_layers = bucket_layers
         if self.enabled:
             vit._grad_stage_hook = self._stage_hook

@@ -149,7 +149,8 @@ class _PatchEmbed(nn.Module):
 class _EncoderFn(torch.autograd.Function):
     """features3D as one autograd node: forward = mfvit_vit_forward, backward = mfvit_vit_backward (stage by stage), or mfvit_vit_backward_ex
     when the image requires a gradient (d loss / d img from the patch-embedding data gradient; no parameter gradient at all when no arena
-    parameter requires one)."""
+    parameter requires one).  params: the arena parameters, then the adapter parameters of mfvit.lora (if attached); with adapters and every
+    arena parameter frozen the backward is mfvit_vit_backward_lora (the data-gradient chain + the adapted Linears' weight gradients)."""
 
     @staticmethod
     def forward(ctx, model, img, need_grad, drop, *params):
@@ -180,8 +181,18 @@ class _EncoderFn(torch.autograd.Function):
             # to consumers on other streams)
             dimg = torch.empty(shape, device=dfeats.device, dtype=torch.float32)
             dimg.record_stream(torch.cuda.current_stream(dfeats.device))
-        want_params = any(ctx.needs_input_grad[4:])
-        grads = model._run_backward(ctx.cfg, ctx.ws, dfeats, drop=ctx.drop, dimg=dimg, want_params=want_params)
+        na = len(model._arena_params)
+        want_params = any(ctx.needs_input_grad[4:4 + na])
+        want_lora = any(ctx.needs_input_grad[4 + na:])
+        if want_lora and not want_params:
+            grads = [None] * na + model._run_backward_lora(ctx.cfg, ctx.ws, dfeats, drop=ctx.drop, dimg=dimg)
+        else:
+            grads = model._run_backward(ctx.cfg, ctx.ws, dfeats, drop=ctx.drop, dimg=dimg, want_params=want_params)
+            if want_lora:       # adapters beside trainable arena parameters: contract the adapted dW slices of the full gradient arena
+                grads = grads + model._lora_grads_from_arena(ctx.cfg, model._last_grad_arena)
+            else:
+                grads = grads + [None] * (len(ctx.needs_input_grad) - 4 - na)
+        grads = [g if need else None for g, need in zip(grads, ctx.needs_input_grad[4:])]
         model._release_ws(ctx.ws)
         ctx.ws = None
         # the single-use feature cache holds the forward's output, i.e. this graph and the parameters' AccumulateGrad nodes (which carry
@@ -266,6 +277,7 @@ class VisionTransformerMoCo(nn.Module):
         self._shadow_key = None
         self._ws_pool = {}
         self._feat_cache = None
+        self._lora = None                   # mfvit.lora.LoraState while adapters are attached
         self._flatten()
 
     # ------------------------------------------------------------------ init (moco-v3 VisionTransformerMoCo)
@@ -423,7 +435,17 @@ class VisionTransformerMoCo(nn.Module):
         return c
 
     def _param_version(self):
-        return sum(p._version for p in self._arena_params)
+        v = sum(p._version for p in self._arena_params)
+        lo = self.__dict__.get("_lora")
+        # with adapters (mfvit.lora): their versions and the attachment's serial number are part of every key the weights enter -
+        # the shadow's and the single-use feature cache's
+        return v if lo is None else (v, lo.serial, sum(p._version for p in lo.params()))
+
+    def _kernel_params(self):
+        """The f32 arena the encoder entry points take as `params`: the parameter arena, or with adapters the effective arena
+        (every adapted weight merged, W + s B A) that _ensure_shadow keeps beside the shadow."""
+        lo = self.__dict__.get("_lora")
+        return self._arena if lo is None else lo.eff
 
     def _ensure_shadow(self, cfg):
         key = (self._param_version(), cfg.dtype, str(self._arena.device))
@@ -435,7 +457,16 @@ class VisionTransformerMoCo(nn.Module):
         nbytes = lib().mfvit_vit_shadow_bytes(cfg)
         if self._shadow is None or self._shadow.numel() != nbytes:
             self._shadow = torch.empty(nbytes, device=self._arena.device, dtype=torch.uint8)
-        check(lib().mfvit_vit_prepare_shadow(cfg, ptr(self._arena), ptr(self._shadow), stream()), "mfvit_vit_prepare_shadow")
+        lo = self.__dict__.get("_lora")
+        if lo is None:
+            check(lib().mfvit_vit_prepare_shadow(cfg, ptr(self._arena), ptr(self._shadow), stream()), "mfvit_vit_prepare_shadow")
+        else:
+            # the shadow of the merged weights; the effective arena is what forward and backward read as `params`
+            if lo.eff is None or lo.eff.shape != self._arena.shape or lo.eff.device != self._arena.device:
+                lo.eff = torch.empty_like(self._arena)
+            req = lo.request(grads=None)
+            check(lib().mfvit_vit_prepare_shadow_lora(cfg, ptr(self._arena), req, ptr(lo.eff), ptr(self._shadow), stream()),
+                  "mfvit_vit_prepare_shadow_lora")
         self._shadow_key = key
         self._feat_cache = None
 
@@ -475,10 +506,10 @@ class VisionTransformerMoCo(nn.Module):
         ws = self._get_ws(cfg, drop, want_dimg)
         feats = torch.empty(img.shape[0], self.num_tokens, self.embed_dim, device=img.device, dtype=torch.float32)
         if drop is None:
-            check(lib().mfvit_vit_forward(cfg, ptr(self._arena), ptr(self._shadow), ptr(img), ptr(ws), ptr(feats), stream()),
+            check(lib().mfvit_vit_forward(cfg, ptr(self._kernel_params()), ptr(self._shadow), ptr(img), ptr(ws), ptr(feats), stream()),
                   "mfvit_vit_forward")
         else:
-            check(lib().mfvit_vit_forward_drop(cfg, drop, ptr(self._arena), ptr(self._shadow), ptr(img), ptr(ws), ptr(feats), stream()),
+            check(lib().mfvit_vit_forward_drop(cfg, drop, ptr(self._kernel_params()), ptr(self._shadow), ptr(img), ptr(ws), ptr(feats), stream()),
                   "mfvit_vit_forward_drop")
         if not save:
             self._release_ws(ws)
@@ -495,7 +526,7 @@ class VisionTransformerMoCo(nn.Module):
         if not want_params:
             if dimg is None:
                 raise _lib.MfvitError("a backward without parameter gradients needs the image gradient")
-            check(lib().mfvit_vit_backward_ex(cfg, drop, ptr(self._arena), ptr(self._shadow), ptr(ws), ptr(dfeats), None, ptr(dimg),
+            check(lib().mfvit_vit_backward_ex(cfg, drop, ptr(self._kernel_params()), ptr(self._shadow), ptr(ws), ptr(dfeats), None, ptr(dimg),
                                               self.depth, -1, stream()), "mfvit_vit_backward_ex")
             return [None] * len(self._arena_params)
         # The flat gradient arena is reused from step to step (stable addresses: the optimizers' device tables stay valid) unless a
@@ -521,7 +552,7 @@ class VisionTransformerMoCo(nn.Module):
 
         def bwd(hi, lo):
             # (drop = NULL, dimg = NULL: exactly mfvit_vit_backward; the call that runs the embedding stage also writes the image gradient)
-            check(lib().mfvit_vit_backward_ex(cfg, drop, ptr(self._arena), ptr(self._shadow), ptr(ws), ptr(dfeats), ptr(gflat),
+            check(lib().mfvit_vit_backward_ex(cfg, drop, ptr(self._kernel_params()), ptr(self._shadow), ptr(ws), ptr(dfeats), ptr(gflat),
                                               ptr(dimg) if lo == -1 else None, hi, lo, stream()), "mfvit_vit_backward_ex")
         if hook is None:
             bwd(self.depth, -1)
@@ -546,11 +577,40 @@ class VisionTransformerMoCo(nn.Module):
         views = torch._utils._unflatten_dense_tensors(gflat, params)
         return [v if p.requires_grad else None for v, p in zip(views, params)]
 
+    def _run_backward_lora(self, cfg, ws, dfeats, drop=None, dimg=None):
+        """The selective backward of a model with adapters whose arena parameters are all frozen (mfvit_vit_backward_lora): returns the
+        adapters' gradients in the order of LoraState.params(), views of one fresh flat tensor (so that .grad accumulation is
+        autograd's).  The dW_eff scratch (one gradient-arena-sized tensor) is kept from step to step."""
+        lo = self._lora
+        dfeats = dfeats.contiguous()
+        if dfeats.dtype != torch.float32:
+            dfeats = dfeats.float()
+        if lo.dw is None or lo.dw.shape != self._arena.shape or lo.dw.device != self._arena.device:
+            lo.dw = torch.empty_like(self._arena)
+        grads = lo.new_grads(self._arena.device)
+        req = lo.request(grads=grads)
+        check(lib().mfvit_vit_backward_lora(cfg, drop, ptr(self._kernel_params()), ptr(self._shadow), ptr(ws), ptr(dfeats), req, ptr(lo.dw),
+                                            ptr(dimg), self.depth, -1 if dimg is not None else 0, stream()), "mfvit_vit_backward_lora")
+        return grads
+
+    def _lora_grads_from_arena(self, cfg, gflat):
+        """Adapters beside trainable arena parameters: the full backward has filled the gradient arena `gflat`; one batched launch
+        contracts its adapted dW slices to dA / dB (mfvit_vit_lora_grad).  Correct, and slower than the selective backward: every weight
+        gradient of every block is formed."""
+        lo = self._lora
+        grads = lo.new_grads(self._arena.device)
+        req = lo.request(grads=grads)
+        check(lib().mfvit_vit_lora_grad(cfg, req, ptr(gflat), stream()), "mfvit_vit_lora_grad")
+        return grads
+
     # ------------------------------------------------------------------ public API (reference call sites)
     def _features(self, x, caller):
         # activations are saved when a parameter or the image needs a gradient (saliency / FGSM with a frozen backbone: the image only)
         need_x = torch.is_grad_enabled() and x.requires_grad
-        need = need_x or (torch.is_grad_enabled() and any(p.requires_grad for p in self._arena_params))
+        lo = self.__dict__.get("_lora")
+        lora_params = lo.params() if lo is not None else []
+        need = need_x or (torch.is_grad_enabled() and (any(p.requires_grad for p in self._arena_params) or
+                                                       any(p.requires_grad for p in lora_params)))
         key = (x._version, need, need_x, self._param_version(), torch.is_grad_enabled())
         c = self._feat_cache
         self._feat_cache = None
@@ -563,7 +623,7 @@ class VisionTransformerMoCo(nn.Module):
             return c[3]
         c = None
         self._grad_arena_lent = False
-        feats = _EncoderFn.apply(self, x, need, drop, *self._arena_params)
+        feats = _EncoderFn.apply(self, x, need, drop, *self._arena_params, *lora_params)
         self._feat_cache = None if stochastic else (x, key, caller, feats)
         return feats
 
@@ -626,7 +686,7 @@ class VisionTransformerMoCo(nn.Module):
             ws = self._get_ws(cfg)
             feats = torch.empty(B, T, self.embed_dim, device=dev, dtype=torch.float32)
             try:
-                check(lib().mfvit_vit_forward_attn(cfg, req, ptr(self._arena), ptr(self._shadow), ptr(img), ptr(ws), ptr(feats), stream()),
+                check(lib().mfvit_vit_forward_attn(cfg, req, ptr(self._kernel_params()), ptr(self._shadow), ptr(img), ptr(ws), ptr(feats), stream()),
                       "mfvit_vit_forward_attn")
             finally:
                 self._release_ws(ws)
@@ -681,7 +741,7 @@ class VisionTransformerMoCo(nn.Module):
             ws = self._get_ws(cfg)
             feats = torch.empty(img.shape[0], self.num_tokens, self.embed_dim, device=img.device, dtype=torch.float32)
             try:
-                check(lib().mfvit_vit_forward(cfg, ptr(self._arena), ptr(self._shadow), ptr(img), ptr(ws), ptr(feats), stream()),
+                check(lib().mfvit_vit_forward(cfg, ptr(self._kernel_params()), ptr(self._shadow), ptr(img), ptr(ws), ptr(feats), stream()),
                       "mfvit_vit_forward")
             except BaseException:
                 self._release_ws(ws)
@@ -703,7 +763,7 @@ class VisionTransformerMoCo(nn.Module):
                 raise _lib.MfvitError("invalid relevance request for this encoder configuration")
             scratch = torch.empty(nbytes, device=dev, dtype=torch.uint8)
             req.scratch = scratch.data_ptr()
-            check(lib().mfvit_vit_backward_rel(cfg, req, ptr(self._arena), ptr(self._shadow), ptr(ws), ptr(dfeats), stream()),
+            check(lib().mfvit_vit_backward_rel(cfg, req, ptr(self._kernel_params()), ptr(self._shadow), ptr(ws), ptr(dfeats), stream()),
                   "mfvit_vit_backward_rel")
         return [maps[i * per:(i + 1) * per].view(B, T, T) for i in range(len(blocks))], rel
 

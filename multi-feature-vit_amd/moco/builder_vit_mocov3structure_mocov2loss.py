@@ -70,6 +70,9 @@ class MoCo(nn.Module):
 
     @torch.no_grad()
     def _momentum_update_key_encoder(self, m):
+        if getattr(self.base_encoder, "_lora", None) is not None or getattr(self.momentum_encoder, "_lora", None) is not None:
+            raise NotImplementedError("the MoCo builders do not take encoders with LoRA adapters (mfvit.lora): the momentum update "
+                                      "averages the flat parameter arenas, which the adapters are not part of")
         ema_update_(self.momentum_encoder.flat_parameters(), self.base_encoder.flat_parameters(), m,
                     self.momentum_encoder._arena_params)
         pb, pm = self._arenas()

@@ -219,7 +219,7 @@ class Fus_CrossViT(nn.Module):
             ws = vit._get_ws(cfg)
             feats = torch.empty(img.shape[0], vit.num_tokens, vit.embed_dim, device=img.device, dtype=torch.float32)
             try:
-                _lib.check(_lib.lib().mfvit_vit_forward(cfg, _lib.ptr(vit._arena), _lib.ptr(vit._shadow), _lib.ptr(img), _lib.ptr(ws),
+                _lib.check(_lib.lib().mfvit_vit_forward(cfg, _lib.ptr(vit._kernel_params()), _lib.ptr(vit._shadow), _lib.ptr(img), _lib.ptr(ws),
                                                         _lib.ptr(feats), _lib.stream()), "mfvit_vit_forward")
             finally:
                 vit._release_ws(ws)
