@@ -330,6 +330,31 @@ int mfvit_linear_wgrad(int dtype, const void* dy, int64_t lddy, const void* x, i
 #define MFVIT_WGRAD_SCRATCH_FLOATS (384 * 128 * 128)
 int mfvit_linear_wgrad_ws(int dtype, const void* dy, int64_t lddy, const void* x, int64_t ldx, float* dw, int64_t lddw, int M, int N,
                           int K, float* scratch, mfvit_stream_t stream);
+/* The widest single-launch form (additive): mfvit_linear_wgrad_ws plus
+ *   dbias[N] (f32, accumulated; may be NULL) += column sums of dy - the nn.Linear bias gradient, taken from the same operand fragments;
+ *   rows_in, rows_out, row_off: reduction row m reads dy row (m / rows_in) * rows_out + m % rows_in + row_off (x is read at row m).  The patch
+ *   embedding's weight gradient reads the token rows 1 .. np of every image of a [B][np + 1][D] gradient this way (np, np + 1, 1).  All three 0:
+ *   no remap; otherwise rows_in > 0, row_off >= 0 and rows_out >= rows_in + row_off, else MFVIT_EINVAL.
+ * Alignment (every weight-gradient entry): dy, x and their row pitches are multiples of 16 bytes (lddy, ldx % 8 == 0 in 16-bit elements, % 4 == 0
+ * in f32) - the kernels read 16-byte vectors; anything else returns MFVIT_EINVAL before a launch. */
+int mfvit_linear_wgrad_ex(int dtype, const void* dy, int64_t lddy, const void* x, int64_t ldx, float* dw, int64_t lddw, int M, int N, int K,
+                          float* scratch, float* dbias, int rows_in, int rows_out, int row_off, mfvit_stream_t stream);
+/* Host only, no GPU needed (additive): what a weight-gradient launch of this shape decides before it launches, reported by the launchers' own
+ * decision code under the same run-time switches (MFVIT_TN_GLDS, mfvit_set_stream_share).  N2 > 0: the paired launch of mfvit_linear_wgrad_pair
+ * with a second gradient of N2 rows (lddy2, ldx2, lddw2: its leading dimensions; MFVIT_ENOSYS where the pair is refused); N2 == 0: a single launch
+ * as mfvit_linear_wgrad_ex issues it.  flags: MFVIT_WGRAD_PLAN_* below.  plan[MFVIT_WGRAD_PLAN_INTS]:
+ *   [0] kernel: 0 small f32 kernel, 1 register-staged tile kernel, 2 LDS-DMA kernel      [1] reduction rows per stage (0: kernel 0)
+ *   [2] splits of the reduction     [3] rows per split (a multiple of [1])                 [4] rows of the last split
+ *   [5] 1: tile partials as plain stores through the scratch, 0: float atomics onto dw    [6] 1: bias sums through the rows behind the tile partials,
+ *   0: float atomics onto dbias     [7] 128 x 128 output tiles (kernel 1 on split bf16: storage tiles of 64 x 64 logical elements).
+ * Returns what the launch would return for a shape outside the domain (MFVIT_EINVAL) and leaves plan untouched then. */
+#define MFVIT_WGRAD_PLAN_BIAS 1            /* dbias given ... */
+#define MFVIT_WGRAD_PLAN_BIAS_UNALIGNED 2  /* ... at an address that is not a multiple of 16 bytes */
+#define MFVIT_WGRAD_PLAN_SCRATCH 4         /* scratch given */
+#define MFVIT_WGRAD_PLAN_REMAP 8           /* rows remapped (rows_in > 0) */
+#define MFVIT_WGRAD_PLAN_INTS 8
+int mfvit_linear_wgrad_plan(int dtype, int M, int N, int K, int N2, int64_t lddy, int64_t ldx, int64_t lddw, int64_t lddy2, int64_t ldx2,
+                            int64_t lddw2, int flags, int32_t* plan);
 /* TWO weight gradients with the same reduction rows M and the same K in ONE launch (the encoder backward's default for dWqkv + dWproj,
  * the nn.Linear pair of the timm attention block, call sites crossvit_2vits_..._sum.py:128-135):
  *   dw_a[Na][K] += dy_a^T x_a ; dbias_a[Na] += column sums of dy_a (may be NULL) ; dw_b[Nb][K] += dy_b^T x_b.

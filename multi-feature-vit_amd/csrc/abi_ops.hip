@@ -88,6 +88,46 @@ int mfvit_linear_wgrad_ws(int dtype, const void* dy, int64_t lddy, const void* x
     p.cpart = scratch;
     return gemm_tn(dtype, p, (hipStream_t)stream);
 }
+static bool wgrad_remap_ok(int rows_in, int rows_out, int row_off) {
+    if (rows_in == 0) return rows_out == 0 && row_off == 0;
+    return rows_in > 0 && row_off >= 0 && rows_out >= rows_in + row_off;
+}
+int mfvit_linear_wgrad_ex(int dtype, const void* dy, int64_t lddy, const void* x, int64_t ldx, float* dw, int64_t lddw, int M, int N, int K,
+                          float* scratch, float* dbias, int rows_in, int rows_out, int row_off, mfvit_stream_t stream) {
+    if (!dy || !x || !dw || !wgrad_remap_ok(rows_in, rows_out, row_off)) return MFVIT_EINVAL;
+    GemmP p = nt(dy, lddy, x, ldx, M, N, K);
+    p.out0 = dw; p.ldo0 = lddw;
+    p.cpart = scratch;
+    p.cs0 = dbias;
+    p.orow_in = rows_in; p.orow_out = rows_out; p.orow_off = row_off;
+    return gemm_tn(dtype, p, (hipStream_t)stream);
+}
+int mfvit_linear_wgrad_plan(int dtype, int M, int N, int K, int N2, int64_t lddy, int64_t ldx, int64_t lddw, int64_t lddy2, int64_t ldx2,
+                            int64_t lddw2, int flags, int32_t* plan) {
+    if (!plan || N2 < 0 || (flags & ~15)) return MFVIT_EINVAL;
+    // stand-ins for the caller's buffers: the decision code looks at whether a pointer is given and at its 16-byte alignment, nothing is read
+    char* const given = (char*)(size_t)4096;
+    GemmP p = nt(given, lddy, given, ldx, M, N, K);
+    p.out0 = given; p.ldo0 = lddw;
+    if (flags & MFVIT_WGRAD_PLAN_BIAS) p.cs0 = (float*)(given + ((flags & MFVIT_WGRAD_PLAN_BIAS_UNALIGNED) ? 4 : 0));
+    if (flags & MFVIT_WGRAD_PLAN_SCRATCH) p.cpart = (float*)given;
+    if (flags & MFVIT_WGRAD_PLAN_REMAP) { p.orow_in = 1; p.orow_out = 1; }
+    TnPlan pl;
+    int rc;
+    if (N2 > 0) {
+        if (flags & (MFVIT_WGRAD_PLAN_SCRATCH | MFVIT_WGRAD_PLAN_REMAP)) return MFVIT_EINVAL;   // (mfvit_linear_wgrad_pair takes neither)
+        GemmP b = nt(given, lddy2, given, ldx2, M, N2, K);
+        b.out0 = given; b.ldo0 = lddw2;
+        rc = gemm_tn_pair_plan(dtype, p, b, &pl);
+    } else {
+        rc = gemm_tn_plan(dtype, p, &pl);
+    }
+    if (rc != MFVIT_OK) return rc;
+    plan[0] = pl.kernel; plan[1] = pl.kr; plan[2] = pl.splits; plan[3] = pl.chunk;
+    plan[4] = M - (pl.splits - 1) * pl.chunk;
+    plan[5] = pl.cpart; plan[6] = pl.kpart; plan[7] = pl.tiles;
+    return MFVIT_OK;
+}
 int mfvit_linear_wgrad_pair(int dtype, const void* dy_a, int64_t lddy_a, const void* x_a, int64_t ldx_a, float* dw_a, int64_t lddw_a, float* dbias_a,
                             int Na, const void* dy_b, int64_t lddy_b, const void* x_b, int64_t ldx_b, float* dw_b, int64_t lddw_b, int Nb, int M, int K,
                             mfvit_stream_t stream) {

@@ -1124,26 +1124,54 @@ template <typename T, int REPI> static int launch_row(const GemmP& p, hipStream_
     }
     return launch_row_v<T, REPI, 2, 128, 64>(p, st);
 }
-template <typename T> static int launch_tn(GemmP p, hipStream_t st) {
+// The host decisions of a gemm_tn_kernel launch (kernels.h::TnPlan): the domain check, the split count, the rows per split, and whether the tile
+// partials and the bias column sums leave through scratch.  launch_tn calls it before it launches; gemm_tn_plan reports what it returned.
+template <typename T> static int plan_tn(const GemmP& p, TnPlan& pl) {
     constexpr int EP = elems_per<T>::value;
     if (p.N * EP % 128 || p.K * EP % 128 || p.M <= 0) return MFVIT_EINVAL;
+    // SStage::load reads 16-byte vectors at base + row * ld + column (a multiple of 16 bytes): the row pitches, the base addresses and the batch
+    // strides must keep them aligned
+    constexpr long V = 16 / (long)sizeof(T);
+    if (p.lda % V || p.ldw % V || (((size_t)p.A | (size_t)p.W) & 15)) return MFVIT_EINVAL;
+    if (p.nb > 1 && ((p.sAo | p.sAi | p.sWo | p.sWi) % V)) return MFVIT_EINVAL;
     constexpr int KR = 128 / (int)sizeof(T);
     const int tiles = (p.N * EP / 128) * (p.K * EP / 128);
-    if (p.splits <= 0) {
+    int splits = p.splits;
+    if (splits <= 0) {
         constexpr int target = 384;
         // Fill the chip evenly: two workgroups fit a CU (2 x 80 KB of LDS), so aim just BELOW a multiple of 256 blocks - 288
         // blocks on 256 CUs leave 224 CUs idle while 32 run two (the makespan is the slowest CU's).
         int s = (tiles >= 16 ? target : (target * 2) / 3) / tiles;
         const int maxs = (p.M + 4 * KR - 1) / (4 * KR);  // at least 4 stages per split
-        p.splits = s < 1 ? 1 : (s > maxs ? maxs : s);
+        splits = s < 1 ? 1 : (s > maxs ? maxs : s);
     }
+    int chunk;
     {   // no empty split (the kernel derives the same chunk from p.splits): with the plain-store partial path every split must write its tile -
         // an empty one used to return early and the reduce pass summed whatever the scratch held (the partial path at M where 28 splits of
         // KR-rounded chunks overshoot M: caught by the switch-matrix run of round 3)
-        int chunk = (p.M + p.splits - 1) / p.splits;
+        chunk = (p.M + splits - 1) / splits;
         chunk = (chunk + KR - 1) / KR * KR;
-        p.splits = (p.M + chunk - 1) / chunk;
+        splits = (p.M + chunk - 1) / chunk;
     }
+    pl.kernel = TN_KERNEL_TILE;
+    pl.kr = KR;
+    pl.splits = splits;
+    pl.chunk = chunk;
+    pl.tiles = tiles;
+    // p.cpart (optional, >= splits * N * K floats): split partials go there as plain stores and are summed by a second kernel
+    pl.cpart = p.cpart && !(p.nb > 1 || splits < 2 || p.ldo0 % 4 || (long)tiles * splits > 384);   // scratch holds 384 tiles
+    // ... and the bias column sums of the splits as [split][N] behind them
+    pl.kpart = pl.cpart && p.cs0 && (long)tiles * splits + 2 <= 384 && p.N % 4 == 0 && (size_t)p.cs0 % 16 == 0;
+    return MFVIT_OK;
+}
+template <typename T> static int launch_tn(GemmP p, hipStream_t st) {
+    constexpr int KR = 128 / (int)sizeof(T);
+    TnPlan pl;
+    MFVIT_TRY(plan_tn<T>(p, pl));
+    const int tiles = pl.tiles;
+    p.splits = pl.splits;
+    if (!pl.cpart) p.cpart = nullptr;
+    p.kpart = pl.kpart ? p.cpart + (long)p.splits * p.N * p.K : nullptr;
     const bool xcd1d = p.splits > 1 && p.nb <= 1;
     constexpr int bytes = 2 * (STile<T, 128, KR>::BYTES * 2);
     static PerDeviceOnce attr_set;
@@ -1151,9 +1179,6 @@ template <typename T> static int launch_tn(GemmP p, hipStream_t st) {
         (void)hipFuncSetAttribute((const void*)gemm_tn_kernel<T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
         (void)hipFuncSetAttribute((const void*)gemm_tn_kernel<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     }
-    // p.cpart (optional, >= splits * N * K floats): split partials go there as plain stores and are summed by a second kernel
-    if (p.nb > 1 || p.splits < 2 || p.ldo0 % 4 || (long)tiles * p.splits > 384) p.cpart = nullptr;   // scratch holds 384 tiles
-    p.kpart = p.cpart && p.cs0 && (long)tiles * p.splits + 2 <= 384 && p.N % 4 == 0 && (size_t)p.cs0 % 16 == 0 ? p.cpart + (long)p.splits * p.N * p.K : nullptr;
     ProfScope ps(PROF_GEMM_TN, 2.0 * p.M * p.N * p.K * (p.nb > 1 ? p.nb : 1), 0, st);
     const dim3 grid = xcd1d ? dim3(tiles * p.splits, 1, 1) : dim3(tiles, p.splits, p.nb > 1 ? p.nb : 1);
     if (p.orow_in)
@@ -1329,14 +1354,30 @@ int gemm_nt_row(int dtype, int repi, const GemmP& p, hipStream_t st) {
     }
     return MFVIT_EINVAL;
 }
+static int tn_plan_by_dtype(int dtype, const GemmP& p, TnPlan& pl) { MFVIT_BY_DTYPE(dtype, (plan_tn<TT>(p, pl))) }
+// which kernel a weight gradient goes to (TN_KERNEL_*); q: what the small kernel is handed
+static int tn_route(int dtype, const GemmP& p, GemmP& q) {
+    if (gemm_tn_glds_supported(dtype, p)) return TN_KERNEL_GLDS;               // gemm_tn2.hip: LDS-DMA ring (16-bit types, large M)
+    // gemm_small.hip: f32, M <= 512 - one workgroup per output tile, no splits: it needs no partial scratch (and is deterministic without one)
+    q = p;
+    q.cpart = nullptr;
+    return gemm_tn_small_supported(dtype, q) ? TN_KERNEL_SMALL : TN_KERNEL_TILE;
+}
 int gemm_tn(int dtype, const GemmP& p, hipStream_t st) {
-    if (gemm_tn_glds_supported(dtype, p)) return gemm_tn_glds(dtype, p, st);   // gemm_tn2.hip: LDS-DMA ring (16-bit types, large M)
-    {   // gemm_small.hip: f32, M <= 512 - one workgroup per output tile, no splits: it needs no partial scratch (and is deterministic without one)
-        GemmP q = p;
-        q.cpart = nullptr;
-        if (gemm_tn_small_supported(dtype, q)) return gemm_tn_small(q, st);
+    GemmP q;
+    switch (tn_route(dtype, p, q)) {
+        case TN_KERNEL_GLDS: return gemm_tn_glds(dtype, p, st);
+        case TN_KERNEL_SMALL: return gemm_tn_small(q, st);
     }
     return tn_by_dtype(dtype, p, st);
+}
+int gemm_tn_plan(int dtype, const GemmP& p, TnPlan* plan) {
+    GemmP q;
+    switch (tn_route(dtype, p, q)) {
+        case TN_KERNEL_GLDS: return gemm_tn_glds_plan(dtype, p, plan);
+        case TN_KERNEL_SMALL: *plan = TnPlan{TN_KERNEL_SMALL, 0, 1, q.M, 0, false, false}; return MFVIT_OK;   // one workgroup per 32 x 32 tile sums every row
+    }
+    return tn_plan_by_dtype(dtype, p, *plan);
 }
 
 }  // namespace mfvit

@@ -420,6 +420,7 @@ bool gemm_tn_glds_supported(int dtype, const GemmP& p) {
     // (M >= 2,048 since round 5: at B = 16 (M = 3,152) the LDS-DMA kernel with the paired dWqkv + dWproj launch is ~3 % of the step ahead of gemm_tn)
     if (p.N % 128 || p.K % 128 || p.M < 2048) return false;     // 128 x 128 LOGICAL tiles in every mode
     if (p.lda % 8 || p.ldw % 8) return false;
+    if (((size_t)p.A | (size_t)p.W) & 15) return false;         // 16-byte LDS-DMA pieces (gemm_tn refuses such operands: gemm.hip::plan_tn)
     return true;
 }
 
@@ -433,26 +434,46 @@ bool gemm_tn_pair_supported(int dtype, const GemmP& a, const GemmP& b) {
     return true;
 }
 
-template <typename T> static int launch_t2(GemmP p, hipStream_t st) {
+// The host decisions of a launch (kernels.h::TnPlan): split count, rows per split, whether the tile partials and the bias column sums leave through
+// scratch.  launch_t2 calls it before it launches; gemm_tn_glds_plan reports what it returned.
+template <typename T> static int plan_t2(const GemmP& p, TnPlan& pl) {
     typedef T2Geo<T> G;
+    if (p.orow_in && !is_split<T>::value) return MFVIT_EINVAL;          // remapped rows: the split-bf16 form only
     const int tiles = ((p.N + p.res_mod) / 128) * (p.K / 128);          // res_mod = N of the paired second GEMM (0: none)
-    if (p.splits <= 0) {
+    int splits = p.splits;
+    if (splits <= 0) {
         // one workgroup per CU (96 KB of LDS): tiles x splits <= 256; with a second kernel stream beside this one (stream_share(), common.cuh) and a
         // reduction short enough that the splits are latency (M < 8,192 rows) half of that, so that the other encoder's launch fits beside it
         const int target = stream_share() >= 2 && p.M < 8192 ? 128 : 256;
         int s = target / tiles;
         const int maxs = (p.M + 4 * G::KR - 1) / (4 * G::KR);
-        p.splits = s < 1 ? 1 : (s > maxs ? maxs : s);
+        splits = s < 1 ? 1 : (s > maxs ? maxs : s);
     }
+    int chunk;
     {   // no empty split (the kernel derives the same chunk from p.splits): every split writes its partial tile
-        int chunk = (p.M + p.splits - 1) / p.splits;
+        chunk = (p.M + splits - 1) / splits;
         chunk = (chunk + G::KR - 1) / G::KR * G::KR;
-        p.splits = (p.M + chunk - 1) / chunk;
+        splits = (p.M + chunk - 1) / chunk;
     }
+    pl.kernel = TN_KERNEL_GLDS;
+    pl.kr = G::KR;
+    pl.splits = splits;
+    pl.chunk = chunk;
+    pl.tiles = tiles;
     // p.cpart (optional scratch of >= 384 tiles of 128 x 128 floats): split partials as plain stores + one reduce pass
-    if (p.splits < 2 || p.ldo0 % 4 || (p.res_mod && p.ldo1 % 4) || (long)tiles * p.splits > 384) p.cpart = nullptr;
+    pl.cpart = p.cpart && !(splits < 2 || p.ldo0 % 4 || (p.res_mod && p.ldo1 % 4) || (long)tiles * splits > 384);
     // ... and the bias column sums of the splits as [split][N] behind them (at most two more tile units: splits x N <= 256 x 128 floats)
-    p.kpart = p.cpart && p.cs0 && (long)tiles * p.splits + 2 <= 384 && p.N % 4 == 0 && (size_t)p.cs0 % 16 == 0 ? p.cpart + (long)p.splits * (p.N + p.res_mod) * p.K : nullptr;
+    pl.kpart = pl.cpart && p.cs0 && (long)tiles * splits + 2 <= 384 && p.N % 4 == 0 && (size_t)p.cs0 % 16 == 0;
+    return MFVIT_OK;
+}
+
+template <typename T> static int launch_t2(GemmP p, hipStream_t st) {
+    TnPlan pl;
+    MFVIT_TRY(plan_t2<T>(p, pl));
+    const int tiles = pl.tiles;
+    p.splits = pl.splits;
+    if (!pl.cpart) p.cpart = nullptr;
+    p.kpart = pl.kpart ? p.cpart + (long)p.splits * (p.N + p.res_mod) * p.K : nullptr;
     constexpr int bytes = (is_split<T>::value ? T2_NSP : T2_NS) * T2_STAGE;   // (the pipelined form's ring; the other split forms use three of the four slots)
     p.rows_per_wg = 0;
     // (eight waves per workgroup and the LDS-DMA issue interleaved with the MFMAs - the W8 / IL template flags of the kernel - are the only forms
@@ -489,19 +510,30 @@ template <typename T> static int launch_t2(GemmP p, hipStream_t st) {
     return MFVIT_OK;
 }
 
-// a and b in one launch (gemm_tn_pair_supported)
-int gemm_tn_glds_pair(int dtype, GemmP a, const GemmP& b, hipStream_t st) {
+// a and b as the parameters of one launch (gemm_tn_pair_supported)
+static GemmP pair_params(GemmP a, const GemmP& b) {
     a.aux = b.A; a.ldaux = b.lda;
     a.res_t = b.W; a.ldres_t = b.ldw;
     a.out1 = b.out0; a.ldo1 = b.ldo0;
     a.res_mod = b.N;
-    return gemm_tn_glds(dtype, a, st);
+    return a;
+}
+int gemm_tn_glds_pair(int dtype, GemmP a, const GemmP& b, hipStream_t st) { return gemm_tn_glds(dtype, pair_params(a, b), st); }
+int gemm_tn_pair_plan(int dtype, const GemmP& a, const GemmP& b, TnPlan* plan) {
+    if (!gemm_tn_pair_supported(dtype, a, b)) return MFVIT_ENOSYS;
+    return gemm_tn_glds_plan(dtype, pair_params(a, b), plan);
 }
 
 int gemm_tn_glds(int dtype, GemmP p, hipStream_t st) {
     if (dtype == MFVIT_BF16) return launch_t2<bf16>(p, st);
     if (dtype == MFVIT_BF16X3) return launch_t2<sbf16>(p, st);
     if (dtype == MFVIT_F16) return launch_t2<f16>(p, st);
+    return MFVIT_EINVAL;
+}
+int gemm_tn_glds_plan(int dtype, const GemmP& p, TnPlan* plan) {
+    if (dtype == MFVIT_BF16) return plan_t2<bf16>(p, *plan);
+    if (dtype == MFVIT_BF16X3) return plan_t2<sbf16>(p, *plan);
+    if (dtype == MFVIT_F16) return plan_t2<f16>(p, *plan);
     return MFVIT_EINVAL;
 }
 

@@ -46,6 +46,15 @@ int boot_points(const float* scores, long ld, long ms, const int64_t* labels, in
 int calib_sums(const float* logits, long ld, long ms, const int64_t* labels, int n, int C, int M, const float* temps, int Kt, int NB,
                unsigned long long* bin_n, unsigned long long* bin_hit, double* bin_conf, double* sums, unsigned long long* skipped, hipStream_t st);
 int gemm_tn(int dtype, const GemmP& p, hipStream_t st);
+// What a weight-gradient launch of `p` decides on the host before it launches: which kernel, the reduction rows per stage, the split count and the
+// KR-rounded rows per split, whether the tile partials go through p.cpart and the bias column sums through the [split][N] rows behind them.  Filled by
+// the launchers' own decision functions (gemm.hip::plan_tn, gemm_tn2.hip::plan_t2), which each launcher calls first; gemm_tn_plan / gemm_tn_pair_plan
+// route like gemm_tn / the paired launch and touch no device.
+enum { TN_KERNEL_SMALL = 0, TN_KERNEL_TILE = 1, TN_KERNEL_GLDS = 2 };
+struct TnPlan { int kernel, kr, splits, chunk, tiles; bool cpart, kpart; };
+int gemm_tn_plan(int dtype, const GemmP& p, TnPlan* plan);
+int gemm_tn_glds_plan(int dtype, const GemmP& p, TnPlan* plan);                       // gemm_tn2.hip
+int gemm_tn_pair_plan(int dtype, const GemmP& a, const GemmP& b, TnPlan* plan);       // gemm_tn2.hip (MFVIT_ENOSYS: not a pair)
 bool gemm_nt_small_supported(int dtype, int epi, const GemmP& p);   // gemm_small.hip: f32, a handful of rows (the fusion module's per-sample rows)
 int gemm_nt_small(int epi, GemmP p, hipStream_t st);
 bool gemm_tn_small_supported(int dtype, const GemmP& p);

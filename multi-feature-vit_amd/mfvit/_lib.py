@@ -97,6 +97,8 @@ SIGNATURES = {
     "mfvit_linear_dgrad_act": (I, [I, P, L, P, L, P, L, P, L, I, I, I, P]),
     "mfvit_linear_wgrad": (I, [I, P, L, P, L, P, L, I, I, I, P]),
     "mfvit_linear_wgrad_ws": (I, [I, P, L, P, L, P, L, I, I, I, P, P]),
+    "mfvit_linear_wgrad_ex": (I, [I, P, L, P, L, P, L, I, I, I, P, P, I, I, I, P]),
+    "mfvit_linear_wgrad_plan": (I, [I, I, I, I, I, L, L, L, L, L, L, I, POINTER(ctypes.c_int32)]),
     "mfvit_linear_wgrad_pair": (I, [I, P, L, P, L, P, L, P, I, P, L, P, L, P, L, I, I, I, P]),
     "mfvit_linear_res_ln_fwd": (I, [I, P, L, P, L, P, P, L, P, P, I, P, P, F, P, P, I, I, P]),
     "mfvit_linear_dgrad_ln_bwd": (I, [I, P, L, P, L, P, P, P, P, P, P, P, P, P, P, I, I, P]),

@@ -116,19 +116,52 @@ def wgrad_scratch(device):
     return t
 
 
-def linear_wgrad(dy, x, out=None, scratch=None, split=False):
+WGRAD_KERNELS = ("small", "tile", "glds")   # mfvit_linear_wgrad_plan, plan[0]: gemm_small.hip / gemm.hip::gemm_tn_kernel / gemm_tn2.hip (LDS-DMA)
+WGRAD_PLAN_BIAS, WGRAD_PLAN_BIAS_UNALIGNED, WGRAD_PLAN_SCRATCH, WGRAD_PLAN_REMAP = 1, 2, 4, 8
+
+
+def linear_wgrad_plan(code, M, N, K, N2=0, bias=False, bias_aligned=True, scratch=False, remap=False, lddy=None, ldx=None, lddw=None,
+                      lddy2=None, ldx2=None, lddw2=None):
+    """What a weight-gradient launch of this shape decides on the host (mfvit_linear_wgrad_plan; no GPU needed), from the launchers' own code
+    under the current run-time switches: dict(kernel, kr, splits, chunk, last_rows, scratch, kpart, tiles).  code: a dtype code; N2 > 0: the
+    paired launch.  Leading dimensions default to dense tensors.  Raises MfvitError where the launch would refuse the shape."""
+    e = 2 if code == BF16X3 else 1
+    flags = (WGRAD_PLAN_BIAS if bias else 0) | (WGRAD_PLAN_BIAS_UNALIGNED if bias and not bias_aligned else 0) | \
+        (WGRAD_PLAN_SCRATCH if scratch else 0) | (WGRAD_PLAN_REMAP if remap else 0)
+    out = (_lib.ctypes.c_int32 * 8)()
+    check(lib().mfvit_linear_wgrad_plan(code, M, N, K, N2, N * e if lddy is None else lddy, K * e if ldx is None else ldx, K if lddw is None else lddw,
+                                        N2 * e if lddy2 is None else lddy2, K * e if ldx2 is None else ldx2, K if lddw2 is None else lddw2,
+                                        flags, out), "mfvit_linear_wgrad_plan")
+    return dict(kernel=WGRAD_KERNELS[out[0]], kr=out[1], splits=out[2], chunk=out[3], last_rows=out[4], scratch=bool(out[5]), kpart=bool(out[6]),
+                tiles=out[7])
+
+
+def linear_wgrad(dy, x, out=None, scratch=None, split=False, dbias=None, remap=None):
     """dW [N,K] (f32) += dy[M,N].T @ x[M,K].  scratch: optional f32 tensor of WGRAD_SCRATCH_FLOATS elements (split partials
-    as plain stores + a reduce pass instead of float atomics).  split=True: dy, x are split-bf16 storage."""
-    require_cuda(dy, x)
+    as plain stores + a reduce pass instead of float atomics).  split=True: dy, x are split-bf16 storage.
+    dbias: optional f32 [N] tensor, += the column sums of dy.  remap: optional (rows_in, rows_out, row_off): reduction row m (M = x.shape[0]
+    rows) reads dy row (m // rows_in) * rows_out + m % rows_in + row_off (mfvit_linear_wgrad_ex)."""
+    require_cuda(dy, x, dbias)
     code = _code_of(dy, split)
     e = 2 if split else 1
     M, N = dy.shape[0], dy.shape[1] // e
     K = x.shape[1] // e
     if out is None:
         out = torch.zeros(N, K, device=dy.device, dtype=torch.float32)
+    if scratch is not None and (scratch.dtype != torch.float32 or scratch.numel() < WGRAD_SCRATCH_FLOATS):
+        raise _lib.MfvitError("wgrad scratch must be float32 with at least WGRAD_SCRATCH_FLOATS elements")
+    if dbias is not None or remap is not None:
+        if dbias is not None and (dbias.dtype != torch.float32 or dbias.numel() < N or dbias.stride(0) != 1):
+            raise _lib.MfvitError(f"linear_wgrad: dbias must be a dense float32 tensor of {N} elements")
+        rin, rout, roff = remap if remap is not None else (0, 0, 0)
+        if remap is not None:
+            M = x.shape[0]
+            if rin <= 0 or roff < 0 or rout < rin + roff or (M - 1) // rin * rout + (M - 1) % rin + roff >= dy.shape[0]:
+                raise _lib.MfvitError(f"linear_wgrad: remap {remap} of {M} rows does not fit the {dy.shape[0]} rows of dy")
+        check(lib().mfvit_linear_wgrad_ex(code, ptr(dy), dy.stride(0), ptr(x), x.stride(0), ptr(out), out.stride(0), M, N, K, ptr(scratch),
+                                          ptr(dbias), rin, rout, roff, stream()), "mfvit_linear_wgrad_ex")
+        return out
     if scratch is not None:
-        if scratch.dtype != torch.float32 or scratch.numel() < WGRAD_SCRATCH_FLOATS:
-            raise _lib.MfvitError("wgrad scratch must be float32 with at least WGRAD_SCRATCH_FLOATS elements")
         check(lib().mfvit_linear_wgrad_ws(code, ptr(dy), dy.stride(0), ptr(x), x.stride(0), ptr(out), out.stride(0), M, N, K,
                                           ptr(scratch), stream()), "mfvit_linear_wgrad_ws")
     else:
@@ -140,7 +173,7 @@ def linear_wgrad(dy, x, out=None, scratch=None, split=False):
 def linear_wgrad_pair(dy_a, x_a, dy_b, x_b, want_dbias=True, split=False):
     """Two weight gradients over the same M rows and the same K in ONE launch (the encoder backward's dWqkv + dWproj):
     returns (dW_a [Na,K], dbias_a [Na] or None, dW_b [Nb,K]), all f32.  Raises MfvitError (ENOSYS) for shapes the paired kernel
-    does not take (M < 4096, N / K not multiples of 128, f32)."""
+    does not take (M < 2048, N / K not multiples of 128, f32)."""
     require_cuda(dy_a, x_a, dy_b, x_b)
     code = _code_of(dy_a, split)
     e = 2 if split else 1
