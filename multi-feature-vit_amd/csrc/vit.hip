@@ -258,6 +258,7 @@ WsLayout ws_layout(const Dims& d) {
 
 // ------------------------------------------------------------------ per-call context of encoder_forward / encoder_backward
 struct EncCtx {
+    const mfvit_vit_cfg* const cfg;
     const Dims d;
     const ParamLayout L;
     const ShadowLayout S;
@@ -275,10 +276,10 @@ struct EncCtx {
     const float eps;
     const DropP off = make_drop(0.f, 0, 0);
 
-    EncCtx(const mfvit_vit_cfg* cfg, const Dims& dims, const float* params_, const void* shadow, void* workspace, mfvit_stream_t stream)
-        : d(dims), L(param_layout(dims)), S(shadow_layout(dims)), W(ws_layout(dims)), ws((char*)workspace), sh((const char*)shadow), params(params_),
+    EncCtx(const mfvit_vit_cfg* cfg_, const Dims& dims, const float* params_, const void* shadow, void* workspace, mfvit_stream_t stream)
+        : cfg(cfg_), d(dims), L(param_layout(dims)), S(shadow_layout(dims)), W(ws_layout(dims)), ws((char*)workspace), sh((const char*)shadow), params(params_),
           st((hipStream_t)stream), D(dims.D), F(dims.F), e(dims.ep), hw(dims.dtype != MFVIT_F32),
-          lean_grad(dims.dtype == MFVIT_BF16X3 && !dims.unfused), eps(cfg->ln_eps) {}
+          lean_grad(dims.dtype == MFVIT_BF16X3 && !dims.unfused), eps(cfg_->ln_eps) {}
 
     // activations are kept per block for a backward (save), in one copy otherwise
     size_t slot(int l) const { return d.save ? (size_t)l : 0; }
@@ -363,7 +364,7 @@ int dgrad_ln_bwd(const EncCtx& c, GemmP p, const float* res, const void* res_t, 
 
 // Weight-gradient GEMMs are leaves of the backward graph: they CAN run on a second (library-owned, lazily created) HIP stream beside the
 // dgrad chain, ordered by events.  Round 3 made the caller's stream the default; round 5 brought the side stream back at small M only (the rule
-// in encoder_backward).  The side stream was worth 3 - 4 % while the weight-gradient and row kernels left half of every CU's LDS and issue slots
+// in wgrad_side_stream).  The side stream was worth 3 - 4 % while the weight-gradient and row kernels left half of every CU's LDS and issue slots
 // free (round 2); now they are one-workgroup-per-CU kernels that own the chip while they run, nothing co-resides with them, and the second queue
 // only adds event waits and a worse launch order: measured on one box, three alternating repeats, 31.25 / 31.33 / 31.36 ms per step with the side
 // stream, 30.81 / 30.80 / 30.86 without (profiles/r03_streams_ab.txt).
@@ -399,6 +400,50 @@ SideStream& side_stream(hipStream_t caller) {
     }
     return x;
 }
+
+// The side stream a backward call runs its weight gradients on, or NULL: everything on the caller's stream.  Decided before the side stream of
+// this caller stream is looked up - and created - at all.
+// (never inside a caller's stream capture: the library-owned side stream is not part of the caller's capture, and its last weight gradients are joined by the
+// NEXT call's fork, not before this one returns - a capture ending in between would hold unjoined work.  The package itself no longer captures steps:
+// the whole-step HIP graph of round 5 gained nothing, 8.22 vs 8.12 ms, and was removed in round 6)
+// (residual dropout / drop path: the masked dY copies live in ONE scratch buffer - everything stays on the caller's stream)
+// Default since round 5: the side stream at SMALL M only (1,024 ... 4,096 token rows: 6 - 20 images) - there no kernel fills the chip, the launches of a
+// block are a dependent chain of ~10 us kernels with ~5 us of dispatch gap each, and the weight gradients (leaves) beside the data-gradient chain
+// shorten it: 20 pairs per step 7.31 -> 6.66 ms, 16 pairs 6.31 -> 6.10 (then host-bound), 8 pairs 5.18 -> 4.96; 4 pairs LOSE (host-bound either way, 5.1 ->
+// 6.9 ms) and 32 pairs gain 1 % (profiles/r05_small_batch.txt).
+SideStream* wgrad_side_stream(const EncCtx& c, bool wg) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    const bool capturing = hipStreamIsCapturing(c.st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+    const bool side_wanted = wg && c.d.M >= 1024 && c.d.M <= 4096 && g_wgrad_stream.load(std::memory_order_relaxed) != 0 && !c.d.rdrop && !capturing;
+    if (!side_wanted) return nullptr;
+    SideStream& ss = side_stream(c.st);
+    return ss.ok && c.W.pp_stride != 0 ? &ss : nullptr;
+}
+
+// Where the weight gradients of one backward call go, and how that queue is ordered against the data-gradient chain on the caller's stream.
+// (with the side stream every weight gradient AND every reduce of their partials runs on it - the patch embedding's too - so the scratch slots
+// are still written and read in one stream's order)
+struct WgradQueue {
+    SideStream* const side;         // NULL: no second queue, every member below but `s` does nothing
+    const hipStream_t main, s;      // the caller's stream; the stream of the weight-gradient GEMMs and of the reduces of their partials
+    const int top;                  // the highest block of this call
+    WgradQueue(SideStream* side_, hipStream_t main_, int top_) : side(side_), main(main_), s(side_ ? side_->s : main_), top(top_) {}
+    // main -> side dependency at this point of the main stream: the side stream may only start after everything already queued on the caller's
+    // stream (activations, zeroed gradients)
+    int fork() const {
+        return !side || (hipEventRecord(side->in, main) == hipSuccess && hipStreamWaitEvent(s, side->in, 0) == hipSuccess) ? MFVIT_OK : MFVIT_ELAUNCH;
+    }
+    int wait_layer(int l) const {   // main waits until the wgrads of layer l (a layer of this call) have finished
+        if (!side || l < 0 || l > top) return MFVIT_OK;
+        return hipStreamWaitEvent(main, side->done[l & 63], 0) == hipSuccess ? MFVIT_OK : MFVIT_ELAUNCH;
+    }
+    int mark_done(int l) const {    // everything queued so far is what layer l's wgrads are
+        return !side || hipEventRecord(side->done[l & 63], s) == hipSuccess ? MFVIT_OK : MFVIT_ELAUNCH;
+    }
+    int join() const {              // everything the side stream did is ordered before whatever the caller queues next
+        return !side || (hipEventRecord(side->end, s) == hipSuccess && hipStreamWaitEvent(main, side->end, 0) == hipSuccess) ? MFVIT_OK : MFVIT_ELAUNCH;
+    }
+};
 
 }  // namespace
 
@@ -499,14 +544,13 @@ static bool lora_plan(const Dims& d, const mfvit_lora_req* r, bool grads, LoraPl
 }
 // The (weight, adapter) pair of item `it` over an arena-layout buffer `base` (the parameters, or a gradient arena); out: the merge's target arena
 static LoraPair lora_pair(const Dims& d, const ParamLayout& L, const mfvit_lora_item& it, const float* base, float* out, bool grad) {
-    const long D = d.D, F = d.F;
+    const long D = d.D;
     long off = L.blk0 + (long)it.block * L.blk_stride;
     int N = d.D, K = d.D;
     if (it.target <= MFVIT_LORA_V) off += L.qkv_w + (long)it.target * D * D;
     else if (it.target == MFVIT_LORA_PROJ) off += L.proj_w;
     else if (it.target == MFVIT_LORA_FC1) { off += L.fc1_w; N = d.F; }
     else { off += L.fc2_w; K = d.F; }
-    (void)F;
     LoraPair p = {base + off, it.a, it.b, grad ? it.da : out + off, grad ? it.db : nullptr, N, K, K, K};
     return p;
 }
@@ -525,8 +569,6 @@ static int lora_run(const Dims& d, const mfvit_lora_req* r, const float* base, f
     return MFVIT_OK;
 }
 
-// Shared forward of the two front ends: ViT-S/16 (img = (B,3,H,W) image, patch embedding + cls token) and the token-input GPT
-// (img = (B,T,dim) tokens, + pos_emb).  Everything behind x_0 / LN1_0 is the same pre-LN block stack.
 // Attention maps (mfvit_vit_forward_attn): validity of a request, and the optional per-block step behind block l's attention forward - its
 // probabilities into req->maps (the block's slot among the selected ones) and, for a rollout, its fused map and row sums into the scratch.
 static bool attn_req_ok(const mfvit_vit_cfg* cfg, const mfvit_vit_attn_req* r, Dims& d) {
@@ -575,6 +617,110 @@ static int rel_block_step(const Dims& d, const mfvit_vit_rel_req* r, int l, int 
     return MFVIT_OK;
 }
 
+// ------------------------------------------------------------------ forward: the embedding, then block 0 .. depth-1
+// x_0 and LN1_0 -> y1_0 from the input, in one of the three embedding forms
+static int fwd_embed(const EncCtx& c, const float* img) {
+    const Dims& d = c.d;
+    const long D = c.D, De = c.D * c.e;
+    const float* const pos = c.params + c.L.pos;
+    float* const x0 = c.xbuf(0);
+    char* const y1_0 = c.blk(0) + c.W.y1;
+    const float *const g0 = c.pblk(0) + c.L.ln1_w, *const b0 = c.pblk(0) + c.L.ln1_b;
+    float *const mean0 = c.stat(0), *const rstd0 = c.stat(0) + d.M;
+    if (d.tok && d.p_embd > 0.f)
+        // x_0 = drop(tokens + pos_emb) (fuseattention.py:187 `self.drop(self.pos_emb + token_embeddings)`); LN1_0 -> y1_0
+        return drop_add_ln_rows(d.dtype, d.D, nullptr, 0, img, D, d.use_pos ? pos : nullptr, D, d.T, nullptr, 0, make_drop(d.p_embd, d.seed, 1), c.off, 1,
+                                x0, D, y1_0, De, 0, g0, b0, c.eps, mean0, rstd0, d.M, c.st);
+    if (d.tok)
+        // token input (fuseattention.py:186-189): x_0 = tokens (+ pos_emb, shared by the batch); LN1_0 -> y1_0.  One row kernel pass.
+        return ln_rows(d.dtype, d.D, img, D, d.use_pos ? pos : nullptr, D, d.T, x0, D, y1_0, De, 0, g0, b0, c.eps, mean0, rstd0, d.M, 1, 0, 0, c.st);
+    // patch embedding: im2col -> GEMM + bias + pos_embed, the patch rows of image b behind its cls row -> x_0, LN1_0 -> y1_0
+    MFVIT_TRY(im2col16(d.dtype, img, c.ws + c.W.patches, d.B, c.cfg->img_h, c.cfg->img_w, c.st));
+    GemmP p = nt(c.ws + c.W.patches, 768 * c.e, c.weight(c.sh + c.S.pe_w, c.params + c.L.pe_w), 768 * c.e, d.Mp, d.D, 768);
+    p.bias = c.params + c.L.pe_b;
+    p.res = pos; p.ldres = D; p.res_mod = d.np; p.res_off = 1;
+    p.orow_in = d.np; p.orow_out = d.T; p.orow_off = 1;
+    p.out0 = x0; p.ldo0 = D;
+    p.out1 = y1_0; p.ldo1 = De;
+    p.gamma = g0; p.beta = b0; p.eps = c.eps;
+    p.mean = mean0; p.rstd = rstd0;
+    MFVIT_TRY(linear_res_ln(c, p, nullptr, PROF_TAG_NONE));
+    // cls rows: x_0[b,0] = cls_token + pos_embed[0]; LN1_0
+    MFVIT_TRY(ln_rows(d.dtype, d.D, c.params + c.L.cls, 0, pos, D, 1, x0, D, y1_0, De, 0, g0, b0, c.eps, mean0, rstd0, d.B, d.T, 0, 1, c.st));
+    if (d.p_embd > 0.f)
+        // timm pos_drop: x_0 = drop(cat(cls, patch_embed(x)) + pos_embed), cls rows included; in place, then LN1_0 again
+        MFVIT_TRY(drop_add_ln_rows(d.dtype, d.D, nullptr, 0, x0, D, nullptr, 0, 0, nullptr, 0, make_drop(d.p_embd, d.seed, 1), c.off, 1, x0, D, y1_0, De, 0,
+                                   g0, b0, c.eps, mean0, rstd0, d.M, c.st));
+    return MFVIT_OK;
+}
+
+// block l: x_l, y1_l -> x_{l+1} and the next LayerNorm's output (the last block: the final norm -> features)
+static int fwd_block(const EncCtx& c, int l, float* features, const mfvit_vit_attn_req* attn) {
+    const Dims& d = c.d;
+    const long D = c.D, F = c.F, De = c.D * c.e, Fe = c.F * c.e;
+    char* const b = c.blk(l);
+    const float* const pb = c.pblk(l);
+    const char* const sb = c.sblk(l);
+    // qkv tensor format: split FP16 for the whole-head attention kernels in bf16x3 mode (attention_mfma.hip), the activation dtype otherwise
+    const int qdt = d.p_attn > 0.f ? d.dtype : attn_qkv_dtype(d.dtype, d.T, d.HD);
+    {   // qkv = y1 Wqkv^T + b
+        GemmP p = nt(b + c.W.y1, De, c.weight(sb + c.S.qkv_w, pb + c.L.qkv_w), De, d.M, 3 * d.D, d.D);
+        p.bias = pb + c.L.qkv_b;
+        p.out0 = b + c.W.qkv; p.ldo0 = 3 * De;
+        ProfTag tag(PROF_TAG_MHSA_QKV);
+        MFVIT_TRY(gemm_nt_tile(d.dtype, qdt == MFVIT_X3F16 ? EPI_BIAS_X3F16 : EPI_BIAS, p, c.st));
+    }
+    if (d.p_attn > 0.f) {
+        if (!attn_tiled_supported(d.dtype, d.T, d.HD)) return MFVIT_ENOSYS;
+        MFVIT_TRY(attn_fwd_tiled_drop(d.dtype, b + c.W.qkv, b + c.W.attn, (float*)(b + c.W.lse), d.B, d.T, d.H, d.HD,
+                                      make_drop(d.p_attn, d.seed, c.site(l, 2)), c.st));
+    } else {
+        MFVIT_TRY(attn_fwd(qdt, b + c.W.qkv, b + c.W.attn, (float*)(b + c.W.lse), d.B, d.T, d.H, d.HD, c.st));
+    }
+    if (attn) MFVIT_TRY(attn_block_step(d, attn, l, qdt, b + c.W.qkv, (const float*)(b + c.W.lse), c.st));
+    {   // xmid = x + attn Wproj^T + b ; y2 = LN2(xmid)
+        // (masked: xmid = x + resid_drop(proj(attn)), fuseattention.py:57; timm: x + drop_path(proj_drop(proj(attn))))
+        GemmP p = nt(b + c.W.attn, De, c.weight(sb + c.S.proj_w, pb + c.L.proj_w), De, d.M, d.D, d.D);
+        p.bias = pb + c.L.proj_b;
+        p.res = c.xbuf(l); p.ldres = D;
+        p.out0 = b + c.W.xmid; p.ldo0 = D;
+        p.out1 = b + c.W.y2; p.ldo1 = De;
+        p.gamma = pb + c.L.ln2_w; p.beta = pb + c.L.ln2_b; p.eps = c.eps;
+        p.mean = (float*)(b + c.W.st2); p.rstd = (float*)(b + c.W.st2) + d.M;
+        p.kpart = c.kpart();
+        const BranchDrop mask = {make_drop(d.p_resid, d.seed, c.site(l, 3)), c.dpath(l, 6)};
+        MFVIT_TRY(linear_res_ln(c, p, &mask, PROF_TAG_MHSA_PROJ));
+    }
+    {   // hpre = y2 W1^T + b1 ; hact = gelu(hpre)   (training: hact = drop(gelu(hpre)), out0 = gelu'(hpre) * mask - timm Mlp.drop)
+        GemmP p = nt(b + c.W.y2, De, c.weight(sb + c.S.fc1_w, pb + c.L.fc1_w), De, d.M, d.F, d.D);
+        p.bias = pb + c.L.fc1_b;
+        p.out0 = d.save ? b + c.W.hpre : nullptr; p.ldo0 = F;      // act'(pre) in act_grad_type<T> (gemm.hip): F elements per row
+        p.out1 = b + c.W.hact; p.ldo1 = Fe;
+        p.drop = make_drop(d.p_gelu, d.seed, c.site(l, 5));
+        MFVIT_TRY(gemm_nt_tile(d.dtype, d.act == 1 ? EPI_BIAS_RELU : (d.p_gelu > 0.f ? EPI_BIAS_GELU_DROP : EPI_BIAS_GELU), p, c.st));
+    }
+    // x_{l+1} = xmid + hact W2^T + b2 ; y = LN(next norm1 | final norm)
+    // (masked: x_{l+1} = xmid + Dropout(fc2(relu(fc1(y2)))), fuseattention.py:67-72,80; timm: xmid + drop_path(drop(fc2(..))))
+    GemmP p = nt(b + c.W.hact, Fe, c.weight(sb + c.S.fc2_w, pb + c.L.fc2_w), Fe, d.M, d.D, d.F);
+    p.bias = pb + c.L.fc2_b;
+    p.res = (const float*)(b + c.W.xmid); p.ldres = D;
+    p.out0 = c.xbuf(l + 1); p.ldo0 = D;
+    if (l + 1 == d.depth) {
+        p.out1 = features; p.ldo1 = D; p.y_f32 = 1;
+        p.gamma = c.params + c.L.norm_w; p.beta = c.params + c.L.norm_b;
+    } else {
+        p.out1 = c.blk(l + 1) + c.W.y1; p.ldo1 = De;
+        p.gamma = c.pblk(l + 1) + c.L.ln1_w; p.beta = c.pblk(l + 1) + c.L.ln1_b;
+    }
+    p.eps = c.eps;
+    p.mean = c.stat(l + 1); p.rstd = c.stat(l + 1) + d.M;
+    p.kpart = c.kpart();
+    const BranchDrop mask = {make_drop(d.p_resid, d.seed, c.site(l, 4)), c.dpath(l, 7)};
+    return linear_res_ln(c, p, &mask, PROF_TAG_NONE);
+}
+
+// Shared forward of the two front ends: ViT-S/16 (img = (B,3,H,W) image, patch embedding + cls token) and the token-input GPT
+// (img = (B,T,dim) tokens, + pos_emb).  Everything behind x_0 / LN1_0 is the same pre-LN block stack.
 static int encoder_forward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* dropcfg, const float* params, const void* shadow, const float* img,
                            void* workspace, float* features, mfvit_stream_t stream, bool want_tokens,
                            const mfvit_vit_attn_req* attn = nullptr) {
@@ -582,153 +728,53 @@ static int encoder_forward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* dropc
     if (!get_dims(cfg, dropcfg, d) || !params || !shadow || !img || !workspace || !features) return MFVIT_EINVAL;
     if (d.tok != want_tokens) return MFVIT_EINVAL;
     const EncCtx c(cfg, d, params, shadow, workspace, stream);
-    const ParamLayout& L = c.L;
-    const ShadowLayout& S = c.S;
-    const WsLayout& W = c.W;
-    char* const ws = c.ws;
-    const hipStream_t st = c.st;
-    const long D = c.D, F = c.F, e = c.e;
-    const float eps = c.eps;
-    // x_0 and LN1_0 -> y1_0: the outputs of every embedding form
-    float* const x0 = c.xbuf(0);
-    char* const y1_0 = c.blk(0) + W.y1;
-    const float* const g0 = c.pblk(0) + L.ln1_w;
-    const float* const b0 = c.pblk(0) + L.ln1_b;
-    float* const mean0 = c.stat(0);
-    float* const rstd0 = c.stat(0) + d.M;
-    if (d.tok && d.p_embd > 0.f) {
-        // x_0 = drop(tokens + pos_emb) (fuseattention.py:187 `self.drop(self.pos_emb + token_embeddings)`); LN1_0 -> y1_0
-        MFVIT_TRY(drop_add_ln_rows(d.dtype, d.D, nullptr, 0, img, D, d.use_pos ? params + L.pos : nullptr, D, d.T, nullptr, 0,
-                                   make_drop(d.p_embd, d.seed, 1), c.off, 1, x0, D, y1_0, D * e, 0, g0, b0, eps, mean0, rstd0, d.M, st));
-    } else if (d.tok) {
-        // token input (fuseattention.py:186-189): x_0 = tokens (+ pos_emb, shared by the batch); LN1_0 -> y1_0.  One row kernel pass.
-        MFVIT_TRY(ln_rows(d.dtype, d.D, img, D, d.use_pos ? params + L.pos : nullptr, D, d.T, x0, D, y1_0, D * e, 0, g0, b0, eps, mean0, rstd0, d.M,
-                          1, 0, 0, st));
-    } else {
-        // patch embedding: im2col -> GEMM + bias + pos_embed, the patch rows of image b behind its cls row -> x_0, LN1_0 -> y1_0
-        MFVIT_TRY(im2col16(d.dtype, img, ws + W.patches, d.B, cfg->img_h, cfg->img_w, st));
-        GemmP p = nt(ws + W.patches, 768 * e, c.weight(c.sh + S.pe_w, params + L.pe_w), 768 * e, d.Mp, d.D, 768);
-        p.bias = params + L.pe_b;
-        p.res = params + L.pos; p.ldres = D; p.res_mod = d.np; p.res_off = 1;
-        p.orow_in = d.np; p.orow_out = d.T; p.orow_off = 1;
-        p.out0 = x0; p.ldo0 = D;
-        p.out1 = y1_0; p.ldo1 = D * e;
-        p.gamma = g0; p.beta = b0; p.eps = eps;
-        p.mean = mean0; p.rstd = rstd0;
-        MFVIT_TRY(linear_res_ln(c, p, nullptr, PROF_TAG_NONE));
-        // cls rows: x_0[b,0] = cls_token + pos_embed[0]; LN1_0
-        MFVIT_TRY(ln_rows(d.dtype, d.D, params + L.cls, 0, params + L.pos, D, 1, x0, D, y1_0, D * e, 0, g0, b0, eps, mean0, rstd0, d.B, d.T, 0, 1, st));
-        if (d.p_embd > 0.f)
-            // timm pos_drop: x_0 = drop(cat(cls, patch_embed(x)) + pos_embed), cls rows included; in place, then LN1_0 again
-            MFVIT_TRY(drop_add_ln_rows(d.dtype, d.D, nullptr, 0, x0, D, nullptr, 0, 0, nullptr, 0, make_drop(d.p_embd, d.seed, 1), c.off, 1, x0, D,
-                                       y1_0, D * e, 0, g0, b0, eps, mean0, rstd0, d.M, st));
-    }
-
-    for (int l = 0; l < d.depth; ++l) {
-        char* b = c.blk(l);
-        const float* pb = c.pblk(l);
-        const char* sb = c.sblk(l);
-        // qkv tensor format: split FP16 for the whole-head attention kernels in bf16x3 mode (attention_mfma.hip), the activation dtype otherwise
-        const int qdt = d.p_attn > 0.f ? d.dtype : attn_qkv_dtype(d.dtype, d.T, d.HD);
-        {   // qkv = y1 Wqkv^T + b
-            GemmP p = nt(b + W.y1, D * e, c.weight(sb + S.qkv_w, pb + L.qkv_w), D * e, d.M, 3 * d.D, d.D);
-            p.bias = pb + L.qkv_b;
-            p.out0 = b + W.qkv; p.ldo0 = 3 * D * e;
-            ProfTag tag(PROF_TAG_MHSA_QKV);
-            MFVIT_TRY(gemm_nt_tile(d.dtype, qdt == MFVIT_X3F16 ? EPI_BIAS_X3F16 : EPI_BIAS, p, st));
-        }
-        if (d.p_attn > 0.f) {
-            if (!attn_tiled_supported(d.dtype, d.T, d.HD)) return MFVIT_ENOSYS;
-            MFVIT_TRY(attn_fwd_tiled_drop(d.dtype, b + W.qkv, b + W.attn, (float*)(b + W.lse), d.B, d.T, d.H, d.HD,
-                                          make_drop(d.p_attn, d.seed, c.site(l, 2)), st));
-        } else {
-            MFVIT_TRY(attn_fwd(qdt, b + W.qkv, b + W.attn, (float*)(b + W.lse), d.B, d.T, d.H, d.HD, st));
-        }
-        if (attn) MFVIT_TRY(attn_block_step(d, attn, l, qdt, b + W.qkv, (const float*)(b + W.lse), st));
-        {   // xmid = x + attn Wproj^T + b ; y2 = LN2(xmid)
-            // (masked: xmid = x + resid_drop(proj(attn)), fuseattention.py:57; timm: x + drop_path(proj_drop(proj(attn))))
-            GemmP p = nt(b + W.attn, D * e, c.weight(sb + S.proj_w, pb + L.proj_w), D * e, d.M, d.D, d.D);
-            p.bias = pb + L.proj_b;
-            p.res = c.xbuf(l); p.ldres = D;
-            p.out0 = b + W.xmid; p.ldo0 = D;
-            p.out1 = b + W.y2; p.ldo1 = D * e;
-            p.gamma = pb + L.ln2_w; p.beta = pb + L.ln2_b; p.eps = eps;
-            p.mean = (float*)(b + W.st2); p.rstd = (float*)(b + W.st2) + d.M;
-            p.kpart = c.kpart();
-            const BranchDrop mask = {make_drop(d.p_resid, d.seed, c.site(l, 3)), c.dpath(l, 6)};
-            MFVIT_TRY(linear_res_ln(c, p, &mask, PROF_TAG_MHSA_PROJ));
-        }
-        {   // hpre = y2 W1^T + b1 ; hact = gelu(hpre)   (training: hact = drop(gelu(hpre)), out0 = gelu'(hpre) * mask - timm Mlp.drop)
-            GemmP p = nt(b + W.y2, D * e, c.weight(sb + S.fc1_w, pb + L.fc1_w), D * e, d.M, d.F, d.D);
-            p.bias = pb + L.fc1_b;
-            p.out0 = d.save ? b + W.hpre : nullptr; p.ldo0 = F;      // act'(pre) in act_grad_type<T> (gemm.hip): F elements per row
-            p.out1 = b + W.hact; p.ldo1 = F * e;
-            p.drop = make_drop(d.p_gelu, d.seed, c.site(l, 5));
-            MFVIT_TRY(gemm_nt_tile(d.dtype, d.act == 1 ? EPI_BIAS_RELU : (d.p_gelu > 0.f ? EPI_BIAS_GELU_DROP : EPI_BIAS_GELU), p, st));
-        }
-        {   // x_{l+1} = xmid + hact W2^T + b2 ; y = LN(next norm1 | final norm)
-            // (masked: x_{l+1} = xmid + Dropout(fc2(relu(fc1(y2)))), fuseattention.py:67-72,80; timm: xmid + drop_path(drop(fc2(..))))
-            const bool last = l + 1 == d.depth;
-            GemmP p = nt(b + W.hact, F * e, c.weight(sb + S.fc2_w, pb + L.fc2_w), F * e, d.M, d.D, d.F);
-            p.bias = pb + L.fc2_b;
-            p.res = (const float*)(b + W.xmid); p.ldres = D;
-            p.out0 = c.xbuf(l + 1); p.ldo0 = D;
-            if (last) {
-                p.out1 = features; p.ldo1 = D; p.y_f32 = 1;
-                p.gamma = params + L.norm_w; p.beta = params + L.norm_b;
-            } else {
-                p.out1 = c.blk(l + 1) + W.y1; p.ldo1 = D * e;
-                p.gamma = c.pblk(l + 1) + L.ln1_w; p.beta = c.pblk(l + 1) + L.ln1_b;
-            }
-            p.eps = eps;
-            p.mean = c.stat(l + 1); p.rstd = c.stat(l + 1) + d.M;
-            p.kpart = c.kpart();
-            const BranchDrop mask = {make_drop(d.p_resid, d.seed, c.site(l, 4)), c.dpath(l, 7)};
-            MFVIT_TRY(linear_res_ln(c, p, &mask, PROF_TAG_NONE));
-        }
-    }
+    MFVIT_TRY(fwd_embed(c, img));
+    for (int l = 0; l < d.depth; ++l) MFVIT_TRY(fwd_block(c, l, features, attn));
     return MFVIT_OK;
 }
 
-// Shared backward; dinput (token-input mode only): d loss / d tokens, written by the embedding stage.  dimg (image mode only, stage_lo == -1; the
-// workspace then has mfvit_vit_workspace_bytes_ex(.., 1) bytes): d loss / d image, overwritten.  dparams == NULL (with dimg): the data-gradient
-// chain alone - no weight-gradient GEMM, no split-partial reduce, no bias / LayerNorm column sum, no side stream.  rel (dparams == dimg == NULL,
-// stages depth .. 0): that chain with the relevance step of mfvit_vit_backward_rel behind every block's attention backward; it ends at block 0's
-// step (no attention backward or LN1 backward of block 0).  lora (dparams == NULL; mfvit_vit_backward_lora): that chain plus the weight-gradient
-// GEMMs of the adapted Linears into lora->dw, the split-partial reduce of each block and, at the end, the batched contraction to dA / dB; without
-// dimg the chain ends behind the weight gradients of the lowest adapted block.
-static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* dropcfg, const float* params, const void* shadow, void* workspace,
-                            const float* dfeatures, float* dparams, float* dinput, float* dimg, int stage_hi, int stage_lo, mfvit_stream_t stream,
-                            bool want_tokens, const mfvit_vit_rel_req* rel = nullptr, const LoraPlan* lora = nullptr) {
-    Dims d;
-    if (!get_dims(cfg, dropcfg, d) || !params || !shadow || !workspace || (!dparams && !dimg && !rel && !lora)) return MFVIT_EINVAL;
-    if (!d.save || d.tok != want_tokens) return MFVIT_EINVAL;
-    if (stage_hi > d.depth || stage_lo < -1 || stage_lo > stage_hi) return MFVIT_EINVAL;
-    if (dimg && (d.tok || stage_lo != -1)) return MFVIT_EINVAL;
-    const bool wg = dparams != nullptr;             // parameter gradients wanted (false: data-gradient-only backward)
-    const EncCtx c(cfg, d, params, shadow, workspace, stream);
-    const ParamLayout& L = c.L;
-    const ShadowLayout& S = c.S;
-    const WsLayout& W = c.W;
-    char* const ws = c.ws;
-    const hipStream_t st = c.st;
-    const long D = c.D, F = c.F, e = c.e;
-    const bool lean_grad = c.lean_grad;
-    float* const gbase = wg ? dparams : (lora ? lora->dw : nullptr);     // where weight gradients go: the gradient arena, or the adapters' dW_eff scratch
-    auto gblk = [&](int l) { return gbase ? gbase + L.blk0 + (long)l * L.blk_stride : nullptr; };
-    // the adapted Linears of block l whose weight gradient this call forms although wg is off (zeroed first: the GEMMs and the reduce accumulate)
-    auto lora_wants = [&](int l, int bits, long off, long count) -> int {
-        if (wg || !lora || !(lora->mask[l] & bits)) return 0;
-        return hipMemsetAsync(gblk(l) + off, 0, (size_t)count * sizeof(float), st) == hipSuccess ? 1 : -1;
-    };
-    float* gx = (float*)(ws + W.gx);
-    float* gmid = (float*)(ws + W.gmid);
-    float* colscr = (float*)(ws + W.colscratch);
+// ------------------------------------------------------------------ backward: the final norm, block depth-1 .. 0, the embedding
+// What a backward call was asked for.  dinput (token-input mode only): d loss / d tokens, written by the embedding stage.  dimg (image mode only,
+// stage_lo == -1; the workspace then has mfvit_vit_workspace_bytes_ex(.., 1) bytes): d loss / d image, overwritten.  dparams == NULL (with dimg):
+// the data-gradient chain alone - no weight-gradient GEMM, no split-partial reduce, no bias / LayerNorm column sum, no side stream.  rel (dparams
+// == dimg == NULL, stages depth .. 0): that chain with the relevance step of mfvit_vit_backward_rel behind every block's attention backward; it
+// ends at block 0's step (no attention backward or LN1 backward of block 0).  lora (dparams == NULL; mfvit_vit_backward_lora): that chain plus
+// the weight-gradient GEMMs of the adapted Linears into lora->dw, the split-partial reduce of each block and, at the end, the batched contraction
+// to dA / dB; without dimg the chain ends behind the weight gradients of the lowest adapted block.
+namespace {
+struct BwdArgs {
+    const float* dfeatures; float *dparams, *dinput, *dimg;
+    int stage_hi, stage_lo;
+    const mfvit_vit_rel_req* rel; const LoraPlan* lora;
+};
+
+// The weight gradients of one block that are not launched where they are built: at_fork - queued behind the block's fork (side stream); pend -
+// dWproj, held back to ride along with dWqkv (one launch for both)
+struct BlockWgrads {
+    GemmP at_fork[2];
+    int n_fork = 0;
+    GemmP pend = {};
+    bool have_pend = false;
+};
+
+// The attention backward's split-fp16 core scales dO (= the proj data gradient) per (image, head) by a power of two from the pair's largest |dO|.  The
+// GEMM that produces dO leaves those maxima behind (GemmP::omax: atomicMax of f32 bits, one slice per block, zeroed for the blocks of a call), and
+// the attention kernel reads ONE number per pair instead of prefetching the hi parts of all of dO's rows a pair ahead.  MFVIT_DO_MAX=0: the prefetch.
+static bool dout_max_applies(const Dims& d, int qdt_bwd) {
+    static int s_domax = INT_MIN;
+    return env_switch("MFVIT_DO_MAX", 1, s_domax) != 0 && qdt_bwd == MFVIT_X3F16 && (d.HD == 32 || d.HD == 64) && d.T >= 64 && d.D % 128 == 0 &&
+           !(d.p_attn > 0.f);
+}
+
+// per-call context of encoder_backward: EncCtx, the request, and the scratch slots and queue the stages share
+struct BwdCtx : EncCtx, BwdArgs {
+    const bool wg;                  // parameter gradients wanted (false: data-gradient-only backward)
+    float* const gbase;             // where weight gradients go: the gradient arena, or the adapters' dW_eff scratch
+    float *const gx, *const gmid, *const colscr;
     // column-sum partials: every row-kernel launch of this call writes its own buffer, ONE batched launch reduces them (before the embedding
     // stage, which reads a sum, and at the end of the call); with residual dropout (intermediate sums are consumed at once) nothing is deferred
     int colpart_used = 0;
-    auto next_colpart = [&]() { return (float*)(ws + W.colpart + (size_t)(colpart_used++ % (3 * d.depth + 2)) * W.colpart_stride); };
-    ColpartScope colpart_scope(!d.rdrop);
+    ColpartScope colpart_scope;
     // split partials of the weight-gradient GEMMs through scratch - plain stores, every launch into its OWN slot - and ONE batched reduce launch at
     // the end of every BLOCK that adds the splits in a fixed order: dW is the same bits on every run (the float atomics it replaces add in whatever
     // order the workgroups finish).  Round 3 measured the same idea with a reduce launch behind EVERY gradient as a loss (77.2 -> 80.8 us per
@@ -736,254 +782,258 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop
     // the reduce launches take most of it back; per block - partials still in the Infinity Cache - beats per call by 0.07 ms).  (With the weight-gradient
     // side stream the partial path stays ON: every weight gradient and every reduce of a call then runs in the side stream's order.)
     int tn_used = 0;
-    auto next_tnpart = [&]() -> float* {       // (more launches than slots between two flushes: float atomics for the rest - never a slot still in use)
-        return tn_used < TN_SLOTS ? (float*)(ws + W.tnpart + (size_t)(tn_used++) * W.tnpart_stride) : nullptr;
-    };
     TnPartScope tnpart_scope;
-    // dY buffers by layer parity (the embed stage counts as layer -1 -> parity 1)
-    auto pp = [&](size_t off, int l) { return (void*)(ws + off + (size_t)(l & 1) * W.pp_stride); };
-    // (side_wanted, below, decides whether the side stream of this caller stream is looked up - and created - at all)
-    // (never inside a caller's stream capture: the library-owned side stream is not part of the caller's capture, and its last weight gradients are joined by the
-    // NEXT call's fork, not before this one returns - a capture ending in between would hold unjoined work.  The package itself no longer captures steps:
-    // the whole-step HIP graph of round 5 gained nothing, 8.22 vs 8.12 ms, and was removed in round 6)
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    const bool capturing = hipStreamIsCapturing(st, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
-    const bool side_wanted = wg && d.M >= 1024 && d.M <= 4096 && g_wgrad_stream.load(std::memory_order_relaxed) != 0 && !d.rdrop &&
-                             !capturing;
-    static SideStream no_side;
-    SideStream& ss = side_wanted ? side_stream(st) : no_side;
-    // (residual dropout / drop path: the masked dY copies live in ONE scratch buffer - everything stays on the caller's stream)
-    // Default since round 5: the side stream at SMALL M only (1,024 ... 4,096 token rows: 6 - 20 images) - there no kernel fills the chip, the launches of a
-    // block are a dependent chain of ~10 us kernels with ~5 us of dispatch gap each, and the weight gradients (leaves) beside the data-gradient chain
-    // shorten it: 20 pairs per step 7.31 -> 6.66 ms, 16 pairs 6.31 -> 6.10 (then host-bound), 8 pairs 5.18 -> 4.96; 4 pairs LOSE (host-bound either way, 5.1 ->
-    // 6.9 ms) and 32 pairs gain 1 % (profiles/r05_small_batch.txt).
-    const bool use_side = side_wanted && ss.ok && W.pp_stride != 0;
-    hipStream_t wst = use_side ? ss.s : st;                       // stream of the weight-gradient GEMMs
-    // (with the side stream every weight gradient AND every reduce of their partials runs on it - the patch embedding's too, below - so the scratch slots
-    // are still written and read in one stream's order)
-    // the side stream may only start after everything already queued on the caller's stream (activations, zeroed gradients)
-    auto fork = [&]() -> int {                                    // main -> side dependency at this point of the main stream
-        if (!use_side) return MFVIT_OK;
-        if (hipEventRecord(ss.in, st) != hipSuccess || hipStreamWaitEvent(ss.s, ss.in, 0) != hipSuccess) return MFVIT_ELAUNCH;
-        return MFVIT_OK;
-    };
-    auto wait_layer = [&](int l) -> int {                         // main waits until the wgrads of layer l have finished
-        if (!use_side || l < 0 || l >= d.depth || l > stage_hi) return MFVIT_OK;
-        return hipStreamWaitEvent(st, ss.done[l & 63], 0) == hipSuccess ? MFVIT_OK : MFVIT_ELAUNCH;
-    };
+    const WgradQueue q;
+    const int qdt_bwd;
+    const bool do_max;              // dout_max_applies
 
-    const bool rdrop = d.rdrop;                     // the bias gradients of proj / fc2 then come from the MASKED dY (wgrad column sums)
-    // The attention backward's split-fp16 core scales dO (= the proj data gradient) per (image, head) by a power of two from the pair's largest |dO|.  The
-    // GEMM that produces dO leaves those maxima behind (GemmP::omax: atomicMax of f32 bits, one slice per block, zeroed here for the blocks of this call), and
-    // the attention kernel reads ONE number per pair instead of prefetching the hi parts of all of dO's rows a pair ahead.  MFVIT_DO_MAX=0: the prefetch.
-    static int s_domax = INT_MIN;
-    const int qdt_bwd = attn_qkv_dtype(d.dtype, d.T, d.HD);
-    const bool do_max = env_switch("MFVIT_DO_MAX", 1, s_domax) != 0 && qdt_bwd == MFVIT_X3F16 && (d.HD == 32 || d.HD == 64) && d.T >= 64 && d.D % 128 == 0 && !(d.p_attn > 0.f);
-    auto domax = [&](int l) { return (unsigned*)(ws + W.domax) + (size_t)l * d.B * d.H; };
-    if (do_max) {
-        const int l0 = stage_lo > 0 ? stage_lo : 0, l1 = stage_hi < d.depth - 1 ? stage_hi : d.depth - 1;
-        if (l1 >= l0 && hipMemsetAsync(domax(l0), 0, (size_t)(l1 - l0 + 1) * d.B * d.H * 4, st) != hipSuccess) return MFVIT_ELAUNCH;
+    BwdCtx(const mfvit_vit_cfg* cfg, const Dims& dims, const float* params_, const void* shadow, void* workspace, mfvit_stream_t stream,
+           const BwdArgs& a)
+        : EncCtx(cfg, dims, params_, shadow, workspace, stream), BwdArgs(a), wg(a.dparams != nullptr),
+          gbase(wg ? a.dparams : (a.lora ? a.lora->dw : nullptr)), gx((float*)(ws + W.gx)), gmid((float*)(ws + W.gmid)),
+          colscr((float*)(ws + W.colscratch)), colpart_scope(!dims.rdrop), q(wgrad_side_stream(*this, wg), st, a.stage_hi < dims.depth ? a.stage_hi : dims.depth - 1),
+          qdt_bwd(attn_qkv_dtype(dims.dtype, dims.T, dims.HD)), do_max(dout_max_applies(dims, qdt_bwd)) {}
+
+    float* gblk(int l) const { return gbase ? gbase + L.blk0 + (long)l * L.blk_stride : nullptr; }
+    float* next_colpart() { return (float*)(ws + W.colpart + (size_t)(colpart_used++ % (3 * d.depth + 2)) * W.colpart_stride); }
+    float* next_tnpart() {          // (more launches than slots between two flushes: float atomics for the rest - never a slot still in use)
+        return tn_used < TN_SLOTS ? (float*)(ws + W.tnpart + (size_t)(tn_used++) * W.tnpart_stride) : nullptr;
     }
-    for (int s = stage_hi; s >= stage_lo; --s) {
-        if (s == d.depth) {
-            // final LayerNorm backward: dfeatures -> gx (grad of x_depth); dcol = d fc2_b of the last block
-            if (!dfeatures) return MFVIT_EINVAL;
-            float* const dcol = !wg ? nullptr : rdrop ? colscr + D : gblk(d.depth - 1) + L.fc2_b;
-            MFVIT_TRY(ln_bwd_rows(d.dtype, d.D, dfeatures, D, c.xbuf(d.depth), D, c.stat(d.depth), c.stat(d.depth) + d.M, params + L.norm_w,
-                                  nullptr, 0, gx, D, pp(W.gxT, d.depth - 1), D * e, wg ? dparams + L.norm_w : nullptr,
-                                  wg ? dparams + L.norm_b : nullptr, dcol, wg ? next_colpart() : nullptr, d.M, 1, 0, st));
-        } else if (s >= 0) {
-            const int l = s;
-            char* b = c.blk(l);
-            const float* pb = c.pblk(l);
-            float* gb = gblk(l);
-            const char* sb = c.sblk(l);
-            void* gxT = pp(W.gxT, l);
-            void* gmidT = pp(W.gmidT, l);
-            void* dhpre = pp(W.dhpre, l);
-            void* dqkv = pp(W.dqkv, l);
-            MFVIT_TRY(wait_layer(l + 2));                         // layer l+2's wgrads read this parity's dhpre / gmidT / dqkv
-            // Side stream: the four weight gradients of a block are queued TOGETHER, behind the attention backward (their last input), with ONE
-            // main -> side dependency per block: an event record + wait costs the host ~9 us on this ROCm, and a fork in front of every gradient made
-            // the host the bottleneck of a small-batch step (B = 8: 5.1 -> 6.1 ms).  Their inputs are this layer parity's copies, untouched until then.
-            GemmP def_tn[2];
-            int ndef = 0;
-            auto tn_now_or_later = [&](const GemmP& g) -> int {
-                if (use_side) { def_tn[ndef++] = g; return MFVIT_OK; }
-                return gemm_tn(d.dtype, g, wst);
-            };
-            const void* gy2 = gxT;                                // dY of fc2: the residual gradient, masked where the branch was dropped
-            if (rdrop) {
-                // (the residual gradient itself passes unscaled: gxT stays the residual operand of the LN2 backward below)
-                MFVIT_TRY(mask_scale_rows(d.dtype, false, gxT, D * e, ws + W.dtmp, D * e, make_drop(d.p_resid, d.seed, c.site(l, 4)), c.dpath(l, 7), d.T,
-                                          d.M, d.D, st));
-                gy2 = ws + W.dtmp;
-            }
-            const int w_fc2 = lora_wants(l, LORA_FC2, L.fc2_w, D * F), w_fc1 = lora_wants(l, LORA_FC1, L.fc1_w, F * D),
-                      w_proj = lora_wants(l, LORA_PROJ, L.proj_w, D * D), w_qkv = lora_wants(l, LORA_QKV, L.qkv_w, 3 * D * D);
-            if (w_fc2 < 0 || w_fc1 < 0 || w_proj < 0 || w_qkv < 0) return MFVIT_ELAUNCH;
-            if (wg || w_fc2) {   // dW2 += gx^T hact
-                GemmP p = nt(gy2, D * e, b + W.hact, F * e, d.M, d.D, d.F);
-                if (rdrop && wg) p.cs0 = gb + L.fc2_b;
-                p.out0 = gb + L.fc2_w; p.ldo0 = F;
-                p.cpart = next_tnpart();                          // split partials: plain stores, reduced in a fixed order at the end of the call
-                MFVIT_TRY(tn_now_or_later(p));
-            }
-            {   // dhpre = (gx W2) * gelu'(hpre)
-                GemmP p = nt(gy2, D * e, sb + S.fc2_t, D * e, d.M, d.F, d.D);
-                p.aux = b + W.hpre; p.ldaux = F;
-                p.out0 = dhpre; p.ldo0 = F * e;
-                if (wg) { p.cs0 = gb + L.fc1_b; p.cpart = next_colpart(); }   // d fc1_b += column sums of dhpre from the accumulators of this epilogue (partials, fixed-order reduce)
-                MFVIT_TRY(gemm_nt_tile(d.dtype, EPI_GELU_BWD, p, st));
-            }
-            if (wg || w_fc1) {   // dW1 += dhpre^T y2
-                GemmP p = nt(dhpre, F * e, b + W.y2, D * e, d.M, d.F, d.D);   // (d fc1_b: from the fc2 data gradient's epilogue, above)
-                p.out0 = gb + L.fc1_w; p.ldo0 = D;
-                p.cpart = next_tnpart();                          // split partials: plain stores, reduced in a fixed order at the end of the call
-                MFVIT_TRY(tn_now_or_later(p));
-            }
-            {   // gmid = LN2bwd(dhpre W1) + gx ; d ln2_w, d ln2_b, d proj_b
-                GemmP p = nt(dhpre, F * e, sb + S.fc1_t, F * e, d.M, d.D, d.F);
-                p.aux = b + W.xmid; p.ldaux = D;
-                p.mean = (float*)(b + W.st2); p.rstd = (float*)(b + W.st2) + d.M;
-                p.gamma = pb + L.ln2_w;
-                p.kpart = c.kpart();
-                if (wg) { p.cs0 = gb + L.ln2_w; p.cs1 = gb + L.ln2_b; p.cs2 = rdrop ? colscr + D : gb + L.proj_b; p.cpart = next_colpart(); }
-                MFVIT_TRY(dgrad_ln_bwd(c, p, gx, gxT, lean_grad ? nullptr : gmid, gmidT));
-            }
-            const void* gyp = gmidT;                              // dY of proj
-            if (rdrop) {
-                MFVIT_TRY(mask_scale_rows(d.dtype, false, gmidT, D * e, ws + W.dtmp, D * e, make_drop(d.p_resid, d.seed, c.site(l, 3)), c.dpath(l, 6), d.T,
-                                          d.M, d.D, st));
-                gyp = ws + W.dtmp;
-            }
-            GemmP pend_proj = {};                                 // dWproj: launched here, or held back to ride along with dWqkv (one launch for both)
-            bool have_pend = false;
-            if (wg || w_proj) {   // dWproj += gmid^T attn
-                GemmP p = nt(gyp, D * e, b + W.attn, D * e, d.M, d.D, d.D);
-                if (rdrop && wg) p.cs0 = gb + L.proj_b;
-                p.out0 = gb + L.proj_w; p.ldo0 = D;
-                p.cpart = next_tnpart();                          // split partials: plain stores, reduced in a fixed order at the end of the call
-                // held back by default when the weight gradients run on the caller's stream (nothing to overlap: one launch less is a pure gain,
-                // 30.81 -> 30.68 ms per step)
-                if (!rdrop) {
-                    pend_proj = p;
-                    have_pend = true;
-                } else {
-                    MFVIT_TRY(gemm_tn(d.dtype, p, wst));
-                }
-            }
-            {   // dattn = gmid Wproj
-                GemmP p = nt(gyp, D * e, sb + S.proj_t, D * e, d.M, d.D, d.D);
-                p.out0 = ws + W.dattn; p.ldo0 = D * e;
-                if (do_max) { p.omax = domax(l); p.omax_rows = d.T; p.omax_hd = d.HD; }
-                MFVIT_TRY(gemm_nt_tile(d.dtype, EPI_NONE, p, st));
-            }
-            if (rel && l == 0) {
-                // the relevance is complete after block 0's step: nothing reads block 0's dqkv or d x_0
-                MFVIT_TRY(rel_block_step(d, rel, l, qdt_bwd, b + W.qkv, (const float*)(b + W.lse), ws + W.dattn, st));
-                continue;
-            }
-            if (d.p_attn > 0.f)
-                MFVIT_TRY(attn_bwd_tiled_drop(d.dtype, b + W.qkv, b + W.attn, ws + W.dattn, (const float*)(b + W.lse), dqkv, d.B, d.T, d.H, d.HD,
-                                              make_drop(d.p_attn, d.seed, c.site(l, 2)), st));
-            else
-            MFVIT_TRY(attn_bwd(qdt_bwd, b + W.qkv, b + W.attn, ws + W.dattn, (const float*)(b + W.lse), dqkv, nullptr,
-                               d.B, d.T, d.H, d.HD, st, do_max ? domax(l) : nullptr));
-            if (rel) MFVIT_TRY(rel_block_step(d, rel, l, qdt_bwd, b + W.qkv, (const float*)(b + W.lse), ws + W.dattn, st));
-            MFVIT_TRY(fork());                                    // dqkv - and with it every input of this block's weight gradients - is ready
-            for (int i = 0; i < ndef; ++i) MFVIT_TRY(gemm_tn(d.dtype, def_tn[i], wst));
-            if (wg || w_qkv) {   // dWqkv += dqkv^T y1 ; d qkv_b += column sums of dqkv (ones-fragment MFMA inside the wgrad kernel)
-                GemmP p = nt(dqkv, 3 * D * e, b + W.y1, D * e, d.M, 3 * d.D, d.D);
-                if (wg) p.cs0 = gb + L.qkv_b;
-                p.out0 = gb + L.qkv_w; p.ldo0 = D;
-                p.cpart = next_tnpart();                          // split partials: plain stores, reduced in a fixed order at the end of the call
-                // dWproj rides along when the LDS-DMA kernel takes both (same rows, same K = 384: 27 + 9 tiles x 7 splits = 252 workgroups): the
-                // float atomics of one launch (16.5 MB, 12.5 us) and one prologue less per block
-                GemmP pend_nc = pend_proj;
-                pend_nc.cpart = nullptr;                          // (in the paired launch both gradients' partials go to dWqkv's slot)
-                if (have_pend && gemm_tn_pair_supported(d.dtype, p, pend_nc)) {
-                    MFVIT_TRY(gemm_tn_glds_pair(d.dtype, p, pend_nc, wst));
-                } else {
-                    if (have_pend) MFVIT_TRY(gemm_tn(d.dtype, pend_proj, wst));
-                    MFVIT_TRY(gemm_tn(d.dtype, p, wst));
-                }
-            } else if (have_pend) {
-                MFVIT_TRY(gemm_tn(d.dtype, pend_proj, wst));      // (adapters on proj without any on q / k / v)
-            }
-            MFVIT_TRY(tnpart_batch_flush(wst));                   // dW += this block's split partials, splits in a fixed order; the slots are free again
-            tn_used = 0;
-            if (use_side && hipEventRecord(ss.done[l & 63], ss.s) != hipSuccess) return MFVIT_ELAUNCH;
-            MFVIT_TRY(wait_layer(l + 1));                         // fc2-wgrad of layer l+1 reads the gxT copy written next
-            if (lora && !dimg && l == stage_lo) continue;         // adapters only: nobody reads d x of the lowest adapted block
-            {   // gx = LN1bwd(dqkv Wqkv) + gmid ; d ln1_w, d ln1_b, d fc2_b of block l-1 (or scratch for the embed stage)
-                if (wg && l == 0 && hipMemsetAsync(colscr, 0, 2 * D * sizeof(float), st) != hipSuccess) return MFVIT_ELAUNCH;
-                GemmP p = nt(dqkv, 3 * D * e, sb + S.qkv_t, 3 * D * e, d.M, d.D, 3 * d.D);
-                p.aux = c.xbuf(l); p.ldaux = D;
-                p.mean = c.stat(l); p.rstd = c.stat(l) + d.M;
-                p.gamma = pb + L.ln1_w;
-                p.kpart = c.kpart();
-                if (wg) { p.cs0 = gb + L.ln1_w; p.cs1 = gb + L.ln1_b; p.cs2 = (l > 0 && !rdrop) ? gblk(l - 1) + L.fc2_b : colscr; p.cpart = next_colpart(); }
-                // (lean_grad keeps the f32 result at block 0 only: the embedding stage reads gx)
-                MFVIT_TRY(dgrad_ln_bwd(c, p, gmid, gmidT, lean_grad && l > 0 ? nullptr : gx, pp(W.gxT, l - 1)));
-            }
-        } else if (d.tok) {
-            MFVIT_TRY(colpart_batch_flush(st));
-            // token-input embedding stage: gx = d x_0 = d tokens; d pos_emb = sum over the batch (fuseattention.py:187)
-            if (d.p_embd > 0.f)      // d (tokens + pos_emb) = d x_0 * mask / (1 - p)
-                MFVIT_TRY(mask_scale_rows(d.dtype, true, gx, D, gx, D, make_drop(d.p_embd, d.seed, 1), c.off, 1, d.M, d.D, st));
-            if (dinput && hipMemcpyAsync(dinput, gx, (size_t)d.M * D * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
-                return MFVIT_ELAUNCH;
-            if (d.use_pos) MFVIT_TRY(batch_sum(gx, dparams + L.pos, d.B, (long)d.T * D, st));
+    // dY buffers by layer parity (the embed stage counts as layer -1 -> parity 1)
+    void* pp(size_t off, int l) const { return (void*)(ws + off + (size_t)(l & 1) * W.pp_stride); }
+    unsigned* domax(int l) const { return (unsigned*)(ws + W.domax) + (size_t)l * d.B * d.H; }
+
+    // Is the weight gradient of a Linear of block l formed (1 / 0; -1: error)?  With wg, all of them; without, the adapted ones (`bits` of
+    // lora->mask[l]) - zeroed first: the GEMMs and the reduce accumulate
+    int wgrad_wanted(int l, int bits, long off, long count) const {
+        if (wg) return 1;
+        if (!lora || !(lora->mask[l] & bits)) return 0;
+        return hipMemsetAsync(gblk(l) + off, 0, (size_t)count * sizeof(float), st) == hipSuccess ? 1 : -1;
+    }
+    // One "weight gradient of a Linear" site of block l: dW [N][K] at `woff` of the block's gradients += dY^T X over the M token rows, the column
+    // sums of dY into `bias` (or NULL); split partials: plain stores into a fresh slot, reduced in a fixed order at the end of the block
+    GemmP wgrad_site(int l, const void* dY, long lddy, const void* X, long ldx, int N, int K, long woff, float* bias) {
+        GemmP p = nt(dY, lddy, X, ldx, d.M, N, K);
+        p.cs0 = bias;
+        p.out0 = gblk(l) + woff; p.ldo0 = K;
+        p.cpart = next_tnpart();
+        return p;
+    }
+    // When a weight gradient of a block is launched - the one place that decides:
+    //   held (pairable = dWproj) to ride along with dWqkv - by default when the weight gradients run on the caller's stream (nothing to overlap: one
+    //     launch less is a pure gain, 30.81 -> 30.68 ms per step) and with the side stream alike; not with a masked branch;
+    //   at the block's fork, with the side stream: the four weight gradients of a block are queued TOGETHER, behind the attention backward (their
+    //     last input), with ONE main -> side dependency per block: an event record + wait costs the host ~9 us on this ROCm, and a fork in front of
+    //     every gradient made the host the bottleneck of a small-batch step (B = 8: 5.1 -> 6.1 ms).  Their inputs are this layer parity's copies,
+    //     untouched until then;
+    //   now, otherwise.
+    int route_wgrad(BlockWgrads& bw, const GemmP& g, bool pairable) const {
+        if (pairable && !d.rdrop) { bw.pend = g; bw.have_pend = true; return MFVIT_OK; }
+        if (q.side) { bw.at_fork[bw.n_fork++] = g; return MFVIT_OK; }
+        return gemm_tn(d.dtype, g, q.s);
+    }
+};
+}  // namespace
+
+// final LayerNorm backward: dfeatures -> gx (grad of x_depth); dcol = d fc2_b of the last block
+static int bwd_final_norm(BwdCtx& c) {
+    const Dims& d = c.d;
+    if (!c.dfeatures) return MFVIT_EINVAL;
+    float* const dcol = !c.wg ? nullptr : d.rdrop ? c.colscr + c.D : c.gblk(d.depth - 1) + c.L.fc2_b;
+    return ln_bwd_rows(d.dtype, d.D, c.dfeatures, c.D, c.xbuf(d.depth), c.D, c.stat(d.depth), c.stat(d.depth) + d.M, c.params + c.L.norm_w, nullptr, 0,
+                       c.gx, c.D, c.pp(c.W.gxT, d.depth - 1), c.D * c.e, c.wg ? c.dparams + c.L.norm_w : nullptr,
+                       c.wg ? c.dparams + c.L.norm_b : nullptr, dcol, c.wg ? c.next_colpart() : nullptr, d.M, 1, 0, c.st);
+}
+
+// dY of a residual branch of block l: the residual gradient itself, or - where the branch was dropped - its masked copy in the scratch buffer
+// (the residual gradient passes unscaled: `dy` stays the residual operand of the LayerNorm backward behind the branch)
+static int mask_branch_grad(const BwdCtx& c, int l, int drop_site, int dpath_site, const void*& dy) {
+    const Dims& d = c.d;
+    if (!d.rdrop) return MFVIT_OK;
+    const long De = c.D * c.e;
+    MFVIT_TRY(mask_scale_rows(d.dtype, false, dy, De, c.ws + c.W.dtmp, De, make_drop(d.p_resid, d.seed, c.site(l, drop_site)), c.dpath(l, dpath_site),
+                              d.T, d.M, d.D, c.st));
+    dy = c.ws + c.W.dtmp;
+    return MFVIT_OK;
+}
+
+// Behind block l's attention backward: dqkv - and with it every input of this block's weight gradients - is ready.  Fork, the gradients queued
+// for it, dWqkv (with the held dWproj), the reduce of the block's split partials, and the block's `done` mark.
+static int bwd_block_wgrads(BwdCtx& c, int l, const BlockWgrads& bw, bool want_qkv, const void* dqkv) {
+    const Dims& d = c.d;
+    const long De = c.D * c.e;
+    MFVIT_TRY(c.q.fork());
+    for (int i = 0; i < bw.n_fork; ++i) MFVIT_TRY(gemm_tn(d.dtype, bw.at_fork[i], c.q.s));
+    if (want_qkv) {   // dWqkv += dqkv^T y1 ; d qkv_b += column sums of dqkv (ones-fragment MFMA inside the wgrad kernel)
+        const GemmP p = c.wgrad_site(l, dqkv, 3 * De, c.blk(l) + c.W.y1, De, 3 * d.D, d.D, c.L.qkv_w, c.wg ? c.gblk(l) + c.L.qkv_b : nullptr);
+        // dWproj rides along when the LDS-DMA kernel takes both (same rows, same K = 384: 27 + 9 tiles x 7 splits = 252 workgroups): the
+        // float atomics of one launch (16.5 MB, 12.5 us) and one prologue less per block
+        GemmP pend_nc = bw.pend;
+        pend_nc.cpart = nullptr;                              // (in the paired launch both gradients' partials go to dWqkv's slot)
+        if (bw.have_pend && gemm_tn_pair_supported(d.dtype, p, pend_nc)) {
+            MFVIT_TRY(gemm_tn_glds_pair(d.dtype, p, pend_nc, c.q.s));
         } else {
-            MFVIT_TRY(colpart_batch_flush(st));                   // (colscr, read below, is one of the deferred sums)
-            if (d.p_embd > 0.f) {
-                // pos_drop: d (cat(cls, patch_embed) + pos_embed) = d x_0 * mask / (1 - p) - the f32 rows (cls, pe_b) and their operand-type copy
-                // (pe_w) - and colscr[0:D] becomes the column sum of the masked rows
-                // (the operand-type copy is cast afresh from the masked f32 rows: no second rounding of the split copy)
-                MFVIT_TRY(mask_scale_rows(d.dtype, true, gx, D, gx, D, make_drop(d.p_embd, d.seed, 1), c.off, 1, d.M, d.D, st));
-                MFVIT_TRY(cast_transpose(d.dtype, gx, pp(W.gxT, -1), nullptr, d.M, d.D, st));
-                if (wg) {
-                    if (hipMemsetAsync(colscr, 0, D * sizeof(float), st) != hipSuccess) return MFVIT_ELAUNCH;
-                    MFVIT_TRY(colsum_rows(gx, D, colscr, d.M, 1, 0, d.D, st));
-                }
-            }
-            if (dimg) {
-                // d img = col2im(gx[patch rows] W_pe): W_pe^T of the operand type into the workspace (the shadow keeps W_pe [D][768] only; W_pe takes
-                // part in the data gradient under stop_grad_conv1 too), then one tile GEMM whose epilogue stores the f32 image (EPI_COL2IM16, gemm.hip).
-                // A = the operand-type copy of gx from token row 1 on: B T - 1 rows, the cls rows of images 1 .. B-1 among them (skipped by the epilogue).
-                char* wpeT = ws + W.wpeT;
-                MFVIT_TRY(cast_transpose(d.dtype, params + L.pe_w, nullptr, wpeT, d.D, 768, st));
-                GemmP p = nt((const char*)pp(W.gxT, -1) + (size_t)D * d.es, D * e, wpeT, D * e, d.M - 1, 768, d.D);
-                p.orow_in = d.np; p.orow_out = d.T;
-                p.out0 = dimg; p.ldo0 = cfg->img_w;
-                MFVIT_TRY(gemm_nt_tile(d.dtype, EPI_COL2IM16, p, st));
-            }
-            if (!wg) continue;
-            // embed stage: gx = d x_0.  d cls_token = sum_b gx[b,0]; d pe_b = sum over patch rows; d pe_w = gx_patch^T patches.
-            // pos_embed is a fixed table (requires_grad = False upstream): no gradient.
-            MFVIT_TRY(colsum_rows(gx, D, dparams + L.cls, d.B, d.T, 0, d.D, st));
-            if (!cfg->stop_grad_conv1) {
-                // colscr[0:D] = sum of gx over ALL rows (cs2 of the LN1_0 backward); colscr[D:2D] = sum over the cls rows
-                MFVIT_TRY(colsum_rows(gx, D, colscr + D, d.B, d.T, 0, d.D, st));
-                MFVIT_TRY(axpy(dparams + L.pe_b, colscr, 1.0f, d.D, st));
-                MFVIT_TRY(axpy(dparams + L.pe_b, colscr + D, -1.0f, d.D, st));
-                GemmP p = nt(pp(W.gxT, -1), D * e, ws + W.patches, 768 * e, d.Mp, d.D, 768);   // d pe_w += gx[patch rows]^T patches
-                p.orow_in = d.np; p.orow_out = d.T; p.orow_off = 1;
-                p.out0 = dparams + L.pe_w; p.ldo0 = 768;
-                p.cpart = next_tnpart();
-                MFVIT_TRY(fork());                                // (the residual gradient of block 0 is ready on the main stream)
-                MFVIT_TRY(gemm_tn(d.dtype, p, wst));
-            }
+            if (bw.have_pend) MFVIT_TRY(gemm_tn(d.dtype, bw.pend, c.q.s));
+            MFVIT_TRY(gemm_tn(d.dtype, p, c.q.s));
+        }
+    } else if (bw.have_pend) {
+        MFVIT_TRY(gemm_tn(d.dtype, bw.pend, c.q.s));          // (adapters on proj without any on q / k / v)
+    }
+    MFVIT_TRY(tnpart_batch_flush(c.q.s));                     // dW += this block's split partials, splits in a fixed order; the slots are free again
+    c.tn_used = 0;
+    return c.q.mark_done(l);
+}
+
+// block l: gx = d x_{l+1} (f32 and / or its operand-type copy of this layer parity) -> d x_l, and the block's parameter gradients
+static int bwd_block(BwdCtx& c, int l) {
+    const Dims& d = c.d;
+    const long D = c.D, F = c.F, De = c.D * c.e, Fe = c.F * c.e;
+    char* const b = c.blk(l);
+    const float* const pb = c.pblk(l);
+    const char* const sb = c.sblk(l);
+    float* const gb = c.gblk(l);
+    void* const gxT = c.pp(c.W.gxT, l);
+    void* const gmidT = c.pp(c.W.gmidT, l);
+    void* const dhpre = c.pp(c.W.dhpre, l);
+    void* const dqkv = c.pp(c.W.dqkv, l);
+    const bool masked_bias = d.rdrop && c.wg;               // the bias gradients of proj / fc2 then come from the MASKED dY (wgrad column sums)
+    MFVIT_TRY(c.q.wait_layer(l + 2));                       // layer l+2's wgrads read this parity's dhpre / gmidT / dqkv
+    BlockWgrads bw;
+    const void* gy2 = gxT;                                  // dY of fc2
+    MFVIT_TRY(mask_branch_grad(c, l, 4, 7, gy2));
+    const int w_fc2 = c.wgrad_wanted(l, LORA_FC2, c.L.fc2_w, D * F), w_fc1 = c.wgrad_wanted(l, LORA_FC1, c.L.fc1_w, F * D),
+              w_proj = c.wgrad_wanted(l, LORA_PROJ, c.L.proj_w, D * D), w_qkv = c.wgrad_wanted(l, LORA_QKV, c.L.qkv_w, 3 * D * D);
+    if (w_fc2 < 0 || w_fc1 < 0 || w_proj < 0 || w_qkv < 0) return MFVIT_ELAUNCH;
+    if (w_fc2)   // dW2 += gx^T hact
+        MFVIT_TRY(c.route_wgrad(bw, c.wgrad_site(l, gy2, De, b + c.W.hact, Fe, d.D, d.F, c.L.fc2_w, masked_bias ? gb + c.L.fc2_b : nullptr), false));
+    {   // dhpre = (gx W2) * gelu'(hpre)
+        GemmP p = nt(gy2, De, sb + c.S.fc2_t, De, d.M, d.F, d.D);
+        p.aux = b + c.W.hpre; p.ldaux = F;
+        p.out0 = dhpre; p.ldo0 = Fe;
+        if (c.wg) { p.cs0 = gb + c.L.fc1_b; p.cpart = c.next_colpart(); }   // d fc1_b += column sums of dhpre from the accumulators of this epilogue (partials, fixed-order reduce)
+        MFVIT_TRY(gemm_nt_tile(d.dtype, EPI_GELU_BWD, p, c.st));
+    }
+    if (w_fc1)   // dW1 += dhpre^T y2   (d fc1_b: from the fc2 data gradient's epilogue, above)
+        MFVIT_TRY(c.route_wgrad(bw, c.wgrad_site(l, dhpre, Fe, b + c.W.y2, De, d.F, d.D, c.L.fc1_w, nullptr), false));
+    {   // gmid = LN2bwd(dhpre W1) + gx ; d ln2_w, d ln2_b, d proj_b
+        GemmP p = nt(dhpre, Fe, sb + c.S.fc1_t, Fe, d.M, d.D, d.F);
+        p.aux = b + c.W.xmid; p.ldaux = D;
+        p.mean = (float*)(b + c.W.st2); p.rstd = (float*)(b + c.W.st2) + d.M;
+        p.gamma = pb + c.L.ln2_w;
+        p.kpart = c.kpart();
+        if (c.wg) { p.cs0 = gb + c.L.ln2_w; p.cs1 = gb + c.L.ln2_b; p.cs2 = d.rdrop ? c.colscr + D : gb + c.L.proj_b; p.cpart = c.next_colpart(); }
+        MFVIT_TRY(dgrad_ln_bwd(c, p, c.gx, gxT, c.lean_grad ? nullptr : c.gmid, gmidT));
+    }
+    const void* gyp = gmidT;                                // dY of proj
+    MFVIT_TRY(mask_branch_grad(c, l, 3, 6, gyp));
+    if (w_proj)   // dWproj += gmid^T attn
+        MFVIT_TRY(c.route_wgrad(bw, c.wgrad_site(l, gyp, De, b + c.W.attn, De, d.D, d.D, c.L.proj_w, masked_bias ? gb + c.L.proj_b : nullptr), true));
+    {   // dattn = gmid Wproj
+        GemmP p = nt(gyp, De, sb + c.S.proj_t, De, d.M, d.D, d.D);
+        p.out0 = c.ws + c.W.dattn; p.ldo0 = De;
+        if (c.do_max) { p.omax = c.domax(l); p.omax_rows = d.T; p.omax_hd = d.HD; }
+        MFVIT_TRY(gemm_nt_tile(d.dtype, EPI_NONE, p, c.st));
+    }
+    if (c.rel && l == 0)   // the relevance is complete after block 0's step: nothing reads block 0's dqkv or d x_0
+        return rel_block_step(d, c.rel, l, c.qdt_bwd, b + c.W.qkv, (const float*)(b + c.W.lse), c.ws + c.W.dattn, c.st);
+    if (d.p_attn > 0.f)
+        MFVIT_TRY(attn_bwd_tiled_drop(d.dtype, b + c.W.qkv, b + c.W.attn, c.ws + c.W.dattn, (const float*)(b + c.W.lse), dqkv, d.B, d.T, d.H, d.HD,
+                                      make_drop(d.p_attn, d.seed, c.site(l, 2)), c.st));
+    else
+        MFVIT_TRY(attn_bwd(c.qdt_bwd, b + c.W.qkv, b + c.W.attn, c.ws + c.W.dattn, (const float*)(b + c.W.lse), dqkv, nullptr, d.B, d.T, d.H, d.HD, c.st,
+                           c.do_max ? c.domax(l) : nullptr));
+    if (c.rel) MFVIT_TRY(rel_block_step(d, c.rel, l, c.qdt_bwd, b + c.W.qkv, (const float*)(b + c.W.lse), c.ws + c.W.dattn, c.st));
+    MFVIT_TRY(bwd_block_wgrads(c, l, bw, w_qkv != 0, dqkv));
+    MFVIT_TRY(c.q.wait_layer(l + 1));                       // fc2-wgrad of layer l+1 reads the gxT copy written next
+    if (c.lora && !c.dimg && l == c.stage_lo) return MFVIT_OK;   // adapters only: nobody reads d x of the lowest adapted block
+    // gx = LN1bwd(dqkv Wqkv) + gmid ; d ln1_w, d ln1_b, d fc2_b of block l-1 (or scratch for the embed stage)
+    if (c.wg && l == 0 && hipMemsetAsync(c.colscr, 0, 2 * D * sizeof(float), c.st) != hipSuccess) return MFVIT_ELAUNCH;
+    GemmP p = nt(dqkv, 3 * De, sb + c.S.qkv_t, 3 * De, d.M, d.D, 3 * d.D);
+    p.aux = c.xbuf(l); p.ldaux = D;
+    p.mean = c.stat(l); p.rstd = c.stat(l) + d.M;
+    p.gamma = pb + c.L.ln1_w;
+    p.kpart = c.kpart();
+    if (c.wg) { p.cs0 = gb + c.L.ln1_w; p.cs1 = gb + c.L.ln1_b; p.cs2 = (l > 0 && !d.rdrop) ? c.gblk(l - 1) + c.L.fc2_b : c.colscr; p.cpart = c.next_colpart(); }
+    // (lean_grad keeps the f32 result at block 0 only: the embedding stage reads gx)
+    return dgrad_ln_bwd(c, p, c.gmid, gmidT, c.lean_grad && l > 0 ? nullptr : c.gx, c.pp(c.W.gxT, l - 1));
+}
+
+// token-input embedding stage: gx = d x_0 = d tokens; d pos_emb = sum over the batch (fuseattention.py:187)
+static int bwd_embed_tokens(BwdCtx& c) {
+    const Dims& d = c.d;
+    MFVIT_TRY(colpart_batch_flush(c.st));
+    if (d.p_embd > 0.f)      // d (tokens + pos_emb) = d x_0 * mask / (1 - p)
+        MFVIT_TRY(mask_scale_rows(d.dtype, true, c.gx, c.D, c.gx, c.D, make_drop(d.p_embd, d.seed, 1), c.off, 1, d.M, d.D, c.st));
+    if (c.dinput && hipMemcpyAsync(c.dinput, c.gx, (size_t)d.M * c.D * sizeof(float), hipMemcpyDeviceToDevice, c.st) != hipSuccess)
+        return MFVIT_ELAUNCH;
+    if (d.use_pos) MFVIT_TRY(batch_sum(c.gx, c.dparams + c.L.pos, d.B, (long)d.T * c.D, c.st));
+    return MFVIT_OK;
+}
+
+// image embedding stage: gx = d x_0 -> d img (the patch-embedding data gradient), d cls_token, d pe_b, d pe_w
+static int bwd_embed_image(BwdCtx& c) {
+    const Dims& d = c.d;
+    const long D = c.D, De = c.D * c.e;
+    MFVIT_TRY(colpart_batch_flush(c.st));                   // (colscr, read below, is one of the deferred sums)
+    if (d.p_embd > 0.f) {
+        // pos_drop: d (cat(cls, patch_embed) + pos_embed) = d x_0 * mask / (1 - p) - the f32 rows (cls, pe_b) and their operand-type copy
+        // (pe_w) - and colscr[0:D] becomes the column sum of the masked rows
+        // (the operand-type copy is cast afresh from the masked f32 rows: no second rounding of the split copy)
+        MFVIT_TRY(mask_scale_rows(d.dtype, true, c.gx, D, c.gx, D, make_drop(d.p_embd, d.seed, 1), c.off, 1, d.M, d.D, c.st));
+        MFVIT_TRY(cast_transpose(d.dtype, c.gx, c.pp(c.W.gxT, -1), nullptr, d.M, d.D, c.st));
+        if (c.wg) {
+            if (hipMemsetAsync(c.colscr, 0, D * sizeof(float), c.st) != hipSuccess) return MFVIT_ELAUNCH;
+            MFVIT_TRY(colsum_rows(c.gx, D, c.colscr, d.M, 1, 0, d.D, c.st));
         }
     }
-    MFVIT_TRY(colpart_batch_flush(st));
-    MFVIT_TRY(tnpart_batch_flush(wst));     // dW += the split partials still pending (the patch embedding's), splits in a fixed order
-    if (lora) MFVIT_TRY(lora_run(d, lora->req, lora->dw, nullptr, true, st));   // dA, dB of every item from the dW_eff slices
-    if (use_side) {   // join: everything the side stream did is ordered before whatever the caller queues next
-        if (hipEventRecord(ss.end, ss.s) != hipSuccess || hipStreamWaitEvent(st, ss.end, 0) != hipSuccess) return MFVIT_ELAUNCH;
+    if (c.dimg) {
+        // d img = col2im(gx[patch rows] W_pe): W_pe^T of the operand type into the workspace (the shadow keeps W_pe [D][768] only; W_pe takes
+        // part in the data gradient under stop_grad_conv1 too), then one tile GEMM whose epilogue stores the f32 image (EPI_COL2IM16, gemm.hip).
+        // A = the operand-type copy of gx from token row 1 on: B T - 1 rows, the cls rows of images 1 .. B-1 among them (skipped by the epilogue).
+        char* const wpeT = c.ws + c.W.wpeT;
+        MFVIT_TRY(cast_transpose(d.dtype, c.params + c.L.pe_w, nullptr, wpeT, d.D, 768, c.st));
+        GemmP p = nt((const char*)c.pp(c.W.gxT, -1) + (size_t)D * d.es, De, wpeT, De, d.M - 1, 768, d.D);
+        p.orow_in = d.np; p.orow_out = d.T;
+        p.out0 = c.dimg; p.ldo0 = c.cfg->img_w;
+        MFVIT_TRY(gemm_nt_tile(d.dtype, EPI_COL2IM16, p, c.st));
     }
-    return MFVIT_OK;
+    if (!c.wg) return MFVIT_OK;
+    // d cls_token = sum_b gx[b,0]; d pe_b = sum over patch rows; d pe_w = gx_patch^T patches.
+    // pos_embed is a fixed table (requires_grad = False upstream): no gradient.
+    MFVIT_TRY(colsum_rows(c.gx, D, c.dparams + c.L.cls, d.B, d.T, 0, d.D, c.st));
+    if (c.cfg->stop_grad_conv1) return MFVIT_OK;
+    // colscr[0:D] = sum of gx over ALL rows (cs2 of the LN1_0 backward); colscr[D:2D] = sum over the cls rows
+    MFVIT_TRY(colsum_rows(c.gx, D, c.colscr + D, d.B, d.T, 0, d.D, c.st));
+    MFVIT_TRY(axpy(c.dparams + c.L.pe_b, c.colscr, 1.0f, d.D, c.st));
+    MFVIT_TRY(axpy(c.dparams + c.L.pe_b, c.colscr + D, -1.0f, d.D, c.st));
+    GemmP p = nt(c.pp(c.W.gxT, -1), De, c.ws + c.W.patches, 768 * c.e, d.Mp, d.D, 768);   // d pe_w += gx[patch rows]^T patches
+    p.orow_in = d.np; p.orow_out = d.T; p.orow_off = 1;
+    p.out0 = c.dparams + c.L.pe_w; p.ldo0 = 768;
+    p.cpart = c.next_tnpart();
+    MFVIT_TRY(c.q.fork());                                  // (the residual gradient of block 0 is ready on the main stream)
+    return gemm_tn(d.dtype, p, c.q.s);
+}
+
+// Shared backward of the two front ends (BwdArgs: what is asked for): stages stage_hi .. stage_lo in descending order - depth: the final norm,
+// depth-1 .. 0: the blocks, -1: the embedding - then whatever the stages left pending.
+static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* dropcfg, const float* params, const void* shadow, void* workspace,
+                            const BwdArgs& a, mfvit_stream_t stream, bool want_tokens) {
+    Dims d;
+    if (!get_dims(cfg, dropcfg, d) || !params || !shadow || !workspace || (!a.dparams && !a.dimg && !a.rel && !a.lora)) return MFVIT_EINVAL;
+    if (!d.save || d.tok != want_tokens) return MFVIT_EINVAL;
+    if (a.stage_hi > d.depth || a.stage_lo < -1 || a.stage_lo > a.stage_hi) return MFVIT_EINVAL;
+    if (a.dimg && (d.tok || a.stage_lo != -1)) return MFVIT_EINVAL;
+    BwdCtx c(cfg, d, params, shadow, workspace, stream, a);
+    if (c.do_max) {   // the maxima of the blocks of this call start at zero
+        const int l0 = a.stage_lo > 0 ? a.stage_lo : 0, l1 = a.stage_hi < d.depth - 1 ? a.stage_hi : d.depth - 1;
+        if (l1 >= l0 && hipMemsetAsync(c.domax(l0), 0, (size_t)(l1 - l0 + 1) * d.B * d.H * 4, c.st) != hipSuccess) return MFVIT_ELAUNCH;
+    }
+    for (int s = a.stage_hi; s >= a.stage_lo; --s)
+        MFVIT_TRY(s == d.depth ? bwd_final_norm(c) : s >= 0 ? bwd_block(c, s) : d.tok ? bwd_embed_tokens(c) : bwd_embed_image(c));
+    MFVIT_TRY(colpart_batch_flush(c.st));
+    MFVIT_TRY(tnpart_batch_flush(c.q.s));   // dW += the split partials still pending (the patch embedding's), splits in a fixed order
+    if (a.lora) MFVIT_TRY(lora_run(d, a.lora->req, a.lora->dw, nullptr, true, c.st));   // dA, dB of every item from the dW_eff slices
+    return c.q.join();
 }
 
 extern "C" {
@@ -1023,33 +1073,33 @@ int mfvit_vit_backward_rel(const mfvit_vit_cfg* cfg, const mfvit_vit_rel_req* re
     Dims d;
     if (!rel_req_ok(cfg, req, d) || !req->scratch || !dfeatures || !params || !shadow || !workspace) return MFVIT_EINVAL;
     ShareScope share(cfg);
-    return encoder_backward(cfg, nullptr, params, shadow, workspace, dfeatures, nullptr, nullptr, nullptr, d.depth, 0, stream, false, req);
+    return encoder_backward(cfg, nullptr, params, shadow, workspace, {dfeatures, nullptr, nullptr, nullptr, d.depth, 0, req}, stream, false);
 }
 int mfvit_vit_backward(const mfvit_vit_cfg* cfg, const float* params, const void* shadow, void* workspace, const float* dfeatures,
                        float* dparams, int stage_hi, int stage_lo, mfvit_stream_t stream) {
     if (!dparams) return MFVIT_EINVAL;
     ShareScope share(cfg);
-    return encoder_backward(cfg, nullptr, params, shadow, workspace, dfeatures, dparams, nullptr, nullptr, stage_hi, stage_lo, stream, false);
+    return encoder_backward(cfg, nullptr, params, shadow, workspace, {dfeatures, dparams, nullptr, nullptr, stage_hi, stage_lo}, stream, false);
 }
 int mfvit_vit_backward_ex(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, const float* params, const void* shadow, void* workspace,
                           const float* dfeatures, float* dparams, float* dimg, int stage_hi, int stage_lo, mfvit_stream_t stream) {
     ShareScope share(cfg);
-    return encoder_backward(cfg, drop, params, shadow, workspace, dfeatures, dparams, nullptr, dimg, stage_hi, stage_lo, stream, false);
+    return encoder_backward(cfg, drop, params, shadow, workspace, {dfeatures, dparams, nullptr, dimg, stage_hi, stage_lo}, stream, false);
 }
 int mfvit_vit_backward_drop(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, const float* params, const void* shadow, void* workspace,
                             const float* dfeatures, float* dparams, int stage_hi, int stage_lo, mfvit_stream_t stream) {
     if (!drop || !dparams) return MFVIT_EINVAL;
     ShareScope share(cfg);
-    return encoder_backward(cfg, drop, params, shadow, workspace, dfeatures, dparams, nullptr, nullptr, stage_hi, stage_lo, stream, false);
+    return encoder_backward(cfg, drop, params, shadow, workspace, {dfeatures, dparams, nullptr, nullptr, stage_hi, stage_lo}, stream, false);
 }
 int mfvit_vit_prepare_shadow_lora(const mfvit_vit_cfg* cfg, const float* params, const mfvit_lora_req* req, float* eff_params, void* shadow,
                                   mfvit_stream_t stream) {
     Dims d;
     LoraPlan pl;
     if (!get_dims(cfg, d) || !params || !shadow || !eff_params || !lora_plan(d, req, false, pl)) return MFVIT_EINVAL;
-    const size_t total = (size_t)param_layout(d).total;
-    if ((eff_params <= params && params < eff_params + total) || (params <= eff_params && eff_params < params + total)) return MFVIT_EINVAL;
     const ParamLayout L = param_layout(d);
+    const size_t total = (size_t)L.total;
+    if ((eff_params <= params && params < eff_params + total) || (params <= eff_params && eff_params < params + total)) return MFVIT_EINVAL;
     for (int i = 0; i < req->n; ++i)
         if (!lora_pair_ok(lora_pair(d, L, req->items[i], params, eff_params, false), req->rank, false)) return MFVIT_EINVAL;
     if (hipMemcpyAsync(eff_params, params, total * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) return MFVIT_ELAUNCH;
@@ -1070,8 +1120,8 @@ int mfvit_vit_backward_lora(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop
             if (!lora_pair_ok(lora_pair(d, L, req->items[i], dw_scratch, nullptr, true), req->rank, true)) return MFVIT_EINVAL;
     }
     ShareScope share(cfg);
-    return encoder_backward(cfg, drop, params, shadow, workspace, dfeatures, nullptr, nullptr, dimg, stage_hi, dimg ? -1 : pl.lowest, stream, false,
-                            nullptr, &pl);
+    return encoder_backward(cfg, drop, params, shadow, workspace, {dfeatures, nullptr, nullptr, dimg, stage_hi, dimg ? -1 : pl.lowest, nullptr, &pl},
+                            stream, false);
 }
 int mfvit_vit_lora_grad(const mfvit_vit_cfg* cfg, const mfvit_lora_req* req, const float* dparams, mfvit_stream_t stream) {
     Dims d;
@@ -1086,10 +1136,9 @@ int mfvit_gpt_forward(const mfvit_vit_cfg* cfg, const float* params, const void*
 }
 int mfvit_gpt_backward(const mfvit_vit_cfg* cfg, const float* params, const void* shadow, void* workspace, const float* dout, float* dparams,
                        float* dtokens, mfvit_stream_t stream) {
-    if (!cfg || !dtokens || !dout) return MFVIT_EINVAL;
+    if (!cfg || !dtokens || !dout || !dparams) return MFVIT_EINVAL;
     ShareScope share(cfg);
-    if (!dparams) return MFVIT_EINVAL;
-    return encoder_backward(cfg, nullptr, params, shadow, workspace, dout, dparams, dtokens, nullptr, cfg->depth, -1, stream, true);
+    return encoder_backward(cfg, nullptr, params, shadow, workspace, {dout, dparams, dtokens, nullptr, cfg->depth, -1}, stream, true);
 }
 
 }  // extern "C"
