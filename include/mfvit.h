@@ -161,6 +161,12 @@ size_t mfvit_vit_workspace_bytes_ex(const mfvit_vit_cfg* cfg, const mfvit_vit_dr
 int mfvit_vit_backward_ex(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, const float* params, const void* shadow, void* workspace,
                           const float* dfeatures, float* dparams, float* dimg, int stage_hi, int stage_lo, mfvit_stream_t stream);
 
+/* Hidden states of the image encoder (host only, additive in ABI 5).  Where the residual stream lies in the workspace after mfvit_vit_forward
+ * with save_for_backward = 1: hidden state l (l = 0: cls + patch embedding + pos_embed, the input of block 0; l = 1 .. depth: the output of
+ * block l - 1, before the final norm) is f32 [batch * tokens][dim], image-major, at workspace + out[0] + l * out[1] bytes.  f32 in every
+ * precision.  MFVIT_EINVAL: invalid cfg, out NULL or save_for_backward == 0. */
+int mfvit_vit_hidden_layout(const mfvit_vit_cfg* cfg, int64_t out[2]);
+
 /* Attention maps of the image encoder (additive in ABI 5): an evaluation forward (no dropout site active) that writes the same `features` as
  * mfvit_vit_forward, on a workspace of mfvit_vit_workspace_bytes(cfg) bytes, plus the softmax probabilities of the requested blocks:
  *   P[b][h][i][j] = exp(scale q_i.k_j - lse_i),  scale = head_dim^-1/2,
@@ -592,6 +598,39 @@ int mfvit_boot_points(const float* scores, int64_t ld, int64_t model_stride, con
                       uint64_t* npos, mfvit_stream_t stream);
 int mfvit_calib_sums(const float* logits, int64_t ld, int64_t model_stride, const int64_t* labels, int n, int C, int M, const float* temps, int Kt,
                      int NB, uint64_t* bin_n, uint64_t* bin_hit, double* bin_conf, double* sums, uint64_t* skipped, mfvit_stream_t stream);
+
+/* Minibatch linear CKA (Kornblith et al. 2019; Nguyen, Raghu & Kornblith 2021; mfvit.similarity drives it): centred Gram matrices of a stack of
+ * representations, and the HSIC sums between two stacks.  Asynchronous on `stream`; no atomics: repeated calls return the same bits.
+ *
+ * mfvit_gram_plan (host only): [0] columns per LDS stage  [1] splits of the column range  [2] columns per split (a multiple of [0])
+ * [3] columns of the last split.  A function of (n, k) ONLY - not of reps, not of the device's state - so a representation computed in a call
+ * with many has the bits of the same representation computed alone.  mfvit_gram_work_bytes: bytes of `work` (0 for an invalid shape).
+ *
+ * mfvit_gram_centered: g[r][i][j] (double [reps][n][n], overwritten, both triangles, g[r][i][j] and g[r][j][i] the same bits)
+ *   = sum_c (x_r[i][c] - m_r[c]) (x_r[j][c] - m_r[c]),   x_r[i][c] = x[r * rep_stride + i * ld + c],  c < k,
+ * m_r[c] = the f32 mean of column c over the n rows, summed in a fixed order.  One workgroup per (representation, split) holds all n rows of a
+ * column stage in LDS: every element of x is fetched once, the means are taken and subtracted there, and the upper triangle of 32 x 32 tiles is
+ * multiplied on v_mfma_f32_32x32x2_f32 (exact f32 products, f32 accumulation within a split).  The splits' partial tiles are added in double, in
+ * split order.  Rows >= n and columns >= k contribute exactly zero; nothing outside the n x k views is read.  A NaN in x_r gives NaN in g[r] and
+ * nowhere else.  Both HSIC estimators below are exactly invariant to the shift m.
+ *
+ * mfvit_hsic_accumulate: acc_ab[i][j] += HSIC(ga[i], gb[j]) (double [ra][rb]); acc_aa[i] += HSIC(ga[i], ga[i]); acc_bb[j] += HSIC(gb[j], gb[j]).
+ * unbiased = 1 (n >= 4), Kt / Lt = K / L with zeroed diagonals (Song et al. 2012):
+ *   HSIC1 = [ sum(Kt o Lt) + (1'Kt1)(1'Lt1) / ((n-1)(n-2)) - 2 / (n-2) * sum_a rowsum(Kt)_a rowsum(Lt)_a ] / (n (n-3))
+ * unbiased = 0 (n >= 2):  HSIC0 = tr(K H L H) / (n-1)^2 from the same three sums with the diagonals kept.
+ * ga, gb: symmetric double [r][n][n] (the output of mfvit_gram_centered); gb == ga is allowed.  All arithmetic in double, one workgroup per output
+ * element, fixed order.
+ *
+ * Domain - anything else is MFVIT_EINVAL before any HIP call: every pointer non-NULL; 1 <= reps, ra, rb <= 64; 2 <= n <= MFVIT_GRAM_MAX_N
+ * (n >= 4 with unbiased); k >= 1 (any k: the tail is masked); ld >= k; ld and rep_stride multiples of 4 and x 16-byte aligned; work_bytes >=
+ * mfvit_gram_work_bytes(reps, n, k). */
+#define MFVIT_GRAM_MAX_N 256
+int mfvit_gram_plan(int n, int64_t k, int32_t plan[4]);
+size_t mfvit_gram_work_bytes(int reps, int n, int64_t k);
+int mfvit_gram_centered(const float* x, int64_t rep_stride, int64_t ld, int reps, int n, int64_t k, double* g, void* work, size_t work_bytes,
+                        mfvit_stream_t stream);
+int mfvit_hsic_accumulate(const double* ga, int ra, const double* gb, int rb, int n, int unbiased, double* acc_ab, double* acc_aa, double* acc_bb,
+                          mfvit_stream_t stream);
 
 /* The perturbation test for patch-relevance maps (Chefer, Gur & Wolf 2021 section 4, positive / negative perturbation; Petsiuk et al. 2018,
  * deletion / insertion; mfvit.perturb drives it): rank the patches, mask them a fraction at a time, score the model's output again.  Three

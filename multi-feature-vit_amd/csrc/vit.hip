@@ -495,6 +495,13 @@ size_t mfvit_vit_workspace_bytes_ex(const mfvit_vit_cfg* cfg, const mfvit_vit_dr
     if (d.tok || !d.save) return 0;                  // the image gradient exists in image mode, behind a forward that saved its activations
     return ws_layout(d).total_dimg;
 }
+int mfvit_vit_hidden_layout(const mfvit_vit_cfg* cfg, int64_t out[2]) {
+    Dims d;
+    if (!get_dims(cfg, d) || !out || !d.save) return MFVIT_EINVAL;
+    const WsLayout W = ws_layout(d);
+    out[0] = (int64_t)W.x0; out[1] = (int64_t)W.x_stride;
+    return MFVIT_OK;
+}
 
 int mfvit_vit_prepare_shadow(const mfvit_vit_cfg* cfg, const float* params, void* shadow, mfvit_stream_t stream) {
     Dims d;

@@ -82,6 +82,7 @@ SIGNATURES = {
     "mfvit_vit_backward_drop": (I, [POINTER(VitCfg), POINTER(VitDrop), P, P, P, P, P, I, I, P]),
     "mfvit_vit_workspace_bytes_ex": (c_size_t, [POINTER(VitCfg), POINTER(VitDrop), I]),
     "mfvit_vit_backward_ex": (I, [POINTER(VitCfg), POINTER(VitDrop), P, P, P, P, P, P, I, I, P]),
+    "mfvit_vit_hidden_layout": (I, [POINTER(VitCfg), POINTER(c_int64)]),
     "mfvit_vit_attn_scratch_bytes": (c_size_t, [POINTER(VitCfg), POINTER(VitAttnReq)]),
     "mfvit_vit_forward_attn": (I, [POINTER(VitCfg), POINTER(VitAttnReq), P, P, P, P, P, P]),
     "mfvit_vit_rel_scratch_bytes": (c_size_t, [POINTER(VitCfg), POINTER(VitRelReq)]),
@@ -161,6 +162,10 @@ SIGNATURES = {
     "mfvit_curve_counts": (I, [P, L, L, P, I, I, I, P, c_size_t, P, P, P, P, P, P, P]),
     "mfvit_boot_points": (I, [P, L, L, P, I, I, I, c_uint64, L, L, I, P, I, P, c_size_t, P, P, P, P, P]),
     "mfvit_calib_sums": (I, [P, L, L, P, I, I, I, P, I, I, P, P, P, P, P, P]),
+    "mfvit_gram_plan": (I, [I, L, POINTER(ctypes.c_int32)]),
+    "mfvit_gram_work_bytes": (c_size_t, [I, I, L]),
+    "mfvit_gram_centered": (I, [P, L, L, I, I, L, P, P, c_size_t, P]),
+    "mfvit_hsic_accumulate": (I, [P, I, P, I, I, I, P, P, P, P]),
     "mfvit_patch_rank": (I, [P, L, P, I, I, P]),
     "mfvit_patch_perturb": (I, [P, P, P, P, P, I, I, I, I, I, P]),
     "mfvit_perturb_score": (I, [P, L, P, I, I, I, P, P, P, P]),

@@ -792,3 +792,53 @@ class VisionTransformerMoCo(nn.Module):
         (B, T, T) f32 tensor per block in block order; target as in attention_relevance."""
         blocks = self._attn_blocks(blocks)
         return self._relevance(x, target, blocks, False)[0]
+
+    # ------------------------------------------------------------------ hidden states (include/mfvit.h, mfvit_vit_hidden_layout)
+    # The f32 residual stream of every layer, as an evaluation forward with saved activations leaves it in its workspace (the pattern of
+    # _rel_forward: no dropout site, no seed, no_grad, the feature cache and the module's state left as they were).
+    def _hidden_view(self, cfg, ws):
+        """(depth + 1, B, T, D) f32 view INTO the workspace of a saved-activations forward: valid until the workspace is released."""
+        out = (ctypes.c_int64 * 2)()
+        check(lib().mfvit_vit_hidden_layout(cfg, out), "mfvit_vit_hidden_layout")
+        B, T, D = cfg.batch, self.num_tokens, self.embed_dim
+        f = ws[out[0]:out[0] + self.depth * out[1] + B * T * D * 4].view(torch.float32)
+        return f.as_strided((self.depth + 1, B, T, D), (out[1] // 4, T * D, D, 1))
+
+    def hidden_states(self, x):
+        """(B,3,H,W) -> (depth + 1, B, T, D) f32: hidden state 0 is cls + patch embedding + pos_embed (the input of block 0), hidden state l
+        the output of block l - 1, before the final norm.  f32 in every precision.  A copy: the workspace goes back to the pool."""
+        cfg, ws, _ = self._rel_forward(x)
+        try:
+            return self._hidden_view(cfg, ws).clone()
+        finally:
+            self._release_ws(ws)
+
+    def _final_norm(self, h):
+        """The encoder's final LayerNorm of f32 rows (.., D), through mfvit_layernorm_fwd."""
+        rows = h.reshape(-1, self.embed_dim).contiguous()
+        with torch.no_grad():
+            y, _, _ = ops.layernorm_fwd(rows, self.norm.weight.detach(), self.norm.bias.detach(), 1e-6)
+        return y.view(h.shape)
+
+    def get_intermediate_layers(self, x, n=1, reshape=False, return_prefix_tokens=False, norm=False):
+        """timm's get_intermediate_layers: a tuple of the (B, T-1, D) patch tokens at the output of the last `n` blocks (int) or of the
+        blocks in `n` (a sequence of indices, negative ones counted from the end), in block order.  reshape: (B, D, gh, gw) each;
+        return_prefix_tokens: (patches, cls) pairs with cls (B, 1, D); norm: the encoder's final LayerNorm applied to every output."""
+        if isinstance(n, bool):
+            raise ValueError(f"n must be an int or a sequence of block indices, got {n!r}")
+        if isinstance(n, int):
+            if not 1 <= n <= self.depth:
+                raise ValueError(f"n = {n} out of range for depth {self.depth}")
+            blocks = list(range(self.depth - n, self.depth))
+        else:
+            blocks = self._attn_blocks(n)
+        hs = self.hidden_states(x)
+        outs = [hs[l + 1] for l in blocks]
+        if norm:
+            outs = [self._final_norm(o) for o in outs]
+        prefix = [o[:, :1] for o in outs]
+        outs = [o[:, 1:] for o in outs]
+        if reshape:
+            gh, gw = self.img_size[0] // 16, self.img_size[1] // 16
+            outs = [o.reshape(o.shape[0], gh, gw, -1).permute(0, 3, 1, 2).contiguous() for o in outs]
+        return tuple(zip(outs, prefix)) if return_prefix_tokens else tuple(outs)

@@ -353,6 +353,23 @@ class Fus_CrossViT(nn.Module):
                 v._feat_cache, v._grad_arena_lent = cache, lent
         return (meter, logits) if return_logits else meter
 
+    # ------------------------------------------------------------------ representation similarity (mfvit.similarity; include/mfvit.h, mfvit_gram_centered ..)
+    def stream_similarity(self, vit_cxr, vit_enh, batches, tokens="all", unbiased=True):
+        """Layer-wise minibatch linear CKA (Nguyen, Raghu & Kornblith 2021) of the two encoders' hidden states: {'cxr_enh': (Lc + 1, Le + 1),
+        'cxr_cxr': (Lc + 1, Lc + 1), 'enh_enh': (Le + 1, Le + 1)} float64 arrays, entry [i, j] between hidden state i of the first and j of the
+        second (VisionTransformerMoCo.hidden_states' numbering).  batches yields (img_cxr, img_enh) pairs of the same examples; tokens and
+        unbiased as mfvit.similarity.cka.  One evaluation forward per encoder and minibatch, under no_grad; training flags, feature caches and
+        p.grad stay as they were.  The exchange layers take no part: the similarity is between the backbones."""
+        from mfvit import similarity
+
+        def pairs():
+            for b in batches:
+                if torch.is_tensor(b) or len(b) != 2:
+                    raise ValueError("stream_similarity takes (img_cxr, img_enh) pairs")
+                yield b
+        ce, cc, ee = similarity.layerwise([vit_cxr, vit_enh], pairs(), [(0, 1), (0, 0), (1, 1)], tokens, unbiased)
+        return {"cxr_enh": ce, "cxr_cxr": cc, "enh_enh": ee}
+
     # ------------------------------------------------------------------ gradient attribution (mfvit.attribution; include/mfvit.h, mfvit_attr_inputs ..)
     # The three methods of mfvit.attribution for the score of attention_relevance, y_t = (fused + x_cxr + x_enh)[t] (MAIN_CA:868), along the JOINT path
     # of both images: ((res_cxr, res_enh), stream_share).  baselines = (baseline_cxr, baseline_enh), each as integrated_gradients takes it;
