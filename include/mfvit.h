@@ -167,6 +167,13 @@ int mfvit_vit_backward_ex(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, 
  * precision.  MFVIT_EINVAL: invalid cfg, out NULL or save_for_backward == 0. */
 int mfvit_vit_hidden_layout(const mfvit_vit_cfg* cfg, int64_t out[2]);
 
+/* Attention state of the image encoder (host only, additive in ABI 5).  Where mfvit_vit_forward with save_for_backward = 1 leaves what
+ * mfvit_attention_stats reads: block l's qkv tensor [batch][tokens][3][heads][head_dim] at workspace + out[0] + l * out[2] bytes, in the
+ * storage format of tag out[3] (= mfvit_attention_qkv_dtype(cfg->dtype, tokens, head_dim)), and its natural-log log-sum-exp, f32
+ * [batch][heads][tokens], at workspace + out[1] + l * out[2] bytes.  MFVIT_EINVAL: invalid cfg, out NULL, save_for_backward == 0 or
+ * token-input mode. */
+int mfvit_vit_attn_layout(const mfvit_vit_cfg* cfg, int64_t out[4]);
+
 /* Attention maps of the image encoder (additive in ABI 5): an evaluation forward (no dropout site active) that writes the same `features` as
  * mfvit_vit_forward, on a workspace of mfvit_vit_workspace_bytes(cfg) bytes, plus the softmax probabilities of the requested blocks:
  *   P[b][h][i][j] = exp(scale q_i.k_j - lse_i),  scale = head_dim^-1/2,
@@ -397,6 +404,31 @@ int mfvit_attention_qkv_dtype(int dtype, int T, int head_dim);
 int mfvit_attention_fwd(int dtype, const void* qkv, void* out, float* lse, int B, int T, int H, int head_dim, mfvit_stream_t stream);
 int mfvit_attention_bwd(int dtype, const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* dbias_qkv,
                         int B, int T, int H, int head_dim, mfvit_stream_t stream);
+/* Per-head statistics of the attention probabilities (additive in ABI 5; mfvit.attnstats drives it): mean attention distance (Dosovitskiy et
+ * al. 2021, Fig. 11; Raghu et al. 2021) and attention entropy of every head of `nblk` blocks, from each block's qkv tensor (storage tag
+ * qkv_dtype: MFVIT_F32 / BF16 / F16 / BF16X3 / X3F16) and log-sum-exp as mfvit_attention_fwd leaves them.  The T x T maps never reach memory.
+ *   P_ij = exp(scale q_i.k_j - lse_i), T = 1 + gh * gw tokens: cls, then the patches row by row; patch token i >= 1 at (y_i, x_i) =
+ *   divmod(i - 1, gw);  d_ij = patch * sqrtf((float)((y_i-y_j)^2 + (x_i-x_j)^2)), `patch` the patch edge in pixels.
+ * stats [nblk][B][H][MFVIT_ATTN_NSTAT], double:
+ *   0 distance         (1/(T-1)) sum_{i>=1} sum_{j>=1} P_ij d_ij        (cls row and column dropped, not renormalised)
+ *   1 distance_renorm  (1/(T-1)) sum_{i>=1} (sum_{j>=1} P_ij d_ij) / (sum_{j>=1} P_ij)
+ *   2 entropy          (1/T) sum_i H(P_i),  H(P_i) = -sum_j P_ij ln P_ij  (nats; all rows, all columns)
+ *   3 cls_entropy      H(P_0)
+ *   4 cls_mass         (1/(T-1)) sum_{i>=1} P_i0                        (the mass the patches send to cls)
+ *   5 self_mass        (1/T) sum_i P_ii
+ * With T = 2 the two distances are 0.  ln P is the exponent the kernel holds (times ln 2), never a logarithm.
+ * Block l's qkv / lse lie l * qkv_stride / l * lse_stride BYTES behind `qkv` / `lse` (mfvit_vit_attn_layout gives the encoder workspace's).
+ * Sums: f32 along a row (a lane over its key tiles, the 32 lanes of a half, the four waves, in that order), double from the rows upward (rows
+ * of a 32-query tile in order, tiles in order, then the factor).  No atomics; a (block, image, head) result depends on that head's data only
+ * and has the same bits whatever else the call covers.  Two launches (the statistics of all blocks; the tile partials), asynchronous on `stream`.
+ * work: mfvit_attention_stats_work_bytes(nblk, B, T, H) bytes (0 for arguments outside the domain), 8-byte aligned.
+ * MFVIT_EINVAL before any HIP call: a NULL pointer; nblk, B, H, gh or gw < 1; T != 1 + gh * gw; a stride that is no multiple of 16; qkv not
+ * 16-byte aligned; work_bytes too small; a grid (nblk * B * H * ceil(T / 32)) above 2^31 - 1; an unknown tag.  MFVIT_ENOSYS: head_dim other than
+ * 32 / 64 / 96. */
+#define MFVIT_ATTN_NSTAT 6
+size_t mfvit_attention_stats_work_bytes(int nblk, int B, int T, int H);
+int mfvit_attention_stats(int qkv_dtype, const void* qkv, const float* lse, int64_t qkv_stride, int64_t lse_stride, int nblk, int B, int T, int H,
+                          int head_dim, int gh, int gw, float patch, double* stats, void* work, size_t work_bytes, mfvit_stream_t stream);
 /* The same with dropout on the attention probabilities (TransFuser GPT, fuseattention.py:52 `att = self.attn_drop(att)`), streaming kernels
  * (16-bit dtypes; head_dim 32 / 64 / 96; B * H * T * T < 2^32).  The keep mask is a counter-based hash of (seed, site, element index
  * ((b * H + h) * T + i) * T + j) >= p * 2^32, regenerated by the backward - nothing is stored; kept values are scaled by 1 / (1 - p).

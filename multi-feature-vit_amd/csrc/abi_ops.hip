@@ -176,6 +176,12 @@ int mfvit_attention_fwd(int dtype, const void* qkv, void* out, float* lse, int B
     return attn_fwd(dtype, qkv, out, lse, B, T, H, head_dim, (hipStream_t)stream);
 }
 int mfvit_attention_qkv_dtype(int dtype, int T, int head_dim) { return attn_qkv_dtype(dtype, T, head_dim); }
+size_t mfvit_attention_stats_work_bytes(int nblk, int B, int T, int H) { return attn_stats_work_bytes(nblk, B, T, H); }
+int mfvit_attention_stats(int qkv_dtype, const void* qkv, const float* lse, int64_t qkv_stride, int64_t lse_stride, int nblk, int B, int T, int H,
+                          int head_dim, int gh, int gw, float patch, double* stats, void* work, size_t work_bytes, mfvit_stream_t stream) {
+    return attn_stats(qkv_dtype, qkv, lse, (long)qkv_stride, (long)lse_stride, nblk, B, T, H, head_dim, gh, gw, patch, stats, work, work_bytes,
+                      (hipStream_t)stream);
+}
 int mfvit_attention_bwd(int dtype, const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* dbias_qkv,
                         int B, int T, int H, int head_dim, mfvit_stream_t stream) {
     if (!qkv || !out || !dout || !lse || !dqkv || B <= 0 || T <= 0 || H <= 0) return MFVIT_EINVAL;

@@ -347,7 +347,202 @@ int probs_by_hd(const void* qkv, const float* lse, int B, int Tn, int H, int HD,
     return MFVIT_ENOSYS;
 }
 
+// Per-head statistics of the probabilities (attn_stats in kernels.h has the definitions): attn_probs_kernel<T, NB, false>'s work split and
+// its load / score / exp2 sequence, so P has the bits of the per-head maps, but nothing is stored: a lane keeps five f32 sums for each of its
+// 16 result rows.  Order of every sum: the lane over its key tiles, ascending -> butterfly over the 32 lanes of a half -> the four waves in
+// order (LDS) -> one thread per row (the quotient of distance_renorm) -> double from here on: the rows of the tile in order -> (finish kernel)
+// the tiles in order, then the 1 / (T - 1) or 1 / T factor.  Grid nblk * B * H * nqt; block l's tensors lie l * stride bytes behind block 0's.
+// part [nblk][B][H][nqt][6] double.  LDS: 4 x 5 x 32 floats + 6 x 32 doubles = 4 KB, and the distance table, (2 gh - 1)(2 gw - 1) floats.
+constexpr int AS_NSTAT = 6, AS_NSUM = 5;
+// The distances come from an LDS table over (dy, dx), tab[(dy + gh - 1) * (2 gw - 1) + dx + gw - 1] = patch * sqrtf((float)(dy^2 + dx^2)), filled once per
+// workgroup: a key's share of the index once per key tile, a row's once per workgroup, one subtraction and one LDS read per element.  TAB = false (a
+// grid whose table does not fit): the same expression per element.
+constexpr size_t AS_TAB_MAX = 60 * 1024;       // (with the 4 KB above: inside 64 KB)
+template <typename T, int NB, bool TAB>
+__global__ __launch_bounds__(256) void attn_stats_kernel(const char* __restrict__ qkv0, const char* __restrict__ lse0, long qstride, long lstride,
+                                                         double* __restrict__ part, int Tn, int B, int H, int nqt, int gh, int gw, float patch,
+                                                         float c) {
+    typedef typename AmStor<T>::E E;
+    constexpr int HD = 32 * NB, EP = AmStor<T>::EP;
+    extern __shared__ float as_tab[];
+    __shared__ float wsum[AM_WAVES][AS_NSUM][32];
+    __shared__ double rowv[AS_NSTAT][32];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5;
+    int bid = blockIdx.x;
+    const int qt = bid % nqt;
+    bid /= nqt;
+    const int h = bid % H;
+    bid /= H;
+    const int b = bid % B, l = bid / B;
+    const int q0 = qt * 32;
+    const long hs = (long)H * HD * EP, rs = 3 * hs;                 // storage elements of one of q / k / v of a token, and of all three
+    const E* base = (const E*)(qkv0 + (long)l * qstride) + (long)b * Tn * rs + (long)h * HD * EP;
+    const float* lrow = (const float*)(lse0 + (long)l * lstride) + ((long)b * H + h) * Tn;
+    const int qrow = min(q0 + (lane & 31), Tn - 1);                  // (rows past the end: a valid row is read, its sums are not counted)
+    const int nkt = (Tn + 31) / 32;
+    const int W = 2 * gw - 1;
+    if constexpr (TAB) {
+        for (int i = threadIdx.x; i < (2 * gh - 1) * W; i += blockDim.x) {
+            const int dy = i / W - (gh - 1), dx = i - (i / W) * W - (gw - 1);
+            as_tab[i] = patch * sqrtf((float)(dy * dy + dx * dx));
+        }
+        __syncthreads();
+    }
+    // once per workgroup: the q fragment, -lse of the lane's 16 result rows in log2 units, and the rows' grid coordinates (the cls row and rows
+    // past the end take a patch's: their distance sums are not counted)
+    float qf[16 * NB], nl[16];
+    int qy[TAB ? 1 : 16], qx[16];                                    // TAB: qx = the row's share of the table index
+    am_load_frag<T, NB>(base + (long)qrow * rs, half, qf);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int q = min(q0 + am_acc_row(r, lane), Tn - 1);
+        nl[r] = -lrow[q] * 1.4426950408889634f;
+        const int qp = max(q, 1) - 1, y = qp / gw, x = qp - y * gw;
+        if constexpr (TAB) qx[r] = (y + gh - 1) * W + x + gw - 1;
+        else { qy[r] = y; qx[r] = x; }
+    }
+    float sd[16], sp[16], se[16], s0[16], sq[16];                    // sum P d, sum P (patch keys); sum P (-log2 P); P at key 0; P at key == query
+#pragma unroll
+    for (int r = 0; r < 16; ++r) sd[r] = sp[r] = se[r] = s0[r] = sq[r] = 0.f;
+    for (int kt = wave; kt < nkt; kt += AM_WAVES) {
+        const int key = kt * 32 + (lane & 31);
+        float kf[16 * NB];
+        am_load_frag<T, NB>(base + (long)min(key, Tn - 1) * rs + hs, half, kf);
+        const f32x16 s = am_scores<NB>(qf, kf);
+        const int kp = max(min(key, Tn - 1), 1) - 1, ky = kp / gw, kx = kp - ky * gw, kidx = ky * W + kx;
+        auto dist = [&](int r) __attribute__((always_inline)) {
+            if constexpr (TAB) return as_tab[qx[r] - kidx];
+            else {
+                const int dy = qy[r] - ky, dx = qx[r] - kx;
+                return patch * sqrtf((float)(dy * dy + dx * dx));
+            }
+        };
+        if (kt == 0 || kt == qt || kt == nkt - 1) {                  // (uniform) the tile with key 0, the diagonal tile, the tile with keys past T
+            const bool kin = key < Tn, kpatch = kin && key >= 1;     // keys at or past T contribute nothing
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float e = fmaf(s[r], c, nl[r]);                // log2 P
+                const float p = exp2f(e);
+                const float pk = kin ? p : 0.f, pp = kpatch ? p : 0.f;
+                sd[r] += pp * dist(r);
+                sp[r] += pp;
+                se[r] += pk * (-e);
+                s0[r] += key == 0 ? p : 0.f;
+                sq[r] += key == q0 + am_acc_row(r, lane) ? pk : 0.f;
+            }
+        } else {                                                     // patch keys inside T, off the diagonal: three sums
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float e = fmaf(s[r], c, nl[r]);
+                const float p = exp2f(e);
+                sd[r] += p * dist(r);
+                sp[r] += p;
+                se[r] += p * (-e);
+            }
+        }
+    }
+    auto reduce = [&](float (&a)[16], int k) __attribute__((always_inline)) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            float v = a[r];
+#pragma unroll
+            for (int m = 1; m < 32; m <<= 1) v += __shfl_xor(v, m, 64);   // within the lane half: every lane ends with the same bits
+            if ((lane & 31) == 0) wsum[wave][k][am_acc_row(r, lane)] = v;
+        }
+    };
+    reduce(sd, 0); reduce(sp, 1); reduce(se, 2); reduce(s0, 3); reduce(sq, 4);
+    __syncthreads();
+    if (threadIdx.x < 32) {
+        const int t = threadIdx.x, q = q0 + t;
+        float v[AS_NSUM];
+#pragma unroll
+        for (int k = 0; k < AS_NSUM; ++k) {
+            v[k] = wsum[0][k][t];
+#pragma unroll
+            for (int w = 1; w < AM_WAVES; ++w) v[k] += wsum[w][k][t];
+        }
+        const bool in = q < Tn, prow = in && q >= 1;                 // rows at or past T are not counted; the distances and cls_mass skip the cls row
+        const double ent = (double)v[2] * 0.6931471805599453;        // nats
+        rowv[0][t] = prow ? (double)v[0] : 0.0;
+        rowv[1][t] = prow && v[1] > 0.f ? (double)v[0] / (double)v[1] : 0.0;
+        rowv[2][t] = in ? ent : 0.0;
+        rowv[3][t] = q == 0 ? ent : 0.0;
+        rowv[4][t] = prow ? (double)v[3] : 0.0;
+        rowv[5][t] = in ? (double)v[4] : 0.0;
+    }
+    __syncthreads();
+    if (threadIdx.x < AS_NSTAT) {
+        double acc = 0.0;
+        for (int i = 0; i < 32; ++i) acc += rowv[threadIdx.x][i];
+        part[(long)blockIdx.x * AS_NSTAT + threadIdx.x] = acc;
+    }
+}
+
+// stats [n][6] = the nqt tile partials of part [n][nqt][6] in tile order, over T - 1 (stats 0, 1, 4), 1 (stat 3) or T (stats 2, 5)
+__global__ __launch_bounds__(256) void attn_stats_finish_kernel(const double* __restrict__ part, double* __restrict__ stats, long n, int nqt, int Tn) {
+    const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
+    if (i >= n * AS_NSTAT) return;
+    const long g = i / AS_NSTAT;
+    const int k = (int)(i % AS_NSTAT);
+    const double* p = part + g * nqt * AS_NSTAT + k;
+    double acc = 0.0;
+    for (int t = 0; t < nqt; ++t) acc += p[(long)t * AS_NSTAT];
+    stats[i] = acc / (double)(k == 3 ? 1 : (k == 2 || k == 5) ? Tn : Tn - 1);
+}
+
+template <typename T, int NB>
+int launch_stats(const void* qkv, const float* lse, long qstride, long lstride, int nblk, int B, int Tn, int H, int gh, int gw, float patch,
+                 double* stats, double* part, hipStream_t st) {
+    const int nqt = (Tn + 31) / 32;
+    const long n = (long)nblk * B * H;
+    const float c = 1.0f / sqrtf((float)(32 * NB)) * 1.4426950408889634f;   // the forward kernels' scale * log2(e)
+    ProfScope ps(PROF_OTHER, 2.0 * n * (double)Tn * Tn * 32 * NB, (double)n * nqt * AS_NSTAT * 16 + (double)n * AS_NSTAT * 8, st);
+    const size_t tab = (size_t)(2 * (long)gh - 1) * (2 * (long)gw - 1) * 4;    // (gh * gw < 2^31: no overflow)
+    if (tab <= AS_TAB_MAX)
+        MFVIT_LAUNCH((attn_stats_kernel<T, NB, true>), dim3((unsigned)(n * nqt)), dim3(64 * AM_WAVES), tab, st, (const char*)qkv, (const char*)lse,
+                     qstride, lstride, part, Tn, B, H, nqt, gh, gw, patch, c);
+    else
+        MFVIT_LAUNCH((attn_stats_kernel<T, NB, false>), dim3((unsigned)(n * nqt)), dim3(64 * AM_WAVES), 0, st, (const char*)qkv, (const char*)lse,
+                     qstride, lstride, part, Tn, B, H, nqt, gh, gw, patch, c);
+    MFVIT_CHECK_LAUNCH();
+    MFVIT_LAUNCH(attn_stats_finish_kernel, dim3((unsigned)((n * AS_NSTAT + 255) / 256)), dim3(256), 0, st, (const double*)part, stats, n, nqt, Tn);
+    MFVIT_CHECK_LAUNCH();
+    return MFVIT_OK;
+}
+template <typename T>
+int stats_by_hd(const void* qkv, const float* lse, long qstride, long lstride, int nblk, int B, int Tn, int H, int HD, int gh, int gw, float patch,
+                double* stats, double* part, hipStream_t st) {
+    if (HD == 32) return launch_stats<T, 1>(qkv, lse, qstride, lstride, nblk, B, Tn, H, gh, gw, patch, stats, part, st);
+    if (HD == 64) return launch_stats<T, 2>(qkv, lse, qstride, lstride, nblk, B, Tn, H, gh, gw, patch, stats, part, st);
+    if (HD == 96) return launch_stats<T, 3>(qkv, lse, qstride, lstride, nblk, B, Tn, H, gh, gw, patch, stats, part, st);
+    return MFVIT_ENOSYS;
+}
+
 }  // namespace
+
+size_t attn_stats_work_bytes(int nblk, int B, int Tn, int H) {
+    if (nblk < 1 || B < 1 || Tn < 2 || H < 1) return 0;
+    const double n = (double)nblk * B * H * ((Tn + 31) / 32);
+    return n > 2147483647.0 ? 0 : (size_t)n * AS_NSTAT * sizeof(double);
+}
+
+int attn_stats(int qdt, const void* qkv, const float* lse, long qstride, long lstride, int nblk, int B, int Tn, int H, int HD, int gh, int gw,
+               float patch, double* stats, void* work, size_t work_bytes, hipStream_t st) {
+    if (!qkv || !lse || !stats || !work || nblk < 1 || B < 1 || H < 1 || gh < 1 || gw < 1) return MFVIT_EINVAL;
+    if ((long)gh * gw + 1 != (long)Tn || (qstride & 15) || (lstride & 15)) return MFVIT_EINVAL;
+    if (((size_t)qkv & 15) || ((size_t)lse & 3) || ((size_t)stats & 7) || ((size_t)work & 7)) return MFVIT_EINVAL;
+    const size_t need = attn_stats_work_bytes(nblk, B, Tn, H);      // (0: a grid above 2^31 - 1)
+    if (!need || work_bytes < need) return MFVIT_EINVAL;
+    double* part = (double*)work;
+    switch (qdt) {
+        case MFVIT_F32: return stats_by_hd<float>(qkv, lse, qstride, lstride, nblk, B, Tn, H, HD, gh, gw, patch, stats, part, st);
+        case MFVIT_BF16: return stats_by_hd<bf16>(qkv, lse, qstride, lstride, nblk, B, Tn, H, HD, gh, gw, patch, stats, part, st);
+        case MFVIT_F16: return stats_by_hd<f16>(qkv, lse, qstride, lstride, nblk, B, Tn, H, HD, gh, gw, patch, stats, part, st);
+        case MFVIT_BF16X3: return stats_by_hd<sbf16>(qkv, lse, qstride, lstride, nblk, B, Tn, H, HD, gh, gw, patch, stats, part, st);
+        case MFVIT_X3F16: return stats_by_hd<sf16>(qkv, lse, qstride, lstride, nblk, B, Tn, H, HD, gh, gw, patch, stats, part, st);
+        default: return MFVIT_EINVAL;
+    }
+}
 
 int attn_probs(int qdt, const void* qkv, const float* lse, int B, int Tn, int H, int HD, int fuse, int cls_only, float* out, float* sums,
                hipStream_t st) {

@@ -161,6 +161,14 @@ int attn_rollout(const float* maps, const float* sums, int depth, int B, int Tn,
 int attn_rel_map(int qdt, int ddt, const void* qkv, const float* lse, const void* dout, int B, int Tn, int H, int HD, float* map, const float* v,
                  float* part, int first, hipStream_t st);
 int attn_rel_update(float* v, const float* part, int B, int Tn, int first, float* out, hipStream_t st);
+// attention_maps.hip, per-head statistics of the same probabilities without the maps: stats [nblk][B][H][6] double = mean attention distance
+// (cls row and column dropped; not renormalised / renormalised per row), mean row entropy, cls-row entropy (nats), the patches' mass on cls, mean
+// diagonal mass - include/mfvit.h, mfvit_attention_stats.  Block l's qkv / lse lie l * qstride / l * lstride BYTES behind block 0's; all blocks in
+// one launch + a finish launch over the tile partials in `work` (attn_stats_work_bytes).  Tn = 1 + gh * gw, patch = the patch edge in pixels.
+// MFVIT_EINVAL before any HIP call for an argument outside the domain, MFVIT_ENOSYS for a head_dim other than 32 / 64 / 96.
+size_t attn_stats_work_bytes(int nblk, int B, int Tn, int H);
+int attn_stats(int qdt, const void* qkv, const float* lse, long qstride, long lstride, int nblk, int B, int Tn, int H, int HD, int gh, int gw,
+               float patch, double* stats, void* work, size_t work_bytes, hipStream_t st);
 
 // lora.hip: low-rank adapters.  One (Linear, adapter) pair of a batched launch; the table rides in the kernel arguments.
 //   merge: o0[n][k] (row stride ldo) = w[n][k] (row stride ldw) + scale * sum_j b[n][j] a[j][k]        (a: [r][K], b: [N][r], both dense)

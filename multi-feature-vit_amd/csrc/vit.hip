@@ -502,6 +502,14 @@ int mfvit_vit_hidden_layout(const mfvit_vit_cfg* cfg, int64_t out[2]) {
     out[0] = (int64_t)W.x0; out[1] = (int64_t)W.x_stride;
     return MFVIT_OK;
 }
+int mfvit_vit_attn_layout(const mfvit_vit_cfg* cfg, int64_t out[4]) {
+    Dims d;
+    if (!get_dims(cfg, d) || !out || !d.save || d.tok) return MFVIT_EINVAL;
+    const WsLayout W = ws_layout(d);
+    out[0] = (int64_t)(W.blk0 + W.qkv); out[1] = (int64_t)(W.blk0 + W.lse); out[2] = (int64_t)W.blk_stride;
+    out[3] = attn_qkv_dtype(d.dtype, d.T, d.HD);     // (image mode: no attention dropout in the cfg's own forward)
+    return MFVIT_OK;
+}
 
 int mfvit_vit_prepare_shadow(const mfvit_vit_cfg* cfg, const float* params, void* shadow, mfvit_stream_t stream) {
     Dims d;

@@ -83,6 +83,7 @@ SIGNATURES = {
     "mfvit_vit_workspace_bytes_ex": (c_size_t, [POINTER(VitCfg), POINTER(VitDrop), I]),
     "mfvit_vit_backward_ex": (I, [POINTER(VitCfg), POINTER(VitDrop), P, P, P, P, P, P, I, I, P]),
     "mfvit_vit_hidden_layout": (I, [POINTER(VitCfg), POINTER(c_int64)]),
+    "mfvit_vit_attn_layout": (I, [POINTER(VitCfg), POINTER(c_int64)]),
     "mfvit_vit_attn_scratch_bytes": (c_size_t, [POINTER(VitCfg), POINTER(VitAttnReq)]),
     "mfvit_vit_forward_attn": (I, [POINTER(VitCfg), POINTER(VitAttnReq), P, P, P, P, P, P]),
     "mfvit_vit_rel_scratch_bytes": (c_size_t, [POINTER(VitCfg), POINTER(VitRelReq)]),
@@ -108,6 +109,8 @@ SIGNATURES = {
     "mfvit_attention_fwd": (I, [I, P, P, P, I, I, I, I, P]),
     "mfvit_attention_bwd": (I, [I, P, P, P, P, P, P, I, I, I, I, P]),
     "mfvit_attention_qkv_dtype": (I, [I, I, I]),
+    "mfvit_attention_stats_work_bytes": (c_size_t, [I, I, I, I]),
+    "mfvit_attention_stats": (I, [I, P, P, L, L, I, I, I, I, I, I, I, F, P, P, c_size_t, P]),
     "mfvit_attention_drop_fwd": (I, [I, P, P, P, I, I, I, I, F, c_uint64, c_uint32, P]),
     "mfvit_attention_drop_bwd": (I, [I, P, P, P, P, P, I, I, I, I, F, c_uint64, c_uint32, P]),
     "mfvit_dropout_mask": (I, [F, c_uint64, c_uint32, L, P, P]),

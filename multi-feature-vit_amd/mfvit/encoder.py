@@ -813,6 +813,43 @@ class VisionTransformerMoCo(nn.Module):
         finally:
             self._release_ws(ws)
 
+    # ------------------------------------------------------------------ per-head attention statistics (include/mfvit.h, mfvit_attention_stats)
+    # The pattern of hidden_states: an evaluation forward with saved activations, then one statistics launch that reads every block's qkv and
+    # log-sum-exp in place from the workspace (mfvit_vit_attn_layout).  The per-head maps are never formed.
+    def _attention_stats(self, cfg, ws, blocks):
+        """(len(blocks), B, H, 6) float64 statistics of the (sorted) blocks from the workspace of a saved-activations forward."""
+        from . import attnstats
+        out = (ctypes.c_int64 * 4)()
+        check(lib().mfvit_vit_attn_layout(cfg, out), "mfvit_vit_attn_layout")
+        # one launch over the evenly spaced blocks lo, lo + step, .. that hold every requested one
+        lo, step = blocks[0], 1
+        if len(blocks) > 1:
+            step = math.gcd(*(b - lo for b in blocks[1:]))
+        span = list(range(lo, blocks[-1] + 1, step))
+        gh, gw = self.img_size[0] // 16, self.img_size[1] // 16
+        st = attnstats.attention_stats(ws[out[0] + lo * out[2]:], ws[out[1] + lo * out[2]:].view(torch.float32), int(out[3]), cfg.batch,
+                                       self.num_tokens, self.num_heads, self.embed_dim // self.num_heads, (gh, gw), 16.0, len(span),
+                                       (step * out[2], step * out[2]))
+        if len(span) != len(blocks):
+            st = st[torch.tensor([span.index(b) for b in blocks], device=st.device)]
+        return st
+
+    def attention_stats(self, x, blocks=None):
+        """(B,3,H,W) -> {name: (len(blocks), B, heads) float64 cuda tensor} for the names of mfvit.attnstats.STATS: mean attention distance in
+        pixels (cls row and column dropped; 'distance' as the public ViT notebook computes it, 'distance_renorm' with every row renormalised
+        over the patches), mean row entropy and the cls row's entropy in nats, the mass the patches send to cls, and the mean diagonal mass -
+        per image and head, of the blocks in `blocks` (indices as in get_attention_maps; default: all) in block order.  One evaluation
+        forward (no dropout site, whatever self.training says) under no_grad; the feature cache and the module's state stay as they were."""
+        from . import attnstats
+        blocks = self._attn_blocks(blocks)
+        cfg, ws, _ = self._rel_forward(x)
+        try:
+            with torch.no_grad():
+                st = self._attention_stats(cfg, ws, blocks)
+        finally:
+            self._release_ws(ws)
+        return {name: st[..., i].contiguous() for i, name in enumerate(attnstats.STATS)}
+
     def _final_norm(self, h):
         """The encoder's final LayerNorm of f32 rows (.., D), through mfvit_layernorm_fwd."""
         rows = h.reshape(-1, self.embed_dim).contiguous()

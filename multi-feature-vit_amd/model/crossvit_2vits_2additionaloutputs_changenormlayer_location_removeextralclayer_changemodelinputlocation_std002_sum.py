@@ -370,6 +370,34 @@ class Fus_CrossViT(nn.Module):
         ce, cc, ee = similarity.layerwise([vit_cxr, vit_enh], pairs(), [(0, 1), (0, 0), (1, 1)], tokens, unbiased)
         return {"cxr_enh": ce, "cxr_cxr": cc, "enh_enh": ee}
 
+    # ------------------------------------------------------------------ per-head attention statistics (mfvit.attnstats; include/mfvit.h, mfvit_attention_stats)
+    def attention_stats(self, vit_cxr, vit_enh, batches):
+        """Mean attention distance, entropy, cls mass and self mass of every head of every block of the two encoders (mfvit.attnstats.STATS;
+        Dosovitskiy et al. 2021, Fig. 11): {'cxr': {name: (Lc, H) float64 array}, 'enh': {name: (Le, H)}}, per-image means over all batches.
+        batches yields (img_cxr, img_enh) pairs.  One evaluation forward per encoder and batch, under no_grad, the statistics accumulated on
+        the device; training flags, feature caches and p.grad stay as they were.  The exchange layers take no part."""
+        from mfvit import attnstats
+        vits = (vit_cxr, vit_enh)
+        for vit, bound, name in ((vit_cxr, self.vit_features_cxr, "vit_cxr"), (vit_enh, self.vit_features_enh, "vit_enh")):
+            if getattr(vit, "features3D", None) != bound:
+                raise ValueError(f"{name} is not the encoder this Fus_CrossViT was built with: its heads would not be the predicting model's")
+        meters = [attnstats.AttentionStatsMeter(v.depth, v.num_heads) for v in vits]
+        for b in batches:
+            if torch.is_tensor(b) or len(b) != 2:
+                raise ValueError("attention_stats takes (img_cxr, img_enh) pairs")
+            if int(b[0].shape[0]) != int(b[1].shape[0]):
+                raise ValueError("img_cxr and img_enh must hold the same number of images")
+            for vit, x, meter in zip(vits, b, meters):
+                cfg, ws, _ = vit._rel_forward(x)
+                try:
+                    with torch.no_grad():
+                        meter.update(vit._attention_stats(cfg, ws, list(range(vit.depth))))
+                finally:
+                    vit._release_ws(ws)
+        if not meters[0].batches:
+            raise ValueError("no batch")
+        return {"cxr": meters[0].result(), "enh": meters[1].result()}
+
     # ------------------------------------------------------------------ gradient attribution (mfvit.attribution; include/mfvit.h, mfvit_attr_inputs ..)
     # The three methods of mfvit.attribution for the score of attention_relevance, y_t = (fused + x_cxr + x_enh)[t] (MAIN_CA:868), along the JOINT path
     # of both images: ((res_cxr, res_enh), stream_share).  baselines = (baseline_cxr, baseline_enh), each as integrated_gradients takes it;
