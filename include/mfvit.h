@@ -314,7 +314,12 @@ int mfvit_vit_lora_grad(const mfvit_vit_cfg* cfg, const mfvit_lora_req* req, con
  *   attn.proj.weight, attn.proj.bias, ln2.weight, ln2.bias, mlp.0.weight, mlp.0.bias, mlp.2.weight, mlp.2.bias,
  * then ln_f.weight, ln_f.bias.  (mfvit_vit_param_layout: [0] = [1] = 0 pos_emb, [2] = [3] = first block, no patch embedding.)
  * forward : out = ln_f(blocks(tokens + pos_emb))   (B, tokens, dim) f32            (fuseattention.py:186-192; dropouts are identity)
- * backward: dtokens (B, tokens, dim) f32 = d loss / d tokens; dparams accumulated (pos_emb gradient = sum over the batch). */
+ * backward: dtokens (B, tokens, dim) f32 = d loss / d tokens; dparams accumulated (pos_emb gradient = sum over the batch).
+ * Domain (tests/test_gpt_edges_*.py): tokens >= 1; dim 384 or 768; head_dim 32 / 64 / 96; mlp_dim % 128 == 0; act 0 or 1; every dtype, except
+ * that MFVIT_F32 has no head_dim 96, no dropout rate and - its exact attention kernels hold a head's K and V in LDS, the backward two [tokens]
+ * vectors more - only 8 tokens head_dim + 8 tokens <= 160 KiB: tokens <= 315 at head_dim 64, <= 620 at head_dim 32.  The same limit holds for
+ * T = 1 + patches in image mode.  Outside the domain: MFVIT_EINVAL before any HIP call from every entry point that takes the cfg, 0 from the
+ * size queries.  Also MFVIT_EINVAL before any HIP call: a NULL pointer, save_for_backward == 0 in the backward, an image-mode cfg. */
 int mfvit_gpt_forward(const mfvit_vit_cfg* cfg, const float* params, const void* shadow, const float* tokens, void* workspace, float* out,
                       mfvit_stream_t stream);
 int mfvit_gpt_backward(const mfvit_vit_cfg* cfg, const float* params, const void* shadow, void* workspace, const float* dout, float* dparams,

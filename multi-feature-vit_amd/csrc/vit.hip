@@ -81,6 +81,10 @@ bool get_dims(const mfvit_vit_cfg* c, Dims& d) {
     if (d.HD != 32 && d.HD != 64 && d.HD != 96) return false;
     if (d.HD == 96 && c->dtype == MFVIT_F32) return false;      // head_dim 96 runs on the streaming MFMA kernels (16-bit types, split bf16)
     if (c->dtype == MFVIT_BF16X3 && d.HD % 32) return false;    // a head's row piece is whole [hi x 32 | lo x 32] groups
+    // MFVIT_F32 runs the exact attention kernels (attention.hip), which hold a head's K and V in LDS: the backward's image, K / V plus two [T]
+    // vectors, is the larger one and must fit 160 KiB (head_dim 64: T <= 315, head_dim 32: T <= 620).  Refused here, with every other limit,
+    // and not by the attention launcher in the middle of block 0.
+    if (c->dtype == MFVIT_F32 && 2 * (size_t)d.T * d.HD * 4 + 2 * (size_t)d.T * 4 > 160 * 1024) return false;
     // MFVIT_UNFUSED_ROWS=1 forces the unfused path at dim 384 too (tests: the same encoder through both paths; tools: A/B at small M)
     // (read on every call, not cached: the workspace layout depends on it, and a test flips it between two encoders of one process)
     const char* ue = getenv("MFVIT_UNFUSED_ROWS");

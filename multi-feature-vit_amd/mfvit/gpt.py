@@ -88,10 +88,11 @@ class GptEngine:
         if T != self.tokens or D != self.dim:
             raise _lib.MfvitError(f"expected (B, {self.tokens}, {self.dim}) tokens, got {tuple(tokens.shape)} (pos_emb is length-bound)")
         cfg = self.cfg(B, save, drop)
-        flat = self._ensure(cfg)
         nbytes = lib().mfvit_vit_workspace_bytes(cfg)
-        if nbytes == 0:
-            raise _lib.MfvitError("invalid GPT configuration for the HIP encoder (dim 384, head_dim in {32, 64, 96}, mlp_dim % 128 == 0)")
+        if nbytes == 0:   # (asked before the arena is laid out: a refused cfg has no parameter count either)
+            raise _lib.MfvitError("invalid GPT configuration for the HIP encoder (dim 384 or 768, head_dim in {32, 64, 96}, mlp_dim % 128 == 0; "
+                                  "'fp32': head_dim 32 or 64 and at most 620 / 315 tokens - its attention keeps a head's K and V in LDS)")
+        flat = self._ensure(cfg)
         pool = self._pool.setdefault(nbytes, [])
         ws = pool.pop() if pool else torch.empty(nbytes, device=tokens.device, dtype=torch.uint8)
         out = torch.empty(B, T, D, device=tokens.device, dtype=torch.float32)

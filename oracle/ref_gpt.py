@@ -70,20 +70,22 @@ def self_attention(p, pre, x, n_head, drop=None, layer=0, pdrops=(0.0, 0.0, 0.0)
     return _drop(F.linear(y, p[pre + "proj.weight"], p[pre + "proj.bias"]), drop, ("proj", layer), pdrops[2])   # :56-57 resid_drop
 
 
-def gpt_forward(p, cxr, enh, n_head=4, pos_embed=True, prefix="", drop=None, pdrops=(0.0, 0.0, 0.0)):
-    """drop: {"embd": (B,T,C), ("attn", l): (B,H,T,T), ("proj", l): (B,T,C), ("mlp", l): (B,T,C)} bool keep masks; pdrops = (embd, attn, resid)."""
+def gpt_forward(p, cxr, enh, n_head=4, pos_embed=True, prefix="", drop=None, pdrops=(0.0, 0.0, 0.0), act="relu"):
+    """act: "relu" (the reference, fuseattention.py:69) or "gelu" (erf-GELU: the C ABI's act = 0 in token-input mode).
+    drop: {"embd": (B,T,C), ("attn", l): (B,H,T,T), ("proj", l): (B,T,C), ("mlp", l): (B,T,C)} bool keep masks; pdrops = (embd, attn, resid)."""
     ftrs = cxr.shape[1]
     x = torch.cat([cxr, enh], dim=1)                                                                          # :184
     if pos_embed:
         x = p[prefix + "pos_emb"] + x                                                                         # :187
     x = _drop(x, drop, "embd", pdrops[0])                                                                     # :187 self.drop(...) (both branches of :186-189)
     C = x.shape[-1]
+    fn = {"relu": F.relu, "gelu": F.gelu}[act]
     i = 0
     while f"{prefix}blocks.{i}.ln1.weight" in p:
         b = f"{prefix}blocks.{i}."
         x = x + self_attention(p, b + "attn.", F.layer_norm(x, (C,), p[b + "ln1.weight"], p[b + "ln1.bias"], 1e-5), n_head, drop, i, pdrops)    # :78
         h = F.layer_norm(x, (C,), p[b + "ln2.weight"], p[b + "ln2.bias"], 1e-5)
-        m = F.linear(F.relu(F.linear(h, p[b + "mlp.0.weight"], p[b + "mlp.0.bias"])), p[b + "mlp.2.weight"], p[b + "mlp.2.bias"])
+        m = F.linear(fn(F.linear(h, p[b + "mlp.0.weight"], p[b + "mlp.0.bias"])), p[b + "mlp.2.weight"], p[b + "mlp.2.bias"])
         x = x + _drop(m, drop, ("mlp", i), pdrops[2])                                                         # :79 (mlp[3] = nn.Dropout(resid_pdrop), :71)
         i += 1
     x = F.layer_norm(x, (C,), p[prefix + "ln_f.weight"], p[prefix + "ln_f.bias"], 1e-5)                        # :192

@@ -318,6 +318,16 @@ void gpt_tiled_unsupported() {
     tr::knob("tiled_ok", 0);
     RC(mfvit_gpt_forward(&c, P, SH, IM, W, FE, MAIN));
 }
+void gpt_f32_too_long() {   // the model's own 394 tokens at head_dim 64: past the exact attention's LDS image (T <= 315), refused with nothing launched
+    mfvit_vit_cfg c = gpt_cfg(MFVIT_F32);
+    c.tokens = 394; c.use_pos = 1; c.act = 1;
+    sizes(c);
+    RC(mfvit_gpt_forward(&c, P, SH, IM, W, FE, MAIN));
+    RC(mfvit_gpt_backward(&c, P, SH, W, DF, DP, DT, MAIN));
+    RC(mfvit_vit_prepare_shadow(&c, P, SH, MAIN));
+    c.tokens = 315;             // the longest accepted sequence
+    sizes(c);
+}
 
 // ------------------------------------------------------------------ 12. weight shadows
 void prepare_shadow() {
@@ -371,7 +381,7 @@ const Scenario SCENARIOS[] = {
     S(stop_grad_conv1), S(dimg_with_dparams), S(dimg_only), S(dimg_pos_dropout),
     S(attn_requests), S(rel_requests),
     S(lora_prepare_shadow), S(lora_every_target), S(lora_proj_only), S(lora_lowest_block_1), S(lora_with_dimg), S(lora_grad), S(lora_duplicate_item),
-    S(gpt_plain), S(gpt_pos_relu_dropout), S(gpt_pos_no_dropout), S(gpt_tiled_unsupported), S(prepare_shadow), S(argument_errors),
+    S(gpt_plain), S(gpt_pos_relu_dropout), S(gpt_pos_no_dropout), S(gpt_tiled_unsupported), S(gpt_f32_too_long), S(prepare_shadow), S(argument_errors),
     S(fail_tile_gemm), S(fail_side_wgrad), S(fail_fork_record),
 };
 #undef S
