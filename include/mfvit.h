@@ -409,6 +409,24 @@ int mfvit_attention_qkv_dtype(int dtype, int T, int head_dim);
 int mfvit_attention_fwd(int dtype, const void* qkv, void* out, float* lse, int B, int T, int H, int head_dim, mfvit_stream_t stream);
 int mfvit_attention_bwd(int dtype, const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* dbias_qkv,
                         int B, int T, int H, int head_dim, mfvit_stream_t stream);
+/* Host only, no GPU needed (additive): which kernel family mfvit_attention_fwd (backward == 0) or mfvit_attention_bwd (backward != 0) launches
+ * for this dtype tag and shape, reported by the launchers' own decision code under the same run-time switch (MFVIT_ATTN_BWD_SP) and the
+ * compute-unit count of the current device (256 where there is none).  plan[MFVIT_ATTN_PLAN_INTS]:
+ *   [0] family (MFVIT_ATTN_* below)
+ *   [1] 32-row tiles of one (image, head) pair, (T + 31) / 32; 0 for the exact kernels (one row per thread)
+ *   [2] dynamic LDS bytes of the launch (streaming backward: of the dQ launch)      [3] workgroups      [4] threads per workgroup
+ *   [5] dynamic LDS bytes of the streaming backward's second launch (dK / dV), else 0.
+ * The column sums for dbias_qkv are a further launch behind every backward family but the exact one and are not part of the plan.
+ * Returns what the launch would return for a refused shape (MFVIT_EINVAL, MFVIT_ENOSYS) and leaves plan untouched then. */
+#define MFVIT_ATTN_EXACT 0          /* f32 arithmetic, one row per thread, K / V of a pair as f32 in LDS (csrc/attention.hip) */
+#define MFVIT_ATTN_PAIR 1           /* forward, one workgroup per pair, whole head in LDS (attn_fwd_mfma_kernel) */
+#define MFVIT_ATTN_FWD_PP 2         /* persistent forward with a producer wave (attn_fwd_pp_kernel; split types, B * H >= 2 x CUs, 5 - 7 tiles) */
+#define MFVIT_ATTN_BWD_PADDED 3     /* two-phase backward, padded LDS images (attn_bwd_mfma_kernel<T, RB + 16>) */
+#define MFVIT_ATTN_BWD_UNPADDED 4   /* two-phase backward, unpadded LDS images (attn_bwd_mfma_kernel<T, RB>; plain types, T = 417 .. 480) */
+#define MFVIT_ATTN_BWD_SP 5         /* single-pass backward (attn_bwd_sp_kernel; 7 tiles, B * H >= 2 x CUs) */
+#define MFVIT_ATTN_STREAM 6         /* streaming kernels, any T, head_dim 32 / 64 / 96 (csrc/attention_tiled.hip) */
+#define MFVIT_ATTN_PLAN_INTS 6
+int mfvit_attention_plan(int dtype, int B, int T, int H, int head_dim, int backward, int32_t* plan);
 /* Per-head statistics of the attention probabilities (additive in ABI 5; mfvit.attnstats drives it): mean attention distance (Dosovitskiy et
  * al. 2021, Fig. 11; Raghu et al. 2021) and attention entropy of every head of `nblk` blocks, from each block's qkv tensor (storage tag
  * qkv_dtype: MFVIT_F32 / BF16 / F16 / BF16X3 / X3F16) and log-sum-exp as mfvit_attention_fwd leaves them.  The T x T maps never reach memory.

@@ -176,6 +176,14 @@ int mfvit_attention_fwd(int dtype, const void* qkv, void* out, float* lse, int B
     return attn_fwd(dtype, qkv, out, lse, B, T, H, head_dim, (hipStream_t)stream);
 }
 int mfvit_attention_qkv_dtype(int dtype, int T, int head_dim) { return attn_qkv_dtype(dtype, T, head_dim); }
+int mfvit_attention_plan(int dtype, int B, int T, int H, int head_dim, int backward, int32_t* plan) {
+    if (!plan || B <= 0 || T <= 0 || H <= 0) return MFVIT_EINVAL;
+    AttnPlan pl;
+    const int rc = attn_plan(dtype, B, T, H, head_dim, backward != 0, &pl);
+    if (rc != MFVIT_OK) return rc;
+    plan[0] = pl.family; plan[1] = pl.tiles; plan[2] = pl.lds; plan[3] = pl.grid; plan[4] = pl.threads; plan[5] = pl.lds2;
+    return MFVIT_OK;
+}
 size_t mfvit_attention_stats_work_bytes(int nblk, int B, int T, int H) { return attn_stats_work_bytes(nblk, B, T, H); }
 int mfvit_attention_stats(int qkv_dtype, const void* qkv, const float* lse, int64_t qkv_stride, int64_t lse_stride, int nblk, int B, int T, int H,
                           int head_dim, int gh, int gw, float patch, double* stats, void* work, size_t work_bytes, mfvit_stream_t stream) {

@@ -218,16 +218,25 @@ __global__ __launch_bounds__(256) void attn_bwd_exact_kernel(const T* __restrict
     }
 }
 
+// the exact kernels' launch decision: K and V (backward: + the D and lse rows) of one (image, head) as f32 in LDS, one workgroup per pair
+static int plan_exact(int HD, int B, int Tn, int H, bool backward, AttnPlan* pl) {
+    const long bytes = 2L * Tn * HD * 4 + (backward ? 2L * Tn * 4 : 0);
+    if (bytes > 160 * 1024) return MFVIT_EINVAL;
+    *pl = AttnPlan{ATTN_EXACT, 0, (int)bytes, B * H, 256, 0};
+    return MFVIT_OK;
+}
+
 template <typename T, int HD>
 static int launch_fwd(const void* qkv, void* out, float* lse, int B, int Tn, int H, hipStream_t st) {
-    const int bytes = 2 * Tn * HD * 4;
-    if (bytes > 160 * 1024) return MFVIT_EINVAL;
+    AttnPlan pl;
+    if (const int rc = plan_exact(HD, B, Tn, H, false, &pl)) return rc;
+    const int bytes = pl.lds;
     static PerDeviceOnce attr_set;
     if (attr_set.first()) {
         (void)hipFuncSetAttribute((const void*)attn_fwd_exact_kernel<T, HD>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     }
     ProfScope ps(PROF_ATTN_FWD, 4.0 * B * H * (double)Tn * Tn * HD, 0, st);
-    MFVIT_LAUNCH((attn_fwd_exact_kernel<T, HD>), dim3(B * H), dim3(256), bytes, st, (const T*)qkv, (T*)out, lse, Tn, H,
+    MFVIT_LAUNCH((attn_fwd_exact_kernel<T, HD>), dim3(pl.grid), dim3(pl.threads), bytes, st, (const T*)qkv, (T*)out, lse, Tn, H,
                        1.0f / sqrtf((float)HD));
     MFVIT_CHECK_LAUNCH();
     return MFVIT_OK;
@@ -235,14 +244,15 @@ static int launch_fwd(const void* qkv, void* out, float* lse, int B, int Tn, int
 template <typename T, int HD>
 static int launch_bwd(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* dbias, int B, int Tn, int H,
                       hipStream_t st) {
-    const int bytes = 2 * Tn * HD * 4 + 2 * Tn * 4;
-    if (bytes > 160 * 1024) return MFVIT_EINVAL;
+    AttnPlan pl;
+    if (const int rc = plan_exact(HD, B, Tn, H, true, &pl)) return rc;
+    const int bytes = pl.lds;
     static PerDeviceOnce attr_set;
     if (attr_set.first()) {
         (void)hipFuncSetAttribute((const void*)attn_bwd_exact_kernel<T, HD>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     }
     ProfScope ps(PROF_ATTN_BWD, 8.0 * B * H * (double)Tn * Tn * HD, 0, st);
-    MFVIT_LAUNCH((attn_bwd_exact_kernel<T, HD>), dim3(B * H), dim3(256), bytes, st, (const T*)qkv, (const T*)out, (const T*)dout, lse,
+    MFVIT_LAUNCH((attn_bwd_exact_kernel<T, HD>), dim3(pl.grid), dim3(pl.threads), bytes, st, (const T*)qkv, (const T*)out, (const T*)dout, lse,
                        (T*)dqkv, dbias, Tn, H, 1.0f / sqrtf((float)HD));
     MFVIT_CHECK_LAUNCH();
     return MFVIT_OK;
@@ -279,6 +289,8 @@ int attn_fwd_tiled(int dtype, const void* qkv, void* out, float* lse, int B, int
 int attn_bwd_tiled(int dtype, const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int B, int Tn, int H, int HDim,
                    hipStream_t st);
 int attn_colsum(int dtype, const void* dqkv, int M, int N, float* dbias, hipStream_t st);
+int attn_mfma_plan(int dtype, int B, int Tn, int H, bool backward, AttnPlan* plan);
+int attn_tiled_plan(int dtype, int B, int Tn, int H, int HDim, bool backward, AttnPlan* plan);
 // whole-(image, head)-in-LDS MFMA kernels where they fit (ViT-S at 224^2: fastest) -> streaming MFMA kernels (long sequences, wide
 // heads, split bf16 beyond the LDS limits) -> exact VALU kernels (f32)
 int attn_qkv_dtype(int dtype, int Tn, int HDim) {
@@ -286,23 +298,52 @@ int attn_qkv_dtype(int dtype, int Tn, int HDim) {
         return MFVIT_X3F16;
     return dtype;
 }
+// which kernel file serves (dtype, T, head_dim) in one direction: the one routing decision of attn_fwd, attn_bwd and attn_plan
+enum { ROUTE_MFMA, ROUTE_TILED, ROUTE_EXACT, ROUTE_NONE };
+static int attn_route(int dtype, int Tn, int HDim, bool backward) {
+    if (dtype == MFVIT_X3F16) return attn_mfma_supported(dtype, Tn, HDim, backward) ? ROUTE_MFMA : ROUTE_NONE;
+    if (attn_mfma_supported(dtype, Tn, HDim, backward)) return ROUTE_MFMA;
+    if (attn_tiled_supported(dtype, Tn, HDim)) return ROUTE_TILED;
+    return ROUTE_EXACT;
+}
 int attn_fwd(int dtype, const void* qkv, void* out, float* lse, int B, int Tn, int H, int HDim, hipStream_t st) {
-    if (dtype == MFVIT_X3F16) return attn_mfma_supported(dtype, Tn, HDim, false) ? attn_fwd_mfma(dtype, qkv, out, lse, B, Tn, H, st) : MFVIT_ENOSYS;
-    if (attn_mfma_supported(dtype, Tn, HDim, false)) return attn_fwd_mfma(dtype, qkv, out, lse, B, Tn, H, st);
-    if (attn_tiled_supported(dtype, Tn, HDim)) return attn_fwd_tiled(dtype, qkv, out, lse, B, Tn, H, HDim, st);
-    return attn_fwd_exact(dtype, qkv, out, lse, B, Tn, H, HDim, st);
+    switch (attn_route(dtype, Tn, HDim, false)) {
+        case ROUTE_MFMA: return attn_fwd_mfma(dtype, qkv, out, lse, B, Tn, H, st);
+        case ROUTE_TILED: return attn_fwd_tiled(dtype, qkv, out, lse, B, Tn, H, HDim, st);
+        case ROUTE_EXACT: return attn_fwd_exact(dtype, qkv, out, lse, B, Tn, H, HDim, st);
+        default: return MFVIT_ENOSYS;
+    }
 }
 int attn_bwd(int dtype, const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* dbias, int B, int Tn, int H,
              int HDim, hipStream_t st, const unsigned* domax) {
-    if (dtype == MFVIT_X3F16)
-        return attn_mfma_supported(dtype, Tn, HDim, true) ? attn_bwd_mfma(dtype, qkv, out, dout, lse, dqkv, dbias, B, Tn, H, st, domax) : MFVIT_ENOSYS;
-    if (attn_mfma_supported(dtype, Tn, HDim, true)) return attn_bwd_mfma(dtype, qkv, out, dout, lse, dqkv, dbias, B, Tn, H, st);
-    if (attn_tiled_supported(dtype, Tn, HDim)) {
-        const int rc = attn_bwd_tiled(dtype, qkv, out, dout, lse, dqkv, B, Tn, H, HDim, st);
-        if (rc != MFVIT_OK || !dbias) return rc;
-        return attn_colsum(dtype, dqkv, B * Tn, 3 * H * HDim, dbias, st);
+    switch (attn_route(dtype, Tn, HDim, true)) {
+        case ROUTE_MFMA: return attn_bwd_mfma(dtype, qkv, out, dout, lse, dqkv, dbias, B, Tn, H, st, dtype == MFVIT_X3F16 ? domax : nullptr);
+        case ROUTE_TILED: {
+            const int rc = attn_bwd_tiled(dtype, qkv, out, dout, lse, dqkv, B, Tn, H, HDim, st);
+            if (rc != MFVIT_OK || !dbias) return rc;
+            return attn_colsum(dtype, dqkv, B * Tn, 3 * H * HDim, dbias, st);
+        }
+        case ROUTE_EXACT: return attn_bwd_exact(dtype, qkv, out, dout, lse, dqkv, dbias, B, Tn, H, HDim, st);
+        default: return MFVIT_ENOSYS;
     }
-    return attn_bwd_exact(dtype, qkv, out, dout, lse, dqkv, dbias, B, Tn, H, HDim, st);
+}
+// host only: the plan of the launch attn_fwd / attn_bwd would make (the same route, the launchers' own decision functions)
+int attn_plan(int dtype, int B, int Tn, int H, int HDim, bool backward, AttnPlan* plan) {
+    AttnPlan pl;
+    int rc;
+    switch (attn_route(dtype, Tn, HDim, backward)) {
+        case ROUTE_MFMA: rc = attn_mfma_plan(dtype, B, Tn, H, backward, &pl); break;
+        case ROUTE_TILED: rc = attn_tiled_plan(dtype, B, Tn, H, HDim, backward, &pl); break;
+        case ROUTE_EXACT:
+            if (HDim != 32 && HDim != 64) return MFVIT_EINVAL;
+            if (dtype == MFVIT_BF16X3) return MFVIT_ENOSYS;
+            if (dtype != MFVIT_F32 && dtype != MFVIT_BF16 && dtype != MFVIT_F16) return MFVIT_EINVAL;
+            rc = plan_exact(HDim, B, Tn, H, backward, &pl);
+            break;
+        default: return MFVIT_ENOSYS;
+    }
+    if (rc == MFVIT_OK) *plan = pl;
+    return rc;
 }
 
 }  // namespace mfvit

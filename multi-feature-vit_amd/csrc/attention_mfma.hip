@@ -2,7 +2,7 @@
 //
 // One workgroup (4 waves) per (image, head); K/V (forward) or Q/K/V/dO (backward) of that head live in LDS as bf16.
 // T = 197 keys fit whole, so the forward does an exact softmax per 32-query tile over register-resident scores
-// (chunks of up to 8 key tiles; longer sequences chain chunks with an online rescale).
+// (chunks of up to 4 key tiles (NKC); longer sequences chain chunks with an online rescale).
 //
 // Operand orientation ("swapped" products, wave64 32x32x16 MFMA):
 //   S^T[key][q]  = K_tile (A, rows = keys)  x  Q^T (B, cols = queries)     -> the query sits on the LANE: row max / row
@@ -1826,32 +1826,63 @@ int attn_cus() {   // CUs of the CURRENT device, a multiple of 8 (a persistent w
     return n >= 8 ? n : 8;
 }
 
-template <typename T> int launch_fwd_t(const void* qkv, void* out, float* lse, int B, int Tn, int H, hipStream_t st) {
-    typedef typename Vec4<T>::elem E;
-    typedef typename AttnT<T>::OE OE;
+// The forward's launch decision (host only; launch_fwd_t calls it first, mfvit_attention_plan reports it).
+template <typename T> AttnPlan plan_fwd_t(int B, int Tn, int H) {
+    const int nt = (Tn + 31) >> 5;
     if constexpr (is_split<T>::value) {
         // persistent pair-synchronous kernel: enough pairs to fill every CU twice, 5 - 7 row tiles per pair (one per computing wave).  The split types
         // only (53 vs 57 - 60 us at the bench shape in split bf16); the plain 16-bit types are faster on the per-pair kernel (27.5 vs 30 us: their steps
         // are too short for the per-step overheads of the pipeline) and are no longer instantiated for it.
         const int cus = attn_cus();
-        const int nt = (Tn + 31) >> 5;
         const int bytes = RingGeo<T>::lds_bytes(Tn);
-        if (B * H >= 2 * cus && nt >= 5 && nt <= RingGeo<T>::NCW && bytes <= 160 * 1024) {
+        if (B * H >= 2 * cus && nt >= 5 && nt <= RingGeo<T>::NCW && bytes <= 160 * 1024) return AttnPlan{ATTN_FWD_PP, nt, bytes, cus, 512, 0};
+    }
+    const int Tpad = (Tn + 31) & ~31;
+    return AttnPlan{ATTN_PAIR, nt, Tpad * (AttnT<T>::RSB + AttnT<T>::RB), B * H, 256, 0};
+}
+template <typename T> int launch_fwd_t(const void* qkv, void* out, float* lse, int B, int Tn, int H, hipStream_t st) {
+    typedef typename Vec4<T>::elem E;
+    typedef typename AttnT<T>::OE OE;
+    const AttnPlan pl = plan_fwd_t<T>(B, Tn, H);
+    if constexpr (is_split<T>::value) {
+        if (pl.family == ATTN_FWD_PP) {
             static PerDeviceOnce attr_pp;
             if (attr_pp.first()) (void)hipFuncSetAttribute((const void*)attn_fwd_pp_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             ProfScope ps(PROF_ATTN_FWD, 4.0 * B * H * (double)Tn * Tn * HD, 0, st);
-            MFVIT_LAUNCH((attn_fwd_pp_kernel<T>), dim3(cus), dim3(512), bytes, st, (const E*)qkv, (OE*)out, lse, Tn, H, 1.0f / sqrtf((float)HD), B * H);
+            MFVIT_LAUNCH((attn_fwd_pp_kernel<T>), dim3(pl.grid), dim3(512), pl.lds, st, (const E*)qkv, (OE*)out, lse, Tn, H, 1.0f / sqrtf((float)HD),
+                         B * H);
             MFVIT_CHECK_LAUNCH();
             return MFVIT_OK;
         }
     }
-    const int Tpad = (Tn + 31) & ~31;
-    const int bytes = Tpad * (AttnT<T>::RSB + AttnT<T>::RB);
     static PerDeviceOnce attr;
     if (attr.first()) { (void)hipFuncSetAttribute((const void*)attn_fwd_mfma_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); }
     ProfScope ps(PROF_ATTN_FWD, 4.0 * B * H * (double)Tn * Tn * HD, 0, st);
-    MFVIT_LAUNCH((attn_fwd_mfma_kernel<T>), dim3(B * H), dim3(256), bytes, st, (const E*)qkv, (OE*)out, lse, Tn, H, 1.0f / sqrtf((float)HD));
+    MFVIT_LAUNCH((attn_fwd_mfma_kernel<T>), dim3(pl.grid), dim3(256), pl.lds, st, (const E*)qkv, (OE*)out, lse, Tn, H, 1.0f / sqrtf((float)HD));
     MFVIT_CHECK_LAUNCH();
+    return MFVIT_OK;
+}
+// The backward's launch decision (host only; launch_bwd_t calls it first, mfvit_attention_plan reports it).
+template <typename T> int plan_bwd_t(int B, int Tn, int H, AttnPlan* pl) {
+    constexpr int RSB = AttnT<T>::RSB, RB = AttnT<T>::RB;
+    const int Tpad = (Tn + 31) & ~31;
+    const int nt = (Tn + 31) >> 5;
+    const bool wide = 4 * Tpad * RSB + 2 * Tpad * 4 + Tpad * RB + 64 <= 160 * 1024;
+    const int bytes = 4 * Tpad * (wide ? RSB : RB) + 2 * Tpad * 4 + Tpad * RB;      // Q, K, V, dO images, lse / D rows, the next pair's O rows
+    // (the unpadded images serve the plain types at Tpad = 448 / 480; the split types stop at Tpad = 224 (attn_mfma_supported), where the padded ones fit)
+    if (AttnT<T>::SP && !wide) return MFVIT_EINVAL;
+    const int cus = attn_cus();
+    {   // single-pass kernel: seven row tiles (T = 193 .. 224), enough pairs to give every CU two.  Default for all 16-bit types
+        // (bench shape: split bf16 115 vs 155 us, bf16 / fp16 62.5 vs 71 us: profiles/r04_kernel_experiments.txt); MFVIT_ATTN_BWD_SP=0: off
+        static int sws = INT_MIN;
+        const int b3 = SpGeo<T>::lds_bytes(Tn);
+        if (env_switch("MFVIT_ATTN_BWD_SP", 1, sws) != 0 && B * H >= 2 * cus && nt == 7 && b3 <= 160 * 1024) {
+            *pl = AttnPlan{ATTN_BWD_SP, nt, b3, cus, 512, 0};
+            return MFVIT_OK;
+        }
+    }
+    // one persistent workgroup per CU (the LDS images allow no second one): a multiple of 8 so that a workgroup's pairs stay on its XCD
+    *pl = AttnPlan{wide ? ATTN_BWD_PADDED : ATTN_BWD_UNPADDED, nt, bytes, B * H < cus ? B * H : cus, 512, 0};
     return MFVIT_OK;
 }
 template <typename T> int launch_bwd_t(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* dbias, int B, int Tn,
@@ -1860,11 +1891,8 @@ template <typename T> int launch_bwd_t(const void* qkv, const void* out, const v
     typedef typename AttnT<T>::OE OE;
     typedef typename AttnT<T>::OT OT;
     constexpr int RSB = AttnT<T>::RSB, RB = AttnT<T>::RB;
-    const int Tpad = (Tn + 31) & ~31;
-    const bool wide = 4 * Tpad * RSB + 2 * Tpad * 4 + Tpad * RB + 64 <= 160 * 1024;
-    const int bytes = 4 * Tpad * (wide ? RSB : RB) + 2 * Tpad * 4 + Tpad * RB;      // Q, K, V, dO images, lse / D rows, the next pair's O rows
-    // (the unpadded images serve the plain types at Tpad = 448 / 480; the split types stop at Tpad = 224 (attn_mfma_supported), where the padded ones fit)
-    if (AttnT<T>::SP && !wide) return MFVIT_EINVAL;
+    AttnPlan pl;
+    if (const int rc = plan_bwd_t<T>(B, Tn, H, &pl)) return rc;
     static PerDeviceOnce attr;
     if (attr.first()) {
         (void)hipFuncSetAttribute((const void*)attn_bwd_mfma_kernel<T, RSB>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
@@ -1878,47 +1906,37 @@ template <typename T> int launch_bwd_t(const void* qkv, const void* out, const v
         MFVIT_CHECK_LAUNCH();
         return MFVIT_OK;
     };
-    {   // single-pass kernel: seven row tiles (T = 193 .. 224), enough pairs to give every CU two.  Default for all 16-bit types
-        // (bench shape: split bf16 115 vs 155 us, bf16 / fp16 62.5 vs 71 us: profiles/r04_kernel_experiments.txt); MFVIT_ATTN_BWD_SP=0: off
-        static int sws = INT_MIN;
-        const int cus3 = attn_cus();
-        const int nt = (Tn + 31) >> 5;
-        const int b3 = SpGeo<T>::lds_bytes(Tn);
-        if (env_switch("MFVIT_ATTN_BWD_SP", 1, sws) != 0 && B * H >= 2 * cus3 && nt == 7 && b3 <= 160 * 1024) {
-            static PerDeviceOnce attr_sp;
-            if (attr_sp.first()) {
-                (void)hipFuncSetAttribute((const void*)attn_bwd_sp_kernel<T, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                if constexpr (AttnT<T>::X)
-                    (void)hipFuncSetAttribute((const void*)attn_bwd_sp_kernel<T, 7, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            }
-            {
-                ProfScope ps(PROF_ATTN_BWD, 8.0 * B * H * (double)Tn * Tn * HD, 0, st);
-                bool done = false;
-                if constexpr (AttnT<T>::X) {
-                    if (domax) {
-                        MFVIT_LAUNCH((attn_bwd_sp_kernel<T, 7, true>), dim3(cus3), dim3(512), b3, st, (const E*)qkv, (const OE*)out, (const OE*)dout, lse,
-                                     (OE*)dqkv, Tn, H, 1.0f / sqrtf((float)HD), B * H, domax);
-                        done = true;
-                    }
-                }
-                if (!done)
-                    MFVIT_LAUNCH((attn_bwd_sp_kernel<T, 7>), dim3(cus3), dim3(512), b3, st, (const E*)qkv, (const OE*)out, (const OE*)dout, lse, (OE*)dqkv,
-                                 Tn, H, 1.0f / sqrtf((float)HD), B * H, (const unsigned*)nullptr);
-                MFVIT_CHECK_LAUNCH();
-            }
-            return colsum();
+    if (pl.family == ATTN_BWD_SP) {
+        static PerDeviceOnce attr_sp;
+        if (attr_sp.first()) {
+            (void)hipFuncSetAttribute((const void*)attn_bwd_sp_kernel<T, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            if constexpr (AttnT<T>::X)
+                (void)hipFuncSetAttribute((const void*)attn_bwd_sp_kernel<T, 7, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         }
+        {
+            ProfScope ps(PROF_ATTN_BWD, 8.0 * B * H * (double)Tn * Tn * HD, 0, st);
+            bool done = false;
+            if constexpr (AttnT<T>::X) {
+                if (domax) {
+                    MFVIT_LAUNCH((attn_bwd_sp_kernel<T, 7, true>), dim3(pl.grid), dim3(512), pl.lds, st, (const E*)qkv, (const OE*)out, (const OE*)dout, lse,
+                                 (OE*)dqkv, Tn, H, 1.0f / sqrtf((float)HD), B * H, domax);
+                    done = true;
+                }
+            }
+            if (!done)
+                MFVIT_LAUNCH((attn_bwd_sp_kernel<T, 7>), dim3(pl.grid), dim3(512), pl.lds, st, (const E*)qkv, (const OE*)out, (const OE*)dout, lse, (OE*)dqkv,
+                             Tn, H, 1.0f / sqrtf((float)HD), B * H, (const unsigned*)nullptr);
+            MFVIT_CHECK_LAUNCH();
+        }
+        return colsum();
     }
     {
         ProfScope ps(PROF_ATTN_BWD, 8.0 * B * H * (double)Tn * Tn * HD, 0, st);
-        // one persistent workgroup per CU (the LDS images allow no second one): a multiple of 8 so that a workgroup's pairs stay on its XCD
-        const int cus = attn_cus();
-        const int grid = B * H < cus ? B * H : cus;
-        if (wide)
-            MFVIT_LAUNCH((attn_bwd_mfma_kernel<T, RSB>), dim3(grid), dim3(512), bytes, st, (const E*)qkv, (const OE*)out, (const OE*)dout, lse,
+        if (pl.family == ATTN_BWD_PADDED)
+            MFVIT_LAUNCH((attn_bwd_mfma_kernel<T, RSB>), dim3(pl.grid), dim3(512), pl.lds, st, (const E*)qkv, (const OE*)out, (const OE*)dout, lse,
                          (OE*)dqkv, Tn, H, 1.0f / sqrtf((float)HD), B * H);
         else if constexpr (!AttnT<T>::SP)
-            MFVIT_LAUNCH((attn_bwd_mfma_kernel<T, RB>), dim3(grid), dim3(512), bytes, st, (const E*)qkv, (const OE*)out, (const OE*)dout, lse,
+            MFVIT_LAUNCH((attn_bwd_mfma_kernel<T, RB>), dim3(pl.grid), dim3(512), pl.lds, st, (const E*)qkv, (const OE*)out, (const OE*)dout, lse,
                          (OE*)dqkv, Tn, H, 1.0f / sqrtf((float)HD), B * H);
         MFVIT_CHECK_LAUNCH();
     }
@@ -1960,6 +1978,23 @@ int attn_bwd_mfma(int dtype, const void* qkv, const void* out, const void* dout,
     if (dtype == MFVIT_BF16X3) return launch_bwd_t<sbf16>(qkv, out, dout, lse, dqkv, dbias, B, Tn, H, st);
     if (dtype == MFVIT_F16) return launch_bwd_t<f16>(qkv, out, dout, lse, dqkv, dbias, B, Tn, H, st);
     if (dtype == MFVIT_X3F16) return launch_bwd_t<sf16>(qkv, out, dout, lse, dqkv, dbias, B, Tn, H, st, domax);
+    return MFVIT_EINVAL;
+}
+
+// host only: what attn_fwd_mfma / attn_bwd_mfma would launch
+int attn_mfma_plan(int dtype, int B, int Tn, int H, bool backward, AttnPlan* plan) {
+    if (!backward) {
+        if (dtype == MFVIT_BF16) *plan = plan_fwd_t<bf16>(B, Tn, H);
+        else if (dtype == MFVIT_BF16X3) *plan = plan_fwd_t<sbf16>(B, Tn, H);
+        else if (dtype == MFVIT_F16) *plan = plan_fwd_t<f16>(B, Tn, H);
+        else if (dtype == MFVIT_X3F16) *plan = plan_fwd_t<sf16>(B, Tn, H);
+        else return MFVIT_EINVAL;
+        return MFVIT_OK;
+    }
+    if (dtype == MFVIT_BF16) return plan_bwd_t<bf16>(B, Tn, H, plan);
+    if (dtype == MFVIT_BF16X3) return plan_bwd_t<sbf16>(B, Tn, H, plan);
+    if (dtype == MFVIT_F16) return plan_bwd_t<f16>(B, Tn, H, plan);
+    if (dtype == MFVIT_X3F16) return plan_bwd_t<sf16>(B, Tn, H, plan);
     return MFVIT_EINVAL;
 }
 

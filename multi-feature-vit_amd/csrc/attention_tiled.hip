@@ -2,7 +2,7 @@
 // bf16, f16 and sbf16 (split bf16: three MFMAs per product, P / dS split in registers).
 //
 // attention_mfma.hip keeps the whole K/V (forward) or Q/K/V/dO (backward) of one (image, head) in LDS: fastest for ViT-S at
-// T = 197, but bounded by the 160 KB of LDS (split bf16: forward T <= 576, backward T <= 288; head_dim 32 only).  The kernels here
+// T = 197, but bounded by the 160 KB of LDS (split bf16: forward T <= 576, backward T <= 224; head_dim 32 only).  The kernels here
 // stream the other operand through LDS in 64-row chunks instead, flash-attention style, with the running row maximum / sum (forward)
 // or the saved log-sum-exp (backward) on the lane.  They serve
 //   * the TransFuser-GPT fusion (fuseattention.py:21-58: 4 heads x 96 over 394 joint tokens),
@@ -439,22 +439,30 @@ __global__ __launch_bounds__(256) void attn_tiled_bwd_dkv_kernel(const typename 
     }
 }
 
+// The streaming kernels' launch decision (host only; the launchers call it first, mfvit_attention_plan reports it): one workgroup per
+// (image, head, block of TL_BLK rows), two TL_CH-row chunks of the streamed operand in LDS (dK / dV: + their lse and D rows)
+template <typename T, int NB> AttnPlan tl_plan(int B, int Tn, int H, bool backward) {
+    typedef TG<T, NB> G;
+    const int nblk = (Tn + TL_BLK - 1) / TL_BLK;
+    const int bytes = 2 * TL_CH * G::PITCH;
+    return AttnPlan{ATTN_STREAM, (Tn + 31) >> 5, bytes, B * H * nblk, 256, backward ? bytes + 2 * TL_CH * 4 : 0};
+}
 template <typename T, int NB> int tl_launch_fwd(const void* qkv, void* out, float* lse, int B, int Tn, int H, hipStream_t st, DropP drop) {
     typedef TG<T, NB> G;
     typedef typename G::E E;
-    const int bytes = 2 * TL_CH * G::PITCH;
+    const AttnPlan pl = tl_plan<T, NB>(B, Tn, H, false);
+    const int bytes = pl.lds;
     static PerDeviceOnce attr;
     if (attr.first()) {
         (void)hipFuncSetAttribute((const void*)attn_tiled_fwd_kernel<T, NB, false>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
         (void)hipFuncSetAttribute((const void*)attn_tiled_fwd_kernel<T, NB, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     }
-    const int nblk = (Tn + TL_BLK - 1) / TL_BLK;
     ProfScope ps(PROF_ATTN_FWD, 4.0 * B * H * (double)Tn * Tn * G::HD, 0, st);
     if (drop.thr)
-        MFVIT_LAUNCH((attn_tiled_fwd_kernel<T, NB, true>), dim3(B * H * nblk), dim3(256), bytes, st, (const E*)qkv, (E*)out, lse, Tn, H,
+        MFVIT_LAUNCH((attn_tiled_fwd_kernel<T, NB, true>), dim3(pl.grid), dim3(256), bytes, st, (const E*)qkv, (E*)out, lse, Tn, H,
                      1.0f / sqrtf((float)G::HD), drop);
     else
-        MFVIT_LAUNCH((attn_tiled_fwd_kernel<T, NB, false>), dim3(B * H * nblk), dim3(256), bytes, st, (const E*)qkv, (E*)out, lse, Tn, H,
+        MFVIT_LAUNCH((attn_tiled_fwd_kernel<T, NB, false>), dim3(pl.grid), dim3(256), bytes, st, (const E*)qkv, (E*)out, lse, Tn, H,
                      1.0f / sqrtf((float)G::HD), drop);
     MFVIT_CHECK_LAUNCH();
     return MFVIT_OK;
@@ -463,7 +471,8 @@ template <typename T, int NB> int tl_launch_bwd(const void* qkv, const void* out
                                                 hipStream_t st, DropP drop) {
     typedef TG<T, NB> G;
     typedef typename G::E E;
-    const int bytes_q = 2 * TL_CH * G::PITCH, bytes_kv = 2 * TL_CH * G::PITCH + 2 * TL_CH * 4;
+    const AttnPlan pl = tl_plan<T, NB>(B, Tn, H, true);
+    const int bytes_q = pl.lds, bytes_kv = pl.lds2;
     static PerDeviceOnce attr;
     if (attr.first()) {
         (void)hipFuncSetAttribute((const void*)attn_tiled_bwd_dq_kernel<T, NB, false>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes_q);
@@ -471,20 +480,19 @@ template <typename T, int NB> int tl_launch_bwd(const void* qkv, const void* out
         (void)hipFuncSetAttribute((const void*)attn_tiled_bwd_dq_kernel<T, NB, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes_q);
         (void)hipFuncSetAttribute((const void*)attn_tiled_bwd_dkv_kernel<T, NB, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes_kv);
     }
-    const int nblk = (Tn + TL_BLK - 1) / TL_BLK;
     const float scale = 1.0f / sqrtf((float)G::HD);
     ProfScope ps(PROF_ATTN_BWD, 8.0 * B * H * (double)Tn * Tn * G::HD, 0, st);
     if (drop.thr) {
-        MFVIT_LAUNCH((attn_tiled_bwd_dq_kernel<T, NB, true>), dim3(B * H * nblk), dim3(256), bytes_q, st, (const E*)qkv, (const E*)out, (const E*)dout,
+        MFVIT_LAUNCH((attn_tiled_bwd_dq_kernel<T, NB, true>), dim3(pl.grid), dim3(256), bytes_q, st, (const E*)qkv, (const E*)out, (const E*)dout,
                      lse, (E*)dqkv, Tn, H, scale, drop);
         MFVIT_CHECK_LAUNCH();
-        MFVIT_LAUNCH((attn_tiled_bwd_dkv_kernel<T, NB, true>), dim3(B * H * nblk), dim3(256), bytes_kv, st, (const E*)qkv, (const E*)out,
+        MFVIT_LAUNCH((attn_tiled_bwd_dkv_kernel<T, NB, true>), dim3(pl.grid), dim3(256), bytes_kv, st, (const E*)qkv, (const E*)out,
                      (const E*)dout, lse, (E*)dqkv, Tn, H, scale, drop);
     } else {
-        MFVIT_LAUNCH((attn_tiled_bwd_dq_kernel<T, NB, false>), dim3(B * H * nblk), dim3(256), bytes_q, st, (const E*)qkv, (const E*)out, (const E*)dout,
+        MFVIT_LAUNCH((attn_tiled_bwd_dq_kernel<T, NB, false>), dim3(pl.grid), dim3(256), bytes_q, st, (const E*)qkv, (const E*)out, (const E*)dout,
                      lse, (E*)dqkv, Tn, H, scale, drop);
         MFVIT_CHECK_LAUNCH();
-        MFVIT_LAUNCH((attn_tiled_bwd_dkv_kernel<T, NB, false>), dim3(B * H * nblk), dim3(256), bytes_kv, st, (const E*)qkv, (const E*)out,
+        MFVIT_LAUNCH((attn_tiled_bwd_dkv_kernel<T, NB, false>), dim3(pl.grid), dim3(256), bytes_kv, st, (const E*)qkv, (const E*)out,
                      (const E*)dout, lse, (E*)dqkv, Tn, H, scale, drop);
     }
     MFVIT_CHECK_LAUNCH();
@@ -508,6 +516,20 @@ template <typename T> static int tl_bwd_by_hd(const void* qkv, const void* out, 
     if (HDim == 32) return tl_launch_bwd<T, 1>(qkv, out, dout, lse, dqkv, B, Tn, H, st, drop);
     if (HDim == 64) return tl_launch_bwd<T, 2>(qkv, out, dout, lse, dqkv, B, Tn, H, st, drop);
     if (HDim == 96) return tl_launch_bwd<T, 3>(qkv, out, dout, lse, dqkv, B, Tn, H, st, drop);
+    return MFVIT_EINVAL;
+}
+template <typename T> static int tl_plan_by_hd(int B, int Tn, int H, int HDim, bool backward, AttnPlan* plan) {
+    if (HDim == 32) *plan = tl_plan<T, 1>(B, Tn, H, backward);
+    else if (HDim == 64) *plan = tl_plan<T, 2>(B, Tn, H, backward);
+    else if (HDim == 96) *plan = tl_plan<T, 3>(B, Tn, H, backward);
+    else return MFVIT_EINVAL;
+    return MFVIT_OK;
+}
+// host only: what attn_fwd_tiled / attn_bwd_tiled would launch
+int attn_tiled_plan(int dtype, int B, int Tn, int H, int HDim, bool backward, AttnPlan* plan) {
+    if (dtype == MFVIT_BF16) return tl_plan_by_hd<bf16>(B, Tn, H, HDim, backward, plan);
+    if (dtype == MFVIT_BF16X3) return tl_plan_by_hd<sbf16>(B, Tn, H, HDim, backward, plan);
+    if (dtype == MFVIT_F16) return tl_plan_by_hd<f16>(B, Tn, H, HDim, backward, plan);
     return MFVIT_EINVAL;
 }
 // drop: attention dropout of the TransFuser GPT (make_drop; thr == 0: none).  Needs B * H * Tn * Tn < 2^32 mask indices.

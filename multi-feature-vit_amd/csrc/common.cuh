@@ -74,6 +74,10 @@ template <typename E, bool SPLIT> __device__ __forceinline__ void cvt_pair(float
 // multiplied by 1 / (1 - p).  thr == 0 switches a site off.  (A two-round multiply-xorshift hash, not Philox: the masks need to be
 // reproducible and well mixed, not cryptographic; mfvit_dropout_mask exports them so that the parity tests use the very same masks.)
 struct DropP { unsigned thr; float scale; unsigned key; };
+// what an attention launch decides on the host (family = MFVIT_ATTN_* of include/mfvit.h; kernels.h::attn_plan)
+enum { ATTN_EXACT = MFVIT_ATTN_EXACT, ATTN_PAIR = MFVIT_ATTN_PAIR, ATTN_FWD_PP = MFVIT_ATTN_FWD_PP, ATTN_BWD_PADDED = MFVIT_ATTN_BWD_PADDED,
+       ATTN_BWD_UNPADDED = MFVIT_ATTN_BWD_UNPADDED, ATTN_BWD_SP = MFVIT_ATTN_BWD_SP, ATTN_STREAM = MFVIT_ATTN_STREAM };
+struct AttnPlan { int family, tiles, lds, grid, threads, lds2; };   // lds2: the second launch of the streaming backward (dK / dV), else 0
 __host__ __device__ inline unsigned lowbias32(unsigned x) {
     x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
     return x;

@@ -110,6 +110,11 @@ int attn_fwd(int dtype, const void* qkv, void* out, float* lse, int B, int Tn, i
 int attn_bwd(int dtype, const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* dbias, int B, int Tn,
              int H, int HD, hipStream_t st, const unsigned* domax = nullptr);
 
+// What an attention launch decides on the host (mfvit_attention_plan, include/mfvit.h): filled by the launchers' own decision functions
+// (attention.hip::plan_exact, attention_mfma.hip::plan_fwd_t / plan_bwd_t, attention_tiled.hip::tl_plan), which each launcher calls first;
+// attn_plan routes like attn_fwd / attn_bwd and touches no device.  (struct AttnPlan: common.cuh)
+int attn_plan(int dtype, int B, int Tn, int H, int HD, bool backward, AttnPlan* plan);
+
 int im2col16(int dtype, const float* img, void* P, int B, int H, int W, hipStream_t st);
 int ln_rows(int dtype, int N, const float* in0, long ld0, const float* in1, long ld1, int mod1, float* xout, long ldx, void* y, long ldy,
             int y_f32, const float* gamma, const float* beta, float eps, float* mean, float* rstd, int rows, int row_stride, int row_off,

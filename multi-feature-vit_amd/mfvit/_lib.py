@@ -109,6 +109,7 @@ SIGNATURES = {
     "mfvit_attention_fwd": (I, [I, P, P, P, I, I, I, I, P]),
     "mfvit_attention_bwd": (I, [I, P, P, P, P, P, P, I, I, I, I, P]),
     "mfvit_attention_qkv_dtype": (I, [I, I, I]),
+    "mfvit_attention_plan": (I, [I, I, I, I, I, I, POINTER(ctypes.c_int32)]),
     "mfvit_attention_stats_work_bytes": (c_size_t, [I, I, I, I]),
     "mfvit_attention_stats": (I, [I, P, P, L, L, I, I, I, I, I, I, I, F, P, P, c_size_t, P]),
     "mfvit_attention_drop_fwd": (I, [I, P, P, P, I, I, I, I, F, c_uint64, c_uint32, P]),

@@ -61,6 +61,18 @@ def attention_qkv_dtype(code, T, head_dim):
     return lib().mfvit_attention_qkv_dtype(code, T, head_dim)
 
 
+ATTN_FAMILIES = ("exact", "pair", "fwd_pp", "bwd_padded", "bwd_unpadded", "bwd_sp", "stream")   # mfvit_attention_plan, plan[0] (MFVIT_ATTN_*)
+
+
+def attention_plan(code, B, T, heads, head_dim, backward=False):
+    """What mfvit_attention_fwd / _bwd decide on the host for this dtype code and shape (mfvit_attention_plan; no GPU needed), from the launchers'
+    own code under the current MFVIT_ATTN_BWD_SP: dict(family, tiles, lds, grid, threads, lds2).  Raises MfvitError where the launch would refuse
+    the shape (-22 / -38)."""
+    out = (_lib.ctypes.c_int32 * 6)()
+    check(lib().mfvit_attention_plan(code, B, T, heads, head_dim, int(bool(backward)), out), "mfvit_attention_plan")
+    return dict(family=ATTN_FAMILIES[out[0]], tiles=out[1], lds=out[2], grid=out[3], threads=out[4], lds2=out[5])
+
+
 def linear_fwd(x, w, bias=None, gelu=False, split=False, want_grad=True, qkv_f16=False):
     """y = x @ w.T + bias (x [M,K], w [N,K] of the same dtype).  gelu=True returns (gelu'(y), gelu(y)); want_grad=False skips the
     derivative (returns (None, gelu(y))).  split=True: x, w and the results are split-bf16 storage ([M,2K], [N,2K] -> [M,2N]) - except
