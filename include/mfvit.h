@@ -989,6 +989,26 @@ int mfvit_grad_clip_coef(const float* partials, const int32_t* row_tensor, int n
                          float* per_tensor, float* out2, mfvit_stream_t stream);
 int mfvit_grad_scale(const int64_t* table, int nchunks, const float* coef, mfvit_stream_t stream);
 
+/* Sharpness-aware minimisation over the same chunk tables (additive in ABI 5): the perturb / restore pair of SAM (Foret et al. 2021,
+ * e = rho g / |g|) and ASAM (Kwon et al. 2021, e = rho w^2 g / | |w| g |), as davda54/sam's first_step / second_step compute them.  state0 of a
+ * row is old_p, the copy of the parameters the second step restores; flag bit 0 of a row says "adaptive".  No atomics, fixed summation order:
+ * the same inputs give the same bits.
+ *
+ * mfvit_sam_norm_partials: partials[row] = the row's sum of g^2 (adaptive = 0: the bits of mfvit_grad_norm_partials with norm_kind 0) or of
+ *   t^2 with t = |w| g rounded to float once (adaptive = 1), in the same summation order; a NaN element gives a NaN partial.  Nothing is
+ *   written but the partials.  Several tables take part in one total by writing to consecutive ranges of one buffer.
+ * mfvit_sam_scale: one total over `nrows` partials, accumulated in double in row order.  out2[0] = the norm, out2[1] = 1 / (norm + 1e-12),
+ *   each rounded to float once - the group's rho is applied by mfvit_sam_perturb.  out2[1] = 0 exactly when the total is not finite, or when
+ *   found_inf (NULL, or the device flag of mfvit_amp_unscale) is not NULL and *found_inf != 0.
+ * mfvit_sam_perturb: inv points at out2[1] on the device.  *inv == 0: nothing is read or written.  Otherwise, per element, with every
+ *   product and the sum rounded to float on its own (nothing contracts to an fma): s = rho * *inv; e = g * s, or ((w * w) * g) * s in an
+ *   adaptive row; old_p = w; w = w + e.  The gradient is not written.
+ * mfvit_sam_restore: w = old_p over every row, unless *inv == 0 (nothing was perturbed: nothing is read or written). */
+int mfvit_sam_norm_partials(const int64_t* table, int nchunks, int adaptive, float* partials, mfvit_stream_t stream);
+int mfvit_sam_scale(const float* partials, int nrows, const float* found_inf, float* out2, mfvit_stream_t stream);
+int mfvit_sam_perturb(const int64_t* table, int nchunks, const float* inv, float rho, mfvit_stream_t stream);
+int mfvit_sam_restore(const int64_t* table, int nchunks, const float* inv, mfvit_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -287,6 +287,168 @@ __global__ __launch_bounds__(256) void grad_scale_kernel(const long* __restrict_
     if (t < ntail) tail[t] *= c;
 }
 
+// ---- sharpness-aware minimisation (SAM, Foret et al. 2021; ASAM, Kwon et al. 2021): norm pass -> scale -> perturb ... restore, on the same tables
+// with state0 = old_p.  The norm must be complete before the first parameter moves (every e depends on the total), so perturb cannot fuse with it.
+// Four floats from p: one 16-byte load when p is on a boundary (`vec`), four 4-byte loads otherwise.
+__device__ __forceinline__ float4 load4(const float* p, bool vec) {
+    if (vec) return *(const float4*)p;
+    return make_float4(p[0], p[1], p[2], p[3]);
+}
+// A product / a sum rounded to float on its own.  (__fmul_rn / __fadd_rn of this toolchain are a plain `x * y` / `x + y`, which the default
+// -ffp-contract=fast-honor-pragmas fuses into an fma with its neighbour: the pragma is what keeps them apart.)
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ float add_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+// the addend of the adaptive norm: t = |w| g rounded once, t^2 goes into the fmaf unrounded
+__device__ __forceinline__ float asam_t(float w, float g) { return mul_rn(fabsf(w), g); }
+
+// partials[row] = sum (|w| g)^2.  The split and the summation order are grad_norm_kernel<0>'s, taken from the GRADIENT pointer: head elements up to
+// g's 16-byte boundary, groups behind them, tail.  w is read in 16-byte groups when it has g's phase and element by element otherwise - the same
+// elements meet the same accumulators either way, so the partial does not depend on w's phase.  8 bytes of HBM traffic per element.
+__global__ __launch_bounds__(256) void sam_norm_adaptive_kernel(const long* __restrict__ tab, float* __restrict__ partials) {
+    const long* e = tab + (long)blockIdx.x * CH;
+    const float* w = (const float*)e[1];
+    const float* g = (const float*)e[2];
+    const long n = e[5];
+    const long head = grad_head(g, n);
+    const long n4 = (n - head) >> 2;
+    const bool wvec = (((size_t)w ^ (size_t)g) & 15) == 0;
+    const float* gb = g + head;
+    const float* wb = w + head;
+    const long toff = head + (n4 << 2);
+    const long ntail = n - toff;
+    const int t = threadIdx.x;
+    __shared__ float sc[4];
+    float s0 = 0.f, s1 = 0.f;
+    if (t < head) { const float x = asam_t(w[t], g[t]); s0 = x * x; }
+    for (long i = t; i < n4; i += 512) {
+        const long j = i + 256;
+        const bool two = j < n4;
+        const float4 ga = *(const float4*)(gb + (i << 2));
+        const float4 wa = load4(wb + (i << 2), wvec);
+        float4 gq = make_float4(0.f, 0.f, 0.f, 0.f), wq = gq;
+        if (two) { gq = *(const float4*)(gb + (j << 2)); wq = load4(wb + (j << 2), wvec); }
+        const float ax = asam_t(wa.x, ga.x), ay = asam_t(wa.y, ga.y), az = asam_t(wa.z, ga.z), aw = asam_t(wa.w, ga.w);
+        const float bx = asam_t(wq.x, gq.x), by = asam_t(wq.y, gq.y), bz = asam_t(wq.z, gq.z), bw = asam_t(wq.w, gq.w);
+        s0 = fmaf(ax, ax, s0); s0 = fmaf(ay, ay, s0); s0 = fmaf(az, az, s0); s0 = fmaf(aw, aw, s0);
+        s1 = fmaf(bx, bx, s1); s1 = fmaf(by, by, s1); s1 = fmaf(bz, bz, s1); s1 = fmaf(bw, bw, s1);
+    }
+    if (t < ntail) { const float x = asam_t(w[toff + t], g[toff + t]); s1 = fmaf(x, x, s1); }
+    const float s = block_sum<256>(s0 + s1, sc);
+    if (t == 0) partials[blockIdx.x] = s;
+}
+
+// One workgroup.  The total of the partials in double, in grad_clip_coef_kernel's order (thread t: rows t, t + 256, ... then the tree), then
+// out2[0] = |.|, out2[1] = 1 / (|.| + 1e-12) - the rho of `rho / (grad_norm + 1e-12)` belongs to the param group and is applied by the perturb
+// pass.  out2[1] = 0 says "do not move": the total is not finite, or the GradScaler's flag is set.
+__global__ __launch_bounds__(256) void sam_scale_kernel(const float* __restrict__ partials, int nrows, const float* __restrict__ found_inf,
+                                                        float* __restrict__ out2) {
+    const int t = threadIdx.x;
+    __shared__ double red[256];
+    double acc = 0.0;
+    for (int r = t; r < nrows; r += 256) acc += (double)partials[r];
+    red[t] = acc;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (t < o) red[t] += red[t + o];
+        __syncthreads();
+    }
+    if (t == 0) {
+        const double total = sqrt(red[0]);
+        const bool ok = total <= 1.7976931348623157e308 && !(found_inf && *found_inf != 0.f);      // (a NaN total compares false)
+        out2[0] = (float)total;
+        out2[1] = ok ? (float)(1.0 / (total + 1e-12)) : 0.f;
+    }
+}
+
+// e = g s (flag bit 0: e = ((w w) g) s), old_p = w, w = w + e with s = rho *inv; every product and the sum rounded on its own (no fma), so a host
+// restatement gives the same bits.  16 bytes of HBM traffic per element; *inv == 0 returns before any other access.
+__device__ __forceinline__ float sam_elem(float w, float g, float s, bool adaptive) {
+    const float e = adaptive ? mul_rn(mul_rn(mul_rn(w, w), g), s) : mul_rn(g, s);
+    return add_rn(w, e);
+}
+__device__ __forceinline__ float4 sam_elem4(float4 w, float4 g, float s, bool adaptive) {
+    return make_float4(sam_elem(w.x, g.x, s, adaptive), sam_elem(w.y, g.y, s, adaptive), sam_elem(w.z, g.z, s, adaptive), sam_elem(w.w, g.w, s, adaptive));
+}
+__global__ __launch_bounds__(256) void sam_perturb_kernel(const long* __restrict__ tab, const float* __restrict__ inv, float rho) {
+    const float iv = *inv;
+    if (iv == 0.f) return;
+    const float s = mul_rn(rho, iv);
+    const long* e = tab + (long)blockIdx.x * CH;
+    float* w = (float*)e[1];
+    const float* g = (const float*)e[2];
+    float* old = (float*)e[3];
+    const long n = e[5];
+    const bool adaptive = e[6] & 1;
+    const int t = threadIdx.x;
+    if (((((size_t)w ^ (size_t)g) | ((size_t)w ^ (size_t)old)) & 15) != 0) {       // the three phases differ: element by element
+        for (long i = t; i < n; i += 256) {
+            const float wv = w[i];
+            old[i] = wv;
+            w[i] = sam_elem(wv, g[i], s, adaptive);
+        }
+        return;
+    }
+    const long head = grad_head(w, n);
+    const long n4 = (n - head) >> 2;
+    float4* w4 = (float4*)(w + head);
+    const float4* g4 = (const float4*)(g + head);
+    float4* o4 = (float4*)(old + head);
+    const long toff = head + (n4 << 2);
+    const long ntail = n - toff;
+    if (t < head) { const float wv = w[t]; old[t] = wv; w[t] = sam_elem(wv, g[t], s, adaptive); }
+    for (long i = t; i < n4; i += 512) {
+        const long j = i + 256;
+        const bool two = j < n4;
+        const float4 wa = w4[i], ga = g4[i];
+        float4 wb = wa, gb = ga;
+        if (two) { wb = w4[j]; gb = g4[j]; }
+        o4[i] = wa;
+        w4[i] = sam_elem4(wa, ga, s, adaptive);
+        if (two) {
+            o4[j] = wb;
+            w4[j] = sam_elem4(wb, gb, s, adaptive);
+        }
+    }
+    if (t < ntail) { const float wv = w[toff + t]; old[toff + t] = wv; w[toff + t] = sam_elem(wv, g[toff + t], s, adaptive); }
+}
+
+// w = old_p: 8 bytes of HBM traffic per element, none when nothing was perturbed (*inv == 0)
+__global__ __launch_bounds__(256) void sam_restore_kernel(const long* __restrict__ tab, const float* __restrict__ inv) {
+    if (*inv == 0.f) return;
+    const long* e = tab + (long)blockIdx.x * CH;
+    float* w = (float*)e[1];
+    const float* old = (const float*)e[3];
+    const long n = e[5];
+    const int t = threadIdx.x;
+    if ((((size_t)w ^ (size_t)old) & 15) != 0) {
+        for (long i = t; i < n; i += 256) w[i] = old[i];
+        return;
+    }
+    const long head = grad_head(w, n);
+    const long n4 = (n - head) >> 2;
+    float4* w4 = (float4*)(w + head);
+    const float4* o4 = (const float4*)(old + head);
+    const long toff = head + (n4 << 2);
+    const long ntail = n - toff;
+    if (t < head) w[t] = old[t];
+    for (long i = t; i < n4; i += 512) {
+        const long j = i + 256;
+        const bool two = j < n4;
+        const float4 a = o4[i];
+        float4 b = a;
+        if (two) b = o4[j];
+        w4[i] = a;
+        if (two) w4[j] = b;
+    }
+    if (t < ntail) w[toff + t] = old[toff + t];
+}
+
 }  // namespace mfvit
 
 using namespace mfvit;
@@ -342,6 +504,33 @@ int mfvit_grad_clip_coef(const float* partials, const int32_t* row_tensor, int n
 int mfvit_grad_scale(const int64_t* table, int nchunks, const float* coef, mfvit_stream_t stream) {
     if (!table || !coef || nchunks <= 0) return MFVIT_EINVAL;
     MFVIT_LAUNCH(grad_scale_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, (const long*)table, coef);
+    MFVIT_CHECK_LAUNCH();
+    return MFVIT_OK;
+}
+int mfvit_sam_norm_partials(const int64_t* table, int nchunks, int adaptive, float* partials, mfvit_stream_t stream) {
+    if (!table || !partials || nchunks <= 0 || (adaptive != 0 && adaptive != 1)) return MFVIT_EINVAL;
+    if (adaptive == 0)          // the plain L2 norm of the gradients: the clipping kernel itself, so the partials are its bits
+        MFVIT_LAUNCH(grad_norm_kernel<0>, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, (const long*)table, partials);
+    else
+        MFVIT_LAUNCH(sam_norm_adaptive_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, (const long*)table, partials);
+    MFVIT_CHECK_LAUNCH();
+    return MFVIT_OK;
+}
+int mfvit_sam_scale(const float* partials, int nrows, const float* found_inf, float* out2, mfvit_stream_t stream) {
+    if (!partials || !out2 || nrows <= 0) return MFVIT_EINVAL;
+    MFVIT_LAUNCH(sam_scale_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, nrows, found_inf, out2);
+    MFVIT_CHECK_LAUNCH();
+    return MFVIT_OK;
+}
+int mfvit_sam_perturb(const int64_t* table, int nchunks, const float* inv, float rho, mfvit_stream_t stream) {
+    if (!table || !inv || nchunks <= 0) return MFVIT_EINVAL;
+    MFVIT_LAUNCH(sam_perturb_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, (const long*)table, inv, rho);
+    MFVIT_CHECK_LAUNCH();
+    return MFVIT_OK;
+}
+int mfvit_sam_restore(const int64_t* table, int nchunks, const float* inv, mfvit_stream_t stream) {
+    if (!table || !inv || nchunks <= 0) return MFVIT_EINVAL;
+    MFVIT_LAUNCH(sam_restore_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, (const long*)table, inv);
     MFVIT_CHECK_LAUNCH();
     return MFVIT_OK;
 }

@@ -151,6 +151,10 @@ SIGNATURES = {
     "mfvit_grad_norm_partials": (I, [P, I, I, P, P]),
     "mfvit_grad_clip_coef": (I, [P, P, I, I, I, D, P, P, P]),
     "mfvit_grad_scale": (I, [P, I, P, P]),
+    "mfvit_sam_norm_partials": (I, [P, I, I, P, P]),
+    "mfvit_sam_scale": (I, [P, I, P, P, P]),
+    "mfvit_sam_perturb": (I, [P, I, P, F, P]),
+    "mfvit_sam_restore": (I, [P, I, P, P]),
     "mfvit_prenorm_xattn_forward": (I, [POINTER(FusionCfg), P, P, P, P, P, P]),
     "mfvit_prenorm_xattn_backward": (I, [POINTER(FusionCfg), P, P, P, P, P, P, P, P, P]),
     "mfvit_xattn_forward": (I, [POINTER(FusionCfg), P, P, P, P, P]),

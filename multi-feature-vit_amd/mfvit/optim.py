@@ -10,7 +10,8 @@ The device chunk tables are runtime caches of raw addresses: they live on the op
 which ``state_dict()`` pickles), are keyed by every address a row holds (parameter, gradient, both state tensors), and are dropped by
 ``load_state_dict``.
 
-``clip_grad_norm_`` / ``grad_norm`` (torch.nn.utils.clip_grad_norm_) run over the same tables: they take the optimizer, not the parameters.
+``clip_grad_norm_`` / ``grad_norm`` (torch.nn.utils.clip_grad_norm_) run over the same tables: they take the optimizer, not the parameters.  ``SAM`` (davda54/sam's wrapper: sharpness-aware minimisation, adaptive or not) perturbs and restores the
+parameters over tables of its own, whose one state column is the scratch copy ``old_p``; what it saves and loads is the base optimizer's state.
 """
 import torch
 
@@ -278,6 +279,129 @@ class SGD(_TableOptimizer):
             check(lib().mfvit_sgd_step(ptr(table), table.shape[0], float(g["lr"]), float(g["momentum"]), float(g["weight_decay"]), 0,
                                        stream()), "mfvit_sgd_step")
             _bump_versions(live)
+
+
+# ------------------------------------------------------------------------------------------------ sharpness-aware minimisation
+class SAM(_TableOptimizer):
+    """davda54/sam's ``SAM(params, base_optimizer, rho=0.05, adaptive=False, **kwargs)`` (Foret et al. 2021; adaptive=True: ASAM, Kwon et al. 2021)
+    on the chunk tables.  ``base_optimizer`` is one of this module's CLASSES; ``kwargs`` are its hyperparameters.  ``param_groups`` are the base
+    optimizer's own list, with ``rho`` / ``adaptive`` as group keys; ONE norm is taken over all groups.
+
+        loss_fn(model(x), y).backward();  opt.first_step(zero_grad=True)      # w += rho g / |g|   (ASAM: rho w^2 g / | |w| g |)
+        loss_fn(model(x), y).backward();  opt.second_step(zero_grad=True)     # w = old_p, then the base optimizer's step on the new gradients
+
+    or ``opt.step(closure)``.  first_step: a norm pass per table (mfvit_sam_norm_partials), one finalize (mfvit_sam_scale), a perturb pass per table
+    (mfvit_sam_perturb); second_step: a restore pass per table (mfvit_sam_restore) and the base step.  Both tell the weight-shadow caches that the
+    parameters moved.  Nothing waits for the GPU.  With a GradScaler pass ``scaler=`` to both steps and call ``scaler.update()`` afterwards: an
+    overflow in either backward moves nothing (decided on the device) and skips the base step.  ``old_p`` is scratch of this object:
+    ``state_dict()`` / ``load_state_dict()`` are the base optimizer's, so checkpoints move between SAM and plain runs."""
+    state_names = ("old_p",)
+
+    def __init__(self, params, base_optimizer, rho=0.05, adaptive=False, **kwargs):
+        if not (isinstance(base_optimizer, type) and issubclass(base_optimizer, _TableOptimizer)) or issubclass(base_optimizer, SAM):
+            raise TypeError("mfvit.optim.SAM takes one of the optimizer classes of mfvit.optim (Adam, AdamW, SGD, LARS) as base_optimizer, not "
+                            f"{base_optimizer!r}: the device chunk tables the kernels stream over live on the optimizer")
+        if not rho >= 0.0:
+            raise ValueError(f"Invalid rho, should be non-negative: {rho}")
+        super().__init__(params, dict(rho=rho, adaptive=adaptive, **kwargs))
+        self.base_optimizer = base_optimizer(self.param_groups, **kwargs)
+        self.param_groups = self.base_optimizer.param_groups
+        self.defaults.update(self.base_optimizer.defaults)
+        self._pending = None       # (tables of the perturbed rows with their live parameters, out2) between first_step and second_step
+
+    def _flag(self, p, group):
+        return 1 if group["adaptive"] else 0
+
+    def _table(self, gi, group):
+        cache = self._cache().setdefault(gi, {})
+        if cache.get("adaptive") != bool(group["adaptive"]):     # the flag column is part of a table
+            cache.clear()
+            cache["adaptive"] = bool(group["adaptive"])
+        return super()._table(gi, group)
+
+    def state_dict(self):
+        return self.base_optimizer.state_dict()
+
+    def load_state_dict(self, state_dict):
+        mine = [(g["rho"], g["adaptive"]) for g in self.param_groups]
+        self.base_optimizer.load_state_dict(state_dict)
+        self.param_groups = self.base_optimizer.param_groups
+        for g, (rho, adaptive) in zip(self.param_groups, mine):       # a checkpoint of a plain run has no SAM keys: the groups keep theirs
+            g.setdefault("rho", rho)
+            g.setdefault("adaptive", adaptive)
+        self._cache().clear()
+
+    def clip_grad_norm_(self, max_norm, norm_type=2.0, error_if_nonfinite=False, per_tensor=False):
+        return self.base_optimizer.clip_grad_norm_(max_norm, norm_type, error_if_nonfinite, per_tensor)
+
+    @torch.no_grad()
+    def first_step(self, zero_grad=False, scaler=None):
+        if self._pending is not None:
+            raise RuntimeError("SAM.first_step() was called twice in a row: the parameters are perturbed, call second_step() first")
+        flag = None
+        if scaler is not None and scaler.is_enabled():
+            dev = next(p for g in self.param_groups for p in g["params"]).device
+            flag = scaler._flag(dev)
+            self.unscale_(1.0 / scaler.get_scale(), flag)       # not registered with the scaler: these gradients never reach a step
+        scratch = self._cache().setdefault("sam", {})
+        part = scratch.get("partials")
+        tabs, rows = [], 0
+        for gi, g in enumerate(self.param_groups):
+            self._pre(gi)
+            table, _, live = self._table(gi, g)
+            if table is None:
+                continue
+            nrows = table.shape[0]
+            if part is None or rows + nrows > part.numel():
+                grown = torch.empty(max(1024, rows + nrows, 2 * (0 if part is None else part.numel())), device=table.device, dtype=torch.float32)
+                if rows:
+                    grown[:rows].copy_(part[:rows])
+                part = scratch["partials"] = grown
+            check(lib().mfvit_sam_norm_partials(ptr(table), nrows, 1 if g["adaptive"] else 0, part.data_ptr() + 4 * rows, stream()),
+                  "mfvit_sam_norm_partials")
+            tabs.append((table, live, float(g["rho"])))
+            rows += nrows
+        out = None
+        if tabs:
+            out = torch.empty(2, device=part.device, dtype=torch.float32)      # a fresh pair per step: second_step reads out[1]
+            check(lib().mfvit_sam_scale(ptr(part), rows, ptr(flag), ptr(out), stream()), "mfvit_sam_scale")
+            for table, live, rho in tabs:
+                check(lib().mfvit_sam_perturb(ptr(table), table.shape[0], out.data_ptr() + 4, rho, stream()), "mfvit_sam_perturb")
+                _bump_versions(live)
+        self._pending = (tabs, out)
+        if zero_grad:
+            self.zero_grad()
+
+    @torch.no_grad()
+    def second_step(self, zero_grad=False, scaler=None):
+        if self._pending is None:
+            raise RuntimeError("SAM.second_step() needs a first_step() before it")
+        cb = self.__dict__.get("before_group")
+        if cb is not None:
+            self.base_optimizer.before_group = cb
+        for gi in range(len(self.param_groups)):
+            self._pre(gi)
+        if scaler is not None and scaler.is_enabled() and id(self.base_optimizer) not in scaler._unscaled:      # (the caller unscales first to clip)
+            scaler.unscale_(self.base_optimizer)
+        # the rows first_step perturbed (its tables: the gradients, and with them the live set, may have changed since); the device decides
+        tabs, out = self._pending
+        self._pending = None
+        for table, live, _ in tabs:
+            check(lib().mfvit_sam_restore(ptr(table), table.shape[0], out.data_ptr() + 4, stream()), "mfvit_sam_restore")
+            _bump_versions(live)
+        ret = scaler.step(self.base_optimizer) if scaler is not None else self.base_optimizer.step()
+        if zero_grad:
+            self.zero_grad()
+        return ret
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        if closure is None:
+            raise RuntimeError("SAM.step() needs a closure that runs the second forward and backward pass")
+        closure = torch.enable_grad()(closure)
+        self.first_step(zero_grad=True)
+        closure()
+        return self.second_step()
 
 
 # ------------------------------------------------------------------------------------------------ gradient-norm clipping
