@@ -161,6 +161,44 @@ size_t mfvit_vit_workspace_bytes_ex(const mfvit_vit_cfg* cfg, const mfvit_vit_dr
 int mfvit_vit_backward_ex(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, const float* params, const void* shadow, void* workspace,
                           const float* dfeatures, float* dparams, float* dimg, int stage_hi, int stage_lo, mfvit_stream_t stream);
 
+/* Patch dropout (additive in ABI 5; mfvit_vit_cfg and mfvit_vit_drop keep their layout): timm >= 0.9 PatchDropout(prob, num_prefix_tokens = 1)
+ * - Liu et al. 2022 "PatchDropout", FLIP.  In training mode the blocks run on cls and K = max(1, int(L (1 - prob))) of the L patch rows per image.
+ *
+ * (1) The image-mode stack on a GIVEN x_0.  cfg: an ordinary image-mode cfg (token_input = 0); params / shadow in the layouts of the full grid (the
+ *   arena's pos_embed keeps 1 + gh gw rows, not read here); every activation, the workspace (mfvit_vit_workspace_bytes_x0) and every launch at
+ *   `tokens` rows per image, 2 <= tokens <= 1 + gh gw.  x0: (batch, tokens, dim) f32 = cat(cls, kept patch embeddings) + their pos_embed rows; the
+ *   forward's embedding stage is one LayerNorm row pass (drop->drop > 0: timm's pos_drop on the shortened rows, site 1), the blocks run exactly as in
+ *   image mode, every site of mfvit_vit_drop and the drop path included (per-sample factors: sample = row / tokens).  features: (batch, tokens, dim).
+ *   Backward: stages as mfvit_vit_backward; stage -1 forms NO parameter gradient, it writes dx0 (batch, tokens, dim) f32 = d loss / d x0 (required
+ *   non-NULL in every call; written by the call with stage_lo == -1).  dparams == NULL: the data-gradient chain alone, as mfvit_vit_backward_ex.
+ *   MFVIT_EINVAL before any HIP call (size query: 0) for tokens out of range, a token-input cfg, a cfg mfvit_vit_forward refuses for the full grid
+ *   (the fp32 limit on the attention kernels' LDS below among them: a shorter sequence only needs less) or a NULL pointer. */
+size_t mfvit_vit_workspace_bytes_x0(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, int tokens);
+int mfvit_vit_forward_x0(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, int tokens, const float* params, const void* shadow, const float* x0,
+                         void* workspace, float* features, mfvit_stream_t stream);
+int mfvit_vit_backward_x0(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, int tokens, const float* params, const void* shadow, void* workspace,
+                          const float* dfeatures, float* dparams, float* dx0, int stage_hi, int stage_lo, mfvit_stream_t stream);
+/* (2) The front end of timm's PatchDropout: the embedding stage on the kept patches.  idx: (batch, keep) int64 patch indices in [0, L), L = (img_h /
+ *   16)(img_w / 16), row-major over the grid, distinct per image (the caller's duty; timm: argsort(randn(B, L))[:, :keep]).
+ *   mfvit_patch_keep_embed: the im2col rows of the kept patches only (batch keep x 768, operand type and column order of the encoder's im2col), the patch
+ *   GEMM with bias, then x0[b, 1 + k] = row + pos_embed[1 + idx[b, k]] and x0[b, 0] = cls_token + pos_embed[0]; x0 (batch, 1 + keep, dim) f32.  pe_w: the
+ *   f32 (dim, 768) weight (cast here).  save != 0: the workspace has mfvit_patch_keep_workspace_bytes(cfg, 1) bytes and keeps what the backward reads.
+ *   mfvit_patch_keep_embed_bwd, from dx0 = d loss / d x0, on the forward's workspace: dcls += column sum of the cls rows, dpe_b += column sum of the kept
+ *   rows, dpe_w (dim, 768) += dx0[kept]^T patches_kept, each NULL = skipped (stop_grad_conv1; a frozen backbone), and dimg (batch, 3, img_h, img_w) f32
+ *   (or NULL) OVERWRITTEN with dx0[kept] W_pe put back through the inverse of the gather: dropped patches are exact zeros.  Every sum runs in a fixed
+ *   order without float atomics: the same bits on every run.
+ *   err: one int32 on the device, zero before the first call: an index outside [0, L) sets it to 1, its row is zeros and it never becomes an address;
+ *   the caller reads the word when it likes.  MFVIT_EINVAL before any HIP call (size query: 0): dtype, batch <= 0, a size no multiple of 16, dim other
+ *   than 384 / 768, keep outside [1, L], batch keep 768 >= 2^31, a NULL pointer. */
+typedef struct mfvit_patch_keep_cfg {
+    int dtype, batch, img_h, img_w, keep, dim;
+} mfvit_patch_keep_cfg;
+size_t mfvit_patch_keep_workspace_bytes(const mfvit_patch_keep_cfg* cfg, int backward);
+int mfvit_patch_keep_embed(const mfvit_patch_keep_cfg* cfg, const float* img, const int64_t* idx, const float* cls_token, const float* pos_embed,
+                           const float* pe_w, const float* pe_b, void* workspace, int save, float* x0, int32_t* err, mfvit_stream_t stream);
+int mfvit_patch_keep_embed_bwd(const mfvit_patch_keep_cfg* cfg, const int64_t* idx, void* workspace, const float* dx0, float* dcls, float* dpe_w,
+                               float* dpe_b, float* dimg, int32_t* err, mfvit_stream_t stream);
+
 /* Hidden states of the image encoder (host only, additive in ABI 5).  Where the residual stream lies in the workspace after mfvit_vit_forward
  * with save_for_backward = 1: hidden state l (l = 0: cls + patch embedding + pos_embed, the input of block 0; l = 1 .. depth: the output of
  * block l - 1, before the final norm) is f32 [batch * tokens][dim], image-major, at workspace + out[0] + l * out[1] bytes.  f32 in every

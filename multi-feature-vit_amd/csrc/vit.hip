@@ -29,6 +29,8 @@ namespace {
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct Dims {
+    int Tp;                             // token rows of the ARENA's pos_embed (= T, but for the given-x0 entry points: 1 + gh gw there, T = the shortened sequence)
+    bool x0in;                          // given-x0 entry points (mfvit_vit_forward_x0): the embedding stage is the caller's, stage -1 of the backward writes d x_0
     int dtype, B, T, np, D, depth, H, HD, F, M, Mp, es, ep;   // es: bytes per LOGICAL element of a dtype tensor; ep: storage elements per logical one
     bool save, tok, use_pos;
     int act;
@@ -55,6 +57,8 @@ bool get_dims(const mfvit_vit_cfg* c, Dims& d) {
     d.B = c->batch;
     d.np = d.tok ? c->tokens : (c->img_h / 16) * (c->img_w / 16);
     d.T = d.tok ? c->tokens : d.np + 1;
+    d.Tp = d.T;
+    d.x0in = false;
     d.use_pos = c->use_pos != 0;
     d.act = c->act;
     d.D = c->dim;
@@ -116,6 +120,18 @@ bool get_dims(const mfvit_vit_cfg* c, const mfvit_vit_drop* x, Dims& d) {
     return true;
 }
 
+// The image-mode stack on a given x_0 of `tokens` rows per image (mfvit_vit_forward_x0; timm PatchDropout shortens the sequence in front of the
+// blocks): an ordinary image-mode cfg whose arena keeps the full grid (Tp = 1 + gh gw rows of pos_embed), every activation and launch at T = tokens.
+// (the limits of get_dims hold for the full grid - the same model runs it in eval() - and with them for every shorter sequence)
+bool get_dims_x0(const mfvit_vit_cfg* c, const mfvit_vit_drop* x, int tokens, Dims& d) {
+    if (!get_dims(c, x, d) || d.tok) return false;
+    if (tokens < 2 || tokens > d.Tp) return false;
+    d.T = tokens;
+    d.M = d.B * tokens;
+    d.x0in = true;
+    return true;
+}
+
 // ------------------------------------------------------------------ parameter arena layout (floats)
 struct ParamLayout {
     long cls, pos, pe_w, pe_b, blk0, blk_stride, norm_w, norm_b, total;
@@ -127,7 +143,7 @@ ParamLayout param_layout(const Dims& d) {
     const long D = d.D, F = d.F;
     long o = 0;
     L.cls = o; o += d.tok ? 0 : D;                   // token-input mode: no cls token, no patch embedding
-    L.pos = o; o += (long)d.T * D;
+    L.pos = o; o += (long)d.Tp * D;
     L.pe_w = o; o += d.tok ? 0 : D * 768;
     L.pe_b = o; o += d.tok ? 0 : D;
     L.blk0 = o;
@@ -204,7 +220,7 @@ WsLayout ws_layout(const Dims& d) {
     const size_t M = d.M, D = d.D, F = d.F, es = d.es;
     const size_t nl = d.save ? d.depth : 1;
     size_t o = 0;
-    W.patches = o; o += d.tok ? 0 : align256((size_t)d.Mp * 768 * es);
+    W.patches = o; o += (d.tok || d.x0in) ? 0 : align256((size_t)d.Mp * 768 * es);
     W.x0 = o; W.x_stride = align256(M * D * 4); o += W.x_stride * (d.save ? d.depth + 1 : 1);
     W.st0 = o; W.st_stride = align256(2 * M * 4); o += W.st_stride * (d.save ? d.depth + 1 : 1);
     W.blk0 = o;
@@ -255,7 +271,7 @@ WsLayout ws_layout(const Dims& d) {
     W.utmp = o; o += align256(M * D * es);     // always there (1 / 200 of the workspace): the layout does not depend on which path a call takes
     W.domax = o; o += d.save ? align256((size_t)d.depth * d.B * d.H * 4) : 0;
     W.total = o;
-    W.wpeT = o; o += (d.save && !d.tok) ? align256((size_t)768 * D * es) : 0;
+    W.wpeT = o; o += (d.save && !d.tok && !d.x0in) ? align256((size_t)768 * D * es) : 0;
     W.total_dimg = o;
     return W;
 }
@@ -646,6 +662,12 @@ static int fwd_embed(const EncCtx& c, const float* img) {
     char* const y1_0 = c.blk(0) + c.W.y1;
     const float *const g0 = c.pblk(0) + c.L.ln1_w, *const b0 = c.pblk(0) + c.L.ln1_b;
     float *const mean0 = c.stat(0), *const rstd0 = c.stat(0) + d.M;
+    if (d.x0in && d.p_embd > 0.f)
+        // given x_0 (img = (B, T, D) f32: cat(cls, kept patches) + their pos_embed rows): timm pos_drop on the shortened rows; LN1_0 -> y1_0
+        return drop_add_ln_rows(d.dtype, d.D, nullptr, 0, img, D, nullptr, 0, 0, nullptr, 0, make_drop(d.p_embd, d.seed, 1), c.off, 1, x0, D, y1_0, De, 0,
+                                g0, b0, c.eps, mean0, rstd0, d.M, c.st);
+    if (d.x0in)
+        return ln_rows(d.dtype, d.D, img, D, nullptr, 0, 0, x0, D, y1_0, De, 0, g0, b0, c.eps, mean0, rstd0, d.M, 1, 0, 0, c.st);
     if (d.tok && d.p_embd > 0.f)
         // x_0 = drop(tokens + pos_emb) (fuseattention.py:187 `self.drop(self.pos_emb + token_embeddings)`); LN1_0 -> y1_0
         return drop_add_ln_rows(d.dtype, d.D, nullptr, 0, img, D, d.use_pos ? pos : nullptr, D, d.T, nullptr, 0, make_drop(d.p_embd, d.seed, 1), c.off, 1,
@@ -742,9 +764,10 @@ static int fwd_block(const EncCtx& c, int l, float* features, const mfvit_vit_at
 // (img = (B,T,dim) tokens, + pos_emb).  Everything behind x_0 / LN1_0 is the same pre-LN block stack.
 static int encoder_forward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* dropcfg, const float* params, const void* shadow, const float* img,
                            void* workspace, float* features, mfvit_stream_t stream, bool want_tokens,
-                           const mfvit_vit_attn_req* attn = nullptr) {
+                           const mfvit_vit_attn_req* attn = nullptr, int x0_tokens = 0) {
     Dims d;
-    if (!get_dims(cfg, dropcfg, d) || !params || !shadow || !img || !workspace || !features) return MFVIT_EINVAL;
+    if (!(x0_tokens ? get_dims_x0(cfg, dropcfg, x0_tokens, d) : get_dims(cfg, dropcfg, d)) || !params || !shadow || !img || !workspace || !features)
+        return MFVIT_EINVAL;
     if (d.tok != want_tokens) return MFVIT_EINVAL;
     const EncCtx c(cfg, d, params, shadow, workspace, stream);
     MFVIT_TRY(fwd_embed(c, img));
@@ -989,6 +1012,17 @@ static int bwd_embed_tokens(BwdCtx& c) {
     return MFVIT_OK;
 }
 
+// given-x0 embedding stage: gx = d x_0 (through pos_drop) -> dinput; no parameter gradient is formed here (the caller's front end owns cls_token and
+// the patch embedding)
+static int bwd_embed_x0(BwdCtx& c) {
+    const Dims& d = c.d;
+    MFVIT_TRY(colpart_batch_flush(c.st));
+    if (d.p_embd > 0.f)
+        MFVIT_TRY(mask_scale_rows(d.dtype, true, c.gx, c.D, c.gx, c.D, make_drop(d.p_embd, d.seed, 1), c.off, 1, d.M, d.D, c.st));
+    if (hipMemcpyAsync(c.dinput, c.gx, (size_t)d.M * c.D * sizeof(float), hipMemcpyDeviceToDevice, c.st) != hipSuccess) return MFVIT_ELAUNCH;
+    return MFVIT_OK;
+}
+
 // image embedding stage: gx = d x_0 -> d img (the patch-embedding data gradient), d cls_token, d pe_b, d pe_w
 static int bwd_embed_image(BwdCtx& c) {
     const Dims& d = c.d;
@@ -1036,9 +1070,10 @@ static int bwd_embed_image(BwdCtx& c) {
 // Shared backward of the two front ends (BwdArgs: what is asked for): stages stage_hi .. stage_lo in descending order - depth: the final norm,
 // depth-1 .. 0: the blocks, -1: the embedding - then whatever the stages left pending.
 static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* dropcfg, const float* params, const void* shadow, void* workspace,
-                            const BwdArgs& a, mfvit_stream_t stream, bool want_tokens) {
+                            const BwdArgs& a, mfvit_stream_t stream, bool want_tokens, int x0_tokens = 0) {
     Dims d;
-    if (!get_dims(cfg, dropcfg, d) || !params || !shadow || !workspace || (!a.dparams && !a.dimg && !a.rel && !a.lora)) return MFVIT_EINVAL;
+    if (!(x0_tokens ? get_dims_x0(cfg, dropcfg, x0_tokens, d) : get_dims(cfg, dropcfg, d)) || !params || !shadow || !workspace) return MFVIT_EINVAL;
+    if (x0_tokens ? (!a.dinput || a.dimg || a.rel || a.lora) : (!a.dparams && !a.dimg && !a.rel && !a.lora)) return MFVIT_EINVAL;
     if (!d.save || d.tok != want_tokens) return MFVIT_EINVAL;
     if (a.stage_hi > d.depth || a.stage_lo < -1 || a.stage_lo > a.stage_hi) return MFVIT_EINVAL;
     if (a.dimg && (d.tok || a.stage_lo != -1)) return MFVIT_EINVAL;
@@ -1048,7 +1083,7 @@ static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop
         if (l1 >= l0 && hipMemsetAsync(c.domax(l0), 0, (size_t)(l1 - l0 + 1) * d.B * d.H * 4, c.st) != hipSuccess) return MFVIT_ELAUNCH;
     }
     for (int s = a.stage_hi; s >= a.stage_lo; --s)
-        MFVIT_TRY(s == d.depth ? bwd_final_norm(c) : s >= 0 ? bwd_block(c, s) : d.tok ? bwd_embed_tokens(c) : bwd_embed_image(c));
+        MFVIT_TRY(s == d.depth ? bwd_final_norm(c) : s >= 0 ? bwd_block(c, s) : d.x0in ? bwd_embed_x0(c) : d.tok ? bwd_embed_tokens(c) : bwd_embed_image(c));
     MFVIT_TRY(colpart_batch_flush(c.st));
     MFVIT_TRY(tnpart_batch_flush(c.q.s));   // dW += the split partials still pending (the patch embedding's), splits in a fixed order
     if (a.lora) MFVIT_TRY(lora_run(d, a.lora->req, a.lora->dw, nullptr, true, c.st));   // dA, dB of every item from the dW_eff slices
@@ -1104,6 +1139,23 @@ int mfvit_vit_backward_ex(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, 
                           const float* dfeatures, float* dparams, float* dimg, int stage_hi, int stage_lo, mfvit_stream_t stream) {
     ShareScope share(cfg);
     return encoder_backward(cfg, drop, params, shadow, workspace, {dfeatures, dparams, nullptr, dimg, stage_hi, stage_lo}, stream, false);
+}
+size_t mfvit_vit_workspace_bytes_x0(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, int tokens) {
+    Dims d;
+    if (!get_dims_x0(cfg, drop, tokens, d)) return 0;
+    return ws_layout(d).total;
+}
+int mfvit_vit_forward_x0(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, int tokens, const float* params, const void* shadow, const float* x0,
+                         void* workspace, float* features, mfvit_stream_t stream) {
+    if (tokens < 2) return MFVIT_EINVAL;
+    ShareScope share(cfg);
+    return encoder_forward(cfg, drop, params, shadow, x0, workspace, features, stream, false, nullptr, tokens);
+}
+int mfvit_vit_backward_x0(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, int tokens, const float* params, const void* shadow, void* workspace,
+                          const float* dfeatures, float* dparams, float* dx0, int stage_hi, int stage_lo, mfvit_stream_t stream) {
+    if (!cfg || tokens < 2 || !dx0 || (!dfeatures && stage_hi >= cfg->depth)) return MFVIT_EINVAL;
+    ShareScope share(cfg);
+    return encoder_backward(cfg, drop, params, shadow, workspace, {dfeatures, dparams, dx0, nullptr, stage_hi, stage_lo}, stream, false, tokens);
 }
 int mfvit_vit_backward_drop(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, const float* params, const void* shadow, void* workspace,
                             const float* dfeatures, float* dparams, int stage_hi, int stage_lo, mfvit_stream_t stream) {

@@ -32,6 +32,11 @@ class VitDrop(Structure):
     _fields_ = [("drop", c_float), ("attn_drop", c_float), ("drop_path", POINTER(c_float)), ("seed", c_uint64)]
 
 
+class PatchKeepCfg(Structure):
+    """mfvit_patch_keep_cfg: the patch-dropout front end's shape (include/mfvit.h; timm PatchDropout)."""
+    _fields_ = [("dtype", c_int), ("batch", c_int), ("img_h", c_int), ("img_w", c_int), ("keep", c_int), ("dim", c_int)]
+
+
 class VitAttnReq(Structure):
     """mfvit_vit_attn_req: which attention maps / rollout an evaluation forward writes (include/mfvit.h)."""
     _fields_ = [("blocks", c_uint64), ("fuse", c_int), ("cls_only", c_int), ("maps", c_void_p), ("rollout", c_void_p), ("scratch", c_void_p)]
@@ -82,6 +87,12 @@ SIGNATURES = {
     "mfvit_vit_backward_drop": (I, [POINTER(VitCfg), POINTER(VitDrop), P, P, P, P, P, I, I, P]),
     "mfvit_vit_workspace_bytes_ex": (c_size_t, [POINTER(VitCfg), POINTER(VitDrop), I]),
     "mfvit_vit_backward_ex": (I, [POINTER(VitCfg), POINTER(VitDrop), P, P, P, P, P, P, I, I, P]),
+    "mfvit_vit_workspace_bytes_x0": (c_size_t, [POINTER(VitCfg), POINTER(VitDrop), I]),
+    "mfvit_vit_forward_x0": (I, [POINTER(VitCfg), POINTER(VitDrop), I, P, P, P, P, P, P]),
+    "mfvit_vit_backward_x0": (I, [POINTER(VitCfg), POINTER(VitDrop), I, P, P, P, P, P, P, I, I, P]),
+    "mfvit_patch_keep_workspace_bytes": (c_size_t, [POINTER(PatchKeepCfg), I]),
+    "mfvit_patch_keep_embed": (I, [POINTER(PatchKeepCfg), P, P, P, P, P, P, P, I, P, P, P]),
+    "mfvit_patch_keep_embed_bwd": (I, [POINTER(PatchKeepCfg), P, P, P, P, P, P, P, P, P]),
     "mfvit_vit_hidden_layout": (I, [POINTER(VitCfg), POINTER(c_int64)]),
     "mfvit_vit_attn_layout": (I, [POINTER(VitCfg), POINTER(c_int64)]),
     "mfvit_vit_attn_scratch_bytes": (c_size_t, [POINTER(VitCfg), POINTER(VitAttnReq)]),

@@ -140,6 +140,31 @@ class DropPath(nn.Module):
         return f"drop_prob={self.drop_prob}"
 
 
+class PatchDropout(nn.Module):
+    """Rate carrier of timm >= 0.9 ``PatchDropout(prob, num_prefix_tokens=1, ordered=False)`` (Liu et al. 2022; FLIP): in training mode the blocks
+    run on cls and ``K = max(1, int(L * (1 - prob)))`` of the L patch rows per image.  The encoder's front end (csrc/patch_drop.hip) applies it,
+    this module is never called."""
+
+    def __init__(self, prob=0.0, num_prefix_tokens=1, ordered=False):
+        super().__init__()
+        self.prob = float(prob)
+        self.num_prefix_tokens = int(num_prefix_tokens)
+        self.ordered = bool(ordered)
+
+    def num_keep(self, L):
+        return max(1, int(L * (1.0 - self.prob)))
+
+    def draw(self, B, L, device):
+        """(B, K) int64 indices of the kept patches, timm's draw: argsort of a normal sample per image, from torch's generator of `device`."""
+        idx = torch.argsort(torch.randn(B, L, device=device), dim=-1)[:, :self.num_keep(L)]
+        if self.ordered:
+            idx = idx.sort(dim=-1)[0]
+        return idx.contiguous()
+
+    def extra_repr(self):
+        return f"prob={self.prob}, num_prefix_tokens={self.num_prefix_tokens}, ordered={self.ordered}"
+
+
 class _PatchEmbed(nn.Module):
     def __init__(self, dim, patch):
         super().__init__()
@@ -203,6 +228,50 @@ class _EncoderFn(torch.autograd.Function):
         return (None, dimg, None, None) + tuple(grads)
 
 
+class _EncoderKeepFn(torch.autograd.Function):
+    """features3D under patch dropout as one autograd node: the front end on the kept patches (mfvit_patch_keep_embed) + the block stack on the
+    shortened sequence (mfvit_vit_forward_x0); backward = mfvit_vit_backward_x0 (stage by stage) + mfvit_patch_keep_embed_bwd with the group that
+    holds stage -1.  No gradient flows to the indices."""
+
+    @staticmethod
+    def forward(ctx, model, img, idx, need_grad, drop, *params):
+        want_dimg = bool(need_grad and ctx.needs_input_grad[1])
+        feats, ws, keep = model._run_forward_keep(img, idx, need_grad, drop)
+        ctx.model = model
+        ctx.ws = ws
+        ctx.keep = keep
+        ctx.cfg = model._cfg(img, need_grad)
+        ctx.drop = drop
+        ctx.want_dimg = want_dimg
+        ctx.img_meta = (img.shape, img.dtype)
+        return feats
+
+    @staticmethod
+    def backward(ctx, dfeats):
+        model = ctx.model
+        if torch.is_grad_enabled():
+            raise _lib.MfvitError("double backward through the encoder (create_graph=True) is not supported: its backward is one HIP call "
+                                  "whose results are not differentiable")
+        if ctx.ws is None:
+            raise _lib.MfvitError("the encoder's saved activations were already released: a second backward through the same forward "
+                                  "(retain_graph=True) is not supported - run the forward again")
+        dimg = None
+        if ctx.want_dimg and ctx.needs_input_grad[1]:
+            shape, dtype = ctx.img_meta
+            dimg = torch.empty(shape, device=dfeats.device, dtype=torch.float32)
+            dimg.record_stream(torch.cuda.current_stream(dfeats.device))
+        want_params = any(ctx.needs_input_grad[5:])
+        grads = model._run_backward(ctx.cfg, ctx.ws, dfeats, drop=ctx.drop, dimg=dimg, want_params=want_params, keep=ctx.keep)
+        grads = [g if need else None for g, need in zip(grads, ctx.needs_input_grad[5:])]
+        model._release_ws(ctx.ws)
+        model._release_ws(ctx.keep[2])
+        ctx.ws = ctx.keep = None
+        model._feat_cache = None
+        if dimg is not None and dimg.dtype != ctx.img_meta[1]:
+            dimg = dimg.to(ctx.img_meta[1])
+        return (None, dimg, None, None, None) + tuple(grads)
+
+
 class _HeadFn(torch.autograd.Function):
     """Small classifier head on the cls rows of a token tensor: y = feats[:, 0] @ W.T + b (f32)."""
 
@@ -234,9 +303,10 @@ class _HeadFn(torch.autograd.Function):
 class VisionTransformerMoCo(nn.Module):
     def __init__(self, img_size=224, patch_size=16, embed_dim=384, depth=12, num_heads=12, mlp_ratio=4.0, qkv_bias=True,
                  num_classes=1000, stop_grad_conv1=False, precision=None, drop_rate=0.0, attn_drop_rate=0.0, drop_path_rate=0.0,
-                 **unused_timm_kwargs):
+                 patch_drop_rate=0.0, patch_drop_ordered=False, **unused_timm_kwargs):
         super().__init__()
-        for name, r in (("drop_rate", drop_rate), ("attn_drop_rate", attn_drop_rate), ("drop_path_rate", drop_path_rate)):
+        for name, r in (("drop_rate", drop_rate), ("attn_drop_rate", attn_drop_rate), ("drop_path_rate", drop_path_rate),
+                        ("patch_drop_rate", patch_drop_rate)):
             if not 0.0 <= float(r) < 1.0:
                 raise ValueError(f"{name} must lie in [0, 1), got {r!r}")
         if patch_size != 16:
@@ -263,6 +333,7 @@ class VisionTransformerMoCo(nn.Module):
         self.pos_embed = nn.Parameter(build_2d_sincos_position_embedding(gh, gw, embed_dim), requires_grad=False)
         self.patch_embed = _PatchEmbed(embed_dim, 16)
         self.pos_drop = nn.Dropout(float(drop_rate))
+        self.patch_drop = PatchDropout(float(patch_drop_rate), 1, bool(patch_drop_ordered))     # (timm: between pos_drop and the blocks)
         dpr = [x.item() for x in torch.linspace(0, float(drop_path_rate), depth)]       # stochastic depth decay rule (timm)
         self.blocks = nn.ModuleList([_Block(embed_dim, self.mlp_dim, float(drop_rate), float(attn_drop_rate), dpr[i]) for i in range(depth)])
         self.norm = _WB((embed_dim,), (embed_dim,))
@@ -278,6 +349,9 @@ class VisionTransformerMoCo(nn.Module):
         self._ws_pool = {}
         self._feat_cache = None
         self._lora = None                   # mfvit.lora.LoraState while adapters are attached
+        self.last_keep_indices = None       # (B, K) int64: the kept patches of the last training-mode forward under patch dropout
+        self._keep_pin = None               # a draw pinned by the model that drives this encoder (Fus_CrossViT: one draw per step)
+        self._keep_err = None               # the front end's device error word (a patch index outside the grid)
         self._flatten()
 
     # ------------------------------------------------------------------ init (moco-v3 VisionTransformerMoCo)
@@ -401,7 +475,77 @@ class VisionTransformerMoCo(nn.Module):
         if not self.training:
             return False
         drop, attn, dpr = self.drop_rates()
-        return drop > 0.0 or attn > 0.0 or any(r > 0.0 for r in dpr)
+        if drop > 0.0 or attn > 0.0 or any(r > 0.0 for r in dpr):
+            return True
+        # patch dropout: a forward of its own per call, unless the driving model has pinned one draw for the step
+        return self._patch_drop_prob() > 0.0 and self.__dict__.get("_keep_pin") is None
+
+    # ------------------------------------------------------------------ patch dropout (timm PatchDropout; csrc/patch_drop.hip)
+    def _patch_drop_prob(self):
+        pd = self._modules.get("patch_drop")
+        p = float(getattr(pd, "prob", 0.0))
+        if not 0.0 <= p < 1.0:
+            raise _lib.MfvitError(f"patch_drop.prob must lie in [0, 1), got {p}")
+        return p
+
+    def draw_keep_indices(self, B, device=None):
+        """The (B, K) int64 kept-patch indices of one training-mode forward as timm's PatchDropout draws them (argsort of randn on the model's
+        device, from torch's generator: `torch.manual_seed` reproduces them), or None in eval() / at rate 0."""
+        if not self.training or self._patch_drop_prob() <= 0.0:
+            return None
+        return self.patch_drop.draw(int(B), self.num_tokens - 1, device if device is not None else self._arena.device)
+
+    @contextlib.contextmanager
+    def pinned_keep_indices(self, idx):
+        """Every forward inside the block keeps the patches `idx` ((B, K) int64 on the model's device, distinct and in range - not checked
+        again; None: nothing pinned): features3D and the head forward of one step then share one draw and the single-use feature cache holds."""
+        prev = self.__dict__.get("_keep_pin")
+        self._keep_pin = idx
+        try:
+            yield
+        finally:
+            self._keep_pin = prev
+
+    def _check_keep_indices(self, idx, B):
+        """Explicit indices, checked on the host (one sync): (B, K) integers, 1 <= K <= L, in [0, L), distinct per image."""
+        L = self.num_tokens - 1
+        if not isinstance(idx, torch.Tensor) or idx.dim() != 2 or idx.dtype.is_floating_point or idx.dtype in (torch.bool, torch.complex64, torch.complex128):
+            raise _lib.MfvitError("keep_indices must be a (B, K) integer tensor")
+        if idx.shape[0] != B or not 1 <= idx.shape[1] <= L:
+            raise _lib.MfvitError(f"keep_indices must have shape ({B}, K) with 1 <= K <= {L}, got {tuple(idx.shape)}")
+        idx = idx.detach().to(self._arena.device, torch.int64).contiguous()
+        srt = idx.sort(dim=-1)[0]
+        bad_range = (srt[:, 0] < 0).any() | (srt[:, -1] >= L).any()
+        dup = (srt[:, 1:] == srt[:, :-1]).any() if idx.shape[1] > 1 else torch.zeros((), dtype=torch.bool, device=idx.device)
+        flags = torch.stack([bad_range, dup]).tolist()
+        if flags[0]:
+            raise _lib.MfvitError(f"keep_indices out of range for {L} patches")
+        if flags[1]:
+            raise _lib.MfvitError("keep_indices repeat a patch within an image")
+        self.check_keep_error()
+        return idx
+
+    def check_keep_error(self):
+        """Raises MfvitError when a front-end kernel met a patch index outside the grid since the last check (such a row is zeros and never
+        becomes an address).  Reads the device error word: one sync.  Called by every forward with explicit indices; call it yourself after
+        forwards that pin or draw indices of your own making."""
+        e = self._keep_err
+        if e is not None and int(e.item()) != 0:
+            e.zero_()
+            raise _lib.MfvitError("patch dropout: a kept-patch index outside the grid reached the device (its row was dropped)")
+
+    def _resolve_keep(self, x, keep_indices):
+        """The (B, K) indices this forward keeps, or None: the full sequence."""
+        if keep_indices is not None and not self.training:
+            raise _lib.MfvitError("keep_indices is a training-mode argument: eval() runs every patch (timm PatchDropout)")
+        pin = self.__dict__.get("_keep_pin") if self.training else None
+        active = keep_indices is not None or pin is not None or (self.training and self._patch_drop_prob() > 0.0)
+        if active and self.__dict__.get("_lora") is not None:       # (before anything is drawn or checked on the device)
+            raise _lib.MfvitError("LoRA adapters together with an active patch dropout are not built: the shortened sequence runs on the plain "
+                                  "parameter arena (set patch_drop.prob = 0, or detach the adapters)")
+        if keep_indices is not None:
+            return self._check_keep_indices(keep_indices, int(x.shape[0]))
+        return pin if pin is not None else self.draw_keep_indices(x.shape[0], x.device)
 
     def _draw_drop(self):
         """mfvit_vit_drop of one training-mode forward (None when no site is active: eval(), or all rates 0).  The seed comes from torch's CPU
@@ -516,16 +660,73 @@ class VisionTransformerMoCo(nn.Module):
             ws = None
         return feats, ws
 
-    def _run_backward(self, cfg, ws, dfeats, on_stage_done=None, drop=None, dimg=None, want_params=True):
+    def _run_forward_keep(self, img, idx, save, drop=None):
+        """Patch dropout: (features (B, 1 + K, D), workspace, keep) with keep = (tokens, mfvit_patch_keep_cfg, front-end workspace, idx)."""
+        img = self._prep_img(img)
+        if idx.device != img.device:
+            raise _lib.MfvitError(f"keep indices on {idx.device} but input on {img.device}")
+        idx.record_stream(torch.cuda.current_stream(img.device))     # (a step's draw is made on the caller's stream and may run on the side stream)
+        cfg = self._cfg(img, save)
+        self._ensure_shadow(cfg)
+        B, K = idx.shape
+        T, D = K + 1, self.embed_dim
+        nbytes = lib().mfvit_vit_workspace_bytes_x0(cfg, drop, T)
+        pk = _lib.PatchKeepCfg(cfg.dtype, B, cfg.img_h, cfg.img_w, K, D)
+        fbytes = lib().mfvit_patch_keep_workspace_bytes(pk, int(bool(save)))
+        if nbytes == 0 or fbytes == 0:
+            raise _lib.MfvitError("invalid encoder configuration for patch dropout (image size a multiple of 16, dim 384 or 768, head_dim 32 / 64 / "
+                                  f"96, 1 <= K <= {self.num_tokens - 1})")
+        dev = img.device
+
+        def take(n):
+            pool = self._ws_pool.setdefault(n, [])
+            return pool.pop() if pool else torch.empty(n, device=dev, dtype=torch.uint8)
+        ws, fws = take(nbytes), take(fbytes)
+        if self._keep_err is None or self._keep_err.device != dev:
+            self._keep_err = torch.zeros(1, device=dev, dtype=torch.int32)
+        a = self._arena.data_ptr()
+        off = self._offsets
+        x0 = torch.empty(B, T, D, device=dev, dtype=torch.float32)
+        feats = torch.empty(B, T, D, device=dev, dtype=torch.float32)
+        check(lib().mfvit_patch_keep_embed(pk, ptr(img), ptr(idx), a + 4 * off["cls_token"][0], a + 4 * off["pos_embed"][0],
+                                           a + 4 * off["patch_embed.proj.weight"][0], a + 4 * off["patch_embed.proj.bias"][0], ptr(fws),
+                                           int(bool(save)), ptr(x0), ptr(self._keep_err), stream()), "mfvit_patch_keep_embed")
+        check(lib().mfvit_vit_forward_x0(cfg, drop, T, ptr(self._arena), ptr(self._shadow), ptr(x0), ptr(ws), ptr(feats), stream()),
+              "mfvit_vit_forward_x0")
+        if not save:
+            self._release_ws(ws)
+            self._release_ws(fws)
+            ws = fws = None
+        return feats, ws, (T, pk, fws, idx)
+
+    def _keep_embed_bwd(self, keep, dx0, gflat, dimg, cfg):
+        """The front end's backward (stage -1 under patch dropout): d cls_token, d pe_b, d pe_w into the gradient arena `gflat` (None: none), dimg."""
+        T, pk, fws, idx = keep
+        off = self._offsets
+        g = (lambda name: gflat.data_ptr() + 4 * off[name][0]) if gflat is not None else (lambda name: None)
+        stop = bool(cfg.stop_grad_conv1) or gflat is None
+        check(lib().mfvit_patch_keep_embed_bwd(pk, ptr(idx), ptr(fws), ptr(dx0), g("cls_token"), None if stop else g("patch_embed.proj.weight"),
+                                               None if stop else g("patch_embed.proj.bias"), ptr(dimg), ptr(self._keep_err), stream()),
+              "mfvit_patch_keep_embed_bwd")
+
+    def _run_backward(self, cfg, ws, dfeats, on_stage_done=None, drop=None, dimg=None, want_params=True, keep=None):
         """Returns per-parameter gradient views (arena order) of a fresh flat gradient arena.  drop: the forward's mfvit_vit_drop (or None).
         dimg: (B,3,H,W) f32, overwritten with d loss / d img (the forward's workspace must come from _get_ws(.., want_dimg=True)).
         want_params=False (needs dimg): the data-gradient-only backward - no gradient arena, every returned gradient None."""
         dfeats = dfeats.contiguous()
         if dfeats.dtype != torch.float32:
             dfeats = dfeats.float()
+        # keep (patch dropout, _run_forward_keep): the stack's backward on the shortened sequence (mfvit_vit_backward_x0 -> dx0), the front end's
+        # backward behind the call that runs stage -1
+        dx0 = torch.empty(cfg.batch, keep[0], self.embed_dim, device=dfeats.device, dtype=torch.float32) if keep is not None else None
         if not want_params:
             if dimg is None:
                 raise _lib.MfvitError("a backward without parameter gradients needs the image gradient")
+            if keep is not None:
+                check(lib().mfvit_vit_backward_x0(cfg, drop, keep[0], ptr(self._arena), ptr(self._shadow), ptr(ws), ptr(dfeats), None, ptr(dx0),
+                                                  self.depth, -1, stream()), "mfvit_vit_backward_x0")
+                self._keep_embed_bwd(keep, dx0, None, dimg, cfg)
+                return [None] * len(self._arena_params)
             check(lib().mfvit_vit_backward_ex(cfg, drop, ptr(self._kernel_params()), ptr(self._shadow), ptr(ws), ptr(dfeats), None, ptr(dimg),
                                               self.depth, -1, stream()), "mfvit_vit_backward_ex")
             return [None] * len(self._arena_params)
@@ -551,6 +752,12 @@ class VisionTransformerMoCo(nn.Module):
         hook = on_stage_done or getattr(self, "_grad_stage_hook", None)
 
         def bwd(hi, lo):
+            if keep is not None:
+                check(lib().mfvit_vit_backward_x0(cfg, drop, keep[0], ptr(self._arena), ptr(self._shadow), ptr(ws), ptr(dfeats), ptr(gflat), ptr(dx0),
+                                                  hi, lo, stream()), "mfvit_vit_backward_x0")
+                if lo == -1:
+                    self._keep_embed_bwd(keep, dx0, gflat, dimg, cfg)
+                return
             # (drop = NULL, dimg = NULL: exactly mfvit_vit_backward; the call that runs the embedding stage also writes the image gradient)
             check(lib().mfvit_vit_backward_ex(cfg, drop, ptr(self._kernel_params()), ptr(self._shadow), ptr(ws), ptr(dfeats), ptr(gflat),
                                               ptr(dimg) if lo == -1 else None, hi, lo, stream()), "mfvit_vit_backward_ex")
@@ -604,7 +811,7 @@ class VisionTransformerMoCo(nn.Module):
         return grads
 
     # ------------------------------------------------------------------ public API (reference call sites)
-    def _features(self, x, caller):
+    def _features(self, x, caller, keep_indices=None):
         # activations are saved when a parameter or the image needs a gradient (saliency / FGSM with a frozen backbone: the image only)
         need_x = torch.is_grad_enabled() and x.requires_grad
         lo = self.__dict__.get("_lora")
@@ -615,21 +822,29 @@ class VisionTransformerMoCo(nn.Module):
         c = self._feat_cache
         self._feat_cache = None
         drop = self._draw_drop()            # (a fresh seed per training-mode forward with dropout; None otherwise)
-        stochastic = drop is not None
-        if c is not None and c[0] is x and c[1] == key and c[2] != caller and not stochastic:
+        pin = self.__dict__.get("_keep_pin") if (self.training and keep_indices is None) else None
+        # patch dropout: a draw of this forward's own makes it stochastic; a pinned draw (one per step, shared by both calls) does not
+        idx = self._resolve_keep(x, keep_indices)
+        stochastic = drop is not None or (idx is not None and pin is None)
+        if c is not None and c[0] is x and c[1] == key and c[2] != caller and not stochastic and (c[4] if len(c) > 4 else None) is idx:
             # the reference runs every backbone twice per step on the same tensor (features3D then __call__, FUS:128+131);
             # without dropout the second result is head(first[:, 0]): computed once.  Single use: a repeated call of
             # the SAME method always recomputes.  (Training mode with dropout / drop path: two forwards with their own masks, as the reference.)
             return c[3]
         c = None
         self._grad_arena_lent = False
-        feats = _EncoderFn.apply(self, x, need, drop, *self._arena_params, *lora_params)
-        self._feat_cache = None if stochastic else (x, key, caller, feats)
+        if idx is not None:
+            self.last_keep_indices = idx
+            feats = _EncoderKeepFn.apply(self, x, idx, need, drop, *self._arena_params)
+        else:
+            feats = _EncoderFn.apply(self, x, need, drop, *self._arena_params, *lora_params)
+        self._feat_cache = None if stochastic else (x, key, caller, feats, idx)
         return feats
 
-    def features3D(self, x):
-        """(B,3,H,W) -> (B, T, 384) tokens after the final LayerNorm (FUS:128,133; crossvit.py:130-146)."""
-        return self._features(x, "features3D")
+    def features3D(self, x, keep_indices=None):
+        """(B,3,H,W) -> (B, T, 384) tokens after the final LayerNorm (FUS:128,133; crossvit.py:130-146).  Training mode with patch dropout
+        (patch_drop.prob > 0, or explicit keep_indices (B, K): distinct patch indices per image): (B, 1 + K, 384), cls and the kept patches."""
+        return self._features(x, "features3D", keep_indices)
 
     def forward_head(self, feats):
         h = self.head
@@ -639,9 +854,9 @@ class VisionTransformerMoCo(nn.Module):
             return _HeadFn.apply(feats, h.weight, h.bias)
         return h(feats[:, 0])      # a module the caller installed (MoCo's projector MLP: HIP Linear / BatchNorm nodes of its own)
 
-    def forward(self, x):
-        """head(features3D(x)[:, 0])  (timm forward_features + head; training mode applies the dropout / drop-path rates)."""
-        return self.forward_head(self._features(x, "forward"))
+    def forward(self, x, keep_indices=None):
+        """head(features3D(x)[:, 0])  (timm forward_features + head; training mode applies the dropout / drop-path / patch-dropout rates)."""
+        return self.forward_head(self._features(x, "forward", keep_indices))
 
     # ------------------------------------------------------------------ attention maps (include/mfvit.h, mfvit_vit_forward_attn)
     # All three run one evaluation forward (no dropout site, whatever self.training says) under no_grad, draw no seed, and leave the feature
