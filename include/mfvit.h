@@ -199,6 +199,41 @@ int mfvit_patch_keep_embed(const mfvit_patch_keep_cfg* cfg, const float* img, co
 int mfvit_patch_keep_embed_bwd(const mfvit_patch_keep_cfg* cfg, const int64_t* idx, void* workspace, const float* dx0, float* dcls, float* dpe_w,
                                float* dpe_b, float* dimg, int32_t* err, mfvit_stream_t stream);
 
+/* Block ranges of the image-mode stack (additive in ABI 5): blocks [block_lo, block_hi) of the model on a residual stream of `tokens` rows per
+ * image - what token pruning between blocks, early exits and per-stage analysis are built from.  cfg, drop, params, shadow: the whole model's, as
+ * for mfvit_vit_forward(_drop); the gradient arena too.  Only the workspace is the range's own (mfvit_vit_workspace_bytes_seg; activations of
+ * block_hi - block_lo blocks at `tokens` rows).  The same launchers as the whole-stack entry points, no other kernel: the range [0, depth) with
+ * image_in = 1 issues the launches of mfvit_vit_forward(_drop) / mfvit_vit_backward_ex, with image_in = 0 those of mfvit_vit_forward_x0 /
+ * mfvit_vit_backward_x0.
+ *   x_in   image_in = 1: the (B,3,H,W) f32 image (block_lo == 0 and tokens == 1 + gh gw only).  image_in = 0: x_{block_lo}, (B, tokens, dim) f32;
+ *          the range enters through the row pass of mfvit_vit_forward_x0 (norm1 of block block_lo); pos_drop (site 1) applies when block_lo == 0 only.
+ *   x_out  (B, tokens, dim) f32: the features behind the final LayerNorm when block_hi == depth, otherwise the raw residual stream x_{block_hi} (the
+ *          LayerNorm output its last fc2 epilogue still forms goes to scratch).
+ *   Dropout sites keep the model's numbers (16 l + k with l the block's index in the model; sample = row / tokens).
+ *   Backward: dx_out = the gradient of whichever x_out was returned.  Stages are the model's numbers: block_hi (the final norm when block_hi ==
+ *   depth, otherwise the entry of dx_out, which also adds its column sums to d fc2_b of block block_hi - 1), the blocks block_hi - 1 .. block_lo,
+ *   and block_lo - 1: what feeds block block_lo - the embedding stage (image_in = 1: dparams / dimg as mfvit_vit_backward_ex) or dx_in (image_in = 0:
+ *   (B, tokens, dim) f32 = d loss / d x_in, required non-NULL in every call, written by the call that runs that stage; no parameter gradient is
+ *   formed there).  block_lo - 1 <= stage_lo <= stage_hi <= block_hi.  dparams == NULL: the data-gradient chain alone (image_in = 1: needs dimg).
+ *   mfvit_vit_attn_layout_seg: where a forward of the range leaves the qkv tensor and log-sum-exp of its blocks: block l at workspace + out[0] +
+ *   (l - block_lo) * out[2] bytes (qkv) and workspace + out[1] + (l - block_lo) * out[2] (lse), in the storage format of tag out[3].  Without
+ *   cfg->save_for_backward out[2] = 0: the one copy holds the range's last block.
+ * MFVIT_EINVAL before any HIP call (size query: 0): seg NULL, a range outside 0 <= block_lo < block_hi <= depth, tokens outside [2, 1 + gh gw],
+ * image_in other than 0 / 1 or set with block_lo != 0 or a shortened sequence, want_dimg with image_in = 0 or without save_for_backward, a stage
+ * outside the range's, a token-input cfg, and every check of mfvit_vit_forward_drop / mfvit_vit_backward_ex. */
+typedef struct mfvit_vit_seg {
+    int block_lo, block_hi;   /* blocks [block_lo, block_hi), 0 <= lo < hi <= cfg->depth */
+    int tokens;               /* rows per image in this segment, 2 <= tokens <= 1 + gh gw */
+    int image_in;             /* 1: x_in is the (B,3,H,W) image (block_lo == 0 and tokens == 1 + gh gw only); 0: (B,tokens,dim) f32 */
+} mfvit_vit_seg;
+size_t mfvit_vit_workspace_bytes_seg(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, const mfvit_vit_seg* seg, int want_dimg);
+int mfvit_vit_attn_layout_seg(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, const mfvit_vit_seg* seg, int64_t out[4]);
+int mfvit_vit_forward_seg(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, const mfvit_vit_seg* seg, const float* params, const void* shadow,
+                          const float* x_in, void* workspace, float* x_out, mfvit_stream_t stream);
+int mfvit_vit_backward_seg(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, const mfvit_vit_seg* seg, const float* params, const void* shadow,
+                           void* workspace, const float* dx_out, float* dparams, float* dx_in, float* dimg, int stage_hi, int stage_lo,
+                           mfvit_stream_t stream);
+
 /* Hidden states of the image encoder (host only, additive in ABI 5).  Where the residual stream lies in the workspace after mfvit_vit_forward
  * with save_for_backward = 1: hidden state l (l = 0: cls + patch embedding + pos_embed, the input of block 0; l = 1 .. depth: the output of
  * block l - 1, before the final norm) is f32 [batch * tokens][dim], image-major, at workspace + out[0] + l * out[1] bytes.  f32 in every
@@ -1046,6 +1081,45 @@ int mfvit_sam_norm_partials(const int64_t* table, int nchunks, int adaptive, flo
 int mfvit_sam_scale(const float* partials, int nrows, const float* found_inf, float* out2, mfvit_stream_t stream);
 int mfvit_sam_perturb(const int64_t* table, int nchunks, const float* inv, float rho, mfvit_stream_t stream);
 int mfvit_sam_restore(const int64_t* table, int nchunks, const float* inv, mfvit_stream_t stream);
+
+/* Attention-guided token pruning between blocks (additive in ABI 5; Liang et al. 2022, "Not All Patches Are What You Need" - EViT's token
+ * reorganisation, here at a block boundary, with normalised weights that receive no gradient).  Behind block l of a sequence of T rows per image
+ * (row 0 = cls): score the T - 1 other rows by the cls token's attention, keep the K best, fold the rest into one row.  Asynchronous on `stream`;
+ * no atomics on memory and every sum in a fixed order: the same bits on every run.
+ *
+ * mfvit_token_score: qkv [B][T][3][H][HD] in the storage format of tag qkv_dtype (MFVIT_F32 .. MFVIT_X3F16, as mfvit_attention_qkv_dtype /
+ *   mfvit_vit_attn_layout report it) and lse f32 [B][H][T] of block l -> score f32 [B][T-1]: score[b][j] = mean over the heads of
+ *   P[b][h][0][1 + j].  The cls row of the launch behind mfvit_vit_forward_attn (fuse = 1, cls_only = 1) into probs (scratch, f32 [B][T]), then
+ *   its cls column dropped: the bits of those maps.  MFVIT_EINVAL (before any HIP call): a NULL pointer, B <= 0, B > 65535, T < 2, T > 8193,
+ *   H <= 0, head_dim other than 32 / 64 / 96, an unknown tag.
+ * mfvit_token_select: score f32 [B][P] (row stride ld), 1 <= K <= P -> idx_keep int32 [B][K] = {j : rank[j] < K} in ascending j, with rank as
+ *   mfvit_patch_rank defines it (ties to the lower index, NaN last); idx_drop int32 [B][P-K], the others, ascending; w f32 [B][P-K]:
+ *   w[j] = score[idx_drop[j]] / s, s = the sum of the dropped scores in list order, one f32 addition each - or 1 / (P - K) for every j when s
+ *   is zero or not finite.  One workgroup per image, exact integers.  K == P: nothing is dropped, idx_drop and w are not touched (may be
+ *   NULL).  forced (NULL, or int32 [B][K], any order): the kept set is what it names instead of the ranking's - the lists and weights of a
+ *   recorded selection, to the bit; err (needed with forced; the word of mfvit_token_reorg_fwd) is set by an index outside [0, P) or named
+ *   twice; idx_keep then holds fewer than K rows and its tail is -1, and nothing is written outside the lists.  MFVIT_EINVAL (before any HIP call): a NULL pointer, B <= 0, B > 65535, P <= 0,
+ *   P > 8192, ld < P, K outside [1, P], forced without err.
+ * mfvit_token_reorg_fwd: x f32 [B][T][D] -> out f32 [B][1 + K + fuse][D]: row 0 = x[b][0]; row 1 + k = x[b][1 + idx_keep[b][k]] (moves:
+ *   bit-exact); with fuse = 1 the last row = sum over j of w[b][j] x[b][1 + idx_drop[b][j]], per column a = w_0 x_0 (one product), then
+ *   a = fma(w_j, x_j, a) in list order - a single dropped row with weight 1 comes back bit for bit.  fuse = 0: idx_drop (may be NULL) is only
+ *   checked, w is not read.
+ * mfvit_token_reorg_bwd: dout f32 [B][1 + K + fuse][D] -> dx f32 [B][T][D], OVERWRITTEN in full, every element written once: row 0 and the kept
+ *   rows moved back, dropped row idx_drop[b][j] = w[b][j] * dout[b][1 + K] (one f32 product; fuse = 0: zeros), a row no list names: zeros.
+ * err (both): one int32 on the device, zero before the first call.  An index outside [0, T - 1) sets it to 1, never becomes an address, and
+ *   its row is zeros (forward, kept) / is skipped (fused sum; backward); an index named twice in keep and drop together sets it too (the
+ *   backward then takes the later list entry).  The caller reads the word when it likes.
+ * MFVIT_EINVAL (both, before any HIP call): a NULL or not 16-byte aligned x / out / dout / dx, in place, idx_keep or err NULL, B <= 0,
+ *   B > 65535, T < 2, T > 8193, D other than 384 / 768, K outside [1, T - 1], B T D >= 2^31, fuse other than 0 / 1, fuse = 1 with K == T - 1
+ *   or with idx_drop / w NULL. */
+int mfvit_token_score(int qkv_dtype, const void* qkv, const float* lse, int B, int T, int H, int HD, float* probs, float* score,
+                      mfvit_stream_t stream);
+int mfvit_token_select(const float* score, int64_t ld, int B, int P, int K, const int32_t* forced, int32_t* idx_keep, int32_t* idx_drop, float* w,
+                       int32_t* err, mfvit_stream_t stream);
+int mfvit_token_reorg_fwd(const float* x, const int32_t* idx_keep, const int32_t* idx_drop, const float* w, float* out, int B, int T, int D, int K,
+                          int fuse, int32_t* err, mfvit_stream_t stream);
+int mfvit_token_reorg_bwd(const float* dout, const int32_t* idx_keep, const int32_t* idx_drop, const float* w, float* dx, int B, int T, int D, int K,
+                          int fuse, int32_t* err, mfvit_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -31,6 +31,7 @@ inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 struct Dims {
     int Tp;                             // token rows of the ARENA's pos_embed (= T, but for the given-x0 entry points: 1 + gh gw there, T = the shortened sequence)
     bool x0in;                          // given-x0 entry points (mfvit_vit_forward_x0): the embedding stage is the caller's, stage -1 of the backward writes d x_0
+    int l0, l1;                         // the blocks [l0, l1) a call runs: the whole stack, but for the block-range entry points (mfvit_vit_forward_seg)
     int dtype, B, T, np, D, depth, H, HD, F, M, Mp, es, ep;   // es: bytes per LOGICAL element of a dtype tensor; ep: storage elements per logical one
     bool save, tok, use_pos;
     int act;
@@ -59,6 +60,8 @@ bool get_dims(const mfvit_vit_cfg* c, Dims& d) {
     d.T = d.tok ? c->tokens : d.np + 1;
     d.Tp = d.T;
     d.x0in = false;
+    d.l0 = 0;
+    d.l1 = c->depth;
     d.use_pos = c->use_pos != 0;
     d.act = c->act;
     d.D = c->dim;
@@ -129,6 +132,21 @@ bool get_dims_x0(const mfvit_vit_cfg* c, const mfvit_vit_drop* x, int tokens, Di
     d.T = tokens;
     d.M = d.B * tokens;
     d.x0in = true;
+    return true;
+}
+
+// A block range of the image-mode stack (mfvit_vit_forward_seg): blocks [block_lo, block_hi) at `tokens` rows per image, entered with the image
+// (the embedding stage: block_lo == 0 on the full grid only) or with the residual stream x_{block_lo} (the row pass of the given-x0 entry).
+bool get_dims_seg(const mfvit_vit_cfg* c, const mfvit_vit_drop* x, const mfvit_vit_seg* s, Dims& d) {
+    if (!s || !get_dims(c, x, d) || d.tok) return false;
+    if (s->block_lo < 0 || s->block_lo >= s->block_hi || s->block_hi > d.depth) return false;
+    if (s->tokens < 2 || s->tokens > d.Tp || (s->image_in != 0 && s->image_in != 1)) return false;
+    if (s->image_in && (s->block_lo != 0 || s->tokens != d.Tp)) return false;
+    d.T = s->tokens;
+    d.M = d.B * s->tokens;
+    d.x0in = !s->image_in;
+    d.l0 = s->block_lo;
+    d.l1 = s->block_hi;
     return true;
 }
 
@@ -213,16 +231,18 @@ struct WsLayout {
     size_t domax;               // backward: the largest |d attn| of every (image, head) of every block, f32 bits [depth][B][H] (proj data gradient -> attention backward)
     size_t pp_stride;           // distance between the two ping-pong copies of gxT / gmidT / dhpre / dqkv (0 = none)
     size_t total;
+    size_t ytail;               // a block range that ends below the final norm: [M][D] of the operand type (the LayerNorm output of its last fc2 epilogue, read by nobody)
     size_t wpeT, total_dimg;    // image gradient (mfvit_vit_backward_ex): W_pe^T [768][D] of the operand type behind `total` - a workspace of total_dimg bytes
 };
 WsLayout ws_layout(const Dims& d) {
     WsLayout W;
     const size_t M = d.M, D = d.D, F = d.F, es = d.es;
-    const size_t nl = d.save ? d.depth : 1;
+    const size_t nl = d.save ? d.l1 - d.l0 : 1;        // block copies: the blocks of this call
+    const size_t nlp = d.save ? d.depth : 1;            // (the column-sum partial buffers keep the whole stack's count: BwdCtx::next_colpart)
     size_t o = 0;
     W.patches = o; o += (d.tok || d.x0in) ? 0 : align256((size_t)d.Mp * 768 * es);
-    W.x0 = o; W.x_stride = align256(M * D * 4); o += W.x_stride * (d.save ? d.depth + 1 : 1);
-    W.st0 = o; W.st_stride = align256(2 * M * 4); o += W.st_stride * (d.save ? d.depth + 1 : 1);
+    W.x0 = o; W.x_stride = align256(M * D * 4); o += W.x_stride * (d.save ? nl + 1 : 1);
+    W.st0 = o; W.st_stride = align256(2 * M * 4); o += W.st_stride * (d.save ? nl + 1 : 1);
     W.blk0 = o;
     size_t b = 0;
     W.y1 = b; b += align256(M * D * es);
@@ -255,7 +275,7 @@ WsLayout ws_layout(const Dims& d) {
             size_t a = tiles_row * 3 * D, b2 = 4 * ((M + 191) / 192) * F, c2 = 256 * 3 * D;      // (b2: the x act' tile epilogue - one row of F sums per wave-row block of a tile; tiles are 256 or 192 rows)
             size_t n = a > b2 ? a : b2;
             n = n > c2 ? n : c2;
-            W.colpart = o; o += (3 * nl + 2) * align256(n * 4);          // one partial buffer per launch of a backward call that leaves column sums (batched reduce)
+            W.colpart = o; o += (3 * nlp + 2) * align256(n * 4);          // one partial buffer per launch of a backward call that leaves column sums (batched reduce)
             W.colpart_stride = align256(n * 4);
         }
         // split partials of the weight-gradient GEMMs: one slot per launch of a BLOCK (at most 4) + 1 for the patch embedding, each tiles * splits <= 384
@@ -270,6 +290,7 @@ WsLayout ws_layout(const Dims& d) {
     W.kpart = o; o += d.D == 384 ? align256((size_t)264 * 7 * 12 * 512 * 4) : 0;
     W.utmp = o; o += align256(M * D * es);     // always there (1 / 200 of the workspace): the layout does not depend on which path a call takes
     W.domax = o; o += d.save ? align256((size_t)d.depth * d.B * d.H * 4) : 0;
+    W.ytail = o; o += d.l1 < d.depth ? align256(M * D * es) : 0;
     W.total = o;
     W.wpeT = o; o += (d.save && !d.tok && !d.x0in) ? align256((size_t)768 * D * es) : 0;
     W.total_dimg = o;
@@ -302,7 +323,7 @@ struct EncCtx {
           lean_grad(dims.dtype == MFVIT_BF16X3 && !dims.unfused), eps(cfg_->ln_eps) {}
 
     // activations are kept per block for a backward (save), in one copy otherwise
-    size_t slot(int l) const { return d.save ? (size_t)l : 0; }
+    size_t slot(int l) const { return d.save ? (size_t)(l - d.l0) : 0; }
     float* xbuf(int l) const { return (float*)(ws + W.x0 + slot(l) * W.x_stride); }
     float* stat(int l) const { return (float*)(ws + W.st0 + slot(l) * W.st_stride); }
     char* blk(int l) const { return ws + W.blk0 + slot(l) * W.blk_stride; }
@@ -658,11 +679,12 @@ static int fwd_embed(const EncCtx& c, const float* img) {
     const Dims& d = c.d;
     const long D = c.D, De = c.D * c.e;
     const float* const pos = c.params + c.L.pos;
-    float* const x0 = c.xbuf(0);
-    char* const y1_0 = c.blk(0) + c.W.y1;
-    const float *const g0 = c.pblk(0) + c.L.ln1_w, *const b0 = c.pblk(0) + c.L.ln1_b;
-    float *const mean0 = c.stat(0), *const rstd0 = c.stat(0) + d.M;
-    if (d.x0in && d.p_embd > 0.f)
+    // (the first block of the call: block 0, but for a block range entered with x_{l0} - always through the given-x0 row pass below)
+    float* const x0 = c.xbuf(d.l0);
+    char* const y1_0 = c.blk(d.l0) + c.W.y1;
+    const float *const g0 = c.pblk(d.l0) + c.L.ln1_w, *const b0 = c.pblk(d.l0) + c.L.ln1_b;
+    float *const mean0 = c.stat(d.l0), *const rstd0 = c.stat(d.l0) + d.M;
+    if (d.x0in && d.p_embd > 0.f && d.l0 == 0)
         // given x_0 (img = (B, T, D) f32: cat(cls, kept patches) + their pos_embed rows): timm pos_drop on the shortened rows; LN1_0 -> y1_0
         return drop_add_ln_rows(d.dtype, d.D, nullptr, 0, img, D, nullptr, 0, 0, nullptr, 0, make_drop(d.p_embd, d.seed, 1), c.off, 1, x0, D, y1_0, De, 0,
                                 g0, b0, c.eps, mean0, rstd0, d.M, c.st);
@@ -749,6 +771,11 @@ static int fwd_block(const EncCtx& c, int l, float* features, const mfvit_vit_at
     if (l + 1 == d.depth) {
         p.out1 = features; p.ldo1 = D; p.y_f32 = 1;
         p.gamma = c.params + c.L.norm_w; p.beta = c.params + c.L.norm_b;
+    } else if (l + 1 == d.l1) {
+        // a block range that ends here: the raw residual stream x_{l1} is the call's output; the epilogue's LayerNorm (block l1's norm1) goes to scratch
+        p.out0 = features;
+        p.out1 = c.ws + c.W.ytail; p.ldo1 = De;
+        p.gamma = c.pblk(l + 1) + c.L.ln1_w; p.beta = c.pblk(l + 1) + c.L.ln1_b;
     } else {
         p.out1 = c.blk(l + 1) + c.W.y1; p.ldo1 = De;
         p.gamma = c.pblk(l + 1) + c.L.ln1_w; p.beta = c.pblk(l + 1) + c.L.ln1_b;
@@ -764,14 +791,15 @@ static int fwd_block(const EncCtx& c, int l, float* features, const mfvit_vit_at
 // (img = (B,T,dim) tokens, + pos_emb).  Everything behind x_0 / LN1_0 is the same pre-LN block stack.
 static int encoder_forward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* dropcfg, const float* params, const void* shadow, const float* img,
                            void* workspace, float* features, mfvit_stream_t stream, bool want_tokens,
-                           const mfvit_vit_attn_req* attn = nullptr, int x0_tokens = 0) {
+                           const mfvit_vit_attn_req* attn = nullptr, int x0_tokens = 0, const mfvit_vit_seg* seg = nullptr) {
     Dims d;
-    if (!(x0_tokens ? get_dims_x0(cfg, dropcfg, x0_tokens, d) : get_dims(cfg, dropcfg, d)) || !params || !shadow || !img || !workspace || !features)
+    if (!(seg ? get_dims_seg(cfg, dropcfg, seg, d) : x0_tokens ? get_dims_x0(cfg, dropcfg, x0_tokens, d) : get_dims(cfg, dropcfg, d)) || !params ||
+        !shadow || !img || !workspace || !features)
         return MFVIT_EINVAL;
     if (d.tok != want_tokens) return MFVIT_EINVAL;
     const EncCtx c(cfg, d, params, shadow, workspace, stream);
     MFVIT_TRY(fwd_embed(c, img));
-    for (int l = 0; l < d.depth; ++l) MFVIT_TRY(fwd_block(c, l, features, attn));
+    for (int l = d.l0; l < d.l1; ++l) MFVIT_TRY(fwd_block(c, l, features, attn));
     return MFVIT_OK;
 }
 
@@ -833,7 +861,7 @@ struct BwdCtx : EncCtx, BwdArgs {
            const BwdArgs& a)
         : EncCtx(cfg, dims, params_, shadow, workspace, stream), BwdArgs(a), wg(a.dparams != nullptr),
           gbase(wg ? a.dparams : (a.lora ? a.lora->dw : nullptr)), gx((float*)(ws + W.gx)), gmid((float*)(ws + W.gmid)),
-          colscr((float*)(ws + W.colscratch)), colpart_scope(!dims.rdrop), q(wgrad_side_stream(*this, wg), st, a.stage_hi < dims.depth ? a.stage_hi : dims.depth - 1),
+          colscr((float*)(ws + W.colscratch)), colpart_scope(!dims.rdrop), q(wgrad_side_stream(*this, wg), st, a.stage_hi < dims.l1 ? a.stage_hi : dims.l1 - 1),
           qdt_bwd(attn_qkv_dtype(dims.dtype, dims.T, dims.HD)), do_max(dout_max_applies(dims, qdt_bwd)) {}
 
     float* gblk(int l) const { return gbase ? gbase + L.blk0 + (long)l * L.blk_stride : nullptr; }
@@ -885,6 +913,18 @@ static int bwd_final_norm(BwdCtx& c) {
     return ln_bwd_rows(d.dtype, d.D, c.dfeatures, c.D, c.xbuf(d.depth), c.D, c.stat(d.depth), c.stat(d.depth) + d.M, c.params + c.L.norm_w, nullptr, 0,
                        c.gx, c.D, c.pp(c.W.gxT, d.depth - 1), c.D * c.e, c.wg ? c.dparams + c.L.norm_w : nullptr,
                        c.wg ? c.dparams + c.L.norm_b : nullptr, dcol, c.wg ? c.next_colpart() : nullptr, d.M, 1, 0, c.st);
+}
+
+// The top stage of a block range that ends below the final norm (stage l1 < depth): dfeatures = d x_{l1} becomes gx and its operand-type copy;
+// its column sums are d fc2_b of block l1 - 1 (what the LayerNorm backward above that block leaves in a whole-stack call)
+static int bwd_seg_entry(BwdCtx& c) {
+    const Dims& d = c.d;
+    if (!c.dfeatures) return MFVIT_EINVAL;
+    if (!c.lean_grad && hipMemcpyAsync(c.gx, c.dfeatures, (size_t)d.M * c.D * sizeof(float), hipMemcpyDeviceToDevice, c.st) != hipSuccess)
+        return MFVIT_ELAUNCH;
+    MFVIT_TRY(cast_transpose(d.dtype, c.dfeatures, c.pp(c.W.gxT, d.l1 - 1), nullptr, d.M, d.D, c.st));
+    if (c.wg && !d.rdrop) MFVIT_TRY(colsum_rows(c.dfeatures, c.D, c.gblk(d.l1 - 1) + c.L.fc2_b, d.M, 1, 0, d.D, c.st));
+    return MFVIT_OK;
 }
 
 // dY of a residual branch of block l: the residual gradient itself, or - where the branch was dropped - its masked copy in the scratch buffer
@@ -989,15 +1029,16 @@ static int bwd_block(BwdCtx& c, int l) {
     MFVIT_TRY(c.q.wait_layer(l + 1));                       // fc2-wgrad of layer l+1 reads the gxT copy written next
     if (c.lora && !c.dimg && l == c.stage_lo) return MFVIT_OK;   // adapters only: nobody reads d x of the lowest adapted block
     // gx = LN1bwd(dqkv Wqkv) + gmid ; d ln1_w, d ln1_b, d fc2_b of block l-1 (or scratch for the embed stage)
-    if (c.wg && l == 0 && hipMemsetAsync(c.colscr, 0, 2 * D * sizeof(float), c.st) != hipSuccess) return MFVIT_ELAUNCH;
+    // (the first block of a block range: the row sums of d x_{l0} belong to no bias of this call - the range below adds its own from its dx_out)
+    if (c.wg && l == d.l0 && hipMemsetAsync(c.colscr, 0, 2 * D * sizeof(float), c.st) != hipSuccess) return MFVIT_ELAUNCH;
     GemmP p = nt(dqkv, 3 * De, sb + c.S.qkv_t, 3 * De, d.M, d.D, 3 * d.D);
     p.aux = c.xbuf(l); p.ldaux = D;
     p.mean = c.stat(l); p.rstd = c.stat(l) + d.M;
     p.gamma = pb + c.L.ln1_w;
     p.kpart = c.kpart();
-    if (c.wg) { p.cs0 = gb + c.L.ln1_w; p.cs1 = gb + c.L.ln1_b; p.cs2 = (l > 0 && !d.rdrop) ? c.gblk(l - 1) + c.L.fc2_b : c.colscr; p.cpart = c.next_colpart(); }
+    if (c.wg) { p.cs0 = gb + c.L.ln1_w; p.cs1 = gb + c.L.ln1_b; p.cs2 = (l > d.l0 && !d.rdrop) ? c.gblk(l - 1) + c.L.fc2_b : c.colscr; p.cpart = c.next_colpart(); }
     // (lean_grad keeps the f32 result at block 0 only: the embedding stage reads gx)
-    return dgrad_ln_bwd(c, p, c.gmid, gmidT, c.lean_grad && l > 0 ? nullptr : c.gx, c.pp(c.W.gxT, l - 1));
+    return dgrad_ln_bwd(c, p, c.gmid, gmidT, c.lean_grad && l > d.l0 ? nullptr : c.gx, c.pp(c.W.gxT, l - 1));
 }
 
 // token-input embedding stage: gx = d x_0 = d tokens; d pos_emb = sum over the batch (fuseattention.py:187)
@@ -1017,7 +1058,7 @@ static int bwd_embed_tokens(BwdCtx& c) {
 static int bwd_embed_x0(BwdCtx& c) {
     const Dims& d = c.d;
     MFVIT_TRY(colpart_batch_flush(c.st));
-    if (d.p_embd > 0.f)
+    if (d.p_embd > 0.f && d.l0 == 0)
         MFVIT_TRY(mask_scale_rows(d.dtype, true, c.gx, c.D, c.gx, c.D, make_drop(d.p_embd, d.seed, 1), c.off, 1, d.M, d.D, c.st));
     if (hipMemcpyAsync(c.dinput, c.gx, (size_t)d.M * c.D * sizeof(float), hipMemcpyDeviceToDevice, c.st) != hipSuccess) return MFVIT_ELAUNCH;
     return MFVIT_OK;
@@ -1070,20 +1111,24 @@ static int bwd_embed_image(BwdCtx& c) {
 // Shared backward of the two front ends (BwdArgs: what is asked for): stages stage_hi .. stage_lo in descending order - depth: the final norm,
 // depth-1 .. 0: the blocks, -1: the embedding - then whatever the stages left pending.
 static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* dropcfg, const float* params, const void* shadow, void* workspace,
-                            const BwdArgs& a, mfvit_stream_t stream, bool want_tokens, int x0_tokens = 0) {
+                            const BwdArgs& a, mfvit_stream_t stream, bool want_tokens, int x0_tokens = 0, const mfvit_vit_seg* seg = nullptr) {
     Dims d;
-    if (!(x0_tokens ? get_dims_x0(cfg, dropcfg, x0_tokens, d) : get_dims(cfg, dropcfg, d)) || !params || !shadow || !workspace) return MFVIT_EINVAL;
-    if (x0_tokens ? (!a.dinput || a.dimg || a.rel || a.lora) : (!a.dparams && !a.dimg && !a.rel && !a.lora)) return MFVIT_EINVAL;
+    if (!(seg ? get_dims_seg(cfg, dropcfg, seg, d) : x0_tokens ? get_dims_x0(cfg, dropcfg, x0_tokens, d) : get_dims(cfg, dropcfg, d)) || !params ||
+        !shadow || !workspace)
+        return MFVIT_EINVAL;
+    if (d.x0in ? (!a.dinput || a.dimg || a.rel || a.lora) : (!a.dparams && !a.dimg && !a.rel && !a.lora)) return MFVIT_EINVAL;
     if (!d.save || d.tok != want_tokens) return MFVIT_EINVAL;
-    if (a.stage_hi > d.depth || a.stage_lo < -1 || a.stage_lo > a.stage_hi) return MFVIT_EINVAL;
+    // stages of a block range [l0, l1): l1 (the final norm, or the range's entry from dx_out) down to l0 - 1 (what feeds block l0)
+    if (a.stage_hi > d.l1 || a.stage_lo < d.l0 - 1 || a.stage_lo > a.stage_hi) return MFVIT_EINVAL;
     if (a.dimg && (d.tok || a.stage_lo != -1)) return MFVIT_EINVAL;
     BwdCtx c(cfg, d, params, shadow, workspace, stream, a);
     if (c.do_max) {   // the maxima of the blocks of this call start at zero
-        const int l0 = a.stage_lo > 0 ? a.stage_lo : 0, l1 = a.stage_hi < d.depth - 1 ? a.stage_hi : d.depth - 1;
+        const int l0 = a.stage_lo > d.l0 ? a.stage_lo : d.l0, l1 = a.stage_hi < d.l1 - 1 ? a.stage_hi : d.l1 - 1;
         if (l1 >= l0 && hipMemsetAsync(c.domax(l0), 0, (size_t)(l1 - l0 + 1) * d.B * d.H * 4, c.st) != hipSuccess) return MFVIT_ELAUNCH;
     }
     for (int s = a.stage_hi; s >= a.stage_lo; --s)
-        MFVIT_TRY(s == d.depth ? bwd_final_norm(c) : s >= 0 ? bwd_block(c, s) : d.x0in ? bwd_embed_x0(c) : d.tok ? bwd_embed_tokens(c) : bwd_embed_image(c));
+        MFVIT_TRY(s == d.depth ? bwd_final_norm(c) : s == d.l1 ? bwd_seg_entry(c) : s >= d.l0 ? bwd_block(c, s) : d.x0in ? bwd_embed_x0(c) :
+                  d.tok ? bwd_embed_tokens(c) : bwd_embed_image(c));
     MFVIT_TRY(colpart_batch_flush(c.st));
     MFVIT_TRY(tnpart_batch_flush(c.q.s));   // dW += the split partials still pending (the patch embedding's), splits in a fixed order
     if (a.lora) MFVIT_TRY(lora_run(d, a.lora->req, a.lora->dw, nullptr, true, c.st));   // dA, dB of every item from the dW_eff slices
@@ -1156,6 +1201,34 @@ int mfvit_vit_backward_x0(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, 
     if (!cfg || tokens < 2 || !dx0 || (!dfeatures && stage_hi >= cfg->depth)) return MFVIT_EINVAL;
     ShareScope share(cfg);
     return encoder_backward(cfg, drop, params, shadow, workspace, {dfeatures, dparams, dx0, nullptr, stage_hi, stage_lo}, stream, false, tokens);
+}
+size_t mfvit_vit_workspace_bytes_seg(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, const mfvit_vit_seg* seg, int want_dimg) {
+    Dims d;
+    if (!get_dims_seg(cfg, drop, seg, d)) return 0;
+    if (!want_dimg) return ws_layout(d).total;
+    if (d.x0in || !d.save) return 0;                 // the image gradient belongs to the range that takes the image, behind a forward that saved
+    return ws_layout(d).total_dimg;
+}
+int mfvit_vit_attn_layout_seg(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, const mfvit_vit_seg* seg, int64_t out[4]) {
+    Dims d;
+    if (!get_dims_seg(cfg, drop, seg, d) || !out) return MFVIT_EINVAL;
+    const WsLayout W = ws_layout(d);
+    out[0] = (int64_t)(W.blk0 + W.qkv); out[1] = (int64_t)(W.blk0 + W.lse); out[2] = d.save ? (int64_t)W.blk_stride : 0;
+    out[3] = d.p_attn > 0.f ? d.dtype : attn_qkv_dtype(d.dtype, d.T, d.HD);
+    return MFVIT_OK;
+}
+int mfvit_vit_forward_seg(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, const mfvit_vit_seg* seg, const float* params, const void* shadow,
+                          const float* x_in, void* workspace, float* x_out, mfvit_stream_t stream) {
+    if (!seg) return MFVIT_EINVAL;
+    ShareScope share(cfg);
+    return encoder_forward(cfg, drop, params, shadow, x_in, workspace, x_out, stream, false, nullptr, 0, seg);
+}
+int mfvit_vit_backward_seg(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, const mfvit_vit_seg* seg, const float* params, const void* shadow,
+                           void* workspace, const float* dx_out, float* dparams, float* dx_in, float* dimg, int stage_hi, int stage_lo,
+                           mfvit_stream_t stream) {
+    if (!cfg || !seg || (!dx_out && stage_hi >= seg->block_hi)) return MFVIT_EINVAL;
+    ShareScope share(cfg);
+    return encoder_backward(cfg, drop, params, shadow, workspace, {dx_out, dparams, dx_in, dimg, stage_hi, stage_lo}, stream, false, 0, seg);
 }
 int mfvit_vit_backward_drop(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, const float* params, const void* shadow, void* workspace,
                             const float* dfeatures, float* dparams, int stage_hi, int stage_lo, mfvit_stream_t stream) {

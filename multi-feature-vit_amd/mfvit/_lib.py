@@ -37,6 +37,11 @@ class PatchKeepCfg(Structure):
     _fields_ = [("dtype", c_int), ("batch", c_int), ("img_h", c_int), ("img_w", c_int), ("keep", c_int), ("dim", c_int)]
 
 
+class VitSeg(Structure):
+    """mfvit_vit_seg: a block range of the image-mode stack at a given sequence length (include/mfvit.h)."""
+    _fields_ = [("block_lo", c_int), ("block_hi", c_int), ("tokens", c_int), ("image_in", c_int)]
+
+
 class VitAttnReq(Structure):
     """mfvit_vit_attn_req: which attention maps / rollout an evaluation forward writes (include/mfvit.h)."""
     _fields_ = [("blocks", c_uint64), ("fuse", c_int), ("cls_only", c_int), ("maps", c_void_p), ("rollout", c_void_p), ("scratch", c_void_p)]
@@ -93,6 +98,10 @@ SIGNATURES = {
     "mfvit_patch_keep_workspace_bytes": (c_size_t, [POINTER(PatchKeepCfg), I]),
     "mfvit_patch_keep_embed": (I, [POINTER(PatchKeepCfg), P, P, P, P, P, P, P, I, P, P, P]),
     "mfvit_patch_keep_embed_bwd": (I, [POINTER(PatchKeepCfg), P, P, P, P, P, P, P, P, P]),
+    "mfvit_vit_workspace_bytes_seg": (c_size_t, [POINTER(VitCfg), POINTER(VitDrop), POINTER(VitSeg), I]),
+    "mfvit_vit_attn_layout_seg": (I, [POINTER(VitCfg), POINTER(VitDrop), POINTER(VitSeg), POINTER(c_int64)]),
+    "mfvit_vit_forward_seg": (I, [POINTER(VitCfg), POINTER(VitDrop), POINTER(VitSeg), P, P, P, P, P, P]),
+    "mfvit_vit_backward_seg": (I, [POINTER(VitCfg), POINTER(VitDrop), POINTER(VitSeg), P, P, P, P, P, P, P, I, I, P]),
     "mfvit_vit_hidden_layout": (I, [POINTER(VitCfg), POINTER(c_int64)]),
     "mfvit_vit_attn_layout": (I, [POINTER(VitCfg), POINTER(c_int64)]),
     "mfvit_vit_attn_scratch_bytes": (c_size_t, [POINTER(VitCfg), POINTER(VitAttnReq)]),
@@ -191,6 +200,10 @@ SIGNATURES = {
     "mfvit_attr_inputs": (I, [P, P, I, P, P, P, I, P, I, I, I, L, P]),
     "mfvit_attr_accumulate": (I, [P, P, P, I, I, L, I, P]),
     "mfvit_attr_finish": (I, [P, P, P, I, I, I, P, P, P, I, I, I, I, P]),
+    "mfvit_token_score": (I, [I, P, P, I, I, I, I, P, P, P]),
+    "mfvit_token_select": (I, [P, L, I, I, I, P, P, P, P, P, P]),
+    "mfvit_token_reorg_fwd": (I, [P, P, P, P, P, I, I, I, I, I, P, P]),
+    "mfvit_token_reorg_bwd": (I, [P, P, P, P, P, I, I, I, I, I, P, P]),
     "mfvit_prof_enable": (I, [I]),
     "mfvit_set_wgrad_stream": (I, [I]),
     "mfvit_set_stream_share": (I, [I]),

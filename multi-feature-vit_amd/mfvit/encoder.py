@@ -272,6 +272,48 @@ class _EncoderKeepFn(torch.autograd.Function):
         return (None, dimg, None, None, None) + tuple(grads)
 
 
+class _EncoderPruneFn(torch.autograd.Function):
+    """features3D under token pruning as one autograd node: block range, score, select, reorganise, block range, .. (mfvit_vit_forward_seg and
+    the mfvit_token_* kernels; patch dropout's front end in front when it is active); the backward walks the same chain in reverse, stage group by
+    stage group.  The selections and the fused row's weights are constants: no gradient flows to block l's attention through them."""
+
+    @staticmethod
+    def forward(ctx, model, img, pidx, forced, need_grad, drop, *params):
+        want_dimg = bool(need_grad and ctx.needs_input_grad[1])
+        feats, state = model._run_forward_prune(img, pidx, forced, need_grad, drop, want_dimg)
+        ctx.model = model
+        ctx.state = state
+        ctx.cfg = model._cfg(img, need_grad)
+        ctx.drop = drop
+        ctx.want_dimg = want_dimg
+        ctx.img_meta = (img.shape, img.dtype)
+        return feats
+
+    @staticmethod
+    def backward(ctx, dfeats):
+        model = ctx.model
+        if torch.is_grad_enabled():
+            raise _lib.MfvitError("double backward through the encoder (create_graph=True) is not supported: its backward is one HIP call "
+                                  "whose results are not differentiable")
+        if ctx.state is None:
+            raise _lib.MfvitError("the encoder's saved activations were already released: a second backward through the same forward "
+                                  "(retain_graph=True) is not supported - run the forward again")
+        dimg = None
+        if ctx.want_dimg and ctx.needs_input_grad[1]:
+            shape, dtype = ctx.img_meta
+            dimg = torch.empty(shape, device=dfeats.device, dtype=torch.float32)
+            dimg.record_stream(torch.cuda.current_stream(dfeats.device))
+        want_params = any(ctx.needs_input_grad[6:])
+        grads = model._run_backward_prune(ctx.cfg, ctx.state, dfeats, drop=ctx.drop, dimg=dimg, want_params=want_params)
+        grads = [g if need else None for g, need in zip(grads, ctx.needs_input_grad[6:])]
+        model._release_prune_state(ctx.state)
+        ctx.state = None
+        model._feat_cache = None
+        if dimg is not None and dimg.dtype != ctx.img_meta[1]:
+            dimg = dimg.to(ctx.img_meta[1])
+        return (None, dimg, None, None, None, None) + tuple(grads)
+
+
 class _HeadFn(torch.autograd.Function):
     """Small classifier head on the cls rows of a token tensor: y = feats[:, 0] @ W.T + b (f32)."""
 
@@ -303,7 +345,8 @@ class _HeadFn(torch.autograd.Function):
 class VisionTransformerMoCo(nn.Module):
     def __init__(self, img_size=224, patch_size=16, embed_dim=384, depth=12, num_heads=12, mlp_ratio=4.0, qkv_bias=True,
                  num_classes=1000, stop_grad_conv1=False, precision=None, drop_rate=0.0, attn_drop_rate=0.0, drop_path_rate=0.0,
-                 patch_drop_rate=0.0, patch_drop_ordered=False, **unused_timm_kwargs):
+                 patch_drop_rate=0.0, patch_drop_ordered=False, token_keep_rate=1.0, token_prune_blocks=None, token_fuse=True,
+                 **unused_timm_kwargs):
         super().__init__()
         for name, r in (("drop_rate", drop_rate), ("attn_drop_rate", attn_drop_rate), ("drop_path_rate", drop_path_rate),
                         ("patch_drop_rate", patch_drop_rate)):
@@ -350,6 +393,15 @@ class VisionTransformerMoCo(nn.Module):
         self._feat_cache = None
         self._lora = None                   # mfvit.lora.LoraState while adapters are attached
         self.last_keep_indices = None       # (B, K) int64: the kept patches of the last training-mode forward under patch dropout
+        # token pruning between blocks (EViT; csrc/token_prune.hip): plain attributes, read on every forward - the rate may change between steps
+        self.token_keep_rate = float(token_keep_rate)
+        self.token_prune_blocks = (tuple(sorted({l for l in (depth // 4, depth // 2, 3 * depth // 4) if 0 <= l <= depth - 2}))
+                                   if token_prune_blocks is None else tuple(token_prune_blocks))
+        self.token_fuse = bool(token_fuse)
+        self._token_plan()                  # (validates)
+        self.last_token_indices = None      # [(B, K) int64 per executed stage, in that stage's own row numbering] of the last pruned forward
+        self._last_token_plan = None        # (T0, fuse) of that forward: what token_origin() composes with
+        self._prune_sizes = {}              # workspace sizes of the current token plan, per kind of call (_retain_prune_sizes)
         self._keep_pin = None               # a draw pinned by the model that drives this encoder (Fus_CrossViT: one draw per step)
         self._keep_err = None               # the front end's device error word (a patch index outside the grid)
         self._flatten()
@@ -420,6 +472,7 @@ class VisionTransformerMoCo(nn.Module):
         self._shadow = None
         self._shadow_key = None
         self._ws_pool = {}
+        self._prune_sizes = {}
         self._feat_cache = None
 
     def _arena_intact(self):
@@ -546,6 +599,91 @@ class VisionTransformerMoCo(nn.Module):
         if keep_indices is not None:
             return self._check_keep_indices(keep_indices, int(x.shape[0]))
         return pin if pin is not None else self.draw_keep_indices(x.shape[0], x.device)
+
+    # ------------------------------------------------------------------ token pruning between blocks (EViT; csrc/token_prune.hip)
+    def _token_plan(self):
+        """(keep_rate, prune_blocks, fuse) as the attributes hold them now, checked; prune_blocks () when nothing is pruned."""
+        rate = float(self.token_keep_rate)
+        if not 0.0 < rate <= 1.0:
+            raise _lib.MfvitError(f"token_keep_rate must lie in (0, 1], got {self.token_keep_rate!r}")
+        try:
+            blocks = tuple(operator.index(l) for l in self.token_prune_blocks)
+        except TypeError:
+            raise _lib.MfvitError(f"token_prune_blocks must hold block indices, got {self.token_prune_blocks!r}") from None
+        if any(not 0 <= l <= self.depth - 2 for l in blocks) or any(a >= b for a, b in zip(blocks, blocks[1:])):
+            raise _lib.MfvitError(f"token_prune_blocks must be strictly increasing block indices in [0, {self.depth - 2}], got {blocks}")
+        return rate, (blocks if rate < 1.0 else ()), bool(self.token_fuse)
+
+    def token_pruning_active(self):
+        """True when a forward would shorten the sequence between blocks (token_keep_rate < 1 and a prune block)."""
+        rate, blocks, _ = self._token_plan()
+        return rate < 1.0 and len(blocks) > 0
+
+    @staticmethod
+    def _token_keep(T, rate):
+        return max(1, min(T - 1, int(math.ceil(rate * (T - 1)))))
+
+    def _token_segments(self, T):
+        """[(block_lo, block_hi, tokens)] of a forward that starts with T rows per image: a new segment behind every prune block whose
+        stage is not skipped (K == T - 1 keeps the sequence)."""
+        rate, blocks, fuse = self._token_plan()
+        segs, lo = [], 0
+        for l in blocks:
+            K = self._token_keep(T, rate)
+            if K < T - 1:
+                segs.append((lo, l + 1, T))
+                lo, T = l + 1, 1 + K + int(fuse)
+        return segs + [(lo, self.depth, T)]
+
+    def token_schedule(self, T=None):
+        """Tokens per image of every segment of a forward that starts with T rows (default: the full grid, cls included).  Host only."""
+        T = self.num_tokens if T is None else operator.index(T)
+        if not 2 <= T <= self.num_tokens:
+            raise _lib.MfvitError(f"T must lie in [2, {self.num_tokens}], got {T}")
+        return [t for _, _, t in self._token_segments(T)]
+
+    def token_origin(self):
+        """(B, T_last - 1) int64: the row (cls not counted) of the sequence in front of block 0 that every non-cls row of the last pruned forward's
+        output came from, -1 for a fused row.  Under patch dropout these are positions in last_keep_indices."""
+        sel = self.last_token_indices
+        if not sel:
+            raise _lib.MfvitError("no pruned forward has run")
+        B = sel[0].shape[0]
+        T0, fuse = self._last_token_plan
+        org = torch.arange(T0 - 1, device=sel[0].device).expand(B, -1)
+        for keep in sel:
+            org = torch.gather(org, 1, keep)
+            if fuse:
+                org = torch.cat([org, org.new_full((B, 1), -1)], dim=1)
+        return org
+
+    def _refuse_if_pruning(self, what):
+        if self.token_pruning_active():
+            raise _lib.MfvitError(f"{what} assumes the full token grid and is not built for an encoder that prunes tokens between blocks: set "
+                                  "token_keep_rate = 1.0 for this call")
+
+    def _check_token_indices(self, token_indices, B, T0):
+        """Forced selections, checked on the host (one sync): one (B, K) integer tensor per stage of the schedule, each in that stage's own row
+        numbering, in range and distinct per image.  Returns them as ascending int32 device tensors."""
+        segs = self._token_segments(T0)
+        if not isinstance(token_indices, (list, tuple)) or len(token_indices) != len(segs) - 1:
+            raise _lib.MfvitError(f"token_indices must be a list of {len(segs) - 1} (B, K) integer tensors, one per pruning stage")
+        out, flags = [], []
+        for (_, _, T), (_, _, Tn), idx in zip(segs, segs[1:], token_indices):
+            K = Tn - 1 - int(self.token_fuse)
+            if not isinstance(idx, torch.Tensor) or idx.dim() != 2 or idx.dtype.is_floating_point or idx.dtype in (torch.bool, torch.complex64,
+                                                                                                                 torch.complex128):
+                raise _lib.MfvitError("token_indices must hold (B, K) integer tensors")
+            if tuple(idx.shape) != (B, K):
+                raise _lib.MfvitError(f"token_indices of the stage on {T} rows must have shape ({B}, {K}), got {tuple(idx.shape)}")
+            srt = idx.detach().to(self._arena.device, torch.int64).sort(dim=-1)[0]
+            flags.append((srt[:, 0] < 0).any() | (srt[:, -1] >= T - 1).any())
+            flags.append((srt[:, 1:] == srt[:, :-1]).any() if K > 1 else torch.zeros((), dtype=torch.bool, device=srt.device))
+            out.append(srt.to(torch.int32).contiguous())
+        if flags and any(torch.stack(flags).tolist()):
+            raise _lib.MfvitError("token_indices out of range for their stage, or repeating a row within an image")
+        self.check_keep_error()
+        return out
 
     def _draw_drop(self):
         """mfvit_vit_drop of one training-mode forward (None when no site is active: eval(), or all rates 0).  The seed comes from torch's CPU
@@ -699,6 +837,157 @@ class VisionTransformerMoCo(nn.Module):
             ws = fws = None
         return feats, ws, (T, pk, fws, idx)
 
+    def _take_ws(self, nbytes, dev):
+        pool = self._ws_pool.setdefault(nbytes, [])
+        return pool.pop() if pool else torch.empty(nbytes, device=dev, dtype=torch.uint8)
+
+    def _run_forward_prune(self, img, pidx, forced, save, drop=None, want_dimg=False):
+        """Token pruning: (features (B, T_last, D), state).  The block ranges of _token_segments run through mfvit_vit_forward_seg, each on a
+        workspace of its own; behind every range but the last the rows are scored by the cls attention of its last block (read in place from the
+        range's workspace), selected and reorganised (csrc/token_prune.hip).  pidx: the kept patches of an active patch dropout (the first range
+        then takes the front end's x0), forced: checked selections (_check_token_indices) or None.  state = (segments, stages, keep) for the
+        backward: per segment (mfvit_vit_seg, workspace), per stage (idx_keep, idx_drop, w, T, K) on the device."""
+        img = self._prep_img(img)
+        dev = img.device
+        cfg = self._cfg(img, save)
+        self._ensure_shadow(cfg)
+        B, D, fuse = img.shape[0], self.embed_dim, int(self.token_fuse)
+        if self._keep_err is None or self._keep_err.device != dev:
+            self._keep_err = torch.zeros(1, device=dev, dtype=torch.int32)
+        keep = None
+        x = img
+        if pidx is not None:        # patch dropout in front: the front end of _run_forward_keep
+            if pidx.device != dev:
+                raise _lib.MfvitError(f"keep indices on {pidx.device} but input on {dev}")
+            pidx.record_stream(torch.cuda.current_stream(dev))
+            pk = _lib.PatchKeepCfg(cfg.dtype, B, cfg.img_h, cfg.img_w, pidx.shape[1], D)
+            fbytes = lib().mfvit_patch_keep_workspace_bytes(pk, int(bool(save)))
+            if fbytes == 0:
+                raise _lib.MfvitError("invalid encoder configuration for patch dropout")
+            fws = self._take_ws(fbytes, dev)
+            a, off = self._arena.data_ptr(), self._offsets
+            x = torch.empty(B, pidx.shape[1] + 1, D, device=dev, dtype=torch.float32)
+            check(lib().mfvit_patch_keep_embed(pk, ptr(img), ptr(pidx), a + 4 * off["cls_token"][0], a + 4 * off["pos_embed"][0],
+                                               a + 4 * off["patch_embed.proj.weight"][0], a + 4 * off["patch_embed.proj.bias"][0], ptr(fws),
+                                               int(bool(save)), ptr(x), ptr(self._keep_err), stream()), "mfvit_patch_keep_embed")
+            keep = (x.shape[1], pk, fws if save else None, pidx)
+            if not save:
+                self._release_ws(fws)
+        T0 = self.num_tokens if pidx is None else x.shape[1]
+        plan = self._token_segments(T0)
+        H, HD = self.num_heads, D // self.num_heads
+        seg_list = [_lib.VitSeg(lo, hi, T, int(i == 0 and pidx is None)) for i, (lo, hi, T) in enumerate(plan)]
+        sizes = [lib().mfvit_vit_workspace_bytes_seg(cfg, drop, seg, int(want_dimg and seg.image_in)) for seg in seg_list]
+        if 0 in sizes:
+            raise _lib.MfvitError("invalid encoder configuration for token pruning (image size a multiple of 16, dim 384 or 768, head_dim "
+                                  "32 / 64 / 96)")
+        self._retain_prune_sizes((bool(save), bool(want_dimg), drop is not None, B, pidx is not None), sizes)
+        segs, stages = [], []
+        for i, (lo, hi, T) in enumerate(plan):
+            seg, nbytes = seg_list[i], sizes[i]
+            ws = self._take_ws(nbytes, dev)
+            out = torch.empty(B, T, D, device=dev, dtype=torch.float32)
+            check(lib().mfvit_vit_forward_seg(cfg, drop, seg, ptr(self._arena), ptr(self._shadow), ptr(x), ptr(ws), ptr(out), stream()),
+                  "mfvit_vit_forward_seg")
+            x = out
+            if i + 1 < len(plan):
+                K = plan[i + 1][2] - 1 - fuse
+                lay = (ctypes.c_int64 * 4)()
+                check(lib().mfvit_vit_attn_layout_seg(cfg, drop, seg, lay), "mfvit_vit_attn_layout_seg")
+                last = (hi - 1 - lo) * lay[2]
+                probs = torch.empty(B, T, device=dev, dtype=torch.float32)
+                score = torch.empty(B, T - 1, device=dev, dtype=torch.float32)
+                check(lib().mfvit_token_score(int(lay[3]), ws.data_ptr() + lay[0] + last, ws.data_ptr() + lay[1] + last, B, T, H, HD, ptr(probs),
+                                              ptr(score), stream()), "mfvit_token_score")
+                ik = torch.empty(B, K, device=dev, dtype=torch.int32)
+                idr = torch.empty(B, T - 1 - K, device=dev, dtype=torch.int32)
+                w = torch.empty(B, T - 1 - K, device=dev, dtype=torch.float32)
+                check(lib().mfvit_token_select(ptr(score), T - 1, B, T - 1, K, ptr(forced[i]) if forced is not None else None, ptr(ik), ptr(idr),
+                                               ptr(w), ptr(self._keep_err), stream()), "mfvit_token_select")
+                out = torch.empty(B, 1 + K + fuse, D, device=dev, dtype=torch.float32)
+                check(lib().mfvit_token_reorg_fwd(ptr(x), ptr(ik), ptr(idr), ptr(w), ptr(out), B, T, D, K, fuse, ptr(self._keep_err), stream()),
+                      "mfvit_token_reorg_fwd")
+                x = out
+                stages.append((ik, idr, w, T, K))
+            if save:
+                segs.append((seg, ws))
+            else:
+                self._release_prune_ws(ws)
+        self.last_token_indices = [st[0].long() for st in stages]
+        self._last_token_plan = (T0, bool(fuse))
+        return x, ((segs, stages, keep, fuse) if save else None)
+
+    # The workspaces of the block ranges are sized by the token plan, and token_keep_rate may change from step to step (EViT warms it up): the
+    # pool keeps the sizes of the CURRENT plan of every kind of call (saving or not, with d img, with dropout, batch size, patch dropout in
+    # front) and lets every other range workspace go - a warm-up through sixty rates holds one plan's buffers, not sixty.
+    def _retain_prune_sizes(self, kind, sizes):
+        new = frozenset(sizes)
+        old = self._prune_sizes.get(kind)
+        self._prune_sizes[kind] = new
+        if old is not None and old != new:
+            live = frozenset().union(*self._prune_sizes.values())
+            for n in old - live:
+                self._ws_pool.pop(n, None)
+
+    def _release_prune_ws(self, ws):
+        if ws is not None and any(ws.numel() in s for s in self._prune_sizes.values()):
+            self._release_ws(ws)
+
+    def _release_prune_state(self, state):
+        if state is not None:
+            for _, ws in state[0]:
+                self._release_prune_ws(ws)
+            if state[2] is not None:
+                self._release_ws(state[2][2])
+
+    def _run_backward_prune(self, cfg, state, dfeats, drop=None, dimg=None, want_params=True):
+        """The backward of _run_forward_prune: the block ranges from the last down (mfvit_vit_backward_seg), mfvit_token_reorg_bwd between two of
+        them, the patch-dropout front end's backward behind the first when it ran.  Stage groups and the stage hook as in _run_backward: a
+        group's model stages [lo, hi] are cut at the range boundaries; a range's entry from its dx_out rides with its top block, what feeds its
+        first block (and the reorganisation's backward) with that block."""
+        segs, stages, keep, fuse = state
+        dev = dfeats.device
+        g = dfeats.contiguous()
+        if g.dtype != torch.float32:
+            g = g.float()
+        B, D = cfg.batch, self.embed_dim
+        if not want_params and dimg is None:
+            raise _lib.MfvitError("a backward without parameter gradients needs the image gradient")
+        gflat = self._take_grad_arena() if want_params else None
+        hook = (getattr(self, "_grad_stage_hook", None)) if want_params else None
+        dx_in = [None if seg.image_in else torch.empty(B, seg.tokens, D, device=dev, dtype=torch.float32) for seg, _ in segs]
+        cur = g                                    # the gradient of the output of the range being walked
+        i = len(segs) - 1
+        for hi, lo in self._stage_groups(hook is not None):
+            while i >= 0:
+                seg, ws = segs[i]
+                a, b = seg.block_lo, seg.block_hi
+                top = min(hi, b - 1)               # the highest block of this range inside the group
+                if top < a or top < lo:
+                    break
+                s_hi = b if (top == b - 1 and (b < self.depth or hi == self.depth)) else top
+                bot = max(lo, a)
+                s_lo = (lo if a == 0 else a - 1) if bot == a else bot
+                check(lib().mfvit_vit_backward_seg(cfg, drop, seg, ptr(self._arena), ptr(self._shadow), ptr(ws), ptr(cur), ptr(gflat), ptr(dx_in[i]),
+                                                   ptr(dimg) if (seg.image_in and s_lo == -1) else None, s_hi, s_lo, stream()),
+                      "mfvit_vit_backward_seg")
+                if s_lo != a - 1:
+                    break                          # the rest of this range belongs to the next group
+                if i > 0:
+                    ik, idr, w, T, K = stages[i - 1]
+                    nxt = torch.empty(B, T, D, device=dev, dtype=torch.float32)
+                    check(lib().mfvit_token_reorg_bwd(ptr(dx_in[i]), ptr(ik), ptr(idr), ptr(w), ptr(nxt), B, T, D, K, fuse, ptr(self._keep_err),
+                                                      stream()), "mfvit_token_reorg_bwd")
+                    cur = nxt
+                elif keep is not None:
+                    self._keep_embed_bwd(keep, dx_in[0], gflat, dimg, cfg)
+                i -= 1
+            if hook is not None:
+                hook(self, hi, lo, gflat)
+        if not want_params:
+            return [None] * len(self._arena_params)
+        return self._grad_views(gflat)
+
     def _keep_embed_bwd(self, keep, dx0, gflat, dimg, cfg):
         """The front end's backward (stage -1 under patch dropout): d cls_token, d pe_b, d pe_w into the gradient arena `gflat` (None: none), dimg."""
         T, pk, fws, idx = keep
@@ -708,6 +997,55 @@ class VisionTransformerMoCo(nn.Module):
         check(lib().mfvit_patch_keep_embed_bwd(pk, ptr(idx), ptr(fws), ptr(dx0), g("cls_token"), None if stop else g("patch_embed.proj.weight"),
                                                None if stop else g("patch_embed.proj.bias"), ptr(dimg), ptr(self._keep_err), stream()),
               "mfvit_patch_keep_embed_bwd")
+
+    def _take_grad_arena(self):
+        """The zeroed flat gradient arena of one backward."""
+        # The flat gradient arena is reused from step to step (stable addresses: the optimizers' device tables stay valid) unless a
+        # parameter still holds a gradient - accumulation over several backward passes, or a second pass through this encoder
+        # inside one autograd run (MoCo-v3 feeds both views through the base encoder) - in which case a fresh one is allocated.
+        # ALIASING CONTRACT (ADVICE r1): gradient tensors handed out by one backward are views of this arena and are overwritten
+        # by the next backward once every parameter's .grad is None again.  A caller that keeps gradients outside .grad across steps
+        # (torch.autograd.grad results, detached copies of views kept after zero_grad(set_to_none=True)) must clone them, or switch
+        # the reuse off: MFVIT_GRAD_ARENA_REUSE=0 / model.reuse_grad_arena = False (a fresh arena per backward, 87 MB per encoder).
+        reuse = getattr(self, "reuse_grad_arena", os.environ.get("MFVIT_GRAD_ARENA_REUSE", "1") != "0")
+        ga = getattr(self, "_grad_arena", None) if reuse else None
+        # (`_grad_arena_lent` covers the second case before autograd has accumulated the first pass's views into p.grad; it is
+        # cleared by the next forward.)
+        if (ga is not None and not getattr(self, "_grad_arena_lent", False) and ga.shape == self._arena.shape
+                and ga.device == self._arena.device and all(p.grad is None for p in self._arena_params)):
+            gflat = ga.zero_()
+        else:
+            gflat = torch.zeros_like(self._arena)
+            if not getattr(self, "_grad_arena_lent", False):
+                self._grad_arena = gflat
+        self._grad_arena_lent = True
+        return gflat
+
+    def _stage_groups(self, staged):
+        """The (hi, lo) stage groups of one backward, descending: one group, or with a stage hook groups of `_grad_bucket_layers` blocks."""
+        if not staged:
+            return [(self.depth, -1)]
+        # stages depth (final norm), depth-1 .. 0 (blocks), -1 (embedding) run in groups of `_grad_bucket_layers` blocks: after
+        # each group its (contiguous) gradient slice can be exchanged while the next group computes.  Every library call joins
+        # its weight-gradient side stream at the end, so fewer, larger groups keep more of that overlap than one call per block.
+        gb = max(1, int(getattr(self, "_grad_bucket_layers", 4)))
+        out, hi = [], self.depth
+        while hi >= -1:
+            lo = max(hi - gb, -1) if hi == self.depth else max(hi - gb + 1, -1)
+            if lo == 0:
+                lo = -1                                   # the embedding stage rides with the last block group
+            out.append((hi, lo))
+            hi = lo - 1
+        return out
+
+    def _grad_views(self, gflat):
+        self._last_grad_arena = gflat
+        # per-parameter views of the flat gradient arena, arena order: ONE C++ call for the 150 views (a Python loop of slice + view cost 0.3 ms
+        # of host time per encoder and step - at 16 pairs per step the host, not the GPU, sets the pace); fresh tensor objects every time, so
+        # autograd's AccumulateGrad can keep them as .grad without copying
+        params = [mod._parameters[attr] for _, mod, attr in self._param_holders()]
+        views = torch._utils._unflatten_dense_tensors(gflat, params)
+        return [v if p.requires_grad else None for v, p in zip(views, params)]
 
     def _run_backward(self, cfg, ws, dfeats, on_stage_done=None, drop=None, dimg=None, want_params=True, keep=None):
         """Returns per-parameter gradient views (arena order) of a fresh flat gradient arena.  drop: the forward's mfvit_vit_drop (or None).
@@ -730,25 +1068,7 @@ class VisionTransformerMoCo(nn.Module):
             check(lib().mfvit_vit_backward_ex(cfg, drop, ptr(self._kernel_params()), ptr(self._shadow), ptr(ws), ptr(dfeats), None, ptr(dimg),
                                               self.depth, -1, stream()), "mfvit_vit_backward_ex")
             return [None] * len(self._arena_params)
-        # The flat gradient arena is reused from step to step (stable addresses: the optimizers' device tables stay valid) unless a
-        # parameter still holds a gradient - accumulation over several backward passes, or a second pass through this encoder
-        # inside one autograd run (MoCo-v3 feeds both views through the base encoder) - in which case a fresh one is allocated.
-        # ALIASING CONTRACT: gradient tensors handed out by one backward are views of this arena and are overwritten
-        # by the next backward once every parameter's .grad is None again.  A caller that keeps gradients outside .grad across steps
-        # (torch.autograd.grad results, detached copies of views kept after zero_grad(set_to_none=True)) must clone them, or switch
-        # the reuse off: MFVIT_GRAD_ARENA_REUSE=0 / model.reuse_grad_arena = False (a fresh arena per backward, 87 MB per encoder).
-        reuse = getattr(self, "reuse_grad_arena", os.environ.get("MFVIT_GRAD_ARENA_REUSE", "1") != "0")
-        ga = getattr(self, "_grad_arena", None) if reuse else None
-        # (`_grad_arena_lent` covers the second case before autograd has accumulated the first pass's views into p.grad; it is
-        # cleared by the next forward.)
-        if (ga is not None and not getattr(self, "_grad_arena_lent", False) and ga.shape == self._arena.shape
-                and ga.device == self._arena.device and all(p.grad is None for p in self._arena_params)):
-            gflat = ga.zero_()
-        else:
-            gflat = torch.zeros_like(self._arena)
-            if not getattr(self, "_grad_arena_lent", False):
-                self._grad_arena = gflat
-        self._grad_arena_lent = True
+        gflat = self._take_grad_arena()
         hook = on_stage_done or getattr(self, "_grad_stage_hook", None)
 
         def bwd(hi, lo):
@@ -761,28 +1081,11 @@ class VisionTransformerMoCo(nn.Module):
             # (drop = NULL, dimg = NULL: exactly mfvit_vit_backward; the call that runs the embedding stage also writes the image gradient)
             check(lib().mfvit_vit_backward_ex(cfg, drop, ptr(self._kernel_params()), ptr(self._shadow), ptr(ws), ptr(dfeats), ptr(gflat),
                                               ptr(dimg) if lo == -1 else None, hi, lo, stream()), "mfvit_vit_backward_ex")
-        if hook is None:
-            bwd(self.depth, -1)
-        else:
-            # stages depth (final norm), depth-1 .. 0 (blocks), -1 (embedding) run in groups of `_grad_bucket_layers` blocks: after
-            # each group its (contiguous) gradient slice can be exchanged while the next group computes.  Every library call joins
-            # its weight-gradient side stream at the end, so fewer, larger groups keep more of that overlap than one call per block.
-            gb = max(1, int(getattr(self, "_grad_bucket_layers", 4)))
-            hi = self.depth
-            while hi >= -1:
-                lo = max(hi - gb, -1) if hi == self.depth else max(hi - gb + 1, -1)
-                if lo == 0:
-                    lo = -1                                   # the embedding stage rides with the last block group
-                bwd(hi, lo)
+        for hi, lo in self._stage_groups(hook is not None):
+            bwd(hi, lo)
+            if hook is not None:
                 hook(self, hi, lo, gflat)
-                hi = lo - 1
-        self._last_grad_arena = gflat
-        # per-parameter views of the flat gradient arena, arena order: ONE C++ call for the 150 views (a Python loop of slice + view cost 0.3 ms
-        # of host time per encoder and step - at 16 pairs per step the host, not the GPU, sets the pace); fresh tensor objects every time, so
-        # autograd's AccumulateGrad can keep them as .grad without copying
-        params = [mod._parameters[attr] for _, mod, attr in self._param_holders()]
-        views = torch._utils._unflatten_dense_tensors(gflat, params)
-        return [v if p.requires_grad else None for v, p in zip(views, params)]
+        return self._grad_views(gflat)
 
     def _run_backward_lora(self, cfg, ws, dfeats, drop=None, dimg=None):
         """The selective backward of a model with adapters whose arena parameters are all frozen (mfvit_vit_backward_lora): returns the
@@ -811,7 +1114,7 @@ class VisionTransformerMoCo(nn.Module):
         return grads
 
     # ------------------------------------------------------------------ public API (reference call sites)
-    def _features(self, x, caller, keep_indices=None):
+    def _features(self, x, caller, keep_indices=None, token_indices=None):
         # activations are saved when a parameter or the image needs a gradient (saliency / FGSM with a frozen backbone: the image only)
         need_x = torch.is_grad_enabled() and x.requires_grad
         lo = self.__dict__.get("_lora")
@@ -826,6 +1129,19 @@ class VisionTransformerMoCo(nn.Module):
         # patch dropout: a draw of this forward's own makes it stochastic; a pinned draw (one per step, shared by both calls) does not
         idx = self._resolve_keep(x, keep_indices)
         stochastic = drop is not None or (idx is not None and pin is None)
+        prune = self.token_pruning_active()
+        if token_indices is not None and not prune:
+            raise _lib.MfvitError("token_indices given, but no token pruning is active (token_keep_rate = 1.0 or no prune block)")
+        if prune:
+            if lo is not None:
+                raise _lib.MfvitError("LoRA adapters together with token pruning are not built: the block ranges run on the plain parameter "
+                                      "arena (set token_keep_rate = 1.0, or detach the adapters)")
+            _lib.require_cuda(x)
+            forced = None
+            if token_indices is not None:
+                forced = self._check_token_indices(token_indices, int(x.shape[0]), self.num_tokens if idx is None else idx.shape[1] + 1)
+                stochastic = True                   # (a forced selection is never served from, or left in, the single-use cache)
+            key = key + (self.token_keep_rate, tuple(self.token_prune_blocks), self.token_fuse)
         if c is not None and c[0] is x and c[1] == key and c[2] != caller and not stochastic and (c[4] if len(c) > 4 else None) is idx:
             # the reference runs every backbone twice per step on the same tensor (features3D then __call__, FUS:128+131);
             # without dropout the second result is head(first[:, 0]): computed once.  Single use: a repeated call of
@@ -835,16 +1151,22 @@ class VisionTransformerMoCo(nn.Module):
         self._grad_arena_lent = False
         if idx is not None:
             self.last_keep_indices = idx
+        if prune:
+            feats = _EncoderPruneFn.apply(self, x, idx, forced, need, drop, *self._arena_params)
+        elif idx is not None:
             feats = _EncoderKeepFn.apply(self, x, idx, need, drop, *self._arena_params)
         else:
             feats = _EncoderFn.apply(self, x, need, drop, *self._arena_params, *lora_params)
         self._feat_cache = None if stochastic else (x, key, caller, feats, idx)
         return feats
 
-    def features3D(self, x, keep_indices=None):
+    def features3D(self, x, keep_indices=None, token_indices=None):
         """(B,3,H,W) -> (B, T, 384) tokens after the final LayerNorm (FUS:128,133; crossvit.py:130-146).  Training mode with patch dropout
-        (patch_drop.prob > 0, or explicit keep_indices (B, K): distinct patch indices per image): (B, 1 + K, 384), cls and the kept patches."""
-        return self._features(x, "features3D", keep_indices)
+        (patch_drop.prob > 0, or explicit keep_indices (B, K): distinct patch indices per image): (B, 1 + K, 384), cls and the kept patches.
+        With token pruning (token_keep_rate < 1; train() and eval() alike): (B, token_schedule()[-1], 384) - cls, the rows kept by every stage
+        and, with token_fuse, the fused rows; last_token_indices / token_origin() say which.  token_indices: the selections to use instead of
+        the model's own (the structure of last_token_indices), for tests and for reproducing a run."""
+        return self._features(x, "features3D", keep_indices, token_indices)
 
     def forward_head(self, feats):
         h = self.head
@@ -854,9 +1176,9 @@ class VisionTransformerMoCo(nn.Module):
             return _HeadFn.apply(feats, h.weight, h.bias)
         return h(feats[:, 0])      # a module the caller installed (MoCo's projector MLP: HIP Linear / BatchNorm nodes of its own)
 
-    def forward(self, x, keep_indices=None):
+    def forward(self, x, keep_indices=None, token_indices=None):
         """head(features3D(x)[:, 0])  (timm forward_features + head; training mode applies the dropout / drop-path / patch-dropout rates)."""
-        return self.forward_head(self._features(x, "forward", keep_indices))
+        return self.forward_head(self._features(x, "forward", keep_indices, token_indices))
 
     # ------------------------------------------------------------------ attention maps (include/mfvit.h, mfvit_vit_forward_attn)
     # All three run one evaluation forward (no dropout site, whatever self.training says) under no_grad, draw no seed, and leave the feature
@@ -880,6 +1202,7 @@ class VisionTransformerMoCo(nn.Module):
         return sorted(out)
 
     def _attn_forward(self, x, blocks, fuse, cls_only, rollout):
+        self._refuse_if_pruning("an attention map / rollout")
         img = self._prep_img(x.detach())
         with torch.no_grad():
             cfg = self._cfg(img, False)
@@ -947,6 +1270,7 @@ class VisionTransformerMoCo(nn.Module):
 
     def _rel_forward(self, x):
         """Evaluation forward with saved activations: (cfg, workspace, features).  The caller releases the workspace."""
+        self._refuse_if_pruning("a relevance map, hidden state or attention statistic")
         img = self._prep_img(x.detach())
         with torch.no_grad():
             cfg = self._cfg(img, True)

@@ -133,7 +133,28 @@ class Fus_CrossViT(nn.Module):
             return idx_c, idx_c
         return idx_c, draw(vit_enh, img_enh)
 
+    @staticmethod
+    def _check_token_pruning(vit_cxr, vit_enh):
+        """Token pruning between blocks (VisionTransformerMoCo.token_keep_rate < 1): the exchange takes ONE token count (mfvit_fusion_cfg), so both
+        encoders must prune alike - same grid, rate, blocks and fuse flag; each stream still selects by its own attention."""
+        def plan(vit):
+            f = getattr(vit, "token_pruning_active", None)
+            if not callable(f) or not f():
+                return None
+            return {"token grid": vit.num_tokens, "token_keep_rate": float(vit.token_keep_rate),
+                    "token_prune_blocks": tuple(vit.token_prune_blocks), "token_fuse": bool(vit.token_fuse)}
+        pc, pe = plan(vit_cxr), plan(vit_enh)
+        if pc == pe:
+            return
+        from mfvit._lib import MfvitError
+        if pc is None or pe is None:
+            raise MfvitError("token pruning is active in one encoder only: the exchange needs the same token count from both streams (set the "
+                             "same token_keep_rate, token_prune_blocks and token_fuse on both)")
+        diff = ", ".join(f"{k} {pc[k]!r} vs {pe[k]!r}" for k in pc if pc[k] != pe[k])
+        raise MfvitError(f"the two encoders prune tokens differently ({diff}): the exchange needs the same token count from both streams")
+
     def forward(self, vit_cxr, vit_enh, img_cxr, img_enh):
+        self._check_token_pruning(vit_cxr, vit_enh)
         idx_c, idx_e = self._draw_patch_keep(vit_cxr, vit_enh, img_cxr, img_enh)
         if idx_c is None and idx_e is None:
             return self._forward(vit_cxr, vit_enh, img_cxr, img_enh)
@@ -241,6 +262,7 @@ class Fus_CrossViT(nn.Module):
     @staticmethod
     def _eval_features(vit, img):
         """features3D of an evaluation forward without saved activations, the feature cache left alone."""
+        vit._refuse_if_pruning("an exchange map / cross-stream relevance")
         img = vit._prep_img(img.detach())
         with torch.no_grad():
             cfg = vit._cfg(img, False)
