@@ -123,20 +123,10 @@ bool get_dims(const mfvit_vit_cfg* c, const mfvit_vit_drop* x, Dims& d) {
     return true;
 }
 
-// The image-mode stack on a given x_0 of `tokens` rows per image (mfvit_vit_forward_x0; timm PatchDropout shortens the sequence in front of the
-// blocks): an ordinary image-mode cfg whose arena keeps the full grid (Tp = 1 + gh gw rows of pos_embed), every activation and launch at T = tokens.
-// (the limits of get_dims hold for the full grid - the same model runs it in eval() - and with them for every shorter sequence)
-bool get_dims_x0(const mfvit_vit_cfg* c, const mfvit_vit_drop* x, int tokens, Dims& d) {
-    if (!get_dims(c, x, d) || d.tok) return false;
-    if (tokens < 2 || tokens > d.Tp) return false;
-    d.T = tokens;
-    d.M = d.B * tokens;
-    d.x0in = true;
-    return true;
-}
-
 // A block range of the image-mode stack (mfvit_vit_forward_seg): blocks [block_lo, block_hi) at `tokens` rows per image, entered with the image
-// (the embedding stage: block_lo == 0 on the full grid only) or with the residual stream x_{block_lo} (the row pass of the given-x0 entry).
+// (the embedding stage: block_lo == 0 on the full grid only) or with the residual stream x_{block_lo}: an ordinary image-mode cfg whose arena keeps
+// the full grid (Tp = 1 + gh gw rows of pos_embed), every activation and launch at T = tokens.
+// (the limits of get_dims hold for the full grid - the same model runs it in eval() - and with them for every shorter sequence)
 bool get_dims_seg(const mfvit_vit_cfg* c, const mfvit_vit_drop* x, const mfvit_vit_seg* s, Dims& d) {
     if (!s || !get_dims(c, x, d) || d.tok) return false;
     if (s->block_lo < 0 || s->block_lo >= s->block_hi || s->block_hi > d.depth) return false;
@@ -149,6 +139,8 @@ bool get_dims_seg(const mfvit_vit_cfg* c, const mfvit_vit_drop* x, const mfvit_v
     d.l1 = s->block_hi;
     return true;
 }
+// the stack on a given x_0 (mfvit_vit_forward_x0; timm PatchDropout shortens the sequence in front of the blocks): the range [0, depth) entered with x_0
+mfvit_vit_seg x0_seg(const mfvit_vit_cfg* c, int tokens) { return {0, c ? c->depth : 0, tokens, 0}; }
 
 // ------------------------------------------------------------------ parameter arena layout (floats)
 struct ParamLayout {
@@ -791,10 +783,9 @@ static int fwd_block(const EncCtx& c, int l, float* features, const mfvit_vit_at
 // (img = (B,T,dim) tokens, + pos_emb).  Everything behind x_0 / LN1_0 is the same pre-LN block stack.
 static int encoder_forward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* dropcfg, const float* params, const void* shadow, const float* img,
                            void* workspace, float* features, mfvit_stream_t stream, bool want_tokens,
-                           const mfvit_vit_attn_req* attn = nullptr, int x0_tokens = 0, const mfvit_vit_seg* seg = nullptr) {
+                           const mfvit_vit_attn_req* attn = nullptr, const mfvit_vit_seg* seg = nullptr) {
     Dims d;
-    if (!(seg ? get_dims_seg(cfg, dropcfg, seg, d) : x0_tokens ? get_dims_x0(cfg, dropcfg, x0_tokens, d) : get_dims(cfg, dropcfg, d)) || !params ||
-        !shadow || !img || !workspace || !features)
+    if (!(seg ? get_dims_seg(cfg, dropcfg, seg, d) : get_dims(cfg, dropcfg, d)) || !params || !shadow || !img || !workspace || !features)
         return MFVIT_EINVAL;
     if (d.tok != want_tokens) return MFVIT_EINVAL;
     const EncCtx c(cfg, d, params, shadow, workspace, stream);
@@ -1111,10 +1102,9 @@ static int bwd_embed_image(BwdCtx& c) {
 // Shared backward of the two front ends (BwdArgs: what is asked for): stages stage_hi .. stage_lo in descending order - depth: the final norm,
 // depth-1 .. 0: the blocks, -1: the embedding - then whatever the stages left pending.
 static int encoder_backward(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* dropcfg, const float* params, const void* shadow, void* workspace,
-                            const BwdArgs& a, mfvit_stream_t stream, bool want_tokens, int x0_tokens = 0, const mfvit_vit_seg* seg = nullptr) {
+                            const BwdArgs& a, mfvit_stream_t stream, bool want_tokens, const mfvit_vit_seg* seg = nullptr) {
     Dims d;
-    if (!(seg ? get_dims_seg(cfg, dropcfg, seg, d) : x0_tokens ? get_dims_x0(cfg, dropcfg, x0_tokens, d) : get_dims(cfg, dropcfg, d)) || !params ||
-        !shadow || !workspace)
+    if (!(seg ? get_dims_seg(cfg, dropcfg, seg, d) : get_dims(cfg, dropcfg, d)) || !params || !shadow || !workspace)
         return MFVIT_EINVAL;
     if (d.x0in ? (!a.dinput || a.dimg || a.rel || a.lora) : (!a.dparams && !a.dimg && !a.rel && !a.lora)) return MFVIT_EINVAL;
     if (!d.save || d.tok != want_tokens) return MFVIT_EINVAL;
@@ -1186,21 +1176,21 @@ int mfvit_vit_backward_ex(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, 
     return encoder_backward(cfg, drop, params, shadow, workspace, {dfeatures, dparams, nullptr, dimg, stage_hi, stage_lo}, stream, false);
 }
 size_t mfvit_vit_workspace_bytes_x0(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, int tokens) {
-    Dims d;
-    if (!get_dims_x0(cfg, drop, tokens, d)) return 0;
-    return ws_layout(d).total;
+    const mfvit_vit_seg seg = x0_seg(cfg, tokens);
+    return mfvit_vit_workspace_bytes_seg(cfg, drop, &seg, 0);
 }
 int mfvit_vit_forward_x0(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, int tokens, const float* params, const void* shadow, const float* x0,
                          void* workspace, float* features, mfvit_stream_t stream) {
-    if (tokens < 2) return MFVIT_EINVAL;
+    const mfvit_vit_seg seg = x0_seg(cfg, tokens);
     ShareScope share(cfg);
-    return encoder_forward(cfg, drop, params, shadow, x0, workspace, features, stream, false, nullptr, tokens);
+    return encoder_forward(cfg, drop, params, shadow, x0, workspace, features, stream, false, nullptr, &seg);
 }
 int mfvit_vit_backward_x0(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, int tokens, const float* params, const void* shadow, void* workspace,
                           const float* dfeatures, float* dparams, float* dx0, int stage_hi, int stage_lo, mfvit_stream_t stream) {
     if (!cfg || tokens < 2 || !dx0 || (!dfeatures && stage_hi >= cfg->depth)) return MFVIT_EINVAL;
+    const mfvit_vit_seg seg = x0_seg(cfg, tokens);
     ShareScope share(cfg);
-    return encoder_backward(cfg, drop, params, shadow, workspace, {dfeatures, dparams, dx0, nullptr, stage_hi, stage_lo}, stream, false, tokens);
+    return encoder_backward(cfg, drop, params, shadow, workspace, {dfeatures, dparams, dx0, nullptr, stage_hi, stage_lo}, stream, false, &seg);
 }
 size_t mfvit_vit_workspace_bytes_seg(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, const mfvit_vit_seg* seg, int want_dimg) {
     Dims d;
@@ -1221,14 +1211,14 @@ int mfvit_vit_forward_seg(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, 
                           const float* x_in, void* workspace, float* x_out, mfvit_stream_t stream) {
     if (!seg) return MFVIT_EINVAL;
     ShareScope share(cfg);
-    return encoder_forward(cfg, drop, params, shadow, x_in, workspace, x_out, stream, false, nullptr, 0, seg);
+    return encoder_forward(cfg, drop, params, shadow, x_in, workspace, x_out, stream, false, nullptr, seg);
 }
 int mfvit_vit_backward_seg(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, const mfvit_vit_seg* seg, const float* params, const void* shadow,
                            void* workspace, const float* dx_out, float* dparams, float* dx_in, float* dimg, int stage_hi, int stage_lo,
                            mfvit_stream_t stream) {
     if (!cfg || !seg || (!dx_out && stage_hi >= seg->block_hi)) return MFVIT_EINVAL;
     ShareScope share(cfg);
-    return encoder_backward(cfg, drop, params, shadow, workspace, {dx_out, dparams, dx_in, dimg, stage_hi, stage_lo}, stream, false, 0, seg);
+    return encoder_backward(cfg, drop, params, shadow, workspace, {dx_out, dparams, dx_in, dimg, stage_hi, stage_lo}, stream, false, seg);
 }
 int mfvit_vit_backward_drop(const mfvit_vit_cfg* cfg, const mfvit_vit_drop* drop, const float* params, const void* shadow, void* workspace,
                             const float* dfeatures, float* dparams, int stage_hi, int stage_lo, mfvit_stream_t stream) {

@@ -80,7 +80,7 @@ class GradSync:
             hs.append(dist.all_reduce(t[n0:], op=op, group=self.group, async_op=True))
         return hs
 
-    # ---- encoder: called from VisionTransformerMoCo._run_backward after every stage
+    # ---- encoder: called from VisionTransformerMoCo._backward_chain after every stage group
     def attach(self, vit, bucket_layers=None):
         import os
         if bucket_layers is None:

@@ -172,119 +172,24 @@ class _PatchEmbed(nn.Module):
 
 
 class _EncoderFn(torch.autograd.Function):
-    """features3D as one autograd node: forward = mfvit_vit_forward, backward = mfvit_vit_backward (stage by stage), or mfvit_vit_backward_ex
-    when the image requires a gradient (d loss / d img from the patch-embedding data gradient; no parameter gradient at all when no arena
-    parameter requires one).  params: the arena parameters, then the adapter parameters of mfvit.lora (if attached); with adapters and every
-    arena parameter frozen the backward is mfvit_vit_backward_lora (the data-gradient chain + the adapted Linears' weight gradients)."""
+    """features3D as one autograd node.  forward: the chain of VisionTransformerMoCo._forward_chain - the patch-dropout front end on the kept
+    patches `idx` (None: the image goes to the first range), then the block ranges of _token_segments with score / select / reorganise between
+    two of them (one range [0, depth) without token pruning; `forced`: checked selections or None).  backward: the same chain in reverse, stage
+    group by stage group (_backward_chain); d loss / d img when the image requires a gradient, and no parameter gradient at all when no arena
+    parameter requires one.  The kept patches, the selections and the fused row's weights are constants: no gradient flows to them.
+    params: the arena parameters, then the adapter parameters of mfvit.lora (if attached); with adapters and every arena parameter frozen the
+    backward is mfvit_vit_backward_lora (the data-gradient chain + the adapted Linears' weight gradients)."""
 
     @staticmethod
-    def forward(ctx, model, img, need_grad, drop, *params):
+    def forward(ctx, model, img, idx, forced, need_grad, drop, *params):
         # drop: the mfvit_vit_drop of THIS forward (None: no dropout site active)
         want_dimg = bool(need_grad and ctx.needs_input_grad[1])
-        feats, ws = model._run_forward(img, need_grad, drop, want_dimg=want_dimg)
-        ctx.model = model
-        ctx.ws = ws
-        ctx.cfg = model._cfg(img, need_grad)
-        ctx.drop = drop                     # the backward rebuilds the same masks from it
-        ctx.want_dimg = want_dimg
-        ctx.img_meta = (img.shape, img.dtype)
-        return feats
-
-    @staticmethod
-    def backward(ctx, dfeats):
-        model = ctx.model
-        if torch.is_grad_enabled():
-            raise _lib.MfvitError("double backward through the encoder (create_graph=True) is not supported: its backward is one HIP call "
-                                  "whose results are not differentiable")
-        if ctx.ws is None:
-            raise _lib.MfvitError("the encoder's saved activations were already released: a second backward through the same forward "
-                                  "(retain_graph=True) is not supported - run the forward again")
-        dimg = None
-        if ctx.want_dimg and ctx.needs_input_grad[1]:
-            shape, dtype = ctx.img_meta
-            # (allocated on the current stream - the side stream of a two-stream model's ENH encoder - and recorded there: autograd hands it
-            # to consumers on other streams)
-            dimg = torch.empty(shape, device=dfeats.device, dtype=torch.float32)
-            dimg.record_stream(torch.cuda.current_stream(dfeats.device))
-        na = len(model._arena_params)
-        want_params = any(ctx.needs_input_grad[4:4 + na])
-        want_lora = any(ctx.needs_input_grad[4 + na:])
-        if want_lora and not want_params:
-            grads = [None] * na + model._run_backward_lora(ctx.cfg, ctx.ws, dfeats, drop=ctx.drop, dimg=dimg)
-        else:
-            grads = model._run_backward(ctx.cfg, ctx.ws, dfeats, drop=ctx.drop, dimg=dimg, want_params=want_params)
-            if want_lora:       # adapters beside trainable arena parameters: contract the adapted dW slices of the full gradient arena
-                grads = grads + model._lora_grads_from_arena(ctx.cfg, model._last_grad_arena)
-            else:
-                grads = grads + [None] * (len(ctx.needs_input_grad) - 4 - na)
-        grads = [g if need else None for g, need in zip(grads, ctx.needs_input_grad[4:])]
-        model._release_ws(ctx.ws)
-        ctx.ws = None
-        # the single-use feature cache holds the forward's output, i.e. this graph and the parameters' AccumulateGrad nodes (which carry
-        # the stream they were created under): once the backward has run it must not keep them alive into the next iteration
-        model._feat_cache = None
-        if dimg is not None and dimg.dtype != ctx.img_meta[1]:
-            dimg = dimg.to(ctx.img_meta[1])
-        return (None, dimg, None, None) + tuple(grads)
-
-
-class _EncoderKeepFn(torch.autograd.Function):
-    """features3D under patch dropout as one autograd node: the front end on the kept patches (mfvit_patch_keep_embed) + the block stack on the
-    shortened sequence (mfvit_vit_forward_x0); backward = mfvit_vit_backward_x0 (stage by stage) + mfvit_patch_keep_embed_bwd with the group that
-    holds stage -1.  No gradient flows to the indices."""
-
-    @staticmethod
-    def forward(ctx, model, img, idx, need_grad, drop, *params):
-        want_dimg = bool(need_grad and ctx.needs_input_grad[1])
-        feats, ws, keep = model._run_forward_keep(img, idx, need_grad, drop)
-        ctx.model = model
-        ctx.ws = ws
-        ctx.keep = keep
-        ctx.cfg = model._cfg(img, need_grad)
-        ctx.drop = drop
-        ctx.want_dimg = want_dimg
-        ctx.img_meta = (img.shape, img.dtype)
-        return feats
-
-    @staticmethod
-    def backward(ctx, dfeats):
-        model = ctx.model
-        if torch.is_grad_enabled():
-            raise _lib.MfvitError("double backward through the encoder (create_graph=True) is not supported: its backward is one HIP call "
-                                  "whose results are not differentiable")
-        if ctx.ws is None:
-            raise _lib.MfvitError("the encoder's saved activations were already released: a second backward through the same forward "
-                                  "(retain_graph=True) is not supported - run the forward again")
-        dimg = None
-        if ctx.want_dimg and ctx.needs_input_grad[1]:
-            shape, dtype = ctx.img_meta
-            dimg = torch.empty(shape, device=dfeats.device, dtype=torch.float32)
-            dimg.record_stream(torch.cuda.current_stream(dfeats.device))
-        want_params = any(ctx.needs_input_grad[5:])
-        grads = model._run_backward(ctx.cfg, ctx.ws, dfeats, drop=ctx.drop, dimg=dimg, want_params=want_params, keep=ctx.keep)
-        grads = [g if need else None for g, need in zip(grads, ctx.needs_input_grad[5:])]
-        model._release_ws(ctx.ws)
-        model._release_ws(ctx.keep[2])
-        ctx.ws = ctx.keep = None
-        model._feat_cache = None
-        if dimg is not None and dimg.dtype != ctx.img_meta[1]:
-            dimg = dimg.to(ctx.img_meta[1])
-        return (None, dimg, None, None, None) + tuple(grads)
-
-
-class _EncoderPruneFn(torch.autograd.Function):
-    """features3D under token pruning as one autograd node: block range, score, select, reorganise, block range, .. (mfvit_vit_forward_seg and
-    the mfvit_token_* kernels; patch dropout's front end in front when it is active); the backward walks the same chain in reverse, stage group by
-    stage group.  The selections and the fused row's weights are constants: no gradient flows to block l's attention through them."""
-
-    @staticmethod
-    def forward(ctx, model, img, pidx, forced, need_grad, drop, *params):
-        want_dimg = bool(need_grad and ctx.needs_input_grad[1])
-        feats, state = model._run_forward_prune(img, pidx, forced, need_grad, drop, want_dimg)
+        plan = model._token_segments(model.num_tokens if idx is None else idx.shape[1] + 1)
+        feats, state = model._forward_chain(img, idx, plan, forced, need_grad, drop, want_dimg)
         ctx.model = model
         ctx.state = state
         ctx.cfg = model._cfg(img, need_grad)
-        ctx.drop = drop
+        ctx.drop = drop                     # the backward rebuilds the same masks from it
         ctx.want_dimg = want_dimg
         ctx.img_meta = (img.shape, img.dtype)
         return feats
@@ -301,13 +206,26 @@ class _EncoderPruneFn(torch.autograd.Function):
         dimg = None
         if ctx.want_dimg and ctx.needs_input_grad[1]:
             shape, dtype = ctx.img_meta
+            # (allocated on the current stream - the side stream of a two-stream model's ENH encoder - and recorded there: autograd hands it
+            # to consumers on other streams)
             dimg = torch.empty(shape, device=dfeats.device, dtype=torch.float32)
             dimg.record_stream(torch.cuda.current_stream(dfeats.device))
-        want_params = any(ctx.needs_input_grad[6:])
-        grads = model._run_backward_prune(ctx.cfg, ctx.state, dfeats, drop=ctx.drop, dimg=dimg, want_params=want_params)
-        grads = [g if need else None for g, need in zip(grads, ctx.needs_input_grad[6:])]
-        model._release_prune_state(ctx.state)
+        na = len(model._arena_params)
+        need = ctx.needs_input_grad[6:]
+        want_params, want_lora = any(need[:na]), any(need[na:])
+        if want_lora and not want_params:       # (adapters run on the full grid only: one range, its workspace)
+            grads = [None] * na + model._run_backward_lora(ctx.cfg, ctx.state[0][0][1], dfeats, drop=ctx.drop, dimg=dimg)
+        else:
+            grads = model._backward_chain(ctx.cfg, ctx.state, dfeats, drop=ctx.drop, dimg=dimg, want_params=want_params)
+            if want_lora:       # adapters beside trainable arena parameters: contract the adapted dW slices of the full gradient arena
+                grads = grads + model._lora_grads_from_arena(ctx.cfg, model._last_grad_arena)
+            else:
+                grads = grads + [None] * (len(need) - na)
+        grads = [g if n else None for g, n in zip(grads, need)]
+        model._release_state(ctx.state)
         ctx.state = None
+        # the single-use feature cache holds the forward's output, i.e. this graph and the parameters' AccumulateGrad nodes (which carry
+        # the stream they were created under): once the backward has run it must not keep them alive into the next iteration
         model._feat_cache = None
         if dimg is not None and dimg.dtype != ctx.img_meta[1]:
             dimg = dimg.to(ctx.img_meta[1])
@@ -752,170 +670,23 @@ class VisionTransformerMoCo(nn.Module):
         self._shadow_key = key
         self._feat_cache = None
 
+    def _take_ws(self, nbytes, dev):
+        """A workspace of nbytes from the pool, or a new one."""
+        pool = self._ws_pool.setdefault(nbytes, [])
+        return pool.pop() if pool else torch.empty(nbytes, device=dev, dtype=torch.uint8)
+
     def _get_ws(self, cfg, drop=None, want_dimg=False):
-        if want_dimg:       # (the image gradient's W_pe^T behind the usual layout: include/mfvit.h, mfvit_vit_workspace_bytes_ex)
-            nbytes = lib().mfvit_vit_workspace_bytes_ex(cfg, drop, 1)
-        else:
-            nbytes = lib().mfvit_vit_workspace_bytes(cfg) if drop is None else lib().mfvit_vit_workspace_bytes_drop(cfg, drop)
+        """A full-grid workspace (want_dimg: the image gradient's W_pe^T behind the usual layout: include/mfvit.h, mfvit_vit_workspace_bytes_ex)."""
+        nbytes = lib().mfvit_vit_workspace_bytes_ex(cfg, drop, int(bool(want_dimg)))
         if nbytes == 0:
             raise _lib.MfvitError("invalid encoder configuration (image size must be a multiple of 16, dim 384 or 768, head_dim 32 / 64 / 96)")
-        pool = self._ws_pool.setdefault(nbytes, [])
-        return pool.pop() if pool else torch.empty(nbytes, device=self._arena.device, dtype=torch.uint8)
+        return self._take_ws(nbytes, self._arena.device)
 
     def _release_ws(self, ws):
         if ws is not None:
             pool = self._ws_pool.setdefault(ws.numel(), [])
             if len(pool) < 2:
                 pool.append(ws)
-
-    def _prep_img(self, img):
-        """The image as the encoder entry points take it (contiguous f32 NCHW on the model's device), or MfvitError."""
-        _lib.require_cuda(img)
-        if img.dtype != torch.float32:
-            img = img.float()
-        img = img.contiguous()
-        if img.shape[1] != 3 or (img.shape[2], img.shape[3]) != self.img_size:
-            raise _lib.MfvitError(f"expected (B,3,{self.img_size[0]},{self.img_size[1]}) images, got {tuple(img.shape)} "
-                                  "(pos_embed is size-bound)")
-        if self._arena.device != img.device:
-            raise _lib.MfvitError(f"model on {self._arena.device} but input on {img.device}")
-        return img
-
-    def _run_forward(self, img, save, drop=None, want_dimg=False):
-        img = self._prep_img(img)
-        cfg = self._cfg(img, save)
-        self._ensure_shadow(cfg)
-        ws = self._get_ws(cfg, drop, want_dimg)
-        feats = torch.empty(img.shape[0], self.num_tokens, self.embed_dim, device=img.device, dtype=torch.float32)
-        if drop is None:
-            check(lib().mfvit_vit_forward(cfg, ptr(self._kernel_params()), ptr(self._shadow), ptr(img), ptr(ws), ptr(feats), stream()),
-                  "mfvit_vit_forward")
-        else:
-            check(lib().mfvit_vit_forward_drop(cfg, drop, ptr(self._kernel_params()), ptr(self._shadow), ptr(img), ptr(ws), ptr(feats), stream()),
-                  "mfvit_vit_forward_drop")
-        if not save:
-            self._release_ws(ws)
-            ws = None
-        return feats, ws
-
-    def _run_forward_keep(self, img, idx, save, drop=None):
-        """Patch dropout: (features (B, 1 + K, D), workspace, keep) with keep = (tokens, mfvit_patch_keep_cfg, front-end workspace, idx)."""
-        img = self._prep_img(img)
-        if idx.device != img.device:
-            raise _lib.MfvitError(f"keep indices on {idx.device} but input on {img.device}")
-        idx.record_stream(torch.cuda.current_stream(img.device))     # (a step's draw is made on the caller's stream and may run on the side stream)
-        cfg = self._cfg(img, save)
-        self._ensure_shadow(cfg)
-        B, K = idx.shape
-        T, D = K + 1, self.embed_dim
-        nbytes = lib().mfvit_vit_workspace_bytes_x0(cfg, drop, T)
-        pk = _lib.PatchKeepCfg(cfg.dtype, B, cfg.img_h, cfg.img_w, K, D)
-        fbytes = lib().mfvit_patch_keep_workspace_bytes(pk, int(bool(save)))
-        if nbytes == 0 or fbytes == 0:
-            raise _lib.MfvitError("invalid encoder configuration for patch dropout (image size a multiple of 16, dim 384 or 768, head_dim 32 / 64 / "
-                                  f"96, 1 <= K <= {self.num_tokens - 1})")
-        dev = img.device
-
-        def take(n):
-            pool = self._ws_pool.setdefault(n, [])
-            return pool.pop() if pool else torch.empty(n, device=dev, dtype=torch.uint8)
-        ws, fws = take(nbytes), take(fbytes)
-        if self._keep_err is None or self._keep_err.device != dev:
-            self._keep_err = torch.zeros(1, device=dev, dtype=torch.int32)
-        a = self._arena.data_ptr()
-        off = self._offsets
-        x0 = torch.empty(B, T, D, device=dev, dtype=torch.float32)
-        feats = torch.empty(B, T, D, device=dev, dtype=torch.float32)
-        check(lib().mfvit_patch_keep_embed(pk, ptr(img), ptr(idx), a + 4 * off["cls_token"][0], a + 4 * off["pos_embed"][0],
-                                           a + 4 * off["patch_embed.proj.weight"][0], a + 4 * off["patch_embed.proj.bias"][0], ptr(fws),
-                                           int(bool(save)), ptr(x0), ptr(self._keep_err), stream()), "mfvit_patch_keep_embed")
-        check(lib().mfvit_vit_forward_x0(cfg, drop, T, ptr(self._arena), ptr(self._shadow), ptr(x0), ptr(ws), ptr(feats), stream()),
-              "mfvit_vit_forward_x0")
-        if not save:
-            self._release_ws(ws)
-            self._release_ws(fws)
-            ws = fws = None
-        return feats, ws, (T, pk, fws, idx)
-
-    def _take_ws(self, nbytes, dev):
-        pool = self._ws_pool.setdefault(nbytes, [])
-        return pool.pop() if pool else torch.empty(nbytes, device=dev, dtype=torch.uint8)
-
-    def _run_forward_prune(self, img, pidx, forced, save, drop=None, want_dimg=False):
-        """Token pruning: (features (B, T_last, D), state).  The block ranges of _token_segments run through mfvit_vit_forward_seg, each on a
-        workspace of its own; behind every range but the last the rows are scored by the cls attention of its last block (read in place from the
-        range's workspace), selected and reorganised (csrc/token_prune.hip).  pidx: the kept patches of an active patch dropout (the first range
-        then takes the front end's x0), forced: checked selections (_check_token_indices) or None.  state = (segments, stages, keep) for the
-        backward: per segment (mfvit_vit_seg, workspace), per stage (idx_keep, idx_drop, w, T, K) on the device."""
-        img = self._prep_img(img)
-        dev = img.device
-        cfg = self._cfg(img, save)
-        self._ensure_shadow(cfg)
-        B, D, fuse = img.shape[0], self.embed_dim, int(self.token_fuse)
-        if self._keep_err is None or self._keep_err.device != dev:
-            self._keep_err = torch.zeros(1, device=dev, dtype=torch.int32)
-        keep = None
-        x = img
-        if pidx is not None:        # patch dropout in front: the front end of _run_forward_keep
-            if pidx.device != dev:
-                raise _lib.MfvitError(f"keep indices on {pidx.device} but input on {dev}")
-            pidx.record_stream(torch.cuda.current_stream(dev))
-            pk = _lib.PatchKeepCfg(cfg.dtype, B, cfg.img_h, cfg.img_w, pidx.shape[1], D)
-            fbytes = lib().mfvit_patch_keep_workspace_bytes(pk, int(bool(save)))
-            if fbytes == 0:
-                raise _lib.MfvitError("invalid encoder configuration for patch dropout")
-            fws = self._take_ws(fbytes, dev)
-            a, off = self._arena.data_ptr(), self._offsets
-            x = torch.empty(B, pidx.shape[1] + 1, D, device=dev, dtype=torch.float32)
-            check(lib().mfvit_patch_keep_embed(pk, ptr(img), ptr(pidx), a + 4 * off["cls_token"][0], a + 4 * off["pos_embed"][0],
-                                               a + 4 * off["patch_embed.proj.weight"][0], a + 4 * off["patch_embed.proj.bias"][0], ptr(fws),
-                                               int(bool(save)), ptr(x), ptr(self._keep_err), stream()), "mfvit_patch_keep_embed")
-            keep = (x.shape[1], pk, fws if save else None, pidx)
-            if not save:
-                self._release_ws(fws)
-        T0 = self.num_tokens if pidx is None else x.shape[1]
-        plan = self._token_segments(T0)
-        H, HD = self.num_heads, D // self.num_heads
-        seg_list = [_lib.VitSeg(lo, hi, T, int(i == 0 and pidx is None)) for i, (lo, hi, T) in enumerate(plan)]
-        sizes = [lib().mfvit_vit_workspace_bytes_seg(cfg, drop, seg, int(want_dimg and seg.image_in)) for seg in seg_list]
-        if 0 in sizes:
-            raise _lib.MfvitError("invalid encoder configuration for token pruning (image size a multiple of 16, dim 384 or 768, head_dim "
-                                  "32 / 64 / 96)")
-        self._retain_prune_sizes((bool(save), bool(want_dimg), drop is not None, B, pidx is not None), sizes)
-        segs, stages = [], []
-        for i, (lo, hi, T) in enumerate(plan):
-            seg, nbytes = seg_list[i], sizes[i]
-            ws = self._take_ws(nbytes, dev)
-            out = torch.empty(B, T, D, device=dev, dtype=torch.float32)
-            check(lib().mfvit_vit_forward_seg(cfg, drop, seg, ptr(self._arena), ptr(self._shadow), ptr(x), ptr(ws), ptr(out), stream()),
-                  "mfvit_vit_forward_seg")
-            x = out
-            if i + 1 < len(plan):
-                K = plan[i + 1][2] - 1 - fuse
-                lay = (ctypes.c_int64 * 4)()
-                check(lib().mfvit_vit_attn_layout_seg(cfg, drop, seg, lay), "mfvit_vit_attn_layout_seg")
-                last = (hi - 1 - lo) * lay[2]
-                probs = torch.empty(B, T, device=dev, dtype=torch.float32)
-                score = torch.empty(B, T - 1, device=dev, dtype=torch.float32)
-                check(lib().mfvit_token_score(int(lay[3]), ws.data_ptr() + lay[0] + last, ws.data_ptr() + lay[1] + last, B, T, H, HD, ptr(probs),
-                                              ptr(score), stream()), "mfvit_token_score")
-                ik = torch.empty(B, K, device=dev, dtype=torch.int32)
-                idr = torch.empty(B, T - 1 - K, device=dev, dtype=torch.int32)
-                w = torch.empty(B, T - 1 - K, device=dev, dtype=torch.float32)
-                check(lib().mfvit_token_select(ptr(score), T - 1, B, T - 1, K, ptr(forced[i]) if forced is not None else None, ptr(ik), ptr(idr),
-                                               ptr(w), ptr(self._keep_err), stream()), "mfvit_token_select")
-                out = torch.empty(B, 1 + K + fuse, D, device=dev, dtype=torch.float32)
-                check(lib().mfvit_token_reorg_fwd(ptr(x), ptr(ik), ptr(idr), ptr(w), ptr(out), B, T, D, K, fuse, ptr(self._keep_err), stream()),
-                      "mfvit_token_reorg_fwd")
-                x = out
-                stages.append((ik, idr, w, T, K))
-            if save:
-                segs.append((seg, ws))
-            else:
-                self._release_prune_ws(ws)
-        self.last_token_indices = [st[0].long() for st in stages]
-        self._last_token_plan = (T0, bool(fuse))
-        return x, ((segs, stages, keep, fuse) if save else None)
 
     # The workspaces of the block ranges are sized by the token plan, and token_keep_rate may change from step to step (EViT warms it up): the
     # pool keeps the sizes of the CURRENT plan of every kind of call (saving or not, with d img, with dropout, batch size, patch dropout in
@@ -933,64 +704,120 @@ class VisionTransformerMoCo(nn.Module):
         if ws is not None and any(ws.numel() in s for s in self._prune_sizes.values()):
             self._release_ws(ws)
 
-    def _release_prune_state(self, state):
-        if state is not None:
-            for _, ws in state[0]:
-                self._release_prune_ws(ws)
-            if state[2] is not None:
-                self._release_ws(state[2][2])
+    def _release_state(self, state):
+        """The workspaces of a forward's state back to the pool: the ranges' by the policy they were taken under, the front end's."""
+        ranges, _, front, _, pruning = state
+        for _, ws in ranges:
+            (self._release_prune_ws if pruning else self._release_ws)(ws)
+        if front is not None:
+            self._release_ws(front[2])
 
-    def _run_backward_prune(self, cfg, state, dfeats, drop=None, dimg=None, want_params=True):
-        """The backward of _run_forward_prune: the block ranges from the last down (mfvit_vit_backward_seg), mfvit_token_reorg_bwd between two of
-        them, the patch-dropout front end's backward behind the first when it ran.  Stage groups and the stage hook as in _run_backward: a
-        group's model stages [lo, hi] are cut at the range boundaries; a range's entry from its dx_out rides with its top block, what feeds its
-        first block (and the reorganisation's backward) with that block."""
-        segs, stages, keep, fuse = state
-        dev = dfeats.device
-        g = dfeats.contiguous()
-        if g.dtype != torch.float32:
-            g = g.float()
-        B, D = cfg.batch, self.embed_dim
-        if not want_params and dimg is None:
-            raise _lib.MfvitError("a backward without parameter gradients needs the image gradient")
-        gflat = self._take_grad_arena() if want_params else None
-        hook = (getattr(self, "_grad_stage_hook", None)) if want_params else None
-        dx_in = [None if seg.image_in else torch.empty(B, seg.tokens, D, device=dev, dtype=torch.float32) for seg, _ in segs]
-        cur = g                                    # the gradient of the output of the range being walked
-        i = len(segs) - 1
-        for hi, lo in self._stage_groups(hook is not None):
-            while i >= 0:
-                seg, ws = segs[i]
-                a, b = seg.block_lo, seg.block_hi
-                top = min(hi, b - 1)               # the highest block of this range inside the group
-                if top < a or top < lo:
-                    break
-                s_hi = b if (top == b - 1 and (b < self.depth or hi == self.depth)) else top
-                bot = max(lo, a)
-                s_lo = (lo if a == 0 else a - 1) if bot == a else bot
-                check(lib().mfvit_vit_backward_seg(cfg, drop, seg, ptr(self._arena), ptr(self._shadow), ptr(ws), ptr(cur), ptr(gflat), ptr(dx_in[i]),
-                                                   ptr(dimg) if (seg.image_in and s_lo == -1) else None, s_hi, s_lo, stream()),
-                      "mfvit_vit_backward_seg")
-                if s_lo != a - 1:
-                    break                          # the rest of this range belongs to the next group
-                if i > 0:
-                    ik, idr, w, T, K = stages[i - 1]
-                    nxt = torch.empty(B, T, D, device=dev, dtype=torch.float32)
-                    check(lib().mfvit_token_reorg_bwd(ptr(dx_in[i]), ptr(ik), ptr(idr), ptr(w), ptr(nxt), B, T, D, K, fuse, ptr(self._keep_err),
-                                                      stream()), "mfvit_token_reorg_bwd")
-                    cur = nxt
-                elif keep is not None:
-                    self._keep_embed_bwd(keep, dx_in[0], gflat, dimg, cfg)
-                i -= 1
-            if hook is not None:
-                hook(self, hi, lo, gflat)
-        if not want_params:
-            return [None] * len(self._arena_params)
-        return self._grad_views(gflat)
+    def _prep_img(self, img):
+        """The image as the encoder entry points take it (contiguous f32 NCHW on the model's device), or MfvitError."""
+        _lib.require_cuda(img)
+        if img.dtype != torch.float32:
+            img = img.float()
+        img = img.contiguous()
+        if img.shape[1] != 3 or (img.shape[2], img.shape[3]) != self.img_size:
+            raise _lib.MfvitError(f"expected (B,3,{self.img_size[0]},{self.img_size[1]}) images, got {tuple(img.shape)} "
+                                  "(pos_embed is size-bound)")
+        if self._arena.device != img.device:
+            raise _lib.MfvitError(f"model on {self._arena.device} but input on {img.device}")
+        return img
 
-    def _keep_embed_bwd(self, keep, dx0, gflat, dimg, cfg):
+    def _keep_embed(self, cfg, img, idx, save):
+        """The patch-dropout front end (csrc/patch_drop.hip): (x0 (B, 1 + K, D), front) with front = (tokens, mfvit_patch_keep_cfg, the front
+        end's workspace or None without save, idx) for _keep_embed_bwd."""
+        dev = img.device
+        if idx.device != dev:
+            raise _lib.MfvitError(f"keep indices on {idx.device} but input on {dev}")
+        idx.record_stream(torch.cuda.current_stream(dev))     # (a step's draw is made on the caller's stream and may run on the side stream)
+        B, K = idx.shape
+        pk = _lib.PatchKeepCfg(cfg.dtype, B, cfg.img_h, cfg.img_w, K, self.embed_dim)
+        fbytes = lib().mfvit_patch_keep_workspace_bytes(pk, int(bool(save)))
+        if fbytes == 0:
+            raise _lib.MfvitError(f"invalid encoder configuration for patch dropout (image size a multiple of 16, dim 384 or 768, 1 <= K <= "
+                                  f"{self.num_tokens - 1})")
+        fws = self._take_ws(fbytes, dev)
+        a, off = self._arena.data_ptr(), self._offsets
+        x0 = torch.empty(B, K + 1, self.embed_dim, device=dev, dtype=torch.float32)
+        check(lib().mfvit_patch_keep_embed(pk, ptr(img), ptr(idx), a + 4 * off["cls_token"][0], a + 4 * off["pos_embed"][0],
+                                           a + 4 * off["patch_embed.proj.weight"][0], a + 4 * off["patch_embed.proj.bias"][0], ptr(fws),
+                                           int(bool(save)), ptr(x0), ptr(self._keep_err), stream()), "mfvit_patch_keep_embed")
+        if not save:
+            self._release_ws(fws)
+            fws = None
+        return x0, (K + 1, pk, fws, idx)
+
+    def _forward_chain(self, img, idx, plan, forced, save, drop=None, want_dimg=False):
+        """Every encoder forward: (features (B, T_last, D), state).  idx: the kept patches of an active patch dropout (the front end then makes
+        the first range's x0) or None (the first range takes the image); plan: [(block_lo, block_hi, tokens)] as _token_segments gives it - one
+        range [0, depth) without token pruning.  The ranges run through mfvit_vit_forward_seg, each on a workspace of its own; behind every range
+        but the last the rows are scored by the cls attention of its last block (read in place from the range's workspace), selected and
+        reorganised (csrc/token_prune.hip); forced: checked selections (_check_token_indices) or None.
+        state (None without save), for the backward: (ranges, stages, front, fuse, pruning) - per range (mfvit_vit_seg, workspace), per stage
+        (idx_keep, idx_drop, w, T, K) on the device, the front end's tuple of _keep_embed or None, and which pool policy the range workspaces
+        are under."""
+        img = self._prep_img(img)
+        dev = img.device
+        cfg = self._cfg(img, save)
+        self._ensure_shadow(cfg)
+        B, D, fuse = img.shape[0], self.embed_dim, int(self.token_fuse)
+        pruning = self.token_pruning_active()
+        if (idx is not None or pruning) and (self._keep_err is None or self._keep_err.device != dev):
+            self._keep_err = torch.zeros(1, device=dev, dtype=torch.int32)
+        segs = [_lib.VitSeg(lo, hi, T, int(i == 0 and idx is None)) for i, (lo, hi, T) in enumerate(plan)]
+        sizes = [lib().mfvit_vit_workspace_bytes_seg(cfg, drop, seg, int(want_dimg and seg.image_in)) for seg in segs]
+        if 0 in sizes:
+            raise _lib.MfvitError("invalid encoder configuration (image size must be a multiple of 16, dim 384 or 768, head_dim 32 / 64 / 96)")
+        if pruning:
+            self._retain_prune_sizes((bool(save), bool(want_dimg), drop is not None, B, idx is not None), sizes)
+        x, front = (img, None) if idx is None else self._keep_embed(cfg, img, idx, save)
+        params = self._kernel_params()
+        H, HD = self.num_heads, D // self.num_heads
+        ranges, stages = [], []
+        for i, (seg, nbytes) in enumerate(zip(segs, sizes)):
+            T = seg.tokens
+            ws = self._take_ws(nbytes, dev)
+            out = torch.empty(B, T, D, device=dev, dtype=torch.float32)
+            check(lib().mfvit_vit_forward_seg(cfg, drop, seg, ptr(params), ptr(self._shadow), ptr(x), ptr(ws), ptr(out), stream()),
+                  "mfvit_vit_forward_seg")
+            x = out
+            if i + 1 < len(segs):
+                K = segs[i + 1].tokens - 1 - fuse
+                lay = (ctypes.c_int64 * 4)()
+                check(lib().mfvit_vit_attn_layout_seg(cfg, drop, seg, lay), "mfvit_vit_attn_layout_seg")
+                last = (seg.block_hi - 1 - seg.block_lo) * lay[2]
+                probs = torch.empty(B, T, device=dev, dtype=torch.float32)
+                score = torch.empty(B, T - 1, device=dev, dtype=torch.float32)
+                check(lib().mfvit_token_score(int(lay[3]), ws.data_ptr() + lay[0] + last, ws.data_ptr() + lay[1] + last, B, T, H, HD, ptr(probs),
+                                              ptr(score), stream()), "mfvit_token_score")
+                ik = torch.empty(B, K, device=dev, dtype=torch.int32)
+                idr = torch.empty(B, T - 1 - K, device=dev, dtype=torch.int32)
+                w = torch.empty(B, T - 1 - K, device=dev, dtype=torch.float32)
+                check(lib().mfvit_token_select(ptr(score), T - 1, B, T - 1, K, ptr(forced[i]) if forced is not None else None, ptr(ik), ptr(idr),
+                                               ptr(w), ptr(self._keep_err), stream()), "mfvit_token_select")
+                x = torch.empty(B, 1 + K + fuse, D, device=dev, dtype=torch.float32)
+                check(lib().mfvit_token_reorg_fwd(ptr(out), ptr(ik), ptr(idr), ptr(w), ptr(x), B, T, D, K, fuse, ptr(self._keep_err), stream()),
+                      "mfvit_token_reorg_fwd")
+                stages.append((ik, idr, w, T, K))
+            if save:
+                ranges.append((seg, ws))
+            else:
+                (self._release_prune_ws if pruning else self._release_ws)(ws)
+        if pruning:
+            self.last_token_indices = [st[0].long() for st in stages]
+            self._last_token_plan = (plan[0][2], bool(fuse))
+        return x, ((ranges, stages, front, fuse, pruning) if save else None)
+
+    def _run_forward(self, img, save, drop=None, want_dimg=False):
+        """The full grid as one range: (features, its workspace - None without save)."""
+        feats, state = self._forward_chain(img, None, [(0, self.depth, self.num_tokens)], None, save, drop, want_dimg)
+        return feats, (state[0][0][1] if save else None)
+
+    def _keep_embed_bwd(self, front, dx0, gflat, dimg, cfg):
         """The front end's backward (stage -1 under patch dropout): d cls_token, d pe_b, d pe_w into the gradient arena `gflat` (None: none), dimg."""
-        T, pk, fws, idx = keep
+        T, pk, fws, idx = front
         off = self._offsets
         g = (lambda name: gflat.data_ptr() + 4 * off[name][0]) if gflat is not None else (lambda name: None)
         stop = bool(cfg.stop_grad_conv1) or gflat is None
@@ -1038,6 +865,32 @@ class VisionTransformerMoCo(nn.Module):
             hi = lo - 1
         return out
 
+    @staticmethod
+    def _backward_calls(ranges, groups, depth, front=False):
+        """The mfvit_vit_backward_seg calls of one backward, host arithmetic only.  ranges: [(block_lo, block_hi)] ascending, contiguous from 0
+        to depth; groups: the (hi, lo) model-stage groups of _stage_groups; front: the patch-dropout front end ran in front of range 0.
+        -> per group the list of (range index, stage_hi, stage_lo, then): a group's stages are cut at the range boundaries; a range's entry
+        stage block_hi (from its dx_out; the final norm for the last range) rides with its top block, block_lo - 1 (what feeds its first block:
+        the embedding for range 0) with that block.  then: what follows the call that reaches block_lo - 1 - "reorg" (mfvit_token_reorg_bwd
+        into the range below), "front" (the front end's backward) - or None."""
+        out, i = [], len(ranges) - 1
+        for hi, lo in groups:
+            calls = []
+            while i >= 0:
+                a, b = ranges[i]
+                top = min(hi, b - 1)               # the highest block of this range inside the group
+                if top < a or top < lo:
+                    break
+                s_hi = b if (top == b - 1 and (b < depth or hi == depth)) else top
+                s_lo = (lo if a == 0 else a - 1) if max(lo, a) == a else lo
+                if s_lo != a - 1:
+                    calls.append((i, s_hi, s_lo, None))
+                    break                          # the rest of this range belongs to the next group
+                calls.append((i, s_hi, s_lo, "reorg" if i > 0 else "front" if front else None))
+                i -= 1
+            out.append(calls)
+        return out
+
     def _grad_views(self, gflat):
         self._last_grad_arena = gflat
         # per-parameter views of the flat gradient arena, arena order: ONE C++ call for the 150 views (a Python loop of slice + view cost 0.3 ms
@@ -1047,45 +900,51 @@ class VisionTransformerMoCo(nn.Module):
         views = torch._utils._unflatten_dense_tensors(gflat, params)
         return [v if p.requires_grad else None for v, p in zip(views, params)]
 
-    def _run_backward(self, cfg, ws, dfeats, on_stage_done=None, drop=None, dimg=None, want_params=True, keep=None):
-        """Returns per-parameter gradient views (arena order) of a fresh flat gradient arena.  drop: the forward's mfvit_vit_drop (or None).
-        dimg: (B,3,H,W) f32, overwritten with d loss / d img (the forward's workspace must come from _get_ws(.., want_dimg=True)).
-        want_params=False (needs dimg): the data-gradient-only backward - no gradient arena, every returned gradient None."""
+    def _backward_chain(self, cfg, state, dfeats, drop=None, dimg=None, want_params=True, on_stage_done=None):
+        """Every encoder backward, on the state of _forward_chain: the block ranges from the last down (mfvit_vit_backward_seg, the calls of
+        _backward_calls), mfvit_token_reorg_bwd between two of them, the front end's backward behind the first when it ran; the stage hook
+        (on_stage_done, or the model's _grad_stage_hook) after every stage group.  Returns per-parameter gradient views (arena order) of a fresh
+        flat gradient arena.  drop: the forward's mfvit_vit_drop (or None).  dimg: (B,3,H,W) f32, overwritten with d loss / d img (the first
+        range's workspace must have been sized with want_dimg).  want_params=False (needs dimg): the data-gradient-only backward - no gradient
+        arena, every returned gradient None."""
+        ranges, stages, front, fuse = state[:4]
+        dev = dfeats.device
         dfeats = dfeats.contiguous()
         if dfeats.dtype != torch.float32:
             dfeats = dfeats.float()
-        # keep (patch dropout, _run_forward_keep): the stack's backward on the shortened sequence (mfvit_vit_backward_x0 -> dx0), the front end's
-        # backward behind the call that runs stage -1
-        dx0 = torch.empty(cfg.batch, keep[0], self.embed_dim, device=dfeats.device, dtype=torch.float32) if keep is not None else None
-        if not want_params:
-            if dimg is None:
-                raise _lib.MfvitError("a backward without parameter gradients needs the image gradient")
-            if keep is not None:
-                check(lib().mfvit_vit_backward_x0(cfg, drop, keep[0], ptr(self._arena), ptr(self._shadow), ptr(ws), ptr(dfeats), None, ptr(dx0),
-                                                  self.depth, -1, stream()), "mfvit_vit_backward_x0")
-                self._keep_embed_bwd(keep, dx0, None, dimg, cfg)
-                return [None] * len(self._arena_params)
-            check(lib().mfvit_vit_backward_ex(cfg, drop, ptr(self._kernel_params()), ptr(self._shadow), ptr(ws), ptr(dfeats), None, ptr(dimg),
-                                              self.depth, -1, stream()), "mfvit_vit_backward_ex")
-            return [None] * len(self._arena_params)
-        gflat = self._take_grad_arena()
-        hook = on_stage_done or getattr(self, "_grad_stage_hook", None)
-
-        def bwd(hi, lo):
-            if keep is not None:
-                check(lib().mfvit_vit_backward_x0(cfg, drop, keep[0], ptr(self._arena), ptr(self._shadow), ptr(ws), ptr(dfeats), ptr(gflat), ptr(dx0),
-                                                  hi, lo, stream()), "mfvit_vit_backward_x0")
-                if lo == -1:
-                    self._keep_embed_bwd(keep, dx0, gflat, dimg, cfg)
-                return
-            # (drop = NULL, dimg = NULL: exactly mfvit_vit_backward; the call that runs the embedding stage also writes the image gradient)
-            check(lib().mfvit_vit_backward_ex(cfg, drop, ptr(self._kernel_params()), ptr(self._shadow), ptr(ws), ptr(dfeats), ptr(gflat),
-                                              ptr(dimg) if lo == -1 else None, hi, lo, stream()), "mfvit_vit_backward_ex")
-        for hi, lo in self._stage_groups(hook is not None):
-            bwd(hi, lo)
+        B, D = cfg.batch, self.embed_dim
+        if not want_params and dimg is None:
+            raise _lib.MfvitError("a backward without parameter gradients needs the image gradient")
+        gflat = self._take_grad_arena() if want_params else None
+        hook = (on_stage_done or getattr(self, "_grad_stage_hook", None)) if want_params else None
+        params = self._kernel_params()
+        dx_in = [None if seg.image_in else torch.empty(B, seg.tokens, D, device=dev, dtype=torch.float32) for seg, _ in ranges]
+        cur = dfeats                               # the gradient of the output of the range being walked
+        groups = self._stage_groups(hook is not None)
+        for (hi, lo), calls in zip(groups, self._backward_calls([(s.block_lo, s.block_hi) for s, _ in ranges], groups, self.depth, front is not None)):
+            for i, s_hi, s_lo, then in calls:
+                seg, ws = ranges[i]
+                # (the call that runs the embedding stage also writes the image gradient)
+                check(lib().mfvit_vit_backward_seg(cfg, drop, seg, ptr(params), ptr(self._shadow), ptr(ws), ptr(cur), ptr(gflat), ptr(dx_in[i]),
+                                                   ptr(dimg) if (seg.image_in and s_lo == -1) else None, s_hi, s_lo, stream()),
+                      "mfvit_vit_backward_seg")
+                if then == "reorg":
+                    ik, idr, w, T, K = stages[i - 1]
+                    cur = torch.empty(B, T, D, device=dev, dtype=torch.float32)
+                    check(lib().mfvit_token_reorg_bwd(ptr(dx_in[i]), ptr(ik), ptr(idr), ptr(w), ptr(cur), B, T, D, K, fuse, ptr(self._keep_err),
+                                                      stream()), "mfvit_token_reorg_bwd")
+                elif then == "front":
+                    self._keep_embed_bwd(front, dx_in[0], gflat, dimg, cfg)
             if hook is not None:
                 hook(self, hi, lo, gflat)
+        if not want_params:
+            return [None] * len(self._arena_params)
         return self._grad_views(gflat)
+
+    def _run_backward(self, cfg, ws, dfeats, on_stage_done=None, drop=None, dimg=None, want_params=True):
+        """The backward of _run_forward: the full grid as one range on the workspace `ws` (from _get_ws(.., want_dimg=True) when dimg is given)."""
+        state = ([(_lib.VitSeg(0, self.depth, self.num_tokens, 1), ws)], [], None, 0, False)
+        return self._backward_chain(cfg, state, dfeats, drop, dimg, want_params, on_stage_done)
 
     def _run_backward_lora(self, cfg, ws, dfeats, drop=None, dimg=None):
         """The selective backward of a model with adapters whose arena parameters are all frozen (mfvit_vit_backward_lora): returns the
@@ -1132,12 +991,12 @@ class VisionTransformerMoCo(nn.Module):
         prune = self.token_pruning_active()
         if token_indices is not None and not prune:
             raise _lib.MfvitError("token_indices given, but no token pruning is active (token_keep_rate = 1.0 or no prune block)")
+        forced = None
         if prune:
             if lo is not None:
                 raise _lib.MfvitError("LoRA adapters together with token pruning are not built: the block ranges run on the plain parameter "
                                       "arena (set token_keep_rate = 1.0, or detach the adapters)")
             _lib.require_cuda(x)
-            forced = None
             if token_indices is not None:
                 forced = self._check_token_indices(token_indices, int(x.shape[0]), self.num_tokens if idx is None else idx.shape[1] + 1)
                 stochastic = True                   # (a forced selection is never served from, or left in, the single-use cache)
@@ -1151,12 +1010,7 @@ class VisionTransformerMoCo(nn.Module):
         self._grad_arena_lent = False
         if idx is not None:
             self.last_keep_indices = idx
-        if prune:
-            feats = _EncoderPruneFn.apply(self, x, idx, forced, need, drop, *self._arena_params)
-        elif idx is not None:
-            feats = _EncoderKeepFn.apply(self, x, idx, need, drop, *self._arena_params)
-        else:
-            feats = _EncoderFn.apply(self, x, need, drop, *self._arena_params, *lora_params)
+        feats = _EncoderFn.apply(self, x, idx, forced, need, drop, *self._arena_params, *lora_params)
         self._feat_cache = None if stochastic else (x, key, caller, feats, idx)
         return feats
 

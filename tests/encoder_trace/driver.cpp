@@ -371,6 +371,70 @@ void fail_tile_gemm() { fail_case("gemm_nt_tile bf16x3 NONE", 1); }   // in the 
 void fail_side_wgrad() { fail_case("gemm_tn ", 1); }
 void fail_fork_record() { fail_case("hipEventRecord ev=ev1 ", 1); }
 
+// ------------------------------------------------------------------ 15. the given-x0 and block-range entry points
+// include/mfvit.h: the range [0, depth) issues exactly the launches of the whole-stack entry points (image_in = 1) / of the given-x0 entry points
+// (image_in = 0).  Each pair of scenarios below makes the same requests through both; the traces must agree in every line but the `call` lines.
+mfvit_vit_cfg range_cfg(int dtype = MFVIT_BF16X3) { return image_cfg(dtype, 2, 64, 384, 6, 2); }   // T = 17
+const int X0_TOKENS = 9;
+const mfvit_vit_drop RANGE_DROP = {0.1f, 0.1f, DPATH, 0x1234567890abcdefull};
+
+// forward, an unstaged and a staged backward with parameter gradients, the data-gradient chain alone; drop: NULL or RANGE_DROP
+void full_image_case(bool seg, const mfvit_vit_drop* x) {
+    mfvit_vit_cfg c = range_cfg(x ? MFVIT_BF16 : MFVIT_BF16X3);
+    const mfvit_vit_seg s = {0, c.depth, 17, 1};
+    auto bwd = [&](float* dp, float* di, int hi, int lo) {
+        if (seg) RC(mfvit_vit_backward_seg(&c, x, &s, P, SH, W, DF, dp, nullptr, di, hi, lo, MAIN));
+        else RC(mfvit_vit_backward_ex(&c, x, P, SH, W, DF, dp, di, hi, lo, MAIN));
+    };
+    if (seg) RC(mfvit_vit_forward_seg(&c, x, &s, P, SH, IM, W, FE, MAIN));
+    else if (x) RC(mfvit_vit_forward_drop(&c, x, P, SH, IM, W, FE, MAIN));
+    else RC(mfvit_vit_forward(&c, P, SH, IM, W, FE, MAIN));
+    bwd(DP, nullptr, c.depth, -1);
+    bwd(DP, DI, c.depth, -1);
+    bwd(DP, nullptr, 2, 1);
+    bwd(DP, nullptr, 0, -1);
+    bwd(DP, nullptr, 2, 1);
+    bwd(DP, DI, 0, -1);
+    bwd(nullptr, DI, c.depth, -1);
+}
+void stack_full_image() { full_image_case(false, nullptr); full_image_case(false, &RANGE_DROP); }
+void seg_full_image() { full_image_case(true, nullptr); full_image_case(true, &RANGE_DROP); }
+
+void full_x0_case(bool seg, const mfvit_vit_drop* x) {
+    mfvit_vit_cfg c = range_cfg(x ? MFVIT_BF16 : MFVIT_BF16X3);
+    const mfvit_vit_seg s = {0, c.depth, X0_TOKENS, 0};
+    auto bwd = [&](float* dp, int hi, int lo) {
+        if (seg) RC(mfvit_vit_backward_seg(&c, x, &s, P, SH, W, DF, dp, DT, nullptr, hi, lo, MAIN));
+        else RC(mfvit_vit_backward_x0(&c, x, X0_TOKENS, P, SH, W, DF, dp, DT, hi, lo, MAIN));
+    };
+    if (seg) RC(mfvit_vit_forward_seg(&c, x, &s, P, SH, IM, W, FE, MAIN));
+    else RC(mfvit_vit_forward_x0(&c, x, X0_TOKENS, P, SH, IM, W, FE, MAIN));
+    bwd(DP, c.depth, -1);
+    bwd(DP, 2, 1);
+    bwd(DP, 0, -1);
+    bwd(nullptr, c.depth, -1);
+}
+void x0_full() { full_x0_case(false, nullptr); full_x0_case(false, &RANGE_DROP); }
+void seg_full_x0() { full_x0_case(true, nullptr); full_x0_case(true, &RANGE_DROP); }
+
+// [0,1) on the full grid, then [1,2) on a shortened sequence, each on a workspace of its own; the backward range by range: every range in one
+// call, then every range cut between its entry stage and its block, and between its block and what feeds it
+void seg_two_ranges() {
+    mfvit_vit_cfg c = range_cfg();
+    const mfvit_vit_seg s0 = {0, 1, 17, 1}, s1 = {1, 2, X0_TOKENS, 0};
+    void* const W1 = at(WS, (size_t)1 << 32);
+    float *const X1 = at<float>(FEATS, (size_t)1 << 28), *const OUT = at<float>(FEATS, (size_t)2 << 28);
+    float *const DX1 = DT, *const DOUT0 = at<float>(DTOKENS, (size_t)1 << 28);
+    RC(mfvit_vit_forward_seg(&c, nullptr, &s0, P, SH, IM, W, FE, MAIN));
+    RC(mfvit_vit_forward_seg(&c, nullptr, &s1, P, SH, X1, W1, OUT, MAIN));
+    RC(mfvit_vit_backward_seg(&c, nullptr, &s1, P, SH, W1, DF, DP, DX1, nullptr, 2, 0, MAIN));
+    RC(mfvit_vit_backward_seg(&c, nullptr, &s0, P, SH, W, DOUT0, DP, nullptr, DI, 1, -1, MAIN));
+    RC(mfvit_vit_backward_seg(&c, nullptr, &s1, P, SH, W1, DF, DP, DX1, nullptr, 2, 2, MAIN));
+    RC(mfvit_vit_backward_seg(&c, nullptr, &s1, P, SH, W1, DF, DP, DX1, nullptr, 1, 0, MAIN));
+    RC(mfvit_vit_backward_seg(&c, nullptr, &s0, P, SH, W, DOUT0, DP, nullptr, nullptr, 1, 0, MAIN));
+    RC(mfvit_vit_backward_seg(&c, nullptr, &s0, P, SH, W, DOUT0, DP, nullptr, DI, -1, -1, MAIN));
+}
+
 struct Scenario { const char* name; void (*run)(); };
 #define S(f) {#f, f}
 const Scenario SCENARIOS[] = {
@@ -383,6 +447,7 @@ const Scenario SCENARIOS[] = {
     S(lora_prepare_shadow), S(lora_every_target), S(lora_proj_only), S(lora_lowest_block_1), S(lora_with_dimg), S(lora_grad), S(lora_duplicate_item),
     S(gpt_plain), S(gpt_pos_relu_dropout), S(gpt_pos_no_dropout), S(gpt_tiled_unsupported), S(gpt_f32_too_long), S(prepare_shadow), S(argument_errors),
     S(fail_tile_gemm), S(fail_side_wgrad), S(fail_fork_record),
+    S(stack_full_image), S(seg_full_image), S(x0_full), S(seg_full_x0), S(seg_two_ranges),
 };
 #undef S
 

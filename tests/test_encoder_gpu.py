@@ -297,3 +297,115 @@ def test_attention_backward_scale_from_the_proj_gradient_epilogue(monkeypatch):
     log(f"attention backward scale from the proj-gradient epilogue vs the prefetch path: {len(two_d)} weight gradients bit-identical, worst 1-D gradient "
         f"difference {worst:.2e} (B = {B}, depth {depth})")
     assert worst < 1e-4, worst
+
+
+# --------------------------------------------------------------------------------------------------- the one forward / backward chain
+# features3D runs every forward as block ranges through mfvit_vit_forward_seg / _backward_seg (mfvit/encoder.py, _forward_chain / _backward_chain).
+# The range [0, depth) issues the launches of the whole-stack and given-x0 entry points in the same order (include/mfvit.h; pinned on the CPU by
+# tests/test_encoder_trace_cpu.py), and every sum has a fixed order: the results are the same bits.  B = 2, 64 x 64 (T = 17), depth 2, 6 heads.
+CHAIN_PRECISIONS = ["bf16x3", "fp32"]
+
+
+def _chain_case(precision, seed, **kw):
+    m, _ = build(precision, seed, depth=2, img=64, **kw)
+    x = rng_tensor(seed + 1, (2, 3, 64, 64)).to("cuda:0")
+    return m.train(), x
+
+
+def _through_model(m, x, r, **kw):
+    """(features, gradient arena, d img) of features3D with every parameter trainable and the image requiring a gradient"""
+    m.zero_grad(set_to_none=True)
+    xg = x.clone().requires_grad_(True)
+    f = m.features3D(xg, **kw)
+    (f * r).sum().backward()                            # (d / d features = r, the same bits)
+    torch.cuda.synchronize()
+    return f.detach().clone(), m._last_grad_arena.clone(), xg.grad.clone()
+
+
+def _whole_stack_calls(m, x, r, drop):
+    """The same through mfvit_vit_forward(_drop) + mfvit_vit_backward_ex on fresh buffers, the model's arena and shadow."""
+    from mfvit._lib import check, lib, ptr, stream
+    cfg = m._cfg(x, True)
+    m._ensure_shadow(cfg)
+    h, arena = lib(), m.flat_parameters()
+    ws = torch.empty(h.mfvit_vit_workspace_bytes_ex(cfg, drop, 1), device=x.device, dtype=torch.uint8)
+    feats = torch.empty(x.shape[0], m.num_tokens, m.embed_dim, device=x.device)
+    if drop is None:
+        check(h.mfvit_vit_forward(cfg, ptr(arena), ptr(m._shadow), ptr(x), ptr(ws), ptr(feats), stream()), "mfvit_vit_forward")
+    else:
+        check(h.mfvit_vit_forward_drop(cfg, drop, ptr(arena), ptr(m._shadow), ptr(x), ptr(ws), ptr(feats), stream()), "mfvit_vit_forward_drop")
+    gflat, dimg = torch.zeros_like(arena), torch.empty_like(x)
+    check(h.mfvit_vit_backward_ex(cfg, drop, ptr(arena), ptr(m._shadow), ptr(ws), ptr(r), ptr(gflat), ptr(dimg), m.depth, -1, stream()),
+          "mfvit_vit_backward_ex")
+    torch.cuda.synchronize()
+    return feats, gflat, dimg
+
+
+@pytest.mark.parametrize("precision", CHAIN_PRECISIONS)
+def test_features3d_gives_the_bits_of_the_whole_stack_entry_points(precision):
+    m, x = _chain_case(precision, 7101)
+    r = rng_tensor(7103, (2, 17, 384)).to("cuda:0")
+    got = _through_model(m, x, r)
+    want = _whole_stack_calls(m, x, r, None)
+    for name, a, b in zip(("features", "gradient arena", "d img"), got, want):
+        assert torch.isfinite(a).all() and float(a.abs().max()) > 0 and torch.equal(a, b), name
+
+
+def test_features3d_with_dropout_gives_the_bits_of_the_whole_stack_entry_points():
+    m, x = _chain_case("bf16x3", 7111, drop_rate=0.1, attn_drop_rate=0.1, drop_path_rate=0.2)
+    r = rng_tensor(7113, (2, 17, 384)).to("cuda:0")
+    got = _through_model(m, x, r)
+    want = _whole_stack_calls(m, x, r, m._last_drop)    # (the masks of the model's forward: the same rates and seed)
+    for name, a, b in zip(("features", "gradient arena", "d img"), got, want):
+        assert torch.isfinite(a).all() and float(a.abs().max()) > 0 and torch.equal(a, b), name
+    with torch.no_grad():                               # (the masks do act: the evaluation forward differs)
+        assert not torch.equal(m.eval().features3D(x), got[0])
+
+
+@pytest.mark.parametrize("precision", CHAIN_PRECISIONS)
+def test_kept_patches_give_the_bits_of_the_given_x0_entry_points(precision):
+    from mfvit import _lib
+    from mfvit._lib import check, lib, ptr, stream
+    m, x = _chain_case(precision, 7121)
+    B, K, D = 2, 8, 384
+    idx = torch.stack([torch.randperm(16, generator=torch.Generator().manual_seed(7123 + b))[:K] for b in range(B)]).to("cuda:0")
+    r = rng_tensor(7124, (B, 1 + K, D)).to("cuda:0")
+    got = _through_model(m, x, r, keep_indices=idx)
+    m.check_keep_error()
+    # mfvit_patch_keep_embed + mfvit_vit_forward_x0 + mfvit_vit_backward_x0 + mfvit_patch_keep_embed_bwd on fresh buffers
+    cfg = m._cfg(x, True)
+    m._ensure_shadow(cfg)
+    h, arena, dev = lib(), m.flat_parameters(), x.device
+    pk = _lib.PatchKeepCfg(cfg.dtype, B, 64, 64, K, D)
+    fws = torch.empty(h.mfvit_patch_keep_workspace_bytes(pk, 1), device=dev, dtype=torch.uint8)
+    ws = torch.empty(h.mfvit_vit_workspace_bytes_x0(cfg, None, 1 + K), device=dev, dtype=torch.uint8)
+    err = torch.zeros(1, device=dev, dtype=torch.int32)
+    x0, feats, dx0 = (torch.empty(B, 1 + K, D, device=dev) for _ in range(3))
+    gflat, dimg = torch.zeros_like(arena), torch.empty_like(x)
+    names = ("cls_token", "pos_embed", "patch_embed.proj.weight", "patch_embed.proj.bias")
+    p_cls, p_pos, p_w, p_b = (arena.data_ptr() + 4 * m.arena_slice(n)[0] for n in names)
+    g_cls, _, g_w, g_b = (gflat.data_ptr() + 4 * m.arena_slice(n)[0] for n in names)
+    check(h.mfvit_patch_keep_embed(pk, ptr(x), ptr(idx), p_cls, p_pos, p_w, p_b, ptr(fws), 1, ptr(x0), ptr(err), stream()), "mfvit_patch_keep_embed")
+    check(h.mfvit_vit_forward_x0(cfg, None, 1 + K, ptr(arena), ptr(m._shadow), ptr(x0), ptr(ws), ptr(feats), stream()), "mfvit_vit_forward_x0")
+    check(h.mfvit_vit_backward_x0(cfg, None, 1 + K, ptr(arena), ptr(m._shadow), ptr(ws), ptr(r), ptr(gflat), ptr(dx0), m.depth, -1, stream()),
+          "mfvit_vit_backward_x0")
+    check(h.mfvit_patch_keep_embed_bwd(pk, ptr(idx), ptr(fws), ptr(dx0), g_cls, g_w, g_b, ptr(dimg), ptr(err), stream()), "mfvit_patch_keep_embed_bwd")
+    torch.cuda.synchronize()
+    assert int(err.item()) == 0 and got[0].shape == (B, 1 + K, D)
+    for name, a, b in zip(("features", "gradient arena", "d img"), got, (feats, gflat, dimg)):
+        assert torch.isfinite(a).all() and float(a.abs().max()) > 0 and torch.equal(a, b), name
+
+
+@pytest.mark.parametrize("precision", CHAIN_PRECISIONS)
+def test_the_stage_hook_sees_every_group_and_leaves_the_bits(precision):
+    m, x = _chain_case(precision, 7131)
+    r = rng_tensor(7133, (2, 17, 384)).to("cuda:0")
+    want = _through_model(m, x, r)
+    seen = []
+    m._grad_bucket_layers = 1
+    m._grad_stage_hook = lambda vit, hi, lo, gflat: seen.append((vit is m, hi, lo, gflat is not None))
+    got = _through_model(m, x, r)
+    del m._grad_stage_hook
+    assert seen == [(True, 2, 1, True), (True, 0, -1, True)]        # depth 2: (depth, depth - 1), (depth - 2, -1)
+    for name, a, b in zip(("features", "gradient arena", "d img"), got, want):
+        assert torch.equal(a, b), name

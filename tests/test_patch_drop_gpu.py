@@ -296,8 +296,8 @@ def test_refusals_launch_nothing():
     m = build(p, hw, depth, "bf16x3", patch_drop_rate=0.5)
     x = R.rng(9602, (B, 3) + hw).to(DEV)
     calls = []
-    real = m._run_forward_keep
-    m._run_forward_keep = lambda *a, **k: calls.append(1) or real(*a, **k)
+    real = m._forward_chain                         # (img, idx, plan, ..): every encoder forward; 1: on kept-patch indices, 0: without
+    m._forward_chain = lambda *a, **k: calls.append(int(a[1] is not None)) or real(*a, **k)
     good = torch.tensor([[0, 5, 3], [15, 2, 7]], device=DEV)
     for bad in (torch.tensor([[0, 5, 16], [1, 2, 3]], device=DEV), torch.tensor([[0, 5, -1], [1, 2, 3]], device=DEV),
                 torch.tensor([[0, 5, 5], [1, 2, 3]], device=DEV), torch.tensor([[0, 5, 3]], device=DEV),
@@ -351,9 +351,8 @@ def build_fus(rate, shared, depth=2, hw=(64, 64), precision="bf16x3"):
 
 
 def count_backbone_forwards(vit, calls):
-    real_k, real_f = vit._run_forward_keep, vit._run_forward
-    vit._run_forward_keep = lambda *a, **k: calls.append("keep") or real_k(*a, **k)
-    vit._run_forward = lambda *a, **k: calls.append("full") or real_f(*a, **k)
+    real = vit._forward_chain                       # (img, idx, plan, ..): "keep" when the call was given kept-patch indices
+    vit._forward_chain = lambda *a, **k: calls.append("full" if a[1] is None else "keep") or real(*a, **k)
 
 
 @pytest.mark.parametrize("shared", [True, False])

@@ -252,7 +252,7 @@ def test_two_stream_ca_step_is_reproducible_and_heads_use_forwards_of_their_own(
     y = torch.tensor([1, 2], device=DEV)
     seeds, forwards = [], []
     for b in backs:
-        orig, orig_fwd = b._draw_drop, b._run_forward
+        orig, orig_fwd = b._draw_drop, b._forward_chain
 
         def rec(orig=orig):
             d = orig()
@@ -261,10 +261,11 @@ def test_two_stream_ca_step_is_reproducible_and_heads_use_forwards_of_their_own(
             return d
 
         def rec_fwd(*a, orig_fwd=orig_fwd, **k):
+            assert a[1] is None and len(a[2]) == 1      # (img, idx, plan, ..): the full grid - no kept-patch indices, one block range
             forwards.append(1)
             return orig_fwd(*a, **k)
         b._draw_drop = rec
-        b._run_forward = rec_fwd
+        b._forward_chain = rec_fwd
     torch.manual_seed(9)
     r1 = _ca_step(model, backs, x, xe, y)
     # x_cxr / x_enh come from forwards independent of the fused features: 2 backbones x (features3D + __call__) = 4 mask seeds
