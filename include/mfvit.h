@@ -1037,6 +1037,30 @@ int mfvit_adam_step(const int64_t* table, int nchunks, float lr, float beta1, fl
                     mfvit_stream_t stream);
 int mfvit_sgd_step(const int64_t* table, int nchunks, float lr, float momentum, float weight_decay, int first_step,
                    mfvit_stream_t stream);
+/* Group-aware Adam / AdamW / SGD steps (additive in ABI 5): ONE launch over the JOINED table of several param groups, each with
+ * hyperparameters of its own (layer-wise learning-rate decay: ~55 groups on the two-stream model).  A row of the joined table names
+ * its entry of `hyper` in the upper half of the flag column: entry = (uint64)flag >> 32; the lower half is not read (the decoupled bit
+ * is the entry's).  Per row the arithmetic is that of mfvit_adam_step / mfvit_sgd_step (first_step = 0) with the entry's values - the
+ * same bits.  `hyper` is a HOST array of `nentries` entries, read before the call returns: the entries travel by value in the kernel
+ * arguments, MFVIT_OPTIM_GROUPS_PER_LAUNCH of them per launch (nothing is uploaded, no buffer outlives the call); more entries mean
+ * ceil(nentries / MFVIT_OPTIM_GROUPS_PER_LAUNCH) launches, each over the whole table, each serving its window of entries (the rows
+ * of the other windows return at once).  bc1 = 1 - beta1^step and bc2_sqrt = sqrt(1 - beta2^step) are computed per entry with the float
+ * expressions of mfvit_adam_step.
+ * A row whose entry index is >= nentries is SKIPPED: nothing of it is read or written, and the index never becomes an address.
+ * MFVIT_EINVAL (before any HIP call): a NULL pointer, nchunks <= 0, nentries <= 0, an Adam entry with step <= 0. */
+#define MFVIT_OPTIM_GROUPS_PER_LAUNCH 64
+typedef struct mfvit_adam_group {
+    float lr, beta1, beta2, eps, weight_decay;
+    int32_t step;        /* counts from 1, as in mfvit_adam_step */
+    int32_t decoupled;   /* != 0: AdamW */
+    int32_t reserved;    /* 0 */
+} mfvit_adam_group;
+typedef struct mfvit_sgd_group {
+    float lr, momentum, weight_decay;
+    int32_t reserved;    /* 0 */
+} mfvit_sgd_group;
+int mfvit_adam_step_groups(const int64_t* table, int nchunks, const mfvit_adam_group* hyper, int nentries, mfvit_stream_t stream);
+int mfvit_sgd_step_groups(const int64_t* table, int nchunks, const mfvit_sgd_group* hyper, int nentries, mfvit_stream_t stream);
 /* torch.cuda.amp.GradScaler.unscale_ over the same chunk table (MAIN_MOCO:349,546-548: scaler.scale(loss).backward();
  * scaler.step(optimizer); scaler.update()): every gradient element is multiplied by inv_scale and *found_inf (device float,
  * cleared by the caller) is set to 1 when any element was inf / nan before the multiplication. */

@@ -61,16 +61,15 @@ __device__ __forceinline__ void adam_elem(float& pv, float gv, float& mv, float&
     pv = pv - (lr / bc1) * mv / (sqrtf(vv) / bc2_sqrt + eps);
 }
 // 28 bytes of HBM traffic per element (p, g, m, v in; p, m, v out) and nothing else: 16-byte accesses, two independent groups per thread in
-// flight (the 4-byte form ran at 2.2 TB/s: 0.56 ms per step for the 45 M parameters of the two-encoder model)
-__global__ __launch_bounds__(256) void adam_kernel(const long* __restrict__ tab, float lr, float beta1, float beta2, float eps, float wd,
-                                                   float bc1, float bc2_sqrt) {
-    const long* e = tab + (long)blockIdx.x * CH;
+// flight (the 4-byte form ran at 2.2 TB/s: 0.56 ms per step for the 45 M parameters of the two-encoder model).  One table row: what adam_kernel
+// and adam_groups_kernel both run, so the two give the same bits for the same hyperparameters.
+__device__ __forceinline__ void adam_row(const long* __restrict__ e, bool decoupled, float lr, float beta1, float beta2, float eps, float wd,
+                                         float bc1, float bc2_sqrt) {
     float* p = (float*)e[1];
     const float* g = (const float*)e[2];
     float* m = (float*)e[3];
     float* v = (float*)e[4];
     const long n = e[5];
-    const bool decoupled = e[6] & 1;
     long done = 0;
     if ((((size_t)p | (size_t)g | (size_t)m | (size_t)v) & 15) == 0) {
         const long n4 = n >> 2;
@@ -107,8 +106,12 @@ __global__ __launch_bounds__(256) void adam_kernel(const long* __restrict__ tab,
         p[i] = pv;
     }
 }
-__global__ __launch_bounds__(256) void sgd_kernel(const long* __restrict__ tab, float lr, float momentum, float wd, int first) {
+__global__ __launch_bounds__(256) void adam_kernel(const long* __restrict__ tab, float lr, float beta1, float beta2, float eps, float wd,
+                                                   float bc1, float bc2_sqrt) {
     const long* e = tab + (long)blockIdx.x * CH;
+    adam_row(e, e[6] & 1, lr, beta1, beta2, eps, wd, bc1, bc2_sqrt);
+}
+__device__ __forceinline__ void sgd_row(const long* __restrict__ e, float lr, float momentum, float wd, int first) {
     float* p = (float*)e[1];
     const float* g = (const float*)e[2];
     float* buf = (float*)e[3];
@@ -121,6 +124,38 @@ __global__ __launch_bounds__(256) void sgd_kernel(const long* __restrict__ tab, 
         }
         p[i] = fmaf(-lr, d, p[i]);
     }
+}
+__global__ __launch_bounds__(256) void sgd_kernel(const long* __restrict__ tab, float lr, float momentum, float wd, int first) {
+    sgd_row(tab + (long)blockIdx.x * CH, lr, momentum, wd, first);
+}
+
+// ---- group-aware steps: ONE launch over the joined table of every param group.  A row names its hyper entry in the upper half of the flag column
+// (flag >> 32); the entries travel BY VALUE in the kernel-argument segment (64 x 32 bytes = 2 KB of the 4 KB HIP allows): nothing is uploaded per
+// step and no buffer can be overwritten under a step still queued.  The index comes from the table through blockIdx, so it is uniform for the
+// workgroup and the entry is fetched with scalar loads from the argument segment.  The launch serves the entries [base, base + count): a row naming
+// another entry returns before it reads anything else - an index never becomes an address outside the array.
+constexpr int GROUPS_CAP = MFVIT_OPTIM_GROUPS_PER_LAUNCH;
+struct adam_entry { float lr, beta1, beta2, eps, wd, bc1, bc2_sqrt; unsigned decoupled; };
+struct adam_entries { adam_entry e[GROUPS_CAP]; };
+struct sgd_entry { float lr, momentum, wd, unused; };
+struct sgd_entries { sgd_entry e[GROUPS_CAP]; };
+static_assert(sizeof(adam_entries) == 2048 && sizeof(sgd_entries) == 1024, "entries are passed by value: stay well inside the 4 KB argument segment");
+
+__device__ __forceinline__ unsigned row_entry(const long* e) { return (unsigned)((unsigned long)e[6] >> 32); }
+
+__global__ __launch_bounds__(256) void adam_groups_kernel(const long* __restrict__ tab, const adam_entries hy, unsigned base, unsigned count) {
+    const long* e = tab + (long)blockIdx.x * CH;
+    const unsigned k = row_entry(e) - base;          // (an index below `base` wraps to a large value)
+    if (k >= count) return;
+    const adam_entry& h = hy.e[k];
+    adam_row(e, h.decoupled != 0, h.lr, h.beta1, h.beta2, h.eps, h.wd, h.bc1, h.bc2_sqrt);
+}
+__global__ __launch_bounds__(256) void sgd_groups_kernel(const long* __restrict__ tab, const sgd_entries hy, unsigned base, unsigned count) {
+    const long* e = tab + (long)blockIdx.x * CH;
+    const unsigned k = row_entry(e) - base;
+    if (k >= count) return;
+    const sgd_entry& h = hy.e[k];
+    sgd_row(e, h.lr, h.momentum, h.wd, 0);
 }
 
 // GradScaler.unscale_ (MAIN_MOCO:546-548 -> torch.cuda.amp.GradScaler.step): g *= inv_scale over every chunk of the table and
@@ -475,6 +510,40 @@ int mfvit_adam_step(const int64_t* table, int nchunks, float lr, float beta1, fl
     MFVIT_LAUNCH(adam_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, (const long*)table, lr, beta1, beta2, eps, weight_decay,
                        bc1, bc2s);
     MFVIT_CHECK_LAUNCH();
+    return MFVIT_OK;
+}
+int mfvit_adam_step_groups(const int64_t* table, int nchunks, const mfvit_adam_group* hyper, int nentries, mfvit_stream_t stream) {
+    if (!table || !hyper || nchunks <= 0 || nentries <= 0) return MFVIT_EINVAL;
+    for (int i = 0; i < nentries; ++i)
+        if (hyper[i].step <= 0) return MFVIT_EINVAL;
+    for (int base = 0; base < nentries; base += GROUPS_CAP) {
+        const int count = nentries - base < GROUPS_CAP ? nentries - base : GROUPS_CAP;
+        adam_entries hy = {};
+        for (int i = 0; i < count; ++i) {
+            const mfvit_adam_group& g = hyper[base + i];
+            adam_entry& d = hy.e[i];
+            d.lr = g.lr; d.beta1 = g.beta1; d.beta2 = g.beta2; d.eps = g.eps; d.wd = g.weight_decay;
+            d.bc1 = 1.f - powf(g.beta1, (float)g.step);                      // (the float expressions of mfvit_adam_step)
+            d.bc2_sqrt = sqrtf(1.f - powf(g.beta2, (float)g.step));
+            d.decoupled = g.decoupled != 0;
+        }
+        MFVIT_LAUNCH(adam_groups_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, (const long*)table, hy, (unsigned)base, (unsigned)count);
+        MFVIT_CHECK_LAUNCH();
+    }
+    return MFVIT_OK;
+}
+int mfvit_sgd_step_groups(const int64_t* table, int nchunks, const mfvit_sgd_group* hyper, int nentries, mfvit_stream_t stream) {
+    if (!table || !hyper || nchunks <= 0 || nentries <= 0) return MFVIT_EINVAL;
+    for (int base = 0; base < nentries; base += GROUPS_CAP) {
+        const int count = nentries - base < GROUPS_CAP ? nentries - base : GROUPS_CAP;
+        sgd_entries hy = {};
+        for (int i = 0; i < count; ++i) {
+            const mfvit_sgd_group& g = hyper[base + i];
+            hy.e[i].lr = g.lr; hy.e[i].momentum = g.momentum; hy.e[i].wd = g.weight_decay;
+        }
+        MFVIT_LAUNCH(sgd_groups_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, (const long*)table, hy, (unsigned)base, (unsigned)count);
+        MFVIT_CHECK_LAUNCH();
+    }
     return MFVIT_OK;
 }
 int mfvit_amp_unscale(const int64_t* table, int nchunks, float inv_scale, float* found_inf, mfvit_stream_t stream) {

@@ -65,6 +65,20 @@ class LoraReq(Structure):
     _fields_ = [("rank", c_int), ("scale", c_float), ("n", c_int), ("items", POINTER(LoraItem))]
 
 
+OPTIM_GROUPS_PER_LAUNCH = 64   # MFVIT_OPTIM_GROUPS_PER_LAUNCH: hyper entries one launch of the group-aware steps carries in its arguments
+
+
+class AdamGroup(Structure):
+    """mfvit_adam_group: the hyperparameters of one param group for mfvit_adam_step_groups (include/mfvit.h)."""
+    _fields_ = [("lr", c_float), ("beta1", c_float), ("beta2", c_float), ("eps", c_float), ("weight_decay", c_float),
+                ("step", ctypes.c_int32), ("decoupled", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class SgdGroup(Structure):
+    """mfvit_sgd_group: the hyperparameters of one param group for mfvit_sgd_step_groups (include/mfvit.h)."""
+    _fields_ = [("lr", c_float), ("momentum", c_float), ("weight_decay", c_float), ("reserved", ctypes.c_int32)]
+
+
 class FusionCfg(Structure):
     _fields_ = [("batch", c_int), ("tokens", c_int), ("dim", c_int), ("heads", c_int), ("num_classes", c_int),
                 ("eps_pre", c_float), ("eps_post", c_float)]
@@ -167,6 +181,8 @@ SIGNATURES = {
     "mfvit_lars_step": (I, [P, I, I, P, F, F, F, F, P]),
     "mfvit_adam_step": (I, [P, I, F, F, F, F, F, I, P]),
     "mfvit_sgd_step": (I, [P, I, F, F, F, I, P]),
+    "mfvit_adam_step_groups": (I, [P, I, P, I, P]),
+    "mfvit_sgd_step_groups": (I, [P, I, P, I, P]),
     "mfvit_amp_unscale": (I, [P, I, F, P, P]),
     "mfvit_grad_norm_partials": (I, [P, I, I, P, P]),
     "mfvit_grad_clip_coef": (I, [P, P, I, I, I, D, P, P, P]),

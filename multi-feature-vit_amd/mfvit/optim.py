@@ -141,10 +141,47 @@ class _TableOptimizer(torch.optim.Optimizer):
         if cb is not None:
             cb(gi)
 
+    # ``single_launch=True`` (Adam / AdamW / SGD): step(), unscale_ and the norm and scale passes of clip_grad_norm_ / grad_norm run ONE launch
+    # each over the joined table of all param groups instead of one per group - what layer-wise learning-rate decay (param_groups_layer_decay:
+    # ~55 groups on the two-stream model) needs.  ``before_group(gi)`` is then called for every group, in order, BEFORE that launch: the
+    # data-parallel overlap of one group's update with the next group's gradient exchange is given up in this mode.
+    single_launch = False
+
+    def _joined(self):
+        """(joined table, parts) over the groups that have gradients, parts = [(gi, group, table, ntensors, live, row_tensor)]; (None, []) when
+        no group has one.  The joined table is the per-group tables back to back, in group order, with the position of the group among `parts`
+        - its hyper entry for mfvit_*_step_groups - in the upper half of the flag column.  Made on the device (a cat and one add; the addend goes
+        up through pinned memory, nothing waits) and cached by the identities of the group tables, which the cached tuple keeps alive."""
+        parts = []
+        for gi, g in enumerate(self.param_groups):
+            self._pre(gi)
+            table, nt, live = self._table(gi, g)
+            if table is not None:
+                parts.append((gi, g, table, nt, live, self._cache()[gi]["row_tensor"]))
+        if not parts:
+            return None, parts
+        cache = self._cache().setdefault("joined", {})
+        key = tuple(id(p[2]) for p in parts)
+        hit = cache.get(key)
+        if hit is None:
+            if len(cache) >= 8:
+                cache.clear()
+            tabs = [p[2] for p in parts]
+            host = torch.tensor([k << 32 for k, t in enumerate(tabs) for _ in range(t.shape[0])], dtype=torch.int64).pin_memory()
+            joined = torch.cat(tabs)
+            joined[:, 6] += host.to(joined.device, non_blocking=True)
+            hit = cache[key] = (joined, tabs, host)
+        return hit[0], parts
+
     @torch.no_grad()
     def unscale_(self, inv_scale, found_inf):
         """GradScaler.unscale_: g *= inv_scale for every gradient of this optimizer; found_inf (device f32[1]) is set to 1 when a
         gradient held an inf / nan (mfvit_amp_unscale)."""
+        if self.single_launch:
+            joined, _ = self._joined()
+            if joined is not None:
+                check(lib().mfvit_amp_unscale(ptr(joined), joined.shape[0], float(inv_scale), ptr(found_inf), stream()), "mfvit_amp_unscale")
+            return
         for gi, g in enumerate(self.param_groups):
             self._pre(gi)
             table, nt, _ = self._table(gi, g)
@@ -186,11 +223,85 @@ class Adam(_TableOptimizer):
     state_names = ("exp_avg", "exp_avg_sq")
     decoupled = False
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, single_launch=False):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        self.single_launch = bool(single_launch)
 
     def _flag(self, p, group):
         return 1 if self.decoupled else 0
+
+    def _launch_runs(self, g, table, live, vals):
+        """The launches of one param group, `vals` = the step numbers of its live parameters before the increment.  One kernel launch serves
+        one step number (bias correction): normally every parameter of the group agrees and the whole table goes out in one launch; otherwise
+        (a parameter whose first gradient arrived later, an unfrozen layer, a loaded torch state dict with mixed steps) the table rows - laid
+        out parameter by parameter - are launched in runs of equal step."""
+        if vals and vals.count(vals[0]) == len(vals):          # the normal case: one step number, the whole table in one launch
+            runs = [[0, table.shape[0], vals[0] + 1]]
+        else:
+            runs = []                                      # (first table row, rows, step after the increment)
+            row = 0
+            for p, v in zip(live, vals):
+                nrows = (p.numel() + CHUNK - 1) // CHUNK
+                if runs and runs[-1][2] == v + 1:
+                    runs[-1][1] += nrows
+                else:
+                    runs.append([row, nrows, v + 1])
+                row += nrows
+            assert row == table.shape[0]
+        for first, nrows, step in runs:
+            check(lib().mfvit_adam_step(ptr(table) + first * table.shape[1] * 8, nrows, float(g["lr"]), float(g["betas"][0]),
+                                        float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), step, stream()), "mfvit_adam_step")
+        _bump_versions(live)
+
+    def _bump_steps_joined(self, parts):
+        """_bump_steps for every group of `parts` at once: the 'step' scalars of ALL live parameters are views of one host vector, so ~55 groups
+        cost one add and one tolist() instead of one pair each.  Returns the values before the increment, group by group."""
+        cache = self._cache().setdefault(("steps", "joined"), {})
+        lives = [part[4] for part in parts]
+        last = cache.get("lives")
+        if last is not None and len(last) == len(lives) and all(a is b for a, b in zip(last, lives)):
+            sts, ends = cache["sts"], cache["ends"]
+        else:
+            sts = [self.state[p] for live in lives for p in live]
+            ends, n = [], 0
+            for live in lives:
+                n += len(live)
+                ends.append(n)
+            cache["lives"], cache["sts"], cache["ends"] = lives, sts, ends
+        views = cache.get("views")
+        if views is None or len(views) != len(sts) or any(st.get("step") is not v for st, v in zip(sts, views)):
+            vals = []
+            for st in sts:
+                t = st.get("step")
+                vals.append(float(t) if t is not None else 0.0)
+            buf = torch.tensor(vals, dtype=torch.float32)
+            views = [buf[i] for i in range(len(vals))]
+            for st, v in zip(sts, views):
+                st["step"] = v
+            cache["buf"], cache["views"] = buf, views
+        buf = cache["buf"]
+        vals = [int(v) for v in buf.tolist()]
+        buf += 1.0
+        return [vals[a:b] for a, b in zip([0] + ends[:-1], ends)]
+
+    def _step_joined(self):
+        """single_launch: every group's rows in one mfvit_adam_step_groups launch, each group with its own lr / betas / eps / weight decay /
+        step.  The rare case - parameters of ONE group at different step numbers - falls back to the per-group launches for this call."""
+        joined, parts = self._joined()
+        if joined is None:
+            return
+        vals = self._bump_steps_joined(parts)
+        if any(v.count(v[0]) != len(v) for v in vals):
+            for (_, g, table, _, live, _), v in zip(parts, vals):
+                self._launch_runs(g, table, live, v)
+            return
+        hyper = (_lib.AdamGroup * len(parts))()
+        for h, (_, g, _, _, _, _), v in zip(hyper, parts, vals):
+            h.lr, h.beta1, h.beta2 = float(g["lr"]), float(g["betas"][0]), float(g["betas"][1])
+            h.eps, h.weight_decay = float(g["eps"]), float(g["weight_decay"])
+            h.step, h.decoupled = v[0] + 1, int(self.decoupled)
+        check(lib().mfvit_adam_step_groups(ptr(joined), joined.shape[0], hyper, len(parts), stream()), "mfvit_adam_step_groups")
+        _bump_versions([p for part in parts for p in part[4]])
 
     def _bump_steps(self, gi, live):
         """state[p]['step'] += 1 for the live parameters; returns the values BEFORE the increment.  The per-parameter f32 scalars of torch.optim
@@ -221,41 +332,23 @@ class Adam(_TableOptimizer):
 
     @torch.no_grad()
     def step(self):
+        if self.single_launch:
+            return self._step_joined()
         for gi, g in enumerate(self.param_groups):
             self._pre(gi)
             table, nt, live = self._table(gi, g)
             if table is None:
                 continue
-            # per-parameter 'step' like torch.optim (f32 scalar tensors on the host).  One kernel launch serves one step number (bias
-            # correction): normally every parameter of the group agrees and the whole table goes out in one launch; otherwise (a parameter
-            # whose first gradient arrived later, an unfrozen layer, a loaded torch state dict with mixed steps) the table rows - laid out
-            # parameter by parameter - are launched in runs of equal step.
-            vals = self._bump_steps(gi, live)
-            if vals and vals.count(vals[0]) == len(vals):          # the normal case: one step number, the whole table in one launch
-                runs = [[0, table.shape[0], vals[0] + 1]]
-            else:
-                runs = []                                      # (first table row, rows, step after the increment)
-                row = 0
-                for p, v in zip(live, vals):
-                    nrows = (p.numel() + CHUNK - 1) // CHUNK
-                    if runs and runs[-1][2] == v + 1:
-                        runs[-1][1] += nrows
-                    else:
-                        runs.append([row, nrows, v + 1])
-                    row += nrows
-                assert row == table.shape[0]
-            for first, nrows, step in runs:
-                check(lib().mfvit_adam_step(ptr(table) + first * table.shape[1] * 8, nrows, float(g["lr"]), float(g["betas"][0]),
-                                            float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), step, stream()), "mfvit_adam_step")
-            _bump_versions(live)
+            # per-parameter 'step' like torch.optim (f32 scalar tensors on the host)
+            self._launch_runs(g, table, live, self._bump_steps(gi, live))
 
 
 class AdamW(Adam):
     """torch.optim.AdamW semantics (decoupled weight decay; default 1e-2 like torch)."""
     decoupled = True
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
-        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, single_launch=False):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, single_launch=single_launch)
 
 
 class SGD(_TableOptimizer):
@@ -263,14 +356,25 @@ class SGD(_TableOptimizer):
     first update d; a zero buffer gives the same first step (momentum * 0 + d), so the kernel never needs the first-step case."""
     state_names = ("momentum_buffer",)
 
-    def __init__(self, params, lr=1e-3, momentum=0, weight_decay=0, dampening=0, nesterov=False):
+    def __init__(self, params, lr=1e-3, momentum=0, weight_decay=0, dampening=0, nesterov=False, single_launch=False):
         if dampening != 0 or nesterov:
             raise NotImplementedError("the HIP SGD kernel implements the reference's configuration (MAIN_CA:445-448): no dampening, no nesterov")
         # dampening / nesterov are kept in the group so that torch.optim.SGD can load this optimizer's state dict (and vice versa)
         super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay, dampening=0, nesterov=False))
+        self.single_launch = bool(single_launch)
 
     @torch.no_grad()
     def step(self):
+        if self.single_launch:      # every group's rows in one mfvit_sgd_step_groups launch, each group with its own lr / momentum / weight decay
+            joined, parts = self._joined()
+            if joined is None:
+                return
+            hyper = (_lib.SgdGroup * len(parts))()
+            for h, (_, g, _, _, _, _) in zip(hyper, parts):
+                h.lr, h.momentum, h.weight_decay = float(g["lr"]), float(g["momentum"]), float(g["weight_decay"])
+            check(lib().mfvit_sgd_step_groups(ptr(joined), joined.shape[0], hyper, len(parts), stream()), "mfvit_sgd_step_groups")
+            _bump_versions([p for part in parts for p in part[4]])
+            return
         for gi, g in enumerate(self.param_groups):
             self._pre(gi)
             table, nt, live = self._table(gi, g)
@@ -303,8 +407,11 @@ class SAM(_TableOptimizer):
                             f"{base_optimizer!r}: the device chunk tables the kernels stream over live on the optimizer")
         if not rho >= 0.0:
             raise ValueError(f"Invalid rho, should be non-negative: {rho}")
+        # single_launch belongs to the base optimizer object (its step, unscale_ and clipping passes), not to the param groups; the perturb and
+        # restore passes keep SAM's own per-group tables
+        single = {"single_launch": True} if kwargs.pop("single_launch", False) else {}
         super().__init__(params, dict(rho=rho, adaptive=adaptive, **kwargs))
-        self.base_optimizer = base_optimizer(self.param_groups, **kwargs)
+        self.base_optimizer = base_optimizer(self.param_groups, **single, **kwargs)
         self.param_groups = self.base_optimizer.param_groups
         self.defaults.update(self.base_optimizer.defaults)
         self._pending = None       # (tables of the perturbed rows with their live parameters, out2) between first_step and second_step
@@ -433,7 +540,25 @@ def _grad_norm(optimizers, max_norm, norm_type, error_if_nonfinite, per_tensor, 
     scratch = opts[0]._cache().setdefault("clip", {})      # partials of the last call (sized by row count) and joined row indices
     part = scratch.get("partials")
     tabs, rows, nt = [], 0, 0
+    launched = []                                           # the tables the norm pass ran over = the ones the scale pass runs over
     for o in opts:
+        if o.single_launch:                                 # one launch over the joined table: the same rows in the same order, so the same partials
+            table, parts = o._joined()
+            if table is None:
+                continue
+            nrows = table.shape[0]
+            if part is None or rows + nrows > part.numel():
+                grown = torch.empty(max(1024, rows + nrows, 2 * (0 if part is None else part.numel())), device=dev, dtype=torch.float32)
+                if rows:
+                    grown[:rows].copy_(part[:rows])
+                part = scratch["partials"] = grown
+            check(h.mfvit_grad_norm_partials(ptr(table), nrows, kind, part.data_ptr() + 4 * rows, st), "mfvit_grad_norm_partials")
+            launched.append(table)
+            for _, _, gtable, n, _, rt in parts:
+                tabs.append((gtable, rt, nt))
+                nt += n
+            rows += nrows
+            continue
         for gi, g in enumerate(o.param_groups):
             o._pre(gi)                                      # data parallel: this group's exchange is joined before its gradients are read
             table, n, _ = o._table(gi, g)
@@ -447,6 +572,7 @@ def _grad_norm(optimizers, max_norm, norm_type, error_if_nonfinite, per_tensor, 
                 part = scratch["partials"] = grown
             check(h.mfvit_grad_norm_partials(ptr(table), nrows, kind, part.data_ptr() + 4 * rows, st), "mfvit_grad_norm_partials")
             tabs.append((table, o._cache()[gi]["row_tensor"], nt))
+            launched.append(table)
             rows += nrows
             nt += n
     if not tabs:
@@ -474,7 +600,7 @@ def _grad_norm(optimizers, max_norm, norm_type, error_if_nonfinite, per_tensor, 
                            "To disable this error and scale the gradients by the non-finite norm anyway, set `error_if_nonfinite=False`")
     if scale:
         coef = out.data_ptr() + 4
-        for table, _, _ in tabs:
+        for table in launched:
             check(h.mfvit_grad_scale(ptr(table), table.shape[0], coef, st), "mfvit_grad_scale")
     return (total, norms) if per_tensor else total
 
@@ -492,3 +618,157 @@ def clip_grad_norm_(optimizers, max_norm, norm_type=2.0, error_if_nonfinite=Fals
 def grad_norm(optimizers, norm_type=2.0, per_tensor=False):
     """The total gradient norm clip_grad_norm_ would return (and the per-tensor norms), for logging: the gradients are not touched."""
     return _grad_norm(optimizers, float("inf"), norm_type, False, per_tensor, False)
+
+
+# ------------------------------------------------------------------------------------------------ layer-wise learning-rate decay
+def _layer_units(module):
+    """[(name prefix, module, is an image encoder)] of `module`: the VisionTransformerMoCo encoders inside it (itself, when it is one), each
+    with a layer map of its own, behind what is left of the module's own parameters."""
+    from .encoder import VisionTransformerMoCo
+    if isinstance(module, VisionTransformerMoCo):
+        return [("", module, True)]
+    vits = []
+    for name, sub in module.named_modules():
+        if isinstance(sub, VisionTransformerMoCo) and not any(name.startswith(v + ".") for v, _, _ in vits):
+            vits.append((name, sub, True))
+    return [("", module, False)] + [(n + ".", s, True) for n, s, _ in vits]
+
+
+def _vit_layer_id(name, depth):
+    if name in ("cls_token", "pos_embed") or name.startswith("patch_embed."):
+        return 0
+    if name.startswith("blocks."):
+        return int(name.split(".")[1]) + 1
+    return depth + 1          # norm.*, head.* and whatever else sits behind the blocks
+
+
+def param_groups_layer_decay(modules, lr, weight_decay=0.05, layer_decay=0.75, no_weight_decay_list=("pos_embed", "cls_token")):
+    """Param groups with layer-wise learning-rate decay (BEiT / MAE ``layer_decay``, timm's ``param_groups_layer_decay``) for Adam / AdamW / SGD.
+    `modules`: a module or a sequence of modules, e.g. ``[fusion, vit_cxr, vit_enh]``.
+
+    A VisionTransformerMoCo of depth L has L + 2 layer ids: cls_token, pos_embed and patch_embed.* are layer 0, blocks.i.* (LoRA tensors
+    included) layer i + 1, norm.* and head.* layer L + 1, and layer k trains at ``lr * layer_decay ** (L + 1 - k)``.  Every other
+    parameter - Fus_CrossViT's own, the projector / predictor around a base encoder - has scale 1 (layer_id None).  No weight decay for
+    parameters with ndim <= 1, for *.bias and for the names of `no_weight_decay_list`; parameters with requires_grad=False are skipped.
+    One group per (module, layer id, decays?) that is not empty: module by module, in ascending layer id, the decaying group first.  A
+    group holds plain values - params, lr (= lr * lr_scale), lr_scale, weight_decay, layer_id, param_names - so optimizer state dicts
+    pickle as before and load into torch.optim.AdamW built from the same groups.  ``mfvit.schedules.adjust_learning_rate`` multiplies by
+    lr_scale; build the optimizer with ``single_launch=True``, or every group costs a launch per operation."""
+    mods = [modules] if isinstance(modules, torch.nn.Module) else list(modules)
+    skip = set(no_weight_decay_list)
+    groups, seen = [], set()
+    for module in mods:
+        units = _layer_units(module)
+        inner = [prefix for prefix, _, is_vit in units if is_vit and prefix]
+        for prefix, unit, is_vit in units:
+            depth = unit.depth if is_vit else None
+            by_key = {}
+            for name, p in unit.named_parameters():
+                if not p.requires_grad or id(p) in seen or (not is_vit and any(name.startswith(i) for i in inner)):
+                    continue
+                seen.add(id(p))
+                layer = _vit_layer_id(name, depth) if is_vit else None
+                decays = not (p.ndim <= 1 or name.endswith(".bias") or name in skip)
+                entry = by_key.setdefault((-1 if layer is None else layer, not decays), (layer, decays, [], []))
+                entry[2].append(p)
+                entry[3].append(prefix + name)
+            for key in sorted(by_key):
+                layer, decays, params, names = by_key[key]
+                scale = 1.0 if layer is None else float(layer_decay) ** (depth + 1 - layer)
+                groups.append({"params": params, "lr": lr * scale, "lr_scale": scale, "weight_decay": float(weight_decay) if decays else 0.0,
+                               "layer_id": layer, "param_names": names})
+    return groups
+
+
+# ------------------------------------------------------------------------------------------------ EMA of the model weights
+def _arena_of(module):
+    """(flat f32 arena, the parameters that are views of it) of a module of this package; TypeError for a module without one."""
+    from .arena import ParamArena
+    flat_fn = getattr(module, "flat_parameters", None)
+    arena = module.__dict__.get("_arena")
+    if callable(flat_fn) and isinstance(arena, ParamArena):
+        return flat_fn(), arena.params
+    if callable(flat_fn) and module.__dict__.get("_arena_params") is not None:
+        return flat_fn(), module._arena_params
+    raise TypeError(f"mfvit.optim.ModelEma needs modules whose parameters live in a flat arena (flat_parameters(): the encoders, Fus_CrossViT), "
+                    f"not {type(module).__name__}: the update is one mfvit_ema_update launch per arena")
+
+
+_RUNTIME_ATTRS = ("_feat_cache", "_ws_pool", "_shadow", "_grad_arena", "_last_grad_arena", "_side")     # caches a copy must not share or clone
+
+
+class ModelEma:
+    """timm's ``ModelEmaV2``: an exponential moving average of the weights, kept for evaluation.  ``ModelEma(modules, decay=0.9998, warmup=False)``
+    holds deep copies of `modules` (a module or a sequence, e.g. ``[fusion, vit_cxr, vit_enh]`` - copied together, so a copied Fus_CrossViT
+    drives the copied encoders) in eval() mode with gradients off.  ``update(modules)`` goes after ``optimizer.step()``:
+    ema = ema * d + w * (1 - d), one mfvit_ema_update launch per arena (and one per parameter outside it: an encoder's head), with the
+    parameter versions bumped so the weight shadows follow; buffers are copied.  d = decay, or with warmup=True min(decay, (1 + t) / (10 + t)),
+    t = the number of updates so far (counted on the host).  ``.modules`` / ``.module`` (the first) run the evaluation forward;
+    ``state_dict()`` / ``load_state_dict()`` carry the copies' state dicts and t."""
+
+    def __init__(self, modules, decay=0.9998, warmup=False):
+        import copy
+        mods = [modules] if isinstance(modules, torch.nn.Module) else list(modules)
+        if not mods:
+            raise ValueError("ModelEma needs at least one module")
+        if not 0.0 <= float(decay) <= 1.0:
+            raise ValueError(f"decay must lie in [0, 1], got {decay!r}")
+        for m in mods:
+            _arena_of(m)
+        memo = {}
+        for m in mods:          # runtime caches (workspaces, shadows, cached features with a graph behind them) are not part of a copy
+            for sub in m.modules():
+                for a in _RUNTIME_ATTRS:
+                    v = sub.__dict__.get(a)
+                    if v is not None:
+                        memo[id(v)] = {} if isinstance(v, dict) else None
+        self.modules = copy.deepcopy(mods, memo)
+        for m in self.modules:
+            m.eval()
+            m.requires_grad_(False)
+            for sub in m.modules():
+                if callable(getattr(sub, "_flatten", None)):
+                    sub._flatten()
+            _arena_of(m)
+        self.decay, self.warmup, self.t = float(decay), bool(warmup), 0
+
+    @property
+    def module(self):
+        return self.modules[0]
+
+    def decay_at(self, t):
+        """d of the update number t (counted from 0)."""
+        return min(self.decay, (1.0 + t) / (10.0 + t)) if self.warmup else self.decay
+
+    @torch.no_grad()
+    def update(self, modules):
+        from .moco_ops import ema_update_
+        mods = [modules] if isinstance(modules, torch.nn.Module) else list(modules)
+        if len(mods) != len(self.modules):
+            raise ValueError(f"ModelEma holds {len(self.modules)} modules, update() was given {len(mods)}")
+        d = self.decay_at(self.t)
+        for ema, live in zip(self.modules, mods):
+            src, src_params = _arena_of(live)
+            dst, dst_params = _arena_of(ema)
+            if dst.numel() != src.numel():
+                raise ValueError(f"{type(live).__name__}: the arena has {src.numel()} elements, its average {dst.numel()}")
+            ema_update_(dst, src, d, dst_params)
+            inside = {id(p) for p in dst_params}
+            for pe, pl in zip(ema.parameters(), live.parameters()):
+                if id(pe) not in inside:
+                    if not (pe.is_contiguous() and pl.is_contiguous() and pe.dtype == pl.dtype == torch.float32 and pe.shape == pl.shape):
+                        raise _lib.MfvitError("ModelEma: parameters outside an arena must be contiguous f32 tensors of equal shape")
+                    ema_update_(pe.detach(), pl.detach(), d, (pe,))
+            for be, bl in zip(ema.buffers(), live.buffers()):
+                be.copy_(bl)
+        self.t += 1
+
+    def state_dict(self):
+        return {"t": self.t, "decay": self.decay, "warmup": self.warmup, "modules": [m.state_dict() for m in self.modules]}
+
+    def load_state_dict(self, sd):
+        if len(sd["modules"]) != len(self.modules):
+            raise ValueError(f"ModelEma holds {len(self.modules)} modules, the state dict {len(sd['modules'])}")
+        for m, s in zip(self.modules, sd["modules"]):
+            m.load_state_dict(s)
+        self.t = int(sd["t"])

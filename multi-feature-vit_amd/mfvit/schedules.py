@@ -4,7 +4,8 @@ import math
 
 def adjust_learning_rate(optimizer, epoch, lr, epochs, warmup_epochs, cos=True, schedule=()):
     """Half-cycle cosine after linear warm-up (cos=True) or step-wise x0.1 at the milestones; writes the value into every
-    param group and returns it (MAIN_MOCO:608-623).  ``epoch`` may be fractional (epoch + i / iters_per_epoch)."""
+    param group and returns it (MAIN_MOCO:608-623).  ``epoch`` may be fractional (epoch + i / iters_per_epoch).  A group with an
+    ``lr_scale`` key (mfvit.optim.param_groups_layer_decay) gets the value times its scale; the unscaled value is returned."""
     if cos:
         if epoch < warmup_epochs:
             lr_ = lr * epoch / warmup_epochs
@@ -16,7 +17,7 @@ def adjust_learning_rate(optimizer, epoch, lr, epochs, warmup_epochs, cos=True, 
             lr_ *= 0.1 if epoch >= milestone else 1.0
     if optimizer is not None:
         for group in optimizer.param_groups:
-            group["lr"] = lr_
+            group["lr"] = lr_ * group["lr_scale"] if "lr_scale" in group else lr_
     return lr_
 
 
